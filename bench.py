@@ -13,20 +13,26 @@ N > 1 is STRONG scaling by default (north_star): the ONE volume 
 shards -- config 2 on 8 GPUs: 2048 points per GPU --, every rank draws the same pupil samples, the trip masks are
 OR-reduced over the ranks (one small all-reduce per step), and the [N/world, 2, ks, ks] blocks the kernels wrote are
 all-gathered to every rank with ONE RCCL collective per step (485 MB received per rank and step at N = 8) on a side
-stream under the next step's kernel -- `value` includes it, `value_no_gather` is the same loop without it; `gather`
+stream under the next step's kernel -- `value` includes it, `value_no_gather` (--full) is the same loop without it; `gather`
 carries the bytes a rank receives per step, the all-gather's own time on its stream and `gather_bound` (does it take
-longer than the kernel it hides under?) and `volume_checksums_equal` (every rank's copy of the volume holds every rank's
-shard bit for bit).  The run ends with `gather.trial`: the same K timed steps with the shards exchanged as seven concurrent
-peer transfers per rank ('direct') instead of RCCL's all-gather, under a deadline; the faster one is `value`, both are
+longer than the kernel it hides under?) and `volume_checksums_equal` (--full: every rank's copy of the volume holds every
+rank's shard bit for bit).  With --full the run ends with `gather.trial`: the same K timed steps with the shards exchanged
+as seven concurrent peer transfers per rank ('direct') instead of RCCL's all-gather, under a deadline; the faster one is `value`, both are
 reported (`value_allgather`, `value_direct`; SDIRT_GATHER_TRIAL=0 or a set SDIRT_GATHER_ALGO skips it).  `--scaling weak`:
 every rank renders its own 16384-point slab of a 32x32x(16*N) volume.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]   (N > 1: starts its own N ranks)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+  python bench.py ... --dump-outputs DIR     (after the timed steps: a fixed sample of the last step's PSFs, DIR/*.npy)
+  python bench.py ... --full                 (everything below beyond the headline)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `roofline`).
+Everything else it measures -- the sustained loop, the two-stream leg, `also`, `cpu_baseline`, and at N > 1 the
+no-gather leg, the checksum comparison and the gather-algorithm trial -- runs with --full only.
 
 Rank 0 prints ONE JSON line (see the driver contract) of less than 4 KB: the contract's keys, `roofline` (the
 dominant kernel, k_psf_lr; the figures that say something -- valu_flops_frac, valu_issue_frac -- as flat scalars),
-`cpu_baseline` (oracle/: a C port of the reference's CPU path, OpenMP over the host cores, and a PyTorch-CPU
+with --full `cpu_baseline` (oracle/: a C port of the reference's CPU path, OpenMP over the host cores, and a PyTorch-CPU
 restatement of the reference's whole-tensor execution model, on a bounded sample of the same workload; oracle/ is only
 loaded for that leg), `also_summary` ([value, ms_per_step, roofline frac] of the staged SoA chain, f1, c4, c3, tcp, fit =
 the loop of 1_fit_psfnet.py, c5 = config 5 end to end)
@@ -1085,6 +1091,22 @@ def gather_algo_trial(loop, steps, dt_default, res, rays):
                 g["gather_bound"] = bool(g_ms > g["compute_ms"])
 
 
+DUMP_POINTS = 1024       # --dump-outputs: points sampled from the volume (L + R at 65 x 65: 35 MB)
+
+
+def dump_outputs(path, loop):
+    """--dump-outputs: the L and R PSFs the last timed step rendered (after its fence) for a fixed, seeded sample of the
+    rank's points, and which points those are -- two builds run with the same arguments can be compared file by file."""
+    s = loop._slots[(loop.steps - 1) % len(loop._slots)]
+    n = loop.n_local
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_POINTS), replace=False))
+    block = s.out[:n][torch.from_numpy(idx).to(s.out.device)].cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "psf_left.npy"), np.ascontiguousarray(block[:, 0], dtype=np.float32))
+    np.save(os.path.join(path, "psf_right.npy"), np.ascontiguousarray(block[:, 1], dtype=np.float32))
+    np.save(os.path.join(path, "point_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1104,16 +1126,24 @@ def main():
                     help="where the full record of the run goes (default: bench_detail.json beside bench.py); the ONE "
                          "line on stdout is its compact form (< 4 KB)")
     ap.add_argument("--verbose", action="store_true", help="also print the full record on stderr")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N = 1: skip the CPU baseline")
     ap.add_argument("--no-two-streams", action="store_true",
-                    help="N = 1: skip the second leg (the same K steps on two alternating render streams) -- the profiling "
+                    help="--full, N = 1: skip the second leg (the same K steps on two alternating render streams) -- the profiling "
                          "recipes: overlapping launches would stand in the kernel trace with twice their duration")
     ap.add_argument("--no-also", action="store_true",
-                    help="default c2 run at N = 1: skip the `also` block (staged SoA chain, f1, c4: a few steps each)")
-    ap.add_argument("--sustain-seconds", type=float, default=20.0,
+                    help="--full c2 run at N = 1: skip the `also` block (staged SoA chain, f1, c4: a few steps each)")
+    ap.add_argument("--sustain-seconds", type=float, default=None,
                     help="after the K timed steps, keep stepping for this long and report "
-                         "ms_per_step_sustained (0 = skip); long enough for a 5-second GPU-activity "
-                         "sampler to see the GPU phase of the run")
+                         "ms_per_step_sustained (0 = skip); default 20 with --full and for the side workloads, 0 otherwise; "
+                         "long enough for a 5-second GPU-activity sampler to see the GPU phase of the run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: the sustained loop, the two-stream "
+                         "leg, the `also` block, the CPU baseline; N > 1: the no-gather leg, the checksums of the gathered "
+                         "volume and the gather-algorithm trial (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="PSF-volume workloads: after the timed steps, write a fixed sample (seeded, at most 1024 points) of "
+                         "the L and R PSFs the last timed step rendered (rank 0's shard) as DIR/psf_left.npy, "
+                         "DIR/psf_right.npy (float32) and the sampled point indices as DIR/point_index.npy (float64)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + list(EXTRA_WORKLOADS), default="c2",
                     help="c2 (default, the headline) / c3 / c3k65 / c4: PSF-volume renders; f1: per-pixel DP-PSF "
                          "convolution of a 512x768 frame (render_psf.py:120-155); tcp: the reference's own "
@@ -1127,6 +1157,10 @@ def main():
                     help="--workload staged: `calls` times the call-by-call chain only (the profiling recipe: one kernel "
                          "per name), `both` also the chain through sdirt_trace2sensor / SDIRT_PSF_NORMALIZE")
     args = ap.parse_args()
+    if args.sustain_seconds is None:
+        args.sustain_seconds = 20.0 if args.full or args.workload in EXTRA_WORKLOADS else 0.0
+    if args.dump_outputs and args.workload in EXTRA_WORKLOADS:
+        ap.error(f"--dump-outputs: the PSF-volume workloads only ({', '.join(sorted(WORKLOADS))})")
     global DETAIL_PATH
     DETAIL_PATH = args.detail_file
     if args.verbose:
@@ -1202,8 +1236,10 @@ def main():
     dt = loop.timed(args.steps)
     relaunches = loop.relaunches - relaunch0
     k_event_ms = loop.kernel_ms()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop)
     # N > 1: every rank's copy of the volume holds every rank's shard, bit for bit (checksums of the last step's blocks)
-    gather_ok = loop.verify_gather() if gather_default else None
+    gather_ok = loop.verify_gather() if gather_default and args.full else None
     host_us = loop.t_step / args.steps * 1e6
     # the all-gathers of the timed steps as the comm stream saw them (start = the shard is final and the previous
     # gather has left the stream, end = every rank's shard has arrived here); MAX over ranks like the wall time
@@ -1216,7 +1252,7 @@ def main():
     # the same K steps without the all-gather (N > 1), and a loop long enough for the clocks to
     # settle (the K-step region lasts a fraction of a second)
     dt_ng = None
-    if gather_default:
+    if gather_default and args.full:
         loop.gather = False
         dt_ng = loop.timed(args.steps)
         loop.gather = True
@@ -1225,7 +1261,7 @@ def main():
         k_sus = max(args.steps, int(math.ceil(args.sustain_seconds / (dt / args.steps))))
         dt_sus = loop.timed(k_sus)
     pupil_last = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # the pupil points of the GPU leg's last step, as the device mapped them (they stand in the slot's scratch)
         s_ = loop._slots[(loop.steps - 1) % len(loop._slots)]
         xy = s_.scratch[loop.scratch_bytes - 4 * loop.n_u:].view(torch.float32).clone()
@@ -1235,7 +1271,7 @@ def main():
     # N = 1: the same K steps once more with consecutive steps on two alternating streams (what a pipelined consumer of
     # batch after batch gets: the next launch's workgroups fill what is left of the previous launch's end)
     dt_two = None
-    if world == 1 and not args.no_two_streams:
+    if world == 1 and args.full and not args.no_two_streams:
         del loop
         torch.cuda.empty_cache()
         loop2 = VolumeStepper(lens, points_local, n_total, KS, SPP, DP, streams=2)
@@ -1359,6 +1395,7 @@ def main():
         if dt_ng is not None:
             res["value_no_gather"] = rays / dt_ng
             res["ms_per_step_no_gather"] = dt_ng / args.steps * 1e3
+        if gather_default:
             gb = 2 * (n_total - n_local) * KS * KS * 4 / 1e9      # received per rank and step
             compute_ms = k_ms[dom]
             width = max(b_ - a_ for a_, b_ in sd.shard_bounds(n_total, world))
@@ -1380,13 +1417,14 @@ def main():
             res["ms_per_step_sustained"] = dt_sus / k_sus * 1e3
             res["value_sustained"] = n_total * SPP * k_sus / dt_sus
             res["sustained_steps"] = k_sus
-        if world == 1 and args.workload == "c2" and not args.no_also:
+        if world == 1 and args.workload == "c2" and args.full and not args.no_also:
             res["also"] = also_block(args, lens, device)
-        if world == 1 and not args.no_cpu_baseline:
+        if pupil_last is not None:
             res["cpu_baseline"] = cpu_baseline(lens, points_all, pupil_last)
     else:
         res = None
-    if gather_default and "SDIRT_GATHER_ALGO" not in os.environ and os.environ.get("SDIRT_GATHER_TRIAL", "1") == "1":
+    if gather_default and args.full and "SDIRT_GATHER_ALGO" not in os.environ and \
+            os.environ.get("SDIRT_GATHER_TRIAL", "1") == "1":
         gather_algo_trial(loop, args.steps, dt, res, n_total * SPP * args.steps)
     if rank == 0:
         emit_line(res)

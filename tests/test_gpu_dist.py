@@ -127,7 +127,7 @@ def test_bench_starts_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--workload", "c3", "--sustain-seconds", "0"],
+                        "--warmup", "1", "--workload", "c3", "--sustain-seconds", "0", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -147,7 +147,7 @@ def test_bench_config3_with_eight_ranks_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2",
-                        "--warmup", "1", "--workload", "c3", "--sustain-seconds", "0"],
+                        "--warmup", "1", "--workload", "c3", "--sustain-seconds", "0", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -173,7 +173,7 @@ def test_bench_strong_scaling_config2_with_eight_ranks_on_one_gpu(algo, tmp_path
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--sustain-seconds", "0", "--detail-file", str(tmp_path / "detail.json")],
+                        "--sustain-seconds", "0", "--full", "--detail-file", str(tmp_path / "detail.json")],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -211,7 +211,7 @@ def test_bench_gather_trial_and_its_deadline(fake, tmp_path):
         env.update(SDIRT_BENCH_FAKE_TRIAL=fake, SDIRT_BENCH_TRIAL_DEADLINE_S="8")
     t0 = time.time()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                        "--workload", "c3", "--sustain-seconds", "0", "--detail-file", str(tmp_path / "detail.json")],
+                        "--workload", "c3", "--sustain-seconds", "0", "--full", "--detail-file", str(tmp_path / "detail.json")],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
