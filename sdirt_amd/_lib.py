@@ -4,8 +4,11 @@ The library is the product: there is NO CPU fallback.  If the shared object is
 missing, `lib()` raises SdirtError telling how to build it; if no MI355X is
 visible, the first device call fails with the HIP error text.
 """
+import collections
 import ctypes as C
 import os
+
+import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SDIRT_AMD_LIB overrides the path (kernel-variant A/B runs in tools/kbench.py only)
@@ -29,6 +32,29 @@ PSF_DETERMINISTIC = 256
 CTL_STATUS, CTL_ANY_VALID, CTL_TRIPS2, CTL_MASKS, CTL_WORDS = 0, 1, 16, 64, 320
 CTL_LANES = 1411
 CTL_TAG = 2
+
+CtlBlock = collections.namedtuple("CtlBlock", "status any_valid masks trips2")
+
+
+def decode_ctl(words, K, one_round=False):
+    """The control block of a device-verified psf call (its CTL_WORDS int32 words as the library leaves them) on a lens
+    of K surfaces -> CtlBlock:
+      status     0: the speculated trip tables were the reference's for the batch; else the device derived new ones
+      any_valid  1 when some sampled ray was valid
+      masks      [primary, chief-ray] convergence masks (K words each) of every round that ran: round 1, and round 2
+                 when status != 0 unless the call ran one round only (SDIRT_PSF_ONE_ROUND)
+      trips2     status != 0: the [primary, chief-ray] trip tables (int32 [K]) the device derived from round 1's masks,
+                 packed as int8 at CTL_TRIPS2 (16 words per pass); None when status == 0"""
+    w = np.asarray(words).astype(np.uint32)                  # a copy: the caller's buffer may be reused at once
+    status = int(w[CTL_STATUS])
+    rows = [w[CTL_MASKS + 64 * r:CTL_MASKS + 64 * r + K] for r in range(4 if status and not one_round else 2)]
+    trips2 = None
+    if status:
+        # little-endian bytes of the words: table entry k is byte k
+        packed = w[CTL_TRIPS2:CTL_TRIPS2 + 32].astype("<u4").view(np.int8).reshape(2, 64)[:, :K].astype(np.int32)
+        trips2 = [packed[0], packed[1]]
+    return CtlBlock(status, int(w[CTL_ANY_VALID]), [rows[i:i + 2] for i in range(0, len(rows), 2)], trips2)
+
 
 KIND_PLANE, KIND_SPHERE, KIND_ASPHERE = 0, 1, 2
 

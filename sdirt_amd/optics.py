@@ -14,7 +14,7 @@ libsdirt_dp.so is not built or no MI355X is visible.
 """
 import ctypes as C
 import json
-
+import types
 import weakref
 
 import numpy as np
@@ -87,19 +87,40 @@ class PendingPSF:
         return self._result
 
 
+class _PsfCall(types.SimpleNamespace):
+    """One psf_lr call after its set-up (Lensgroup._psf_request): what every launch of it takes, and the stream it was
+    enqueued on -- every later round of the call runs there, whatever stream is current when the call is settled."""
+
+    def result(self):
+        return _epilogue(self.L, self.R, self.want_r, self.single_point)
+
+
+def _epilogue(L, R, want_r, single_point):
+    """(L, R) as psf_lr returns them: R all zero when a right grid is wanted but none was rendered (the reference's
+    default param_list, monte_carlo.py:231), a single point's grids without the batch axis."""
+    if R is None and want_r:
+        R = torch.zeros_like(L)
+    if single_point:
+        L, R = L.squeeze(0), (R.squeeze(0) if R is not None else None)
+    return L, R
+
+
+def _parse_param_list(param_list):
+    """psf_diff's param_list = (h, f, w, r, direct) -> (dual-pixel parameters or None, whether the right grid is wanted)."""
+    if param_list is None:
+        return None, False
+    h, f, w, r, direct = param_list
+    return (h, f, w, r), direct != "l"
+
+
+def _c_trips(t):
+    """A trip table as the int32 array the library takes."""
+    t = np.asarray(t, np.int32)
+    return (C.c_int32 * t.size)(*t.tolist())
+
+
 class Lensgroup:
     """optics.py:22-116.  `device` must be a CUDA (ROCm) device for anything that traces."""
-
-    #: psf_lr(defer=True) of the fitting shape (few points, many samples) through ONE library call (sdirt_psf_call, as the
-    #: synchronous call) instead of the general path's separate launches.  Alone it is the faster producer -- 0.25 against
-    #: 0.30 ms per 64 x 20000 batch with two in flight, 0.18 against 0.27 ms of host work (tools/psf_defer_ab.py).  Beside
-    #: the fitting loop's hipGraph it is bimodal (tools/fit_ab.py, six fresh train_psfnet calls per setting): 0.73 ms per
-    #: iteration against the general path's 0.79 in most calls, 1.03-1.09 in the others -- and in three runs out of three
-    #: inside bench.py's process -- when the PSF batches and the step end up serialised (a batch's workgroups are one
-    #: generation that fills every wave slot of the chip; the general path's separate launches leave the gaps the step's
-    #: small kernels slip through).  Off by default: train_psfnet, the caller of defer=True, keeps the path whose worst case
-    #: is the better one; a pure data generator may switch it on.
-    defer_one_call = False
 
     def __init__(self, filename=None, sensor_res=(1024, 1024), use_roc=False,
                  post_computation=True, device=None):
@@ -205,7 +226,7 @@ class Lensgroup:
 
     # nn.Module-style switches: the reference's Lensgroup / PSFNet inherit them from DeepObj(nn.Module)
     # (basics.py:165-213) and its scripts call them (dfdp/factory.py:15,31-32: lens.to(device), lens.eval())
-    _DEVICE_CACHES = ("_stage_ring", "_sample_stream", "_readback_stream", "_ctl_pools", "_p2o_cache", "_ctl_host", "_ctl_host_ring",
+    _DEVICE_CACHES = ("_stage_ring", "_sample_stream", "_readback_stream", "_ctl_pools", "_p2o_cache", "_ctl_host",
                       "_right_streak", "_n_cus", "_pinned_out")
 
     def train(self, mode=True):
@@ -476,9 +497,7 @@ class Lensgroup:
         # (they run beside the previous call's kernel instead of behind it) and the caller's
         # stream waits for their event.
         main = torch.cuda.current_stream(self.device)
-        side = self.__dict__.get("_sample_stream")
-        if side is None:
-            side = self.__dict__["_sample_stream"] = torch.cuda.Stream(self.device)
+        side = self._side_stream("_sample_stream")
         with torch.cuda.stream(side):
             stage, done = self._staging(spp)
             _hostrng.rand_into(stage[0])
@@ -776,14 +795,10 @@ class Lensgroup:
                  param_list=None, _defer=False):
         """optics.py:934-996: normalised points [N,3] (or [3]) -> max-normalised
         PSF [N,ks,ks] (or [ks,ks]) of the left sub-pixel (right if param_list[4] != 'l')."""
-        dp, direct = None, "l"
-        if param_list is not None:
-            h, f, w, r, direct = param_list
-            dp = (h, f, w, r)
-        res = self.psf_lr(points, ks=ks, wvln=wvln, spp=spp, center=center, dp=dp,
-                          want_r=(param_list is not None and direct != "l"),
+        dp, right = _parse_param_list(param_list)
+        res = self.psf_lr(points, ks=ks, wvln=wvln, spp=spp, center=center, dp=dp, want_r=right,
                           _default_r_zero=(param_list is None), defer=_defer)
-        pick = (lambda lr: lr[0]) if direct == "l" else (lambda lr: lr[1])
+        pick = (lambda lr: lr[1]) if right else (lambda lr: lr[0])
         if _defer:
             return PendingPSF(lambda: pick(res.wait()))
         return pick(res)
@@ -823,6 +838,17 @@ class Lensgroup:
                 and tuple(center_out.shape) == (N, 2)):
             raise ValueError("center_out must be a contiguous float32 CUDA [N, 2] tensor")
         return center_out
+
+    def _on_device(self, v):
+        """Explicit pupil sample points (tensor or array, on any device) -> contiguous float32 on the lens's device."""
+        return torch.as_tensor(v).to(self.device, torch.float32).contiguous()
+
+    def _pinhole_centres(self, points, cen):
+        """cen[:] = the pinhole image points of the normalised `points` (optics.py:973-975): the centres of center=False."""
+        pts = points.to(self.device, torch.float32)
+        cen[:, 0] = pts[:, 0] * (self.sensor_size[1] / 2)
+        cen[:, 1] = pts[:, 1] * (self.sensor_size[0] / 2)
+        return cen
 
     def _psf_buffers(self, out, N, ks, need_r):
         """(L, R) [N, ks, ks] of a psf call: the caller's `out` pair (checked) or fresh tensors; R is None when
@@ -872,7 +898,8 @@ class Lensgroup:
         and return a `PendingPSF` at once; its `.wait()` reads the convergence masks back,
         verifies them (re-launching in the rare case the speculation was wrong) and returns
         (L, R).  A caller that renders batch after batch keeps one call in flight -- the GPU
-        starts batch i+1 while the host checks batch i -- without giving up the check."""
+        starts batch i+1 while the host checks batch i -- without giving up the check.  Every
+        round of a call runs on the stream that was current when it was enqueued."""
         self._require_gpu()
         if not torch.is_tensor(points):
             points = torch.tensor(points)
@@ -882,8 +909,8 @@ class Lensgroup:
         N = points.shape[0]
         if torch.is_tensor(out) and (dp is None or _default_r_zero or not want_r):
             raise ValueError("out=[N, 2, ks, ks] holds a left AND a right grid per point: needs dp and want_r")
-        if N == 0 and not (self.mask_reduce is not None and center
-                           and self.trip_policy == "reference"):
+        reference = self.trip_policy == "reference"
+        if N == 0 and not (self.mask_reduce is not None and center and reference):
             # empty batch: nothing to trace, no random numbers drawn
             e = torch.empty((0, ks, ks), dtype=torch.float32, device=self.device)
             res = (e, (e.clone() if want_r else None))
@@ -891,229 +918,239 @@ class Lensgroup:
         # (an empty SHARD of a multi-rank call goes on: its rank must enter the same mask
         # reductions and take the same re-launch decisions as its peers, with nothing to launch)
         po = self._points_to_object(points) if N else torch.empty((0, 3), device=self.device)
-        # RNG order of the reference: primary pupil samples first (optics.py:963),
-        # then the chief-ray samples inside psf_center (optics.py:969).
-        pupilz, pupilr = self.entrance_pupil()
         if ks > _lib.MAX_KS:
             # a point's two grids no longer fit in LDS (draw_mtf: ks 256): the staged chain
             if defer or torch.is_tensor(out):
                 raise ValueError(f"defer=True / out=[N, 2, ks, ks] need ks <= {_lib.MAX_KS}")
             return self._psf_lr_staged(points, po, N, ks, wvln, spp, center, dp, normalize, want_r,
                                        _default_r_zero, pupil_xy, center_pupil_xy, out, center_out, single_point)
-        if (center and pupil_xy is None and center_pupil_xy is None and N > 0 and (not defer or self.defer_one_call)
-                and self.trip_policy == "reference" and self.mask_reduce is None and self.pupil_mapping == "device"
-                and self.kernel_events is None and self._spp_slices(N, spp) > 1):
-            # the fitting shape (few points, many samples): launch-latency-bound, so everything between the random
-            # draw and the check of what the device did is ONE library call -- followed by a stream synchronisation
-            # (the synchronous call) or by a PendingPSF that waits for the call's own event (defer=True: the fitting
-            # loop keeps two batches in flight; ~0.1 ms of host work per batch instead of ~0.4 through the general path)
-            return self._psf_call_one(points, po, N, ks, wvln, spp, dp, normalize, want_r, _default_r_zero, out,
-                                      center_out, single_point, defer=defer)
-        both_drawn = None
-        if pupil_xy is None and center and center_pupil_xy is None:
-            # both sample sets of the call in one draw / upload (same numbers, same order)
-            both_drawn = self._pupil_samples_pair(spp, pupilr, GEO_SPP, self.entrance_pupil(shrink_pupil=True)[1],
-                                                  side_stream=defer)
-            x2, y2 = both_drawn[:2]
-        elif pupil_xy is None:
-            x2, y2 = self._pupil_samples(spp, pupilr)
-        else:
-            x2, y2 = [torch.as_tensor(v).to(self.device, torch.float32).contiguous()
-                      for v in pupil_xy]
-            spp = x2.shape[0]
-        cen = self._centre_buffer(center_out, N)
+        if defer and not center:
+            raise ValueError("defer=True needs center=True")
+        call = self._psf_request(po, ks, wvln, center, dp, normalize, want_r, _default_r_zero, out, center_out,
+                                 single_point)
+        if (center and pupil_xy is None and center_pupil_xy is None and N > 0 and not defer and reference
+                and self.mask_reduce is None and self.pupil_mapping == "device" and self.kernel_events is None
+                and self._spp_slices(N, spp) > 1):
+            return self._psf_call_one(call, spp)
+        self._draw_pupil_points(call, points, spp, center, pupil_xy, center_pupil_xy, side_stream=defer)
+        if not center:
+            return self._psf_uncentred(call)
+        if not reference:
+            return self._psf_fixed(call, defer)
+        if self.mask_reduce is None and N > 0 and self._spp_slices(N, call.spp) > 1:
+            return self._psf_device_verified(call, defer)
+        return self._psf_host_verified(call, defer)
+
+    def _psf_request(self, po, ks, wvln, center, dp, normalize, want_r, default_r_zero, out, center_out, single_point):
+        """What every launch of a psf_lr call takes, but its pupil points: output and centre buffers, dual-pixel
+        parameters, flags, lens handles (the chief-ray pass always through the green lens, optics.py:900), trip-table
+        keys and the caller's current stream (`st`: as the library's stream argument)."""
+        N = po.shape[0]
+        L, R = self._psf_buffers(out, N, ks, want_r and not default_r_zero)
+        dpp = None if (dp is None or default_r_zero) else _lib.DpParams(*[float(v) for v in dp])
+        wkey = round(float(wvln if wvln < 10 else wvln * 1e-3), 6)
+        stream = torch.cuda.current_stream(self.device)
+        return _PsfCall(N=N, ks=ks, po=po, L=L, R=R, cen=self._centre_buffer(center_out, N), want_r=want_r,
+                        single_point=single_point, dp=C.byref(dpp) if dpp is not None else None,
+                        flags=(_lib.PSF_NORMALIZE if normalize else 0) | self._psf_flags()
+                        | (_lib.PSF_INTERLEAVED if torch.is_tensor(out) else 0),
+                        handle=self.dev_lens(wvln), handle_c=self.dev_lens(DEFAULT_WAVE) if center else None,
+                        pupilz=self.entrance_pupil()[0], keys=[("psf", wkey, self.precision), ("center", self.precision)],
+                        stream=stream, st=_lib.StreamArg(stream.cuda_stream, self.device.index))
+
+    def _draw_pupil_points(self, call, points, spp, center, pupil_xy, center_pupil_xy, side_stream):
+        """The call's pupil sample points -- the explicit ones, or drawn in the reference's order: primary samples first
+        (optics.py:963), then the chief-ray samples of psf_center (optics.py:969), both sets in one draw and upload when
+        both are drawn -- and, with center=False, its centres: the pinhole image points."""
+        pupilr, pupilr_c = self.entrance_pupil()[1], self.entrance_pupil(shrink_pupil=True)[1]
         xc = yc = None
-        if center:
-            _, pupilr_c = self.entrance_pupil(shrink_pupil=True)
-            if both_drawn is not None:
-                xc, yc = both_drawn[2:]
-            elif center_pupil_xy is None:
-                xc, yc = self._pupil_samples(GEO_SPP, pupilr_c)
-            else:
-                xc, yc = [torch.as_tensor(v).to(self.device, torch.float32).contiguous()
-                          for v in center_pupil_xy]
+        if pupil_xy is None and center and center_pupil_xy is None:
+            x2, y2, xc, yc = self._pupil_samples_pair(spp, pupilr, GEO_SPP, pupilr_c, side_stream=side_stream)
         else:
-            pts = points.to(self.device, torch.float32)
-            cen[:, 0] = pts[:, 0] * (self.sensor_size[1] / 2)      # optics.py:973-975
-            cen[:, 1] = pts[:, 1] * (self.sensor_size[0] / 2)
+            x2, y2 = self._pupil_samples(spp, pupilr) if pupil_xy is None else map(self._on_device, pupil_xy)
+            if center:
+                xc, yc = (self._pupil_samples(GEO_SPP, pupilr_c) if center_pupil_xy is None
+                          else map(self._on_device, center_pupil_xy))
+        if not center:
+            self._pinhole_centres(points, call.cen)
+        call.x2, call.y2, call.xc, call.yc, call.spp = x2, y2, xc, yc, x2.shape[0]
         #: the pupil sample points of the most recent psf_lr call (x2, y2, xc, yc), device tensors
         self.last_pupil_points = (x2, y2, xc, yc)
-        need_r = want_r and not _default_r_zero
-        L, R = self._psf_buffers(out, N, ks, need_r)
-        dpp = None if (dp is None or _default_r_zero) else _lib.DpParams(*[float(v) for v in dp])
-        dp_ref = C.byref(dpp) if dpp is not None else None
-        handle = self.dev_lens(wvln)
-        flags = (_lib.PSF_NORMALIZE if normalize else 0) | self._psf_flags() \
-            | (_lib.PSF_INTERLEAVED if torch.is_tensor(out) else 0)
-        wkey = round(float(wvln if wvln < 10 else wvln * 1e-3), 6)
-        K = len(self.surfaces)
-        if center:
-            # chief-ray pass (always through the green lens, optics.py:900) and primary pass in
-            # one C call -- one kernel launch when a workgroup owns a point -- and ONE
-            # verification round for both trip tables
-            handle_c = self.dev_lens(DEFAULT_WAVE)
-            MS = _lib.MAX_SURFACES
-            # one control block: [primary masks | chief-ray masks | any-valid flag] -> one readback
-            reference = self.trip_policy == "reference"
-            verified = (reference and self.mask_reduce is None and N > 0
-                        and self._spp_slices(N, spp) > 1)
-            ctl = None if verified else self._zeroed_control_block(2 * MS + 1)
 
-            def enqueue2(tp, tc):
-                if N == 0:
-                    return
-                masks, anyv = ctl[:2 * MS].view(2, MS), ctl[2 * MS:]
-                with self._timed("psf_lr_centered"):
-                    _lib.check(_lib.lib().sdirt_psf_lr_centered(
-                        handle, handle_c, dptr(po), N, dptr(x2), dptr(y2), spp, dptr(xc), dptr(yc),
-                        xc.shape[0], float(pupilz), float(self.d_sensor), float(self.pixel_size), ks,
-                        dp_ref, (C.c_int32 * K)(*[int(t) for t in tp]),
-                        (C.c_int32 * K)(*[int(t) for t in tc]), flags, dptr(cen), dptr(anyv),
-                        dptr(L), dptr(R), dptr(masks[0]) if reference else None,
-                        dptr(masks[1]) if reference else None, stream_ptr(self.device)))
+    def _psf_call_one(self, call, spp):
+        """The fitting shape (few points, many samples: launch-latency-bound) through ONE library call, sdirt_psf_call:
+        the host draws the 2 spp + 2 x 2048 uniforms (one torch.rand, the reference's order) into page-locked memory; the
+        call enqueues their upload, the two pupil mappings, both rounds of the device-verified render and the copy of
+        the control block into the lens's page-locked mirror; the host waits for it and checks what the device did.
+        Same results as the general path."""
+        h, K, Sc = _lib.lib(), len(self.surfaces), GEO_SPP
+        # a long streak of right bets (a caller rendering the same batch again and again): the correction
+        # round is not even enqueued -- if the device's check fails after all, the host launches it (_settle)
+        if self.__dict__.get("_right_streak", 0) >= 32:
+            call.flags |= _lib.PSF_ONE_ROUND
+        tables = [self.trips.initial(k, self._curved()) for k in call.keys]
+        n = 2 * (spp + Sc)
+        words = int(h.sdirt_psf_call_scratch_bytes(call.N, spp, Sc) // 4)
+        scratch = self._zeroed_control_block(words)
+        hbuf = self._ctl_mirror()
+        stage, uploaded = self._staging(n, rows=1)
+        _hostrng.rand_into(stage[0])                         # the reference's four draws, in one (see _pupil_samples_pair)
+        _lib.check(h.sdirt_psf_call(
+            call.handle, call.handle_c, dptr(call.po), call.N, C.c_void_p(stage.data_ptr()), spp, Sc,
+            float(self.entrance_pupil()[1]), float(self.entrance_pupil(shrink_pupil=True)[1]), float(call.pupilz),
+            float(self.d_sensor), float(self.pixel_size), call.ks, call.dp, _c_trips(tables[0]), _c_trips(tables[1]),
+            call.flags, dptr(call.cen), dptr(call.L), dptr(call.R), dptr(scratch), C.c_void_p(hbuf.data_ptr()),
+            call.st))
+        uploaded.record(call.stream)
+        done = torch.cuda.Event()
+        done.record(call.stream)
+        done.synchronize()
+        # the pupil points the device mapped: behind the control block and the partial sums in `scratch`
+        xy = scratch[words - n:].view(torch.float32)
+        call.x2, call.y2, call.xc, call.yc = xy[:spp], xy[spp:2 * spp], xy[2 * spp:2 * spp + Sc], xy[2 * spp + Sc:]
+        call.spp = spp
+        self.last_pupil_points = (call.x2, call.y2, call.xc, call.yc)
+        ctl = _lib.decode_ctl(hbuf.numpy(), K, one_round=bool(call.flags & _lib.PSF_ONE_ROUND))
+        self.__dict__["_right_streak"] = self.__dict__.get("_right_streak", 0) + 1 if ctl.status == 0 else 0
+        return self._settle_ctl(call, tables, ctl)
 
-            def squeeze(L_, R_):
-                if R_ is None and want_r:
-                    R_ = torch.zeros_like(L_)
-                if single_point:
-                    L_ = L_.squeeze(0)
-                    R_ = R_.squeeze(0) if R_ is not None else None
-                return L_, R_
+    def _psf_device_verified(self, call, defer):
+        """Few points, many samples (several workgroups per point): speculate, verify ON THE DEVICE, re-render once
+        behind it -- no host round trip when the bet on the trip tables was wrong (sdirt_psf_lr_verified).  The control
+        block is copied into the lens's page-locked mirror and the stream waited for, or (defer=True) copied on the
+        read-back stream and checked in .wait()."""
+        words = _lib.lib().sdirt_psf_verified_scratch_bytes(call.N, call.xc.shape[0]) // 4
+        scratch = self._zeroed_control_block(int(words))
+        tables = [self.trips.initial(k, self._curved()) for k in call.keys]
+        with self._timed("psf_lr_verified"):
+            _lib.check(_lib.lib().sdirt_psf_lr_verified(
+                call.handle, call.handle_c, dptr(call.po), call.N, dptr(call.x2), dptr(call.y2), call.spp,
+                dptr(call.xc), dptr(call.yc), call.xc.shape[0], float(call.pupilz), float(self.d_sensor),
+                float(self.pixel_size), call.ks, call.dp, _c_trips(tables[0]), _c_trips(tables[1]), call.flags,
+                dptr(call.cen), dptr(call.L), dptr(call.R), dptr(scratch), call.st))
+        if defer:
+            host, done = self._readback(scratch, _lib.CTL_WORDS)
 
-            if reference:
-                keys = [("psf", wkey, self.precision), ("center", self.precision)]
-                keep = (po, x2, y2, xc, yc, cen)              # alive until the kernel has run
+            def finish():
+                done.synchronize()
+                return self._settle_ctl(call, tables, _lib.decode_ctl(host.numpy(), len(self.surfaces)))
+            return PendingPSF(finish)
+        hbuf = self._ctl_mirror()
+        hbuf.copy_(scratch[:_lib.CTL_WORDS], non_blocking=True)
+        call.stream.synchronize()
+        return self._settle_ctl(call, tables, _lib.decode_ctl(hbuf.numpy(), len(self.surfaces)))
 
-                def enqueue_round(tables, again=True, reduce=True):
-                    nonlocal ctl
-                    if again:                                  # a re-launch: a fresh zeroed block
-                        ctl = self._zeroed_control_block(2 * MS + 1)
-                    enqueue2(tables[0], tables[1])
-                    if reduce and self.mask_reduce is not None:
-                        # masks AND the any-valid flag, OR-ed over ranks: every rank verifies the
-                        # same block, so all of them re-launch -- or raise -- together
-                        ctl.copy_(self.mask_reduce(ctl))
+    def _psf_host_verified(self, call, defer):
+        """Every round read back and checked by the host (one workgroup per point, or a mask reduction over ranks).
+        defer=True: the first round's control block -- OR-ed over the ranks, if a reduction is installed -- is copied
+        on the read-back stream and checked in .wait()."""
+        if not defer:
+            return self._settle(call, [])
+        n = 2 * _lib.MAX_SURFACES + 1
+        tables = [self.trips.initial(k, self._curved()) for k in call.keys]
+        ctl = self._zeroed_control_block(n)
+        self._enqueue_centred(call, tables, ctl)
+        host, done = self._readback(ctl, n, reduce=self.mask_reduce)
 
-                def read_masks(host):
-                    m = host[:2 * MS].reshape(2, MS)[:, :K].astype(np.int64) & 0xFFFFFFFF
-                    return [m[0], m[1]]
+        def finish():
+            done.synchronize()
+            masks, any_valid = self._round_result(host.numpy())
+            return self._settle(call, [(tables, masks)], any_valid)
+        return PendingPSF(finish)
 
-                def launch(tables):
-                    enqueue_round(tables)
-                    host = ctl.cpu().numpy()
-                    launch.any_valid = int(host[2 * MS])
-                    return read_masks(host)
+    def _psf_fixed(self, call, defer):
+        """trip_policy 'max' / 'adaptive': one launch with the fixed trip table, nothing to check."""
+        full = self._fixed_trips()
+        self._enqueue_centred(call, (full, full), self._zeroed_control_block(2 * _lib.MAX_SURFACES + 1), masks=False)
+        res = call.result()
+        return PendingPSF(lambda: res) if defer else res
 
-                def readback(block, n_words, reduce=None):
-                    """Asynchronous copy of the first n_words of a control block into page-locked
-                    memory on the read-back stream (on the caller's it would sit between this call's
-                    kernels and the next call's); -> (host tensor, event).  reduce: the mask reduction
-                    over ranks (a collective), issued on the read-back stream as well -- the caller's
-                    stream goes straight on to the next call's kernel instead of waiting for it."""
-                    main = torch.cuda.current_stream(self.device)
-                    rb = self._side_stream("_readback_stream")
-                    rb.wait_stream(main)
-                    host = torch.empty(n_words, dtype=block.dtype, pin_memory=True)
-                    with torch.cuda.stream(rb):
-                        src = block if reduce is None else reduce(block)
-                        host.copy_(src[:n_words], non_blocking=True)
-                    block.record_stream(rb)
-                    done = torch.cuda.Event()
-                    done.record(rb)
-                    return host, done
+    def _psf_uncentred(self, call):
+        """center=False: the primary pass alone (sdirt_psf_lr), centred on the pinhole image points."""
+        def enqueue(trips, mask_ptr):
+            with self._timed("psf_lr"):
+                _lib.check(_lib.lib().sdirt_psf_lr(
+                    call.handle, dptr(call.po), call.N, dptr(call.x2), dptr(call.y2), call.spp, float(call.pupilz),
+                    float(self.d_sensor), float(self.pixel_size), call.ks, dptr(call.cen), call.dp, trips, call.flags,
+                    dptr(call.L), dptr(call.R), mask_ptr, call.st))
+        self._run_with_trips(call.keys[0], range(len(self.surfaces)), enqueue)
+        return call.result()
 
-                if verified:
-                    # few points, many samples (the PSFNet fitting loop): several workgroups per point.
-                    # Speculate, verify ON THE DEVICE, re-render once behind it -- no host round trip
-                    # when the bet on the trip tables was wrong (sdirt_psf_lr_verified).
-                    W_ = _lib.CTL_WORDS
-                    words = _lib.lib().sdirt_psf_verified_scratch_bytes(N, xc.shape[0]) // 4
-                    scratch = self._zeroed_control_block(int(words))
-                    tables = [self.trips.initial(k, self._curved()) for k in keys]
-                    with self._timed("psf_lr_verified"):
-                        _lib.check(_lib.lib().sdirt_psf_lr_verified(
-                            handle, handle_c, dptr(po), N, dptr(x2), dptr(y2), spp, dptr(xc), dptr(yc),
-                            xc.shape[0], float(pupilz), float(self.d_sensor), float(self.pixel_size), ks, dp_ref,
-                            (C.c_int32 * K)(*[int(t) for t in tables[0]]),
-                            (C.c_int32 * K)(*[int(t) for t in tables[1]]), flags, dptr(cen), dptr(L), dptr(R),
-                            dptr(scratch), stream_ptr(self.device)))
+    def _enqueue_centred(self, call, tables, ctl, masks=True):
+        """sdirt_psf_lr_centered of `call` on the call's stream: chief-ray pass and primary pass in one C call -- one
+        kernel launch when a workgroup owns a point -- with the trip tables (primary, chief-ray), OR-ing into the zeroed
+        control block ctl = [primary masks | chief-ray masks | any-valid] (masks=False: into the any-valid word only)."""
+        if call.N == 0:
+            return
+        MS = _lib.MAX_SURFACES
+        with self._timed("psf_lr_centered"):
+            _lib.check(_lib.lib().sdirt_psf_lr_centered(
+                call.handle, call.handle_c, dptr(call.po), call.N, dptr(call.x2), dptr(call.y2), call.spp,
+                dptr(call.xc), dptr(call.yc), call.xc.shape[0], float(call.pupilz), float(self.d_sensor),
+                float(self.pixel_size), call.ks, call.dp, _c_trips(tables[0]), _c_trips(tables[1]), call.flags,
+                dptr(call.cen), dptr(ctl[2 * MS:]), dptr(call.L), dptr(call.R), dptr(ctl[:MS]) if masks else None,
+                dptr(ctl[MS:2 * MS]) if masks else None, call.st))
 
-                    def settle(h):
-                        h = h.astype(np.int64) & 0xFFFFFFFF
-                        launch.any_valid = int(h[_lib.CTL_ANY_VALID])
-                        rounds = [(tables, [h[_lib.CTL_MASKS:_lib.CTL_MASKS + K],
-                                            h[_lib.CTL_MASKS + 64:_lib.CTL_MASKS + 64 + K]])]
-                        if h[_lib.CTL_STATUS]:
-                            unpack = lambda w: np.array([((int(w[k >> 2]) >> ((k & 3) * 8)) & 0xFF) for k in range(K)],
-                                                        np.int32).astype(np.int8).astype(np.int32)
-                            t2 = [unpack(h[_lib.CTL_TRIPS2:_lib.CTL_TRIPS2 + 16]),
-                                  unpack(h[_lib.CTL_TRIPS2 + 16:_lib.CTL_TRIPS2 + 32])]
-                            rounds.append((t2, [h[_lib.CTL_MASKS + 128:_lib.CTL_MASKS + 128 + K],
-                                                h[_lib.CTL_MASKS + 192:_lib.CTL_MASKS + 192 + K]]))
-                        self.trips.run_many(keys, self._curved(), list(range(K)), launch, done=rounds)
-                        assert launch.any_valid == 1, "No sampled rays is valid."   # optics.py:902
-                        return squeeze(L, R) if keep else None
+    def _centred_round(self, call, tables):
+        """One host-driven round of a centred call, on the stream the call was enqueued on: the launch into a fresh
+        zeroed control block from that stream's pool, the block OR-ed over the ranks when a mask reduction is installed
+        (every rank verifies the same block, so all of them re-launch -- or raise -- together), read back.
+        -> ([primary, chief-ray] masks, any-valid)."""
+        with torch.cuda.stream(call.stream):
+            ctl = self._zeroed_control_block(2 * _lib.MAX_SURFACES + 1)
+            self._enqueue_centred(call, tables, ctl)
+            if self.mask_reduce is not None:
+                ctl.copy_(self.mask_reduce(ctl))
+            return self._round_result(ctl.cpu().numpy())
 
-                    if defer:
-                        host, done = readback(scratch, W_)
+    def _round_result(self, host):
+        """A host-driven round's control block on the host -> ([primary, chief-ray] masks, any-valid)."""
+        MS = _lib.MAX_SURFACES
+        m = host[:2 * MS].reshape(2, MS)[:, :len(self.surfaces)].astype(np.int64) & 0xFFFFFFFF
+        return [m[0], m[1]], int(host[2 * MS])
 
-                        def finish_v():
-                            done.synchronize()
-                            return settle(host.numpy())
-                        return PendingPSF(finish_v)
-                    # synchronous form: into a page-locked buffer kept on the lens, then wait for the stream
-                    hbuf = self.__dict__.get("_ctl_host")
-                    if hbuf is None:
-                        hbuf = self.__dict__["_ctl_host"] = torch.empty(W_, dtype=torch.int32, pin_memory=True)
-                    hbuf.copy_(scratch[:W_], non_blocking=True)
-                    torch.cuda.current_stream(self.device).synchronize()
-                    return settle(hbuf.numpy().copy())
+    def _settle_ctl(self, call, tables, ctl):
+        """What a device-verified call did (_lib.decode_ctl): round 1 with `tables`, round 2 -- if it ran -- with the
+        device's own correction; checked, and corrected further by the host if need be.  -> (L, R)."""
+        rounds = [(tables, ctl.masks[0])] + [(ctl.trips2, m) for m in ctl.masks[1:]]
+        return self._settle(call, rounds, ctl.any_valid)
 
-                if defer:
-                    tables = [self.trips.initial(k, self._curved()) for k in keys]
-                    enqueue_round(tables, again=False, reduce=False)
-                    host, done = readback(ctl, 2 * MS + 1, reduce=self.mask_reduce)
+    def _settle(self, call, rounds, any_valid=None):
+        """Check the rounds a centred call has run -- [(tables, masks)]; none yet for the synchronous host-verified call
+        -- with the reference's rule, and run host-driven rounds until it accepts (TripPlanner.run_many).  -> (L, R)."""
+        state = [any_valid]
 
-                    def finish():
-                        done.synchronize()
-                        h = host.numpy()
-                        launch.any_valid = int(h[2 * MS])
-                        self.trips.run_many(keys, self._curved(), list(range(K)), launch,
-                                            first=(tables, read_masks(h)))
-                        assert launch.any_valid == 1, "No sampled rays is valid."   # optics.py:902
-                        return squeeze(L, R) if keep else None
-                    return PendingPSF(finish)
-                first_round = [True]
+        def launch(tables):
+            masks, state[0] = self._centred_round(call, tables)
+            return masks
+        self.trips.run_many(call.keys, self._curved(), list(range(len(self.surfaces))), launch, done=rounds)
+        assert state[0] == 1, "No sampled rays is valid."   # optics.py:902
+        return call.result()
 
-                def launch_sync(tables):
-                    enqueue_round(tables, again=not first_round[0])
-                    first_round[0] = False
-                    host = ctl.cpu().numpy()
-                    launch.any_valid = int(host[2 * MS])
-                    return read_masks(host)
-                self.trips.run_many(keys, self._curved(), list(range(K)), launch_sync)
-                assert launch.any_valid == 1, "No sampled rays is valid."   # optics.py:902
-            else:
-                full = self._fixed_trips()
-                enqueue2(full, full)
-            if defer:
-                return PendingPSF(lambda: squeeze(L, R))
-        else:
-            if defer:
-                raise ValueError("defer=True needs center=True")
-            def enqueue(trips, mask_ptr):
-                with self._timed("psf_lr"):
-                    _lib.check(_lib.lib().sdirt_psf_lr(
-                        handle, dptr(po), N, dptr(x2), dptr(y2), spp, float(pupilz),
-                        float(self.d_sensor), float(self.pixel_size), ks, dptr(cen), dp_ref, trips,
-                        flags, dptr(L), dptr(R), mask_ptr, stream_ptr(self.device)))
-            self._run_with_trips(("psf", wkey, self.precision), range(K), enqueue)
-        if R is None and want_r:
-            R = torch.zeros_like(L)
-        if single_point:
-            L = L.squeeze(0)
-            R = R.squeeze(0) if R is not None else None
-        return L, R
+    def _readback(self, block, n_words, reduce=None):
+        """Asynchronous copy of the first n_words of a control block into page-locked memory on the read-back stream (on
+        the caller's it would sit between this call's kernels and the next call's); -> (host tensor, event).  reduce: the
+        mask reduction over ranks (a collective), issued on the read-back stream as well -- the caller's stream goes
+        straight on to the next call's kernel instead of waiting for it."""
+        main = torch.cuda.current_stream(self.device)
+        rb = self._side_stream("_readback_stream")
+        rb.wait_stream(main)
+        host = torch.empty(n_words, dtype=block.dtype, pin_memory=True)
+        with torch.cuda.stream(rb):
+            src = block if reduce is None else reduce(block)
+            host.copy_(src[:n_words], non_blocking=True)
+        block.record_stream(rb)
+        done = torch.cuda.Event()
+        done.record(rb)
+        return host, done
+
+    def _ctl_mirror(self):
+        """The lens's page-locked CTL_WORDS mirror of a control block, shared by the synchronous device-verified calls:
+        each reads it before it returns."""
+        hbuf = self.__dict__.get("_ctl_host")
+        if hbuf is None:
+            hbuf = self.__dict__["_ctl_host"] = torch.empty(_lib.CTL_WORDS, dtype=torch.int32, pin_memory=True)
+        return hbuf
 
     def _psf_lr_staged(self, points, po, N, ks, wvln, spp, center, dp, normalize, want_r, default_r_zero,
                        pupil_xy, center_pupil_xy, out, center_out, single_point):
@@ -1125,11 +1162,9 @@ class Lensgroup:
         if not 2 <= ks <= _lib.MAX_KS_STAGED:
             raise _lib.SdirtError(f"ks={ks} outside [2,{_lib.MAX_KS_STAGED}]")
         pupilz, pupilr = self.entrance_pupil()
-        if pupil_xy is None:
-            x2, y2 = self._pupil_samples(spp, pupilr)                       # optics.py:963 (first two draws)
-        else:
-            x2, y2 = [torch.as_tensor(v).to(self.device, torch.float32).contiguous() for v in pupil_xy]
-            spp = x2.shape[0]
+        # optics.py:963 (first two draws)
+        x2, y2 = self._pupil_samples(spp, pupilr) if pupil_xy is None else map(self._on_device, pupil_xy)
+        spp = x2.shape[0]
         ray = Ray.empty((spp, N), wvln, self.device)
         _lib.check(_lib.lib().sdirt_sample_rays(dptr(po), N, dptr(x2), dptr(y2), spp, float(pupilz), ray.c_rays(),
                                                 stream_ptr(self.device)))
@@ -1137,19 +1172,15 @@ class Lensgroup:
         xc = yc = None
         if center:
             pupilz_c, pupilr_c = self.entrance_pupil(shrink_pupil=True)
-            if center_pupil_xy is None:
-                xc, yc = self._pupil_samples(GEO_SPP, pupilr_c)             # optics.py:969 (draws three and four)
-            else:
-                xc, yc = [torch.as_tensor(v).to(self.device, torch.float32).contiguous() for v in center_pupil_xy]
+            # optics.py:969 (draws three and four)
+            xc, yc = (self._pupil_samples(GEO_SPP, pupilr_c) if center_pupil_xy is None
+                      else map(self._on_device, center_pupil_xy))
             self._chief_center(po, xc, yc, pupilz_c, cen)
         else:
-            pts = points.to(self.device, torch.float32)
-            cen[:, 0] = pts[:, 0] * (self.sensor_size[1] / 2)               # optics.py:973-975
-            cen[:, 1] = pts[:, 1] * (self.sensor_size[0] / 2)
+            self._pinhole_centres(points, cen)
         self.last_pupil_points = (x2, y2, xc, yc)
         self.trace(ray, forward=True, _to_sensor=self.d_sensor)        # trace2sensor, one pass
-        need_r = want_r and not default_r_zero
-        L, R = self._psf_buffers(out, N, ks, need_r)
+        L, R = self._psf_buffers(out, N, ks, want_r and not default_r_zero)
         dpp = None if (dp is None or default_r_zero) else _lib.DpParams(*[float(v) for v in dp])
         h, st = _lib.lib(), stream_ptr(self.device)
         with self._timed("forward_integral"):
@@ -1158,119 +1189,7 @@ class Lensgroup:
                                                 C.byref(dpp) if dpp is not None else None,
                                                 self._math_flags() | (_lib.PSF_NORMALIZE if normalize else 0),
                                                 dptr(L), dptr(R), st))
-        if R is None and want_r:
-            R = torch.zeros_like(L)
-        if single_point:
-            L = L.squeeze(0)
-            R = R.squeeze(0) if R is not None else None
-        return L, R
-
-    def _ctl_host_slot(self):
-        """A page-locked control-block mirror for one call in flight (ring of eight; a slot whose call has not been waited
-        for yet is settled first -- its numbers are read before anybody may overwrite them)."""
-        ring = self.__dict__.setdefault("_ctl_host_ring", {"slots": [], "next": 0})
-        if len(ring["slots"]) < 8:
-            ring["slots"].append([torch.empty(_lib.CTL_WORDS, dtype=torch.int32, pin_memory=True), None])
-            return ring["slots"][-1]
-        slot = ring["slots"][ring["next"]]
-        ring["next"] = (ring["next"] + 1) % 8
-        if slot[1] is not None:
-            slot[1].wait()
-        return slot
-
-    def _psf_call_one(self, points, po, N, ks, wvln, spp, dp, normalize, want_r, default_r_zero, out, center_out,
-                      single_point, defer=False):
-        """psf_lr(center=True) for sdirt_psf_spp_slices(N, spp) > 1 through sdirt_psf_call (defer: the check of what the
-        device did moves into the returned PendingPSF, which waits for the call's own event instead of the stream):
-        the host draws the 2 spp + 2 x 2048 uniforms (one torch.rand, the reference's order) into page-locked
-        memory; ONE library call enqueues their upload, the two pupil mappings, both rounds of the
-        device-verified render and the copy of the control block back; the host waits for the stream and
-        checks what the device did (TripPlanner.run_many(done=...)).  Same results as the general path."""
-        h, K, MS = _lib.lib(), len(self.surfaces), _lib.MAX_SURFACES
-        Sc = GEO_SPP
-        pupilz, pupilr = self.entrance_pupil()
-        pupilr_c = self.entrance_pupil(shrink_pupil=True)[1]
-        need_r = want_r and not default_r_zero
-        cen = self._centre_buffer(center_out, N)
-        L, R = self._psf_buffers(out, N, ks, need_r)
-        dpp = None if (dp is None or default_r_zero) else _lib.DpParams(*[float(v) for v in dp])
-        dp_ref = C.byref(dpp) if dpp is not None else None
-        handle, handle_c = self.dev_lens(wvln), self.dev_lens(DEFAULT_WAVE)
-        flags = (_lib.PSF_NORMALIZE if normalize else 0) | self._psf_flags() \
-            | (_lib.PSF_INTERLEAVED if torch.is_tensor(out) else 0)
-        wkey = round(float(wvln if wvln < 10 else wvln * 1e-3), 6)
-        keys = [("psf", wkey, self.precision), ("center", self.precision)]
-        curved = self._curved()
-        tables = [self.trips.initial(k, curved) for k in keys]
-        # a long streak of right bets (a caller rendering the same batch again and again): the correction
-        # round is not even enqueued -- if the device's check fails after all, the host launches it (below)
-        streak = self.__dict__.get("_right_streak", 0)
-        if streak >= 32:
-            flags |= _lib.PSF_ONE_ROUND
-        n = 2 * (spp + Sc)
-        words = int(h.sdirt_psf_call_scratch_bytes(N, spp, Sc) // 4)
-        scratch = self._zeroed_control_block(words)
-        slot = self._ctl_host_slot()
-        hbuf = slot[0]
-        stage, uploaded = self._staging(n, rows=1)
-        st = stream_ptr(self.device)
-        _hostrng.rand_into(stage[0])                         # the reference's four draws, in one (see _pupil_samples_pair)
-        _lib.check(h.sdirt_psf_call(
-            handle, handle_c, dptr(po), N, C.c_void_p(stage.data_ptr()), spp, Sc, float(pupilr), float(pupilr_c),
-            float(pupilz), float(self.d_sensor), float(self.pixel_size), ks, dp_ref,
-            (C.c_int32 * K)(*[int(t) for t in tables[0]]), (C.c_int32 * K)(*[int(t) for t in tables[1]]), flags,
-            dptr(cen), dptr(L), dptr(R), dptr(scratch), C.c_void_p(hbuf.data_ptr()), st))
-        stream = torch.cuda.current_stream(self.device)
-        uploaded.record(stream)
-        done = torch.cuda.Event()
-        done.record(stream)
-        keep = (po, scratch, stage, cen)                      # alive until the call has run
-
-        def finish():
-            done.synchronize()
-            hh = hbuf.numpy().view(np.uint32).copy()
-            slot[1] = None
-            # the pupil points the device mapped: behind the control block and the partial sums in `scratch`
-            base = words - 2 * n
-            xy = keep[1][base + n:].view(torch.float32)
-            x2, y2, xc, yc = xy[:spp], xy[spp:2 * spp], xy[2 * spp:2 * spp + Sc], xy[2 * spp + Sc:]
-            self.last_pupil_points = (x2, y2, xc, yc)
-            state = {"any": int(hh[_lib.CTL_ANY_VALID])}
-            self.__dict__["_right_streak"] = self.__dict__.get("_right_streak", 0) + 1 if hh[_lib.CTL_STATUS] == 0 else 0
-            rounds = [(tables, [hh[_lib.CTL_MASKS:_lib.CTL_MASKS + K], hh[_lib.CTL_MASKS + 64:_lib.CTL_MASKS + 64 + K]])]
-            if hh[_lib.CTL_STATUS] and not (flags & _lib.PSF_ONE_ROUND):
-                unpack = lambda w: np.array([((int(w[k >> 2]) >> ((k & 3) * 8)) & 0xFF) for k in range(K)],
-                                            np.int32).astype(np.int8).astype(np.int32)
-                rounds.append(([unpack(hh[_lib.CTL_TRIPS2:_lib.CTL_TRIPS2 + 16]),
-                                unpack(hh[_lib.CTL_TRIPS2 + 16:_lib.CTL_TRIPS2 + 32])],
-                               [hh[_lib.CTL_MASKS + 128:_lib.CTL_MASKS + 128 + K],
-                                hh[_lib.CTL_MASKS + 192:_lib.CTL_MASKS + 192 + K]]))
-
-            def launch(tabs):                                    # a further, host-driven round (rare)
-                ctl = self._zeroed_control_block(2 * MS + 1)
-                masks, anyv = ctl[:2 * MS].view(2, MS), ctl[2 * MS:]
-                _lib.check(h.sdirt_psf_lr_centered(
-                    handle, handle_c, dptr(po), N, dptr(x2), dptr(y2), spp, dptr(xc), dptr(yc), Sc, float(pupilz),
-                    float(self.d_sensor), float(self.pixel_size), ks, dp_ref, (C.c_int32 * K)(*[int(t) for t in tabs[0]]),
-                    (C.c_int32 * K)(*[int(t) for t in tabs[1]]), flags, dptr(cen), dptr(anyv), dptr(L), dptr(R),
-                    dptr(masks[0]), dptr(masks[1]), stream_ptr(self.device)))
-                host = ctl.cpu().numpy()
-                state["any"] = int(host[2 * MS])
-                m = host[:2 * MS].reshape(2, MS)[:, :K].astype(np.int64) & 0xFFFFFFFF
-                return [m[0], m[1]]
-            self.trips.run_many(keys, curved, list(range(K)), launch, done=rounds)
-            assert state["any"] == 1, "No sampled rays is valid."   # optics.py:902
-            L_, R_ = L, R
-            if R_ is None and want_r:
-                R_ = torch.zeros_like(L_)
-            if single_point:
-                L_ = L_.squeeze(0)
-                R_ = R_.squeeze(0) if R_ is not None else None
-            return L_, R_
-
-        pending = PendingPSF(finish)
-        slot[1] = pending
-        return pending if defer else pending.wait()
+        return _epilogue(L, R, want_r, single_point)
 
     def psf_rgb(self, points, ks=31, spp=GEO_SPP, center=True, param_list=None, pupil_xy=None,
                 center_pupil_xy=None):
@@ -1283,43 +1202,35 @@ class Lensgroup:
         wavelength instead of random draws (ray-level parity hand-off)."""
         if not torch.is_tensor(points):
             points = torch.tensor(points)
+        if center_pupil_xy is not None and not center:
+            raise ValueError("center=False runs no chief-ray pass")
         n_points = points.shape[0] if points.dim() == 2 else 1
-        fused = n_points > 0 and self.device.type == "cuda" and self.mask_reduce is None and ks <= _lib.MAX_KS
-        if fused and center:
-            return self._psf_rgb_fused(points, ks, spp, param_list, pupil_xy, center_pupil_xy)
-        if fused:
-            if center_pupil_xy is not None:
-                raise ValueError("center=False runs no chief-ray pass")
-            return self._psf_rgb_uncentred(points, ks, spp, param_list, pupil_xy)
-        if pupil_xy is not None or center_pupil_xy is not None:
-            # not one launch (grids above SDIRT_MAX_KS, or a rank of a sharded run): wavelength by wavelength through
-            # psf_lr, which takes the explicit points of that wavelength on every path
-            if center_pupil_xy is not None and not center:
-                raise ValueError("center=False runs no chief-ray pass")
-            dp, direct = (None, "l") if param_list is None else (tuple(param_list[:4]), param_list[4])
-            psfs = []
-            for i, w in enumerate(WAVE_RGB):
-                lr = self.psf_lr(points, ks=ks, wvln=w, spp=spp, center=center, dp=dp,
-                                 want_r=(param_list is not None and direct != "l"), _default_r_zero=(param_list is None),
-                                 pupil_xy=None if pupil_xy is None else (pupil_xy[0][i], pupil_xy[1][i]),
-                                 center_pupil_xy=None if center_pupil_xy is None else (center_pupil_xy[0][i], center_pupil_xy[1][i]))
-                psfs.append(lr[0] if direct == "l" else lr[1])
-            return torch.stack(psfs, dim=-3)
-        psfs = [self.psf_diff(points=points, wvln=w, ks=ks, spp=spp, center=center,
-                              param_list=param_list) for w in WAVE_RGB]
+        if n_points > 0 and self.device.type == "cuda" and self.mask_reduce is None and ks <= _lib.MAX_KS:
+            return self._psf_rgb_fused(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy)
+        # not one launch (grids above SDIRT_MAX_KS, or a rank of a sharded run): wavelength by wavelength through
+        # psf_lr, which takes the explicit points of that wavelength on every path
+        dp, right = _parse_param_list(param_list)
+        psfs = []
+        for i, w in enumerate(WAVE_RGB):
+            lr = self.psf_lr(points, ks=ks, wvln=w, spp=spp, center=center, dp=dp, want_r=right,
+                             _default_r_zero=(param_list is None),
+                             pupil_xy=None if pupil_xy is None else (pupil_xy[0][i], pupil_xy[1][i]),
+                             center_pupil_xy=None if center_pupil_xy is None else (center_pupil_xy[0][i], center_pupil_xy[1][i]))
+            psfs.append(lr[1] if right else lr[0])
         return torch.stack(psfs, dim=-3)
 
     @torch.no_grad()
-    def _psf_rgb_fused(self, points, ks, spp, param_list, pupil_xy=None, center_pupil_xy=None):
+    def _psf_rgb_fused(self, points, ks, spp, center, param_list, pupil_xy=None, center_pupil_xy=None):
+        """psf_rgb as one launch: three wavelength slots, one fresh primary sample set per wavelength (two random
+        vectors each, optics.py:963) and, with center=True, one chief-ray set after it (sdirt_psf_rgb_centered); with
+        center=False the PSFs centred on the pinhole image points (sdirt_psf_rgb, optics.py:972-976).  One
+        control-block readback for all the trip checks."""
         single_point = points.dim() == 1
         pts = points.reshape(-1, 3)
         N, W, K, MS = pts.shape[0], len(WAVE_RGB), len(self.surfaces), _lib.MAX_SURFACES
-        direct, dp_ref, dpp = "l", None, None
-        if param_list is not None:
-            h, f, w_, r, direct = param_list
-            dpp = _lib.DpParams(float(h), float(f), float(w_), float(r))
-            dp_ref = C.byref(dpp)
-        want_r = direct != "l"
+        dp, want_r = _parse_param_list(param_list)
+        dpp = None if dp is None else _lib.DpParams(*[float(v) for v in dp])
+        dp_ref = C.byref(dpp) if dpp is not None else None
         po = self._points_to_object(pts)
         pupilz, pupilr = self.entrance_pupil()
         _, pupilr_c = self.entrance_pupil(shrink_pupil=True)
@@ -1328,105 +1239,59 @@ class Lensgroup:
         for _ in WAVE_RGB:
             if pupil_xy is None:
                 prim.append(torch.stack(self._pupil_samples(spp, pupilr)))
-            if center_pupil_xy is None:
+            if center and center_pupil_xy is None:
                 cent.append(torch.stack(self._pupil_samples(GEO_SPP, pupilr_c)))
-        as_dev = lambda v: torch.as_tensor(v).to(self.device, torch.float32).contiguous()
-        prim = torch.stack(prim, 1).contiguous() if pupil_xy is None else as_dev(pupil_xy)              # [2, W, S]
-        cent = torch.stack(cent, 1).contiguous() if center_pupil_xy is None else as_dev(center_pupil_xy)
+        prim = torch.stack(prim, 1).contiguous() if pupil_xy is None else self._on_device(pupil_xy)     # [2, W, S]
         spp = prim.shape[2]
         handles = (C.c_void_p * W)(*[self.dev_lens(w).value for w in WAVE_RGB])
-        handle_c = self.dev_lens(DEFAULT_WAVE)                # optics.py:900: always green
-        cen = torch.empty((W, N, 2), dtype=torch.float32, device=self.device)
+        if center:
+            cent = torch.stack(cent, 1).contiguous() if center_pupil_xy is None else self._on_device(center_pupil_xy)
+            handle_c = self.dev_lens(DEFAULT_WAVE)                # optics.py:900: always green
+            cen = torch.empty((W, N, 2), dtype=torch.float32, device=self.device)
+        else:
+            one = self._pinhole_centres(pts, torch.empty((N, 2), dtype=torch.float32, device=self.device))
+            cen = one.unsqueeze(0).expand(W, N, 2).contiguous()                                      # the same for every colour
         L = torch.empty((N, W, ks, ks), dtype=torch.float32, device=self.device)
         R = torch.empty_like(L) if want_r else None
         flags = _lib.PSF_NORMALIZE | self._psf_flags()
-        # one control block: [primary masks W x MS | chief-ray masks W x MS | any-valid W]
-        ctl = torch.zeros(2 * W * MS + W, dtype=torch.int32, device=self.device)
-        masks = ctl[:2 * W * MS].view(2, W, MS)
-        anyv = ctl[2 * W * MS:]
+        # one control block: [primary masks W x MS | chief-ray masks W x MS (center=True) | any-valid W]
+        P = 2 if center else 1
+        ctl = torch.zeros(P * W * MS + W, dtype=torch.int32, device=self.device)
+        masks = ctl[:P * W * MS].view(P, W, MS)
         reference = self.trip_policy == "reference"
 
         def enqueue(tables):
-            tp = np.concatenate([np.asarray(t, np.int32) for t in tables[:W]])
-            tc = np.concatenate([np.asarray(t, np.int32) for t in tables[W:]])
+            tp = _c_trips(np.concatenate([np.asarray(t, np.int32) for t in tables[:W]]))
+            if not center:
+                with self._timed("psf_rgb"):
+                    _lib.check(_lib.lib().sdirt_psf_rgb(
+                        handles, W, dptr(po), N, dptr(prim[0]), dptr(prim[1]), spp, float(pupilz), float(self.d_sensor),
+                        float(self.pixel_size), ks, dptr(cen), dp_ref, tp, flags, dptr(L), dptr(R),
+                        dptr(masks[0]) if reference else None, stream_ptr(self.device)))
+                return
+            tc = _c_trips(np.concatenate([np.asarray(t, np.int32) for t in tables[W:]]))
             with self._timed("psf_rgb_centered"):
                 _lib.check(_lib.lib().sdirt_psf_rgb_centered(
                     handles, W, handle_c, dptr(po), N, dptr(prim[0]), dptr(prim[1]), spp,
                     dptr(cent[0]), dptr(cent[1]), GEO_SPP, float(pupilz), float(self.d_sensor),
-                    float(self.pixel_size), ks, dp_ref, (C.c_int32 * (W * K))(*tp.tolist()),
-                    (C.c_int32 * (W * K))(*tc.tolist()), flags, dptr(cen), dptr(anyv), dptr(L), dptr(R),
+                    float(self.pixel_size), ks, dp_ref, tp, tc, flags, dptr(cen), dptr(ctl[P * W * MS:]), dptr(L), dptr(R),
                     dptr(masks[0]) if reference else None, dptr(masks[1]) if reference else None,
                     stream_ptr(self.device)))
 
         if reference:
             keys = [("psf", round(float(w), 6), self.precision) for w in WAVE_RGB] + \
-                   [("center", self.precision)] * W
+                   ([("center", self.precision)] * W if center else [])
 
             def launch(tables):
                 ctl.zero_()
                 enqueue(tables)
                 host = ctl.cpu().numpy()
-                launch.any_valid = host[2 * W * MS:]
-                m = host[:2 * W * MS].reshape(2 * W, MS)[:, :K].astype(np.int64) & 0xFFFFFFFF
-                return list(m)
+                launch.any_valid = host[P * W * MS:]
+                return list(host[:P * W * MS].reshape(P * W, MS)[:, :K].astype(np.int64) & 0xFFFFFFFF)
             self.trips.run_many(keys, self._curved(), list(range(K)), launch)
-            assert bool(np.all(launch.any_valid == 1)), "No sampled rays is valid."   # optics.py:902
+            assert not center or bool(np.all(launch.any_valid == 1)), "No sampled rays is valid."   # optics.py:902
         else:
-            full = self._fixed_trips()
-            enqueue([full] * (2 * W))
-        out = R if want_r else L
-        return out.squeeze(0) if single_point else out
-
-    @torch.no_grad()
-    def _psf_rgb_uncentred(self, points, ks, spp, param_list, pupil_xy=None):
-        """psf_rgb(center=False) as one launch (sdirt_psf_rgb): three wavelength slots, the PSFs centred on
-        the pinhole image points (optics.py:972-976), one fresh primary sample set per wavelength (two
-        random vectors each, optics.py:963), one control-block readback for the three trip checks."""
-        single_point = points.dim() == 1
-        pts = points.reshape(-1, 3)
-        N, W, K, MS = pts.shape[0], len(WAVE_RGB), len(self.surfaces), _lib.MAX_SURFACES
-        direct, dp_ref, dpp = "l", None, None
-        if param_list is not None:
-            h, f, w_, r, direct = param_list
-            dpp = _lib.DpParams(float(h), float(f), float(w_), float(r))
-            dp_ref = C.byref(dpp)
-        want_r = direct != "l"
-        po = self._points_to_object(pts)
-        pupilz, pupilr = self.entrance_pupil()
-        if pupil_xy is None:
-            prim = torch.stack([torch.stack(self._pupil_samples(spp, pupilr)) for _ in WAVE_RGB], 1).contiguous()
-        else:
-            prim = torch.as_tensor(pupil_xy).to(self.device, torch.float32).contiguous()              # [2, W, S]
-        spp = prim.shape[2]
-        ptd = pts.to(self.device, torch.float32)
-        one = torch.stack((ptd[:, 0] * (self.sensor_size[1] / 2), ptd[:, 1] * (self.sensor_size[0] / 2)), -1)
-        cen = one.unsqueeze(0).expand(W, N, 2).contiguous()                                          # the same for every colour
-        handles = (C.c_void_p * W)(*[self.dev_lens(w).value for w in WAVE_RGB])
-        L = torch.empty((N, W, ks, ks), dtype=torch.float32, device=self.device)
-        R = torch.empty_like(L) if want_r else None
-        flags = _lib.PSF_NORMALIZE | self._psf_flags()
-        masks = torch.zeros((W, MS), dtype=torch.int32, device=self.device)
-        reference = self.trip_policy == "reference"
-
-        def enqueue(tables):
-            tp = np.concatenate([np.asarray(t, np.int32) for t in tables])
-            with self._timed("psf_rgb"):
-                _lib.check(_lib.lib().sdirt_psf_rgb(
-                    handles, W, dptr(po), N, dptr(prim[0]), dptr(prim[1]), spp, float(pupilz), float(self.d_sensor),
-                    float(self.pixel_size), ks, dptr(cen), dp_ref, (C.c_int32 * (W * K))(*tp.tolist()), flags,
-                    dptr(L), dptr(R), dptr(masks) if reference else None, stream_ptr(self.device)))
-
-        if reference:
-            keys = [("psf", round(float(w), 6), self.precision) for w in WAVE_RGB]
-
-            def launch(tables):
-                masks.zero_()
-                enqueue(tables)
-                m = masks.cpu().numpy()[:, :K].astype(np.int64) & 0xFFFFFFFF
-                return list(m)
-            self.trips.run_many(keys, self._curved(), list(range(K)), launch)
-        else:
-            enqueue([self._fixed_trips()] * W)
+            enqueue([self._fixed_trips()] * (P * W))
         out = R if want_r else L
         return out.squeeze(0) if single_point else out
 

@@ -222,10 +222,9 @@ class PSFNet(Lensgroup):
 
             def consume(item):
                 inp, pend = item
-                with torch.cuda.stream(side):
-                    psf = pend.wait()                          # re-launches (rare) go to `side` too
-                    ready = torch.cuda.Event()
-                    ready.record(side)
+                psf = pend.wait()                              # re-launches (rare) go to `side`, where the batch was enqueued
+                ready = torch.cuda.Event()
+                ready.record(side)
                 return inp, psf, ready
 
             side.wait_stream(main)

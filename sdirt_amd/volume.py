@@ -287,12 +287,10 @@ class VolumeStepper:
         with torch.cuda.stream(s.stream):
             st = _lib.StreamArg(s.stream.cuda_stream, self.device.index)
             for _ in range(3 * K + 3):
-                w = s.ctl_host.numpy().view(np.uint32)
-                unpack = lambda off: [int(np.int8((int(w[off + (k >> 2)]) >> ((k & 3) * 8)) & 0xFF)) for k in range(K)]
-                tp, tc = unpack(_lib.CTL_TRIPS2), unpack(_lib.CTL_TRIPS2 + 16)
+                tp, tc = _lib.decode_ctl(s.ctl_host.numpy(), K).trips2
                 self.relaunches += 1
                 lens.trips.relaunches += 1
-                ctp, ctc = (C.c_int32 * K)(*tp), (C.c_int32 * K)(*tc)
+                ctp, ctc = (C.c_int32 * K)(*tp.tolist()), (C.c_int32 * K)(*tc.tolist())
                 ctl = s.scratch[:4 * _lib.CTL_WORDS].view(torch.int32)
                 ctl.zero_()
                 base = s.scratch.data_ptr()
@@ -310,7 +308,7 @@ class VolumeStepper:
                 s.stream.synchronize()
                 if int(s.ctl_host[_lib.CTL_STATUS]) == 0:
                     for key, t in zip(self.keys, (tp, tc)):
-                        lens.trips.learn(key, np.asarray(t, np.int32))
+                        lens.trips.learn(key, t)
                     self._take_tables()
                     s.ev_kernel.record(s.stream)
                     return

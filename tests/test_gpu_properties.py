@@ -301,16 +301,31 @@ def test_deferred_trip_check_equals_the_immediate_one():
     L2, _ = p2.wait()
     assert torch.allclose(L0, L1, atol=2e-6) and torch.allclose(R0, R1, atol=2e-6)
     assert torch.allclose(L0[:5], L2, atol=2e-6)
-    # wrong speculation: one trip short on a curved surface of both passes
-    for k in list(lens.trips.cache):
-        bad = lens.trips.cache[k].copy()
-        bad[1] = max(1, bad[1] - 1)
-        lens.trips.cache[k] = bad
-        lens.trips.votes[k] = {tuple(int(x) for x in bad): 99}
+    def poison():
+        # wrong speculation: one trip short on a curved surface of both passes
+        for k in list(lens.trips.cache):
+            bad = lens.trips.cache[k].copy()
+            bad[1] = max(1, bad[1] - 1)
+            lens.trips.cache[k] = bad
+            lens.trips.votes[k] = {tuple(int(x) for x in bad): 99}
+    poison()
     before = lens.trips.relaunches
     L3, R3 = lens.psf_lr(pts, defer=True, **kw).wait()
     assert lens.trips.relaunches > before
     assert torch.allclose(L0, L3, atol=2e-6) and torch.allclose(R0, R3, atol=2e-6)
+    for k, v in tabs.items():
+        assert np.array_equal(lens.trips.cache[k], v), k
+    # the same wrong bet, waited for under another stream: the relaunch runs on the stream the call was enqueued on,
+    # with a control block from that stream's pool
+    poison()
+    before = lens.trips.relaunches
+    pend = lens.psf_lr(pts, defer=True, **kw)
+    other = torch.cuda.Stream(DEV)
+    with torch.cuda.stream(other):
+        L4, R4 = pend.wait()
+    assert lens.trips.relaunches > before
+    assert not any(key[1] == other.cuda_stream for key in lens.__dict__.get("_ctl_pools", {}))
+    assert torch.allclose(L0, L4, atol=2e-6) and torch.allclose(R0, R4, atol=2e-6)
     for k, v in tabs.items():
         assert np.array_equal(lens.trips.cache[k], v), k
 

@@ -205,6 +205,44 @@ def test_python_constants_match_the_c_header():
         assert getattr(_lib, k) == v, (k, v, getattr(_lib, k))
 
 
+def test_control_block_decoder_reads_the_library_layout():
+    """_lib.decode_ctl on a control block written by hand for K = 21 (the rf35mm prescription): status and any-valid
+    words, the mask rows of round 1 (CTL_MASKS + 0 / 64) and round 2 (+ 128 / 192), the corrected tables packed as
+    int8 at CTL_TRIPS2 (16 words per pass, entry k in byte k % 4 of word k // 4)."""
+    from sdirt_amd import _lib
+    K = 21
+    rng = np.random.default_rng(7)
+    tables = rng.integers(-10, 11, (2, 64))
+    tables[0, :4] = (-10, -1, 0, 10)                         # negative entries: up to |t| trips, per wave
+    tables[1, K - 2:K] = (10, -10)
+    masks = rng.integers(0, 1 << 32, (4, 64), dtype=np.uint64).astype(np.uint32)
+    masks[:, 0] = (0xFFFFFFFF, 0x80000001, 0x7FE, 1)            # the sign bit of an int32 word set / clear
+    words = np.zeros(_lib.CTL_WORDS, np.uint32)
+    for p in range(2):
+        for k in range(64):                                  # entries past K are junk the decoder must not read
+            words[_lib.CTL_TRIPS2 + 16 * p + k // 4] |= (int(tables[p, k]) & 0xFF) << (8 * (k % 4))
+    words[_lib.CTL_MASKS:_lib.CTL_MASKS + 256] = masks.ravel()
+    words[_lib.CTL_ANY_VALID] = 1
+    rows = [[int(v) for v in masks[r, :K]] for r in range(4)]
+    as_ints = lambda a: [int(v) for v in a]
+
+    ok = _lib.decode_ctl(words.view(np.int32), K)                # status 0: the bet was right, round 1 alone ran
+    assert ok.status == 0 and ok.any_valid == 1 and ok.trips2 is None
+    assert [[as_ints(m) for m in rnd] for rnd in ok.masks] == [rows[0:2]]
+
+    words[_lib.CTL_STATUS] = 3
+    words[_lib.CTL_ANY_VALID] = 0
+    bad = _lib.decode_ctl(words.view(np.int32), K)               # status != 0: the device re-rendered with its tables
+    assert bad.status == 3 and bad.any_valid == 0
+    assert [[as_ints(m) for m in rnd] for rnd in bad.masks] == [rows[0:2], rows[2:4]]
+    assert [t.dtype for t in bad.trips2] == [np.int32, np.int32]
+    assert [as_ints(t) for t in bad.trips2] == [as_ints(tables[0, :K]), as_ints(tables[1, :K])]
+
+    one = _lib.decode_ctl(words.view(np.int32), K, one_round=True)   # SDIRT_PSF_ONE_ROUND: no second round ran
+    assert [[as_ints(m) for m in rnd] for rnd in one.masks] == [rows[0:2]]
+    assert [as_ints(t) for t in one.trips2] == [as_ints(t) for t in bad.trips2]
+
+
 def test_ctypes_structs_match_the_c_header(tmp_path):
     """Compile include/sdirt_dp.h as plain C and compare struct layouts with the ctypes mirror."""
     import subprocess
