@@ -269,6 +269,26 @@ int sdirt_forward_integral(sdirt_rays rays, int64_t spp, int64_t n_points, doubl
 int sdirt_forward_integral_plan(int64_t n_points, int64_t spp, int32_t ks, int32_t both, int32_t n_cus,
                                 int64_t* plan /*host [6]*/);
 
+/* The backward pass of sdirt_forward_integral (deeplens/monte_carlo.py:9-68 with
+ * assign_points_to_pixels_small_r :135-240 / _big_r :242-372, as torch's autograd differentiates them there): given
+ * grad_l / grad_r = dLoss/d(RAW l_grid / r_grid) [N,ks,ks] (either may be NULL: no gradient from that grid), the
+ * gradients with respect to the dual-pixel parameters h, f, w and the centres pointc_ref.  The rays, r and the
+ * direction letter get none (the reference samples the rays under no_grad and re-wraps r with torch.tensor(r),
+ * :167, :274).  Same arguments as the forward call -- rays, centres, dp (NULL: defaults, and grad_r is ignored),
+ * SDIRT_PSF_STRICT_IEEE -- so that the window test, the taps and every clamp decision are the forward's.
+ * partial (dev float64 [N, n_slices, 5], fully overwritten) = per point and slice of the spp axis the sums
+ * (dh, df, dw, dcx, dcy); the caller sums over the slices.  n_slices must be
+ * sdirt_forward_integral_grad_slices(N, spp, n_cus) of the current device.  No atomics: the same bits every run. */
+int sdirt_forward_integral_grad(sdirt_rays rays, int64_t spp, int64_t n_points, double ps, int32_t ks,
+                                const float* center /*dev [N,2]*/, const sdirt_dp_params* dp /*host*/,
+                                uint32_t flags /*SDIRT_PSF_STRICT_IEEE or 0*/, const float* grad_l /*dev or NULL*/,
+                                const float* grad_r /*dev or NULL*/, double* partial /*dev [N,n_slices,5]*/,
+                                int32_t n_slices, void* stream);
+
+/* Slices of the spp axis sdirt_forward_integral_grad cuts a batch into on a device of n_cus compute units (host
+ * arithmetic only); 0 for a bad argument. */
+int32_t sdirt_forward_integral_grad_slices(int64_t n_points, int64_t spp, int32_t n_cus);
+
 /* deeplens/optics.py:983-987: psf / (max + 1e-6), per point, in place. */
 int sdirt_psf_normalize(float* psf /*dev [N,ks,ks]*/, int64_t n_points, int32_t ks, void* stream);
 

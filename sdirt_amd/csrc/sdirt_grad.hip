@@ -1,0 +1,299 @@
+// sdirt_grad.hip -- the backward pass of the splat stage (deeplens/monte_carlo.py:9-68, 135-240, 242-372): the
+// gradients of a loss with respect to the dual-pixel parameters (h, f, w) and the PSF centres, given its gradients
+// with respect to the RAW left and right grids.  The rays carry no gradient (the reference's sample_from_points and
+// psf_center run under no_grad), nor does the microlens radius r (it is re-wrapped by torch.tensor(r) at :167, :274).
+//
+// Per ray: the window test, the four bilinear taps and the sub-pixel areas s_l, s_r are recomputed with the
+// forward's own fp32 operations (the same rays in and out of the window, the same clamp decisions), then
+//   d/d(h, f, w) : ra * (gl . taps * ds_l/dtheta + gr . taps * ds_r/dtheta)
+//   d/d(cx, cy)  : ra * (s_l * d(gl . taps)/dc + s_r * d(gr . taps)/dc)      (through the bilinear weights)
+// in float64.  A segment area A(x) = r^2 (u - sin(2u)/2), u = acos(x/r), is differentiated by its chord,
+// dA/dx = -2 sqrt(r^2 - x^2): no acos in the derivative, and 0 where |x| = r (the reference's autograd gives a
+// non-finite value there).  Every torch.clamp passes the gradient where lo <= x <= hi and stops it outside.
+//
+// Reduction: one workgroup per (point, slice of the spp axis); the ray terms are summed in float64 registers, across
+// the wave with shuffles, across the workgroup through LDS, and ONE float64 partial of 5 values is stored per
+// (point, slice).  No atomics: the gradients are the same bits from run to run.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "../../include/sdirt_dp.h"
+#include "sdirt_host.hpp"
+
+using namespace sdirt;
+
+namespace {
+
+constexpr int kGradThreads = 256;
+constexpr int kGradComps = 5;                       // h, f, w, cx, cy
+constexpr int kGradLdsBytes = 48 * 1024;            // both grids staged in LDS up to ks 78
+
+// The float64 copies of the parameters the derivatives are evaluated at.
+struct DpGrad {
+    double h, f, w, r, fmh;
+};
+
+struct GradLaunch {
+    int64_t chunk;        // samples per slice
+    int nslices;          // slices of the spp axis per point
+    double dwr_dcx;       // d(column fraction)/d(cx) = -ksm1 / dx_rng (times the ray's weight)
+    double dwb_dcy;       // d(row fraction)/d(cy)    = -ksm1 / dy_rng
+};
+
+// Window test and bilinear taps of one ray: splat_taps' operations, one by one (the same rays in the window, the
+// same taps), keeping the row / column fractions and the weight the bilinear weights are made of.
+struct GradTaps {
+    int i_tl, i_tr, i_bl, i_br;
+    float wb, wr, w;
+};
+
+template <class DivY, class DivX>
+__device__ __forceinline__ bool grad_taps(const SplatGeom& gm, const DivY& div_dy, const DivX& div_dx, float sx,
+                                          float sy, float cx, float cy, float ra, GradTaps& tp)
+{
+    float px = (-sx) - cx;
+    float py = (-sy) - cy;
+    float w = ra * (__builtin_fabsf(px) < gm.lim ? 1.0f : 0.0f);
+    w = w * (__builtin_fabsf(py) < gm.lim ? 1.0f : 0.0f);
+    if (!(w != 0.0f)) return false;
+    px = px * w; py = py * w;
+    const float pf0 = div_dy(py - gm.y_max) * gm.ksm1;
+    const float pf1 = div_dx(px - gm.x_min) * gm.ksm1;
+    const float fl0 = __builtin_floorf(pf0), fl1 = __builtin_floorf(pf1);
+    tp.wb = pf0 - fl0; tp.wr = pf1 - fl1; tp.w = w;
+    const int r0 = (int)fl0, c0 = (int)fl1;
+    const int r1 = (int)__builtin_floorf(pf0 + 1.0f), c1 = (int)__builtin_floorf(pf1 + 1.0f);
+    const int ks = gm.ks;
+    tp.i_tl = r0 * ks + c0;
+    tp.i_tr = r0 * ks + c1;
+    tp.i_bl = r1 * ks + c0;
+    tp.i_br = (r0 + 1) * ks + (c0 + 1);
+    return r0 >= 0 && c0 >= 0 && r1 < ks && c1 < ks && (r0 + 1) < ks && (c0 + 1) < ks;
+}
+
+__device__ __forceinline__ bool in_range(float x, float lo, float hi) { return x >= lo && x <= hi; }
+
+// dA/dx of the segment area at x (inside [-r, r]): the chord -2 sqrt(r^2 - x^2)
+__device__ __forceinline__ double chord(double r, double x)
+{
+    return -2.0 * sqrt(fmax((r - x) * (r + x), 0.0));
+}
+
+// d/d(h, f, w) of the boundary a*w - (f*t - a*w)*h/(f - h) projected through the microlens (monte_carlo.py:169-171),
+// a = +1 (right), 0 (middle), -1 (left)
+__device__ __forceinline__ void d_lens(const DpGrad& q, double t, double a, double d[3])
+{
+    const double D = q.fmh, u = q.f * t - a * q.w;
+    d[0] = -u * q.f / (D * D);
+    d[1] = -q.h * t / D + u * q.h / (D * D);
+    d[2] = a * q.f / D;
+}
+
+// d/d(h, f, w) of Z_a, a = +1, 0, -1 (right, middle, left), where s_r = Z_m - Z_r and s_l = Z_l - Z_m.
+//  small r (monte_carlo.py:169-206): Z = A(clamp(x1, -r, r)) - c2 - A(clamp(c2, -r, r)), c2 = clamp(x2, -0.5, 0.5)
+//  big r (:278-338): Z = T(x1) - c2 - T(x2), T(x) = A(c) - r^2 seg(clamp(u, tr, tl)) - r cos(clamp(u, tr, tl)),
+//       c = clamp(x, -0.5, 0.5), u = acos(c / r); with the u clamp open T's derivative is -dc (the area terms cancel),
+//       closed it is A'(c) dc
+// with x1 = the lens-projected boundary (d_lens) and x2 = a*w - h*t the margin boundary (:186-188).
+// The clamp decisions are taken on the forward's fp32 values (x1f, x2f, and for big r the fp32 acos of the forward).
+template <bool BIG, class M, class Div>
+__device__ __forceinline__ void dz_boundaries(const DevDpParams& p, const Div& div_fmh, const DpGrad& q, float x_tan,
+                                              double dZ[3][3])
+{
+    const float fx = p.f * x_tan, hx = p.h * x_tan;
+    float x1f[3], x2f[3];
+    if (BIG) {      // dp_weights_big divides with '/'
+        x1f[0] = p.w - ((fx - p.w) * p.h) / p.fmh;
+        x1f[1] = ((-fx) * p.h) / p.fmh;
+        x1f[2] = (-p.w) - ((fx + p.w) * p.h) / p.fmh;
+    } else {
+        x1f[0] = p.w - div_fmh((fx - p.w) * p.h);
+        x1f[1] = div_fmh((-fx) * p.h);
+        x1f[2] = (-p.w) - div_fmh((fx + p.w) * p.h);
+    }
+    x2f[0] = p.w - hx; x2f[1] = 0.0f - hx; x2f[2] = (-p.w) - hx;
+    const double t = (double)x_tan;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double a = 1.0 - (double)k;                 // +1, 0, -1
+        double d1[3];
+        d_lens(q, t, a, d1);
+        const double x1 = a * q.w - (q.f * t - a * q.w) * q.h / q.fmh;
+        const double x2 = a * q.w - q.h * t;
+        const double d2[3] = {-t, 0.0, a};
+        double c1, c2;                                     // dZ = c1 * dx1 + c2 * dx2
+        if (BIG) {
+            const bool g1 = in_range(x1f[k], -0.5f, 0.5f), g2 = in_range(x2f[k], -0.5f, 0.5f);
+            const float u1 = __ocml_acos_f32(clampf(x1f[k], -0.5f, 0.5f) / p.r);
+            const float u2 = __ocml_acos_f32(clampf(x2f[k], -0.5f, 0.5f) / p.r);
+            const bool gu1 = in_range(u1, p.tr, p.tl), gu2 = in_range(u2, p.tr, p.tl);
+            c1 = g1 ? (gu1 ? -1.0 : chord(q.r, x1)) : 0.0;
+            c2 = g2 ? -1.0 - (gu2 ? -1.0 : chord(q.r, x2)) : 0.0;
+        } else {
+            const bool g1 = in_range(x1f[k], -p.r, p.r), g2 = in_range(x2f[k], -0.5f, 0.5f);
+            const bool gi = in_range(clampf(x2f[k], -0.5f, 0.5f), -p.r, p.r);
+            c1 = g1 ? chord(q.r, x1) : 0.0;
+            c2 = g2 ? -1.0 - (gi ? chord(q.r, x2) : 0.0) : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < 3; ++j) dZ[k][j] = c1 * d1[j] + c2 * d2[j];
+    }
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// One workgroup per (point n, slice j): blockIdx.x = n * nslices + j.  LDS: the point's two upstream grids (when
+// they fit, else they are read through L2) and the per-wave sums.
+template <bool BIG, class M, bool STAGE>
+__global__ void __launch_bounds__(kGradThreads)
+k_forward_integral_grad(sdirt_rays R, int64_t S, SplatGeom gm, DevDpParams dp, DpGrad q, GradLaunch gl_,
+                        const float* __restrict__ center, const float* __restrict__ gl, const float* __restrict__ gr,
+                        double* __restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) float g_lds[];
+    __shared__ double red[kGradThreads / 64][kGradComps];
+    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
+    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
+    const int tile = gm.ks * gm.ks;
+    const float* GL = gl ? gl + n * tile : nullptr;
+    const float* GR = gr ? gr + n * tile : nullptr;
+    if (STAGE) {
+        for (int e = threadIdx.x; e < tile; e += kGradThreads) {
+            g_lds[e] = GL ? GL[e] : 0.0f;
+            g_lds[tile + e] = GR ? GR[e] : 0.0f;
+        }
+        __syncthreads();
+    }
+    const float cx = center[2 * n], cy = center[2 * n + 1];
+    const auto div_dy = UDiv<M>::make(gm.dy_rng), div_dx = UDiv<M>::make(gm.dx_rng);
+    const auto div_fmh = UDiv<M>::make(dp.fmh);
+    double acc[kGradComps] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
+    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
+        const int64_t i = n * S + s;
+        const float ox = R.ox[i], oy = R.oy[i], dx = R.dx[i], dz = R.dz[i], ra = R.ra[i];
+        GradTaps tp;
+        if (!grad_taps(gm, div_dy, div_dx, ox, oy, cx, cy, ra, tp)) continue;
+        const float x_tan = (-dx) / dz;                   // monte_carlo.py:48
+        float sl, sr;
+        if (BIG) dp_weights_big(dp, x_tan, sl, sr);
+        else dp_weights_small<M>(dp, div_fmh, x_tan, sl, sr);
+        // upstream gradients at the four taps
+        double lt, lr_, lb, lbr, rt = 0.0, rr_ = 0.0, rb = 0.0, rbr = 0.0;
+        if (STAGE) {
+            lt = g_lds[tp.i_tl]; lr_ = g_lds[tp.i_tr]; lb = g_lds[tp.i_bl]; lbr = g_lds[tp.i_br];
+            rt = g_lds[tile + tp.i_tl]; rr_ = g_lds[tile + tp.i_tr]; rb = g_lds[tile + tp.i_bl];
+            rbr = g_lds[tile + tp.i_br];
+        } else {
+            lt = GL ? GL[tp.i_tl] : 0.0f; lr_ = GL ? GL[tp.i_tr] : 0.0f;
+            lb = GL ? GL[tp.i_bl] : 0.0f; lbr = GL ? GL[tp.i_br] : 0.0f;
+            if (GR) { rt = GR[tp.i_tl]; rr_ = GR[tp.i_tr]; rb = GR[tp.i_bl]; rbr = GR[tp.i_br]; }
+        }
+        const double wb = tp.wb, wr = tp.wr, w = tp.w;
+        // g . bilinear weights, and its derivatives by the column (wr) and row (wb) fractions
+        const double bl = (1.0 - wb) * ((1.0 - wr) * lt + wr * lr_) + wb * ((1.0 - wr) * lb + wr * lbr);
+        const double br = (1.0 - wb) * ((1.0 - wr) * rt + wr * rr_) + wb * ((1.0 - wr) * rb + wr * rbr);
+        const double bl_wr = (1.0 - wb) * (lr_ - lt) + wb * (lbr - lb), bl_wb = (1.0 - wr) * (lb - lt) + wr * (lbr - lr_);
+        const double br_wr = (1.0 - wb) * (rr_ - rt) + wb * (rbr - rb), br_wb = (1.0 - wr) * (rb - rt) + wr * (rbr - rr_);
+        double dZ[3][3];
+        dz_boundaries<BIG, M>(dp, div_fmh, q, x_tan, dZ);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double dsr = dZ[1][c] - dZ[0][c], dsl = dZ[2][c] - dZ[1][c];
+            acc[c] += w * (bl * dsl + br * dsr);
+        }
+        // the centre moves the shifted point (times the weight, :38) and so the bilinear fractions
+        const double cs = w * ((double)sl * bl_wr + (double)sr * br_wr), cr = w * ((double)sl * bl_wb + (double)sr * br_wb);
+        acc[3] += w * gl_.dwr_dcx * cs;
+        acc[4] += w * gl_.dwb_dcy * cr;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < kGradComps; ++c) {
+        const double v = wave_sum(acc[c]);
+        if (lane == 0) red[wave][c] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kGradComps) {
+        double v = 0.0;
+        for (int k = 0; k < kGradThreads / 64; ++k) v += red[k][threadIdx.x];
+        partial[(n * gl_.nslices + j) * kGradComps + threadIdx.x] = v;
+    }
+}
+
+GradLaunch plan_grad(int64_t N, int64_t S, int ncu)
+{
+    GradLaunch g{};
+    // about eight workgroups per CU in all, each with at least four rays per thread
+    int64_t ns = std::max<int64_t>(1, (8 * (int64_t)ncu + N - 1) / std::max<int64_t>(N, 1));
+    ns = std::min<int64_t>(ns, std::max<int64_t>(1, S / (4 * kGradThreads)));
+    g.chunk = std::max<int64_t>(1, (S + ns - 1) / ns);
+    g.nslices = (int)std::max<int64_t>(1, (S + g.chunk - 1) / g.chunk);
+    return g;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t sdirt_forward_integral_grad_slices(int64_t n_points, int64_t spp, int32_t n_cus)
+{
+    if (n_points < 1 || spp < 0 || n_cus < 1) return 0;
+    return plan_grad(n_points, spp, n_cus).nslices;
+}
+
+int sdirt_forward_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps, int32_t ks, const float* center,
+                                const sdirt_dp_params* dp, uint32_t flags, const float* grad_l, const float* grad_r,
+                                double* partial, int32_t n_slices, void* stream)
+{
+    if (int rc = check_rays(rays)) return rc;
+    if (int rc = check_ks(ks, SDIRT_MAX_KS_STAGED)) return rc;
+    if (!center || !partial || S < 0 || N < 0 || N > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
+    if (dp && !(dp->f != dp->h)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->f must differ from dp->h");
+    if (N == 0) return SDIRT_OK;
+    int ncu = 0;
+    if (int rc = device_cus(&ncu)) return rc;
+    GradLaunch gl = plan_grad(N, S, ncu);
+    if (n_slices != gl.nslices)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_slices=%d, the launch has %d (sdirt_forward_integral_grad_slices)",
+                    n_slices, gl.nslices);
+    hipStream_t st = as_stream(stream);
+    const SplatGeom gm = make_geom(ps, ks);
+    const DevDpParams dpp = make_dp(dp);
+    const DpGrad q{dp ? dp->h : 0.78, dp ? dp->f : 1.44, dp ? dp->w : 0.3, dp ? dp->r : 0.5,
+                   (dp ? dp->f : 1.44) - (dp ? dp->h : 0.78)};
+    gl.dwr_dcx = -(double)gm.ksm1 / (double)gm.dx_rng;
+    gl.dwb_dcy = -(double)gm.ksm1 / (double)gm.dy_rng;
+    // param_list=None: the R grid is all zero, nothing flows back from it
+    const float* gr = dpp.have_r ? grad_r : nullptr;
+    const bool strict = (flags & SDIRT_PSF_STRICT_IEEE) != 0;
+    const size_t lds = 2 * sizeof(float) * (size_t)ks * ks;
+    const bool stage = lds <= (size_t)kGradLdsBytes;
+    const unsigned grid = (unsigned)(N * gl.nslices);
+#define SDIRT_LAUNCH_GRAD(BG, MM, STG)                                                                    \
+    k_forward_integral_grad<BG, MM, STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(rays, S, gm, dpp, q, gl, \
+                                                                                   center, grad_l, gr, partial)
+#define SDIRT_LAUNCH_GRAD_M(BG, STG)                                  \
+    do {                                                              \
+        if (strict) SDIRT_LAUNCH_GRAD(BG, Ieee, STG); else SDIRT_LAUNCH_GRAD(BG, Lean, STG); \
+    } while (0)
+    if (dpp.big) {
+        if (stage) SDIRT_LAUNCH_GRAD_M(true, true); else SDIRT_LAUNCH_GRAD_M(true, false);
+    } else {
+        if (stage) SDIRT_LAUNCH_GRAD_M(false, true); else SDIRT_LAUNCH_GRAD_M(false, false);
+    }
+#undef SDIRT_LAUNCH_GRAD_M
+#undef SDIRT_LAUNCH_GRAD
+    LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+
+}  // extern "C"

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 
@@ -143,6 +144,40 @@ inline bool rays_aligned16(const sdirt_rays& R)
     const uintptr_t a = (uintptr_t)R.ox | (uintptr_t)R.oy | (uintptr_t)R.oz | (uintptr_t)R.dx | (uintptr_t)R.dy |
                         (uintptr_t)R.dz | (uintptr_t)R.ra | (uintptr_t)R.obliq;
     return (a & 15) == 0;
+}
+
+// The device-side constants of a dual-pixel parameter block (NULL: the reference's defaults) and of a splat window,
+// as every kernel that splats or differentiates a splat (sdirt_psf.hip, sdirt_grad.hip) computes them.
+inline sdirt::DevDpParams make_dp(const sdirt_dp_params* dp)
+{
+    sdirt::DevDpParams p;
+    const double h = dp ? dp->h : 0.78, f = dp ? dp->f : 1.44, w = dp ? dp->w : 0.3,
+                 r = dp ? dp->r : 0.5;
+    p.h = (float)h; p.f = (float)f; p.w = (float)w; p.r = (float)r;
+    p.fmh = (float)(f - h);
+    p.rr = p.r * p.r;
+    p.big = r > 0.5;
+    p.have_r = dp != nullptr;
+    int ex = 0;
+    p.r_pow2 = std::frexp(p.r, &ex) == 0.5f;
+    p.inv_r = 1.0f / p.r;
+    p.tr = std::asin((1.0f / p.r) * 0.5f);
+    p.tl = (float)3.141592653589793 - p.tr;
+    return p;
+}
+
+inline sdirt::SplatGeom make_geom(double ps, int ks)
+{
+    sdirt::SplatGeom g;
+    const double hi = (ks / 2.0 - 0.5) * ps, lo = (-ks / 2.0 + 0.5) * ps;
+    g.lim = (float)(hi - 0.01 * ps);
+    g.x_min = (float)lo;
+    g.y_max = (float)hi;
+    g.dx_rng = (float)(hi - lo);
+    g.dy_rng = (float)(lo - hi);
+    g.ksm1 = (float)(ks - 1);
+    g.ks = ks;
+    return g;
 }
 
 inline int check_ks(int ks, int max_ks = SDIRT_MAX_KS)

@@ -18,38 +18,6 @@
 
 using namespace sdirt;
 
-static DevDpParams make_dp(const sdirt_dp_params* dp)
-{
-    DevDpParams p;
-    const double h = dp ? dp->h : 0.78, f = dp ? dp->f : 1.44, w = dp ? dp->w : 0.3,
-                 r = dp ? dp->r : 0.5;
-    p.h = (float)h; p.f = (float)f; p.w = (float)w; p.r = (float)r;
-    p.fmh = (float)(f - h);
-    p.rr = p.r * p.r;
-    p.big = r > 0.5;
-    p.have_r = dp != nullptr;
-    int ex = 0;
-    p.r_pow2 = std::frexp(p.r, &ex) == 0.5f;
-    p.inv_r = 1.0f / p.r;
-    p.tr = std::asin((1.0f / p.r) * 0.5f);
-    p.tl = (float)3.141592653589793 - p.tr;
-    return p;
-}
-
-static SplatGeom make_geom(double ps, int ks)
-{
-    SplatGeom g;
-    const double hi = (ks / 2.0 - 0.5) * ps, lo = (-ks / 2.0 + 0.5) * ps;
-    g.lim = (float)(hi - 0.01 * ps);
-    g.x_min = (float)lo;
-    g.y_max = (float)hi;
-    g.dx_rng = (float)(hi - lo);
-    g.dy_rng = (float)(lo - hi);
-    g.ksm1 = (float)(ks - 1);
-    g.ks = ks;
-    return g;
-}
-
 // Everything the splat of one ray needs (window geometry + dual-pixel parameters), as ONE
 // 64-byte block at offset 0 of k_psf_lr's kernel-argument segment: the kernel fetches it with one
 // scalar load per RAY, right before the splat, instead of keeping ~20 SGPRs alive through the

@@ -20,6 +20,72 @@ def _dp(param_list):
     return _lib.DpParams(float(h), float(f), float(w), float(r)), direct
 
 
+def _requires_grad(*vals):
+    """Whether autograd is recording and one of `vals` (tensors, Python numbers, None) requires a gradient."""
+    return torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in vals)
+
+
+class SplatFunction(torch.autograd.Function):
+    """The splat stage as an autograd op: (h, f, w, centres) -> RAW (l_grid, r_grid) [N, ks, ks] of
+    sdirt_forward_integral, differentiable in h, f, w (0-d tensors; Python numbers get no gradient) and in the
+    centres [N, 2] (pointc_ref).  The rays, r and the precision are constants, as in the reference (its rays are
+    sampled under no_grad, r is re-wrapped by torch.tensor(r) at monte_carlo.py:167, :274).  The backward is one
+    kernel, sdirt_forward_integral_grad, on the same rays, centres and parameters: the forward's window, taps and
+    clamp decisions, float64 sums, no atomics."""
+
+    @staticmethod
+    def forward(ctx, h, f, w, center, ray, ps, ks, r, have_dp, precision):
+        S, N = ray.shape
+        dev = ray.device
+        center = center.detach().to(dev, torch.float32).reshape(N, 2).contiguous()
+        dp = _lib.DpParams(float(h), float(f), float(w), float(r)) if have_dp else None
+        lg = torch.empty((N, ks, ks), dtype=torch.float32, device=dev)
+        rg = torch.empty_like(lg)
+        _lib.check(_lib.lib().sdirt_forward_integral(
+            ray.c_rays(), S, N, float(ps), int(ks), dptr(center), C.byref(dp) if dp is not None else None,
+            _flags(precision), dptr(lg), dptr(rg), stream_ptr(dev)))
+        ctx.ray, ctx.dp, ctx.geom, ctx.precision = ray, dp, (S, N, float(ps), int(ks)), precision
+        ctx.meta = [(v.dtype, v.device) if torch.is_tensor(v) else None for v in (h, f, w)]
+        ctx.save_for_backward(center)
+        return lg, rg
+
+    @staticmethod
+    def backward(ctx, gl, gr):
+        (center,) = ctx.saved_tensors
+        S, N, ps, ks = ctx.geom
+        dev = center.device
+        ncu = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+        ns = int(_lib.lib().sdirt_forward_integral_grad_slices(N, S, ncu))
+        partial = torch.empty((N, ns, 5), dtype=torch.float64, device=dev)
+        gl = gl.to(torch.float32).contiguous() if gl is not None else None
+        gr = gr.to(torch.float32).contiguous() if gr is not None else None
+        dp = ctx.dp
+        _lib.check(_lib.lib().sdirt_forward_integral_grad(
+            ctx.ray.c_rays(), S, N, ps, ks, dptr(center), C.byref(dp) if dp is not None else None,
+            _flags(ctx.precision), dptr(gl), dptr(gr), dptr(partial), ns, stream_ptr(dev)))
+        tot = partial.sum(1)                                   # [N, 5] float64: the slices in a fixed order
+        theta = tot[:, :3].sum(0)
+        grads = [theta[i].to(device=ctx.meta[i][1], dtype=ctx.meta[i][0]) if ctx.needs_input_grad[i] else None
+                 for i in range(3)]
+        gc = tot[:, 3:].to(torch.float32) if ctx.needs_input_grad[3] else None
+        return (*grads, gc, None, None, None, None, None, None)
+
+
+def _as_scalar(v):
+    """A DP parameter as SplatFunction takes it: a tensor that requires grad stays itself (autograd casts the
+    gradient back to its dtype and device), anything else becomes a plain number."""
+    return v.reshape(()) if torch.is_tensor(v) and v.requires_grad else float(v)
+
+
+def splat_autograd(ray, ps, ks, center, param_list, precision="lean"):
+    """RAW (l_grid, r_grid) through SplatFunction: param_list = (h, f, w, r, direct) or None (the reference's
+    defaults, R all zero); r and direct get no gradient.  The grids are NOT swapped for direct != 'l'."""
+    have_dp = param_list is not None
+    h, f, w, r = (param_list[:4] if have_dp else (0.78, 1.44, 0.3, 0.5))
+    h, f, w = (_as_scalar(v) for v in (h, f, w))
+    return SplatFunction.apply(h, f, w, center, ray, ps, ks, float(r), have_dp, precision)
+
+
 def _flags(precision):
     if precision not in ("lean", "ieee"):
         raise ValueError("precision must be 'lean' or 'ieee'")
@@ -30,18 +96,26 @@ def forward_integral_lr(ray, ps, ks, pointc_ref=None, param_list=None, precision
     """RAW (l_grid, r_grid), each [N, ks, ks]; r_grid is all-zero when
     param_list is None exactly as in monte_carlo.py:230-235.  precision='ieee': the reference's literal
     sequence for the sub-pixel areas (arccos, sin) and the compiler's full-range divisions instead of the
-    fused segment-area polynomial (SDIRT_PSF_STRICT_IEEE)."""
+    fused segment-area polynomial (SDIRT_PSF_STRICT_IEEE).  Differentiable in param_list's h, f, w and in
+    pointc_ref when one of them requires a gradient (SplatFunction); otherwise the grids carry no grad_fn.
+    (The RMS centre of pointc_ref=None depends on the rays only, and the rays carry no gradient.)"""
     if len(ray.shape) != 2:
         raise ValueError("ray must have shape [spp, N]")
     S, N = ray.shape
     dev = ray.device
+    grad = _requires_grad(pointc_ref, *(param_list[:3] if param_list is not None else ()))
     if pointc_ref is None:
         # RMS centre, monte_carlo.py:28-31
         center = torch.empty((N, 2), dtype=torch.float32, device=dev)
         _lib.check(_lib.lib().sdirt_center_from_rays(ray.c_rays(), S, N, dptr(center), None,
                                                      stream_ptr(dev)))
+    elif grad:
+        center = pointc_ref.to(dev, torch.float32).reshape(N, 2)
     else:
         center = pointc_ref.to(dev, torch.float32).reshape(N, 2).contiguous()
+    if grad:
+        # h, f, w or pointc_ref require a gradient: the same forward kernel behind SplatFunction
+        return splat_autograd(ray, ps, ks, center, param_list, precision)
     dp, _ = _dp(param_list)
     lg = torch.empty((N, ks, ks), dtype=torch.float32, device=dev)
     rg = torch.empty_like(lg)

@@ -22,6 +22,7 @@ import torch
 
 from . import _hostrng, _lib, basics
 from .basics import DEFAULT_WAVE, DEPTH, GEO_SPP, WAVE_RGB, Ray, dptr, stream_ptr
+from .monte_carlo import _requires_grad, splat_autograd
 from .newton import NEWTON_MAXITER, TripPlanner
 from .surfaces import Aspheric
 
@@ -111,6 +112,15 @@ def _parse_param_list(param_list):
         return None, False
     h, f, w, r, direct = param_list
     return (h, f, w, r), direct != "l"
+
+
+def _psf_needs_grad(dp, points, center):
+    """Whether a psf call records gradients: grad mode is on and h, f or w of dp -- or, with center=False (the
+    pinhole centres, optics.py:973-976), the points -- require one.  r never gets a gradient (monte_carlo.py:167)."""
+    vals = list(dp[:3]) if dp is not None else []
+    if not center:
+        vals.append(points)
+    return _requires_grad(*vals)
 
 
 def _c_trips(t):
@@ -871,7 +881,6 @@ class Lensgroup:
                 raise ValueError("out tensors must be contiguous float32 CUDA [N, ks, ks]")
         return L, R
 
-    @torch.no_grad()
     def psf_lr(self, points, ks=31, wvln=DEFAULT_WAVE, spp=GEO_SPP, center=True,
                dp=(0.78, 1.44, 0.3, 0.5), normalize=True, want_r=True, _default_r_zero=False,
                pupil_xy=None, center_pupil_xy=None, out=None, defer=False, center_out=None):
@@ -899,7 +908,22 @@ class Lensgroup:
         verifies them (re-launching in the rare case the speculation was wrong) and returns
         (L, R).  A caller that renders batch after batch keeps one call in flight -- the GPU
         starts batch i+1 while the host checks batch i -- without giving up the check.  Every
-        round of a call runs on the stream that was current when it was enqueued."""
+        round of a call runs on the stream that was current when it was enqueued.
+
+        Differentiable (optics.py:934-996 under autograd) when grad mode is on and h, f or w of dp -- or, with
+        center=False, `points` -- require a gradient: the call then runs the staged chain and the splat through
+        monte_carlo.SplatFunction (_psf_lr_grad).  r, the wavelength, the lens, the rays and, with center=True,
+        the points get no gradient.  out=, center_out= and defer=True are refused there."""
+        if _psf_needs_grad(dp if not _default_r_zero else None, points, center):
+            return self._psf_lr_grad(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero,
+                                     pupil_xy, center_pupil_xy, out, defer, center_out)
+        return self._psf_lr(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
+                            center_pupil_xy, out, defer, center_out)
+
+    @torch.no_grad()
+    def _psf_lr(self, points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
+                center_pupil_xy, out, defer, center_out):
+        """psf_lr without autograd: the fused kernels (ks <= SDIRT_MAX_KS) or the staged chain."""
         self._require_gpu()
         if not torch.is_tensor(points):
             points = torch.tensor(points)
@@ -1161,6 +1185,22 @@ class Lensgroup:
         handful of points."""
         if not 2 <= ks <= _lib.MAX_KS_STAGED:
             raise _lib.SdirtError(f"ks={ks} outside [2,{_lib.MAX_KS_STAGED}]")
+        cen = self._centre_buffer(center_out, N)
+        ray, spp = self._staged_rays(points, po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen)
+        L, R = self._psf_buffers(out, N, ks, want_r and not default_r_zero)
+        dpp = None if (dp is None or default_r_zero) else _lib.DpParams(*[float(v) for v in dp])
+        h, st = _lib.lib(), stream_ptr(self.device)
+        with self._timed("forward_integral"):
+            # normalised on the way out of the tiles (optics.py:983-987): no second pass over the grids
+            _lib.check(h.sdirt_forward_integral(ray.c_rays(), spp, N, float(self.pixel_size), int(ks), dptr(cen),
+                                                C.byref(dpp) if dpp is not None else None,
+                                                self._math_flags() | (_lib.PSF_NORMALIZE if normalize else 0),
+                                                dptr(L), dptr(R), st))
+        return _epilogue(L, R, want_r, single_point)
+
+    def _staged_rays(self, points, po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen):
+        """The first stages of the staged chain: sample_from_points, psf_center (or the pinhole centres of
+        center=False) into `cen`, trace2sensor.  -> (the [spp, N] sensor-plane rays, spp)."""
         pupilz, pupilr = self.entrance_pupil()
         # optics.py:963 (first two draws)
         x2, y2 = self._pupil_samples(spp, pupilr) if pupil_xy is None else map(self._on_device, pupil_xy)
@@ -1168,7 +1208,6 @@ class Lensgroup:
         ray = Ray.empty((spp, N), wvln, self.device)
         _lib.check(_lib.lib().sdirt_sample_rays(dptr(po), N, dptr(x2), dptr(y2), spp, float(pupilz), ray.c_rays(),
                                                 stream_ptr(self.device)))
-        cen = self._centre_buffer(center_out, N)
         xc = yc = None
         if center:
             pupilz_c, pupilr_c = self.entrance_pupil(shrink_pupil=True)
@@ -1180,15 +1219,40 @@ class Lensgroup:
             self._pinhole_centres(points, cen)
         self.last_pupil_points = (x2, y2, xc, yc)
         self.trace(ray, forward=True, _to_sensor=self.d_sensor)        # trace2sensor, one pass
-        L, R = self._psf_buffers(out, N, ks, want_r and not default_r_zero)
-        dpp = None if (dp is None or default_r_zero) else _lib.DpParams(*[float(v) for v in dp])
-        h, st = _lib.lib(), stream_ptr(self.device)
-        with self._timed("forward_integral"):
-            # normalised on the way out of the tiles (optics.py:983-987): no second pass over the grids
-            _lib.check(h.sdirt_forward_integral(ray.c_rays(), spp, N, float(self.pixel_size), int(ks), dptr(cen),
-                                                C.byref(dpp) if dpp is not None else None,
-                                                self._math_flags() | (_lib.PSF_NORMALIZE if normalize else 0),
-                                                dptr(L), dptr(R), st))
+        return ray, spp
+
+    def _psf_lr_grad(self, points, ks, wvln, spp, center, dp, normalize, want_r, default_r_zero, pupil_xy,
+                     center_pupil_xy, out, defer, center_out):
+        """psf_lr under autograd: the staged chain's rays and centres (no gradient: optics.py:459, :888 are no_grad),
+        then the RAW grids through monte_carlo.SplatFunction -- differentiable in h, f, w and, with center=False, in
+        the pinhole centres points[:, :2] * sensor_size / 2 (optics.py:973-976) -- and the max-normalisation of
+        optics.py:983-987 as torch ops, so that its gradient goes to the arg-max pixel as in the reference."""
+        if defer or out is not None or center_out is not None:
+            raise ValueError("defer=True, out= and center_out= are not supported when psf_lr records gradients")
+        self._require_gpu()
+        if not torch.is_tensor(points):
+            points = torch.tensor(points)
+        single_point = points.dim() == 1
+        if single_point:
+            points = points.unsqueeze(0)
+        N = points.shape[0]
+        if not 2 <= ks <= _lib.MAX_KS_STAGED:
+            raise _lib.SdirtError(f"ks={ks} outside [2,{_lib.MAX_KS_STAGED}]")
+        with torch.no_grad():
+            po = self._points_to_object(points.detach())
+            cen = torch.empty((N, 2), dtype=torch.float32, device=self.device)
+            ray, spp = self._staged_rays(points.detach(), po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen)
+        if not center:
+            # the pinhole centres of _pinhole_centres as torch ops on the caller's points: the same fp32 products
+            pts = points.to(self.device, torch.float32)
+            cen = torch.stack((pts[:, 0] * (self.sensor_size[1] / 2), pts[:, 1] * (self.sensor_size[0] / 2)), -1)
+        param_list = None if (dp is None or default_r_zero) else (*dp[:4], "l")
+        L, R = splat_autograd(ray, self.pixel_size, ks, cen, param_list, self.precision)
+        if normalize:
+            L = L / (L.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
+            R = R / (R.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
+        if not want_r:
+            R = None
         return _epilogue(L, R, want_r, single_point)
 
     def psf_rgb(self, points, ks=31, spp=GEO_SPP, center=True, param_list=None, pupil_xy=None,
@@ -1205,11 +1269,13 @@ class Lensgroup:
         if center_pupil_xy is not None and not center:
             raise ValueError("center=False runs no chief-ray pass")
         n_points = points.shape[0] if points.dim() == 2 else 1
-        if n_points > 0 and self.device.type == "cuda" and self.mask_reduce is None and ks <= _lib.MAX_KS:
-            return self._psf_rgb_fused(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy)
-        # not one launch (grids above SDIRT_MAX_KS, or a rank of a sharded run): wavelength by wavelength through
-        # psf_lr, which takes the explicit points of that wavelength on every path
         dp, right = _parse_param_list(param_list)
+        if (n_points > 0 and self.device.type == "cuda" and self.mask_reduce is None and ks <= _lib.MAX_KS
+                and not _psf_needs_grad(dp, points, center)):
+            return self._psf_rgb_fused(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy)
+        # not one launch (grids above SDIRT_MAX_KS, a rank of a sharded run, or a call that records gradients: one
+        # differentiable psf_diff per wavelength, stacked, as optics.py:1010-1014 does): wavelength by wavelength
+        # through psf_lr, which takes the explicit points of that wavelength on every path
         psfs = []
         for i, w in enumerate(WAVE_RGB):
             lr = self.psf_lr(points, ks=ks, wvln=w, spp=spp, center=center, dp=dp, want_r=right,
