@@ -274,24 +274,15 @@ int sdirt_forward_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps
     gl.dwb_dcy = -(double)gm.ksm1 / (double)gm.dy_rng;
     // param_list=None: the R grid is all zero, nothing flows back from it
     const float* gr = dpp.have_r ? grad_r : nullptr;
-    const bool strict = (flags & SDIRT_PSF_STRICT_IEEE) != 0;
     const size_t lds = 2 * sizeof(float) * (size_t)ks * ks;
     const bool stage = lds <= (size_t)kGradLdsBytes;
     const unsigned grid = (unsigned)(N * gl.nslices);
-#define SDIRT_LAUNCH_GRAD(BG, MM, STG)                                                                    \
-    k_forward_integral_grad<BG, MM, STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(rays, S, gm, dpp, q, gl, \
-                                                                                   center, grad_l, gr, partial)
-#define SDIRT_LAUNCH_GRAD_M(BG, STG)                                  \
-    do {                                                              \
-        if (strict) SDIRT_LAUNCH_GRAD(BG, Ieee, STG); else SDIRT_LAUNCH_GRAD(BG, Lean, STG); \
-    } while (0)
-    if (dpp.big) {
-        if (stage) SDIRT_LAUNCH_GRAD_M(true, true); else SDIRT_LAUNCH_GRAD_M(true, false);
-    } else {
-        if (stage) SDIRT_LAUNCH_GRAD_M(false, true); else SDIRT_LAUNCH_GRAD_M(false, false);
-    }
-#undef SDIRT_LAUNCH_GRAD_M
-#undef SDIRT_LAUNCH_GRAD
+    with_bool(dpp.big, [&](auto bg) { return with_bool(stage, [&](auto stg) { return with_math(flags, [&](auto m) {
+        constexpr bool STG = decltype(stg)::value;
+        k_forward_integral_grad<decltype(bg)::value, decltype(m), STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(
+            rays, S, gm, dpp, q, gl, center, grad_l, gr, partial);
+        return 0;
+    }); }); });
     LAUNCH_CHECK();
     return SDIRT_OK;
 }

@@ -9,6 +9,7 @@
 #include <cstdio>
 
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sdirt_dp.h"
@@ -178,6 +179,19 @@ inline sdirt::SplatGeom make_geom(double ps, int ks)
     g.ksm1 = (float)(ks - 1);
     g.ks = ks;
     return g;
+}
+
+// Run-time switches to template arguments, for the launchers that pick one instantiation of a kernel template:
+// f(sdirt::Lean{}) or -- SDIRT_PSF_STRICT_IEEE -- f(sdirt::Ieee{}); f(std::true_type{}) or f(std::false_type{}).
+template <class F>
+inline int with_math(uint32_t flags, F&& f)
+{
+    return (flags & SDIRT_PSF_STRICT_IEEE) ? f(sdirt::Ieee{}) : f(sdirt::Lean{});
+}
+template <class F>
+inline int with_bool(bool b, F&& f)
+{
+    return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
 inline int check_ks(int ks, int max_ks = SDIRT_MAX_KS)

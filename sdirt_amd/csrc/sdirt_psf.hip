@@ -256,6 +256,22 @@ __device__ __forceinline__ void prio_by_work_left(int passes_left)
     else __builtin_amdgcn_s_setprio(0);
 }
 
+// The chief-ray centroid's fp64 sums of a workgroup, each lane's (x * ra, y * ra, ra) stored at red[3][THREADS],
+// added up in a fixed tree order (deterministic): the totals end in red[0], red[THREADS], red[2 * THREADS].
+template <int THREADS>
+__device__ __forceinline__ void reduce_centroid(double* red)
+{
+    __syncthreads();
+    for (int off = THREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            red[threadIdx.x] += red[threadIdx.x + off];
+            red[THREADS + threadIdx.x] += red[THREADS + threadIdx.x + off];
+            red[2 * THREADS + threadIdx.x] += red[2 * THREADS + threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+}
+
 // psf_center: one workgroup per point, Sc rays, fp64 partial sums reduced in a
 // fixed order (deterministic).
 template <class HotMath>
@@ -291,15 +307,7 @@ k_chief_center(TripTable trips /* kernarg offset 0 */, const DevSurface* __restr
     if (by_work_left) __builtin_amdgcn_s_setprio(0);
     red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy; red[2][threadIdx.x] = sr;
     if (any) red_any = 1;
-    __syncthreads();
-    for (int off = kFused / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + off];
-            red[1][threadIdx.x] += red[1][threadIdx.x + off];
-            red[2][threadIdx.x] += red[2][threadIdx.x + off];
-        }
-        __syncthreads();
-    }
+    reduce_centroid<kFused>(&red[0][0]);
     if (threadIdx.x == 0) {
         const float den = (float)red[2][0] + (float)1e-9;
         center[2 * n] = -((float)red[0][0] / den);
@@ -370,15 +378,7 @@ k_chief_slices(TripTable trips /* kernarg offset 0 */, SplitArgs sa, const DevSu
     }
     red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy; red[2][threadIdx.x] = sr;
     if (any) red_any = 1;
-    __syncthreads();
-    for (int off = kFused / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + off];
-            red[1][threadIdx.x] += red[1][threadIdx.x + off];
-            red[2][threadIdx.x] += red[2][threadIdx.x + off];
-        }
-        __syncthreads();
-    }
+    reduce_centroid<kFused>(&red[0][0]);
     if (threadIdx.x == 0) {
         double* o = part + (int64_t)blockIdx.x * 3;
         o[0] = red[0][0]; o[1] = red[1][0]; o[2] = red[2][0];
@@ -433,14 +433,22 @@ __global__ void __launch_bounds__(kBlock) k_pupil_pair(const float* __restrict__
     }
 }
 
+// The trip verdict of round 1: tp and tc ran and left their masks in the control block; the tables round 2 should run
+// go beside them, and status 0 when both were the reference's, else 1 | 2 (tp wrong) | 4 (tc wrong).  One thread.
+__device__ __forceinline__ void verify_round(uint32_t* ctl, const DevSurface* lens, int K, const TripTable& tp,
+                                             const TripTable& tc)
+{
+    const bool okp = verify_trips(tp, ctl + kCtlMask1P, lens, K, ctl + kCtlTrips2P);
+    const bool okc = verify_trips(tc, ctl + kCtlMask1C, lens, K, ctl + kCtlTrips2C);
+    ctl[kCtlStatus] = (okp && okc) ? 0u : (1u | (okp ? 0u : 2u) | (okc ? 0u : 4u));
+}
+
 // The trip rule on the device for a call with one workgroup per point (sdirt_psf_call): round 1's masks stand in the
 // control block; status and the tables a correction would run go beside them.  One thread.
 __global__ void k_ctl_verify(uint32_t* __restrict__ ctl, const DevSurface* __restrict__ lens, int K, TripTable tp, TripTable tc)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const bool okp = verify_trips(tp, ctl + kCtlMask1P, lens, K, ctl + kCtlTrips2P);
-    const bool okc = verify_trips(tc, ctl + kCtlMask1C, lens, K, ctl + kCtlTrips2C);
-    ctl[kCtlStatus] = (okp && okc) ? 0u : (1u | (okp ? 0u : 2u) | (okc ? 0u : 4u));
+    verify_round(ctl, lens, K, tp, tc);
 }
 
 // Round 1's masks and the any-valid flag of a control block as 0 / 1 lanes -- [primary | chief][surface][bit 0..10],
@@ -468,11 +476,7 @@ __global__ void __launch_bounds__(2 * SDIRT_MAX_SURFACES) k_ctl_from_lanes(const
     if (word == 0) ctl[kCtlAnyValid] = lanes[kMaskLanes] != 0 ? 1u : 0u;
     if (word == 1 || word == 2) ctl[SDIRT_CTL_TAG + word - 1] = (uint32_t)lanes[kMaskLanes + word];
     __syncthreads();
-    if (word == 0 && lens) {
-        const bool okp = verify_trips(tp, ctl + kCtlMask1P, lens, K, ctl + kCtlTrips2P);
-        const bool okc = verify_trips(tc, ctl + kCtlMask1C, lens, K, ctl + kCtlTrips2C);
-        ctl[kCtlStatus] = (okp && okc) ? 0u : (1u | (okp ? 0u : 2u) | (okc ? 0u : 4u));
-    }
+    if (word == 0 && lens) verify_round(ctl, lens, K, tp, tc);
 }
 
 // Last kernel of a round of the split path: max-normalise L (blockIdx.y 0) and R (1), and -- round 1
@@ -499,11 +503,7 @@ __global__ void __launch_bounds__(kBlock) k_psf_finish(float* __restrict__ l, fl
         const float den = mx + 1e-6f;
         for (int i = threadIdx.x; i < tile; i += blockDim.x) g[i] = g[i] / den;
     }
-    if (fa.ctl && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-        const bool okp = verify_trips(fa.tp, fa.ctl + kCtlMask1P, fa.lens, fa.K, fa.ctl + kCtlTrips2P);
-        const bool okc = verify_trips(fa.tc, fa.ctl + kCtlMask1C, fa.lens, fa.K, fa.ctl + kCtlTrips2C);
-        fa.ctl[kCtlStatus] = (okp && okc) ? 0u : (1u | (okp ? 0u : 2u) | (okc ? 0u : 4u));
-    }
+    if (fa.ctl && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) verify_round(fa.ctl, fa.lens, fa.K, fa.tp, fa.tc);
 }
 
 // psf_diff fused: sample -> trace -> propagate -> window -> DP weights -> LDS
@@ -542,7 +542,7 @@ struct TripSet {
 // ACC = the accumulator type of the LDS tiles.  float: ds_add_f32, which gfx950 executes lane by lane (~193 cycles
 // of the CU's LDS per wave instruction whatever the addresses, profiles/r04/lds_atomic_bench.txt); double:
 // ds_add_f64 (17-33 cycles), the sum rounded to fp32 once on the way out like k_forward_integral_tiles -- chosen by
-// launch_psf whenever the double tiles still leave room for four workgroups per CU (L + R: ks <= 49).
+// plan_psf whenever the double tiles still leave room for four workgroups per CU (L + R: ks <= 49).
 // THREADS = 1024 (SDIRT_PSF_DETERMINISTIC on grids of 50 to 70 pixels): double tiles in workgroups of 16 waves, two per
 // CU -- the same 8 waves per SIMD; a workgroup waits at its barriers for the slowest of 16 waves: +0.5 % (profiles/r05/ab_tiles.txt).
 template <bool HAVE_R, bool BIG, class HotMath, bool CENTER, class ACC, int THREADS = kFused>
@@ -745,6 +745,279 @@ static int last_generation_from(int64_t blocks)
     return (int)std::max<int64_t>(0, blocks - 4ll * device_cus_or_default());
 }
 
+constexpr size_t kWideTilesMax = 39 * 1024;
+
+static int spp_split(int64_t N, int64_t S, int* chunk_out, int n_cus = 0)
+{
+    // Fill the chip: at least ~4 workgroups per CU; split the spp axis when the
+    // number of points alone cannot (e.g. PSFNet training: N=64, S=20000).
+    int nsplit = 1;
+    const int64_t want_blocks = (int64_t)(n_cus > 0 ? n_cus : device_cus_or_default()) * 4;
+    if (N < want_blocks && S > 2 * kFused) {
+        nsplit = (int)((want_blocks + N - 1) / N);
+        const int max_split = (int)((S + 2 * kFused - 1) / (2 * kFused));
+        if (nsplit > max_split) nsplit = max_split;
+        if (nsplit < 1) nsplit = 1;
+    }
+    // slices of equal length up to a wave: a slice rounded up to whole workgroup passes (512) left the
+    // last slice nearly empty and the CUs unevenly loaded (20000 spp: 13 x 1536 + 32 -> 16 x 1280, 17 % faster)
+    int chunk = (int)((S + nsplit - 1) / nsplit);
+    chunk = ((chunk + 63) / 64) * 64;
+    nsplit = (int)((S + chunk - 1) / (chunk > 0 ? chunk : 1));
+    if (nsplit < 1) nsplit = 1;
+    if (chunk_out) *chunk_out = chunk;
+    return nsplit;
+}
+
+// The chief-ray pass of the split path in slices: enough workgroups to touch every CU, at least
+// one ray per lane and slice.
+static int chief_slices(int64_t N, int64_t Sc, int* chunk_out)
+{
+    int64_t ns = std::min<int64_t>((Sc + kFused - 1) / kFused,
+                                   (device_cus_or_default() + N - 1) / std::max<int64_t>(N, 1));
+    if (ns < 1) ns = 1;
+    int chunk = (int)((Sc + ns - 1) / ns);
+    chunk = (chunk + 63) / 64 * 64;
+    if (chunk < 64) chunk = 64;
+    ns = (Sc + chunk - 1) / chunk;
+    if (ns < 1) ns = 1;
+    if (chunk_out) *chunk_out = chunk;
+    return (int)ns;
+}
+
+// k_psf_lr's LDS tiles: float or double accumulators in workgroups of kFused, double ones in workgroups of
+// 2 * kFused (SDIRT_PSF_DETERMINISTIC), float ones for the big-radius microlens branch
+enum class Tiles { Float, Double, Double1024, BigFloat };
+
+// One PSF call: the entry point's arguments, checked (check_psf_args), and how k_psf_lr runs them (plan_psf).
+// W wavelength slots (W > 1 needs nsplit == 1): lens[w], trips[w], x2 / y2 [W][S], outputs [N][W][ks][ks], masks
+// [W][SDIRT_MAX_SURFACES].  A chief-ray pass (`centered`) runs inside k_psf_lr when one workgroup owns a point
+// (`fused`), as a launch of its own before it otherwise.
+struct PsfLaunch {
+    LensSet ls;
+    TripSet tt, ttc;                 // primary and chief-ray trip tables
+    int W, K, ks;
+    int64_t N, S;
+    const float* po;
+    const float* x2;
+    const float* y2;
+    float pz, zs;
+    uint32_t flags;
+    const float* center;
+    CenterArgs ca;                   // the chief-ray pass: xc / yc [W][Sc], center_out [W][N][2]
+    bool centered;
+    float* l;
+    float* r;
+    uint32_t* conv_mask;
+    SplitArgs sa;
+    hipStream_t st;
+    // the plan
+    SplatBlock sblk;
+    DevDpParams dpp;
+    bool both, interleaved, fused;
+    int nsplit, chunk, threads;
+    Tiles tiles;
+    size_t lds_bytes;
+    int64_t pstride;
+};
+
+// What the PSF entry points share: pointers, sizes, the W primary lens tables (the surface count of lens_c if
+// there is one, else of lens[0]), ks, dp and the trip tables.  primary = false: the chief-ray pass alone
+// (sdirt_chief_center: no x2 / y2 / l_psf, no ks or dp).
+static int check_psf_args(PsfLaunch& L, bool primary, const sdirt_lens* const* lens, int W, const sdirt_lens* lens_c,
+                          const float* point_obj, int64_t N, const float* x2, const float* y2, int64_t S,
+                          const float* xc, const float* yc, int64_t Sc, double pupil_z, double d_sensor, int ks,
+                          const sdirt_dp_params* dp, const int32_t* trips, const int32_t* trips_c, const float* center,
+                          const float* l_psf)
+{
+    if (!point_obj || !center || N < 0 || N > (1ll << 30) ||
+        (primary && (!lens || W < 1 || W > SDIRT_MAX_WAVELENGTHS || !x2 || !y2 || !l_psf || S < 0 || S > (1ll << 30))) ||
+        (lens_c && (!xc || !yc || Sc < 0 || Sc > (1ll << 30))) || (!primary && !lens_c))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    const sdirt_lens* ref = lens_c ? lens_c : lens[0];
+    for (int w = 0; primary && w < W; ++w)
+        if (!lens[w] || lens[w]->n_surfaces != ref->n_surfaces)
+            return fail(SDIRT_ERR_INVALID_ARGUMENT, "lens[%d] missing or surface count differs from %s", w,
+                        lens_c ? "lens_center" : "lens[0]");
+    if (primary) {
+        if (int rc = check_ks(ks)) return rc;
+        if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
+    }
+    const int K = ref->n_surfaces;
+    L = PsfLaunch{};
+    for (int w = 0; primary && w < W; ++w) {
+        L.ls.p[w] = lens[w]->dev;
+        if (int rc = make_trips(lens[w], trips ? trips + (size_t)w * K : nullptr, L.tt.t[w])) return rc;
+    }
+    for (int w = 0; lens_c && w < std::max(W, 1); ++w)
+        if (int rc = make_trips(lens_c, trips_c ? trips_c + (size_t)w * K : nullptr, L.ttc.t[w])) return rc;
+    L.W = W; L.K = K; L.ks = ks; L.N = N; L.S = S;
+    L.po = point_obj; L.x2 = x2; L.y2 = y2; L.pz = (float)pupil_z; L.zs = (float)d_sensor; L.center = center;
+    if (lens_c) {
+        L.centered = true;
+        L.ca.lens_c = lens_c->dev; L.ca.xc = xc; L.ca.yc = yc; L.ca.Sc = (int)Sc;
+    }
+    return SDIRT_OK;
+}
+
+// The launch plan of a checked call: spp slices, the tile form, LDS and workgroup size -- or the refusal of
+// SDIRT_PSF_INTERLEAVED / SDIRT_PSF_DETERMINISTIC.
+static int plan_psf(PsfLaunch& L, double ps, const sdirt_dp_params* dp, uint32_t flags, float* l_psf, float* r_psf,
+                    uint32_t* conv_mask, void* stream)
+{
+    const int tile = L.ks * L.ks;
+    L.flags = flags; L.l = l_psf; L.r = r_psf; L.conv_mask = conv_mask; L.st = as_stream(stream);
+    // SDIRT_PSF_INTERLEAVED: l_psf / r_psf are the two halves of ONE [N, 2, ks, ks] array
+    L.interleaved = (flags & SDIRT_PSF_INTERLEAVED) != 0;
+    if (L.interleaved && (L.W != 1 || !dp || !r_psf || r_psf != l_psf + tile))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "SDIRT_PSF_INTERLEAVED: one wavelength, dp != NULL and r_psf == l_psf + ks * ks "
+                                                "(the two halves of one [N, 2, ks, ks] array)");
+    L.pstride = L.interleaved ? 2 * (int64_t)tile : (int64_t)L.W * tile;
+    if ((int64_t)L.W * tile > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "grids too large");
+    // a multi-wavelength launch keeps one workgroup per (point, wavelength): the chief-ray pass
+    // stays fused and the whole of psf_rgb is one kernel, also for the few points of a psf_map
+    L.chunk = ((int)L.S + kFused - 1) / kFused * kFused;
+    L.nsplit = L.W > 1 ? 1 : spp_split(L.N, L.S, &L.chunk);
+    L.fused = L.centered && L.nsplit == 1;
+    L.dpp = make_dp(dp);
+    L.sblk = make_splat_block(make_geom(ps, L.ks), L.dpp);
+    L.both = r_psf != nullptr && L.dpp.have_r;
+    // double accumulators (ACC of k_psf_lr) whenever they leave room for four workgroups per CU, i.e. for the
+    // kernel's 8 waves per SIMD: 4 x (39 KiB + 0.4 KiB of static LDS) <= 160 KiB -- L + R up to ks 49, L alone up to 70
+    const size_t n_acc = (size_t)tile * (L.both ? 2 : 1);
+    // the corner-clipped microlens branch runs at 4 waves per SIMD whatever the tiles: float tiles only
+    L.tiles = L.dpp.big ? Tiles::BigFloat : sizeof(double) * n_acc <= kWideTilesMax ? Tiles::Double : Tiles::Float;
+    // SDIRT_PSF_DETERMINISTIC: double tiles also where only TWO workgroups per CU have room for them (L + R up to ks 70)
+    // -- those then have 1024 threads; beyond that (or with the spp axis cut: partial grids meet in global float
+    // atomics) there is no order-independent sum to offer
+    if ((flags & SDIRT_PSF_DETERMINISTIC) && L.tiles != Tiles::Double) {
+        if (L.dpp.big || L.nsplit > 1 || sizeof(double) * n_acc > 2 * kWideTilesMax)
+            return fail(SDIRT_ERR_UNSUPPORTED, "SDIRT_PSF_DETERMINISTIC: float64 tiles need ks <= 70 (L + R; L alone: 99), r <= 0.5 and "
+                                               "one workgroup per point (sdirt_psf_spp_slices == 1)");
+        L.tiles = Tiles::Double1024;
+    }
+    if ((flags & SDIRT_PSF_DETERMINISTIC) && L.nsplit > 1)
+        return fail(SDIRT_ERR_UNSUPPORTED, "SDIRT_PSF_DETERMINISTIC: the spp axis is cut for this batch (sdirt_psf_spp_slices > 1): "
+                                           "partial grids are added with global float atomics");
+    L.threads = L.tiles == Tiles::Double1024 ? 2 * kFused : kFused;
+    L.lds_bytes = (L.tiles == Tiles::Float || L.tiles == Tiles::BigFloat ? sizeof(float) : sizeof(double)) * n_acc;
+    if (L.fused) L.lds_bytes = std::max(L.lds_bytes, sizeof(double) * 3 * L.threads);  // fp64 reduction scratch
+    return SDIRT_OK;
+}
+
+template <bool HAVE_R, bool BIG, class M, bool CENTER, class ACC, int THREADS>
+static int launch_psf_lr_as(const PsfLaunch& L)
+{
+    constexpr auto kernel = &k_psf_lr<HAVE_R, BIG, M, CENTER, ACC, THREADS>;
+    if (L.lds_bytes > 48 * 1024)        // large tiles: opt in to the full 160 KiB of LDS
+        if (int rc = allow_large_lds<kernel>()) return rc;
+    const dim3 grid((unsigned)(L.N * L.nsplit), (unsigned)L.W);
+    kernel<<<grid, THREADS, L.lds_bytes, L.st>>>(
+        L.sblk, L.tt, L.ttc, L.ls, L.K, L.po, L.x2, L.y2, (int)L.S, L.nsplit, L.chunk, L.pz,
+        L.zs, L.ks, (int)L.pstride, L.dpp.tr, L.dpp.tl, L.center, L.flags, L.l, L.both ? L.r : nullptr, L.conv_mask,
+        L.ca, L.sa, last_generation_from((int64_t)grid.x * grid.y));
+    return SDIRT_OK;
+}
+
+// The one of k_psf_lr's 32 instantiations the plan asks for: tile form x HAVE_R x math x CENTER
+static int launch_psf_lr(const PsfLaunch& L)
+{
+    return with_bool(L.both, [&](auto hr) { return with_bool(L.fused, [&](auto ct) { return with_math(L.flags, [&](auto m) {
+        constexpr bool HR = decltype(hr)::value, CT = decltype(ct)::value;
+        using M = decltype(m);
+        switch (L.tiles) {
+        case Tiles::Float: return launch_psf_lr_as<HR, false, M, CT, float, kFused>(L);
+        case Tiles::Double: return launch_psf_lr_as<HR, false, M, CT, double, kFused>(L);
+        case Tiles::Double1024: return launch_psf_lr_as<HR, false, M, CT, double, 2 * kFused>(L);
+        case Tiles::BigFloat: break;
+        }
+        return launch_psf_lr_as<HR, true, M, CT, float, kFused>(L);
+    }); }); });
+}
+
+static int launch_chief_center(const PsfLaunch& L)
+{
+    with_math(L.flags, [&](auto m) {
+        k_chief_center<decltype(m)><<<(int)L.N, kFused, 0, L.st>>>(
+            L.ttc.t[0], L.ca.lens_c, L.K, L.po, L.ca.xc, L.ca.yc, L.ca.Sc, L.pz, L.zs, L.ca.center_out, L.ca.any_valid,
+            L.ca.conv_mask_c, last_generation_from(L.N));
+        return 0;
+    });
+    LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+
+// Uncentred, fused-centre and split-centre calls: [k_chief_center ->] k_psf_lr [-> normalisation].
+static int launch_psf(PsfLaunch& L)
+{
+    const int tile = L.ks * L.ks;
+    if (L.centered && !L.fused) {                // split spp axis: centre as its own launch
+        if (int rc = launch_chief_center(L)) return rc;
+        L.center = L.ca.center_out;
+    }
+    if (L.nsplit > 1) {
+        HIP_TRY(hipMemsetAsync(L.l, 0, sizeof(float) * (size_t)L.N * tile * (L.interleaved ? 2 : 1), L.st));
+        if (L.r && !L.interleaved) HIP_TRY(hipMemsetAsync(L.r, 0, sizeof(float) * (size_t)L.N * tile, L.st));
+    }
+    if (int rc = launch_psf_lr(L)) return rc;
+    LAUNCH_CHECK();
+    // param_list=None leaves the R grid all-zero (monte_carlo.py:230-235)
+    if (!L.both && L.r) HIP_TRY(hipMemsetAsync(L.r, 0, sizeof(float) * (size_t)L.N * L.W * tile, L.st));
+    if (L.nsplit > 1 && (L.flags & SDIRT_PSF_NORMALIZE)) {
+        launch_normalize(L.l, L.N, tile, L.st, L.pstride);
+        if (L.both) launch_normalize(L.r, L.N, tile, L.st, L.pstride);
+        LAUNCH_CHECK();
+    }
+    return SDIRT_OK;
+}
+
+// A verified call on the split path, scratch = control block (zeroed by the caller) + chief-ray partial sums: round 1
+// with the speculated tables, the tables checked on the device by the round's last kernel, round 2 with the corrected
+// tables enqueued right behind it -- its kernels return at once when round 1 was right.  No host round trip in between.
+// A round is k_chief_slices -> k_psf_lr -> k_psf_finish.
+static int launch_psf_verified(PsfLaunch& L, uint32_t* ctl, double* part)
+{
+    if (L.nsplit == 1)
+        return fail(SDIRT_ERR_UNSUPPORTED, "verified call: one workgroup per point here (sdirt_psf_spp_slices == 1); "
+                                           "use sdirt_psf_lr_centered");
+    const int tile = L.ks * L.ks;
+    int chunk_c = 0;
+    const int nslice_c = chief_slices(L.N, L.ca.Sc, &chunk_c);
+    float* zr = (L.both && !L.interleaved) ? L.r : nullptr;      // interleaved: one run of N * 2 * tile floats
+    const int64_t zn = L.N * tile * (L.interleaved ? 2 : 1);
+    L.center = nullptr;
+    L.sa.part = part;
+    L.sa.nslice = nslice_c;
+    const int rounds = (L.flags & SDIRT_PSF_ONE_ROUND) ? 1 : 2;
+    for (int round = 0; round < rounds; ++round) {
+        L.sa.gate = round ? ctl : nullptr;
+        L.sa.trips_dev = round ? ctl + kCtlTrips2C : nullptr;
+        uint32_t* mask_c = ctl + (round ? kCtlMask2C : kCtlMask1C);
+        with_math(L.flags, [&](auto m) {
+            k_chief_slices<decltype(m)><<<(int)(L.N * nslice_c), kFused, 0, L.st>>>(
+                L.ttc.t[0], L.sa, L.ca.lens_c, L.K, L.po, L.ca.xc, L.ca.yc, L.ca.Sc, chunk_c, L.pz, L.zs, part,
+                ctl + kCtlAnyValid, mask_c, L.l, zr, zn);
+            return 0;
+        });
+        LAUNCH_CHECK();
+        L.sa.trips_dev = round ? ctl + kCtlTrips2P : nullptr;
+        L.conv_mask = ctl + (round ? kCtlMask2P : kCtlMask1P);
+        if (int rc = launch_psf_lr(L)) return rc;
+        LAUNCH_CHECK();
+        FinishArgs fa;
+        std::memset(&fa, 0, sizeof(fa));
+        fa.gate = round ? ctl : nullptr;
+        fa.ctl = round ? nullptr : ctl;
+        fa.lens = L.ls.p[0]; fa.K = L.K; fa.tp = L.tt.t[0]; fa.tc = L.ttc.t[0];
+        k_psf_finish<<<dim3((unsigned)L.N, L.both ? 2u : 1u), kBlock, 0, L.st>>>(
+            L.l, L.r, tile, L.pstride, (L.flags & SDIRT_PSF_NORMALIZE) ? 1 : 0, fa);
+        LAUNCH_CHECK();
+    }
+    // param_list=None leaves the R grid all-zero (monte_carlo.py:230-235)
+    if (!L.both && L.r) HIP_TRY(hipMemsetAsync(L.r, 0, sizeof(float) * (size_t)L.N * tile, L.st));
+    return SDIRT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -807,7 +1080,6 @@ int sdirt_forward_integral(sdirt_rays rays, int64_t S, int64_t N, double ps, int
     const size_t bytes = sizeof(float) * (size_t)N * ks * ks;
     const DevDpParams dpp = make_dp(dp);
     const bool both = r_grid != nullptr && dpp.have_r;
-    const bool strict = (flags & SDIRT_PSF_STRICT_IEEE) != 0;
     FiLaunch fl;
     int ncu = 0;
     if (int rc = device_cus(&ncu)) return rc;
@@ -832,30 +1104,18 @@ int sdirt_forward_integral(sdirt_rays rays, int64_t S, int64_t N, double ps, int
     }
     const size_t lds_bytes = (wide ? sizeof(double) : sizeof(float)) * (size_t)fl.P * fl.stride;
     const unsigned grid = (unsigned)fl.ngroups * (unsigned)fl.nsplit;
-#define SDIRT_LAUNCH_FI_M(HR, BG, AC, MM)                                                         \
-    do {                                                                                          \
-        if (lds_bytes > 48 * 1024)                                                                \
-            if (int rc_ = allow_large_lds<&k_forward_integral_tiles<HR, BG, AC, MM>>()) return rc_; \
-        k_forward_integral_tiles<HR, BG, AC, MM><<<grid, kFiThreads, lds_bytes, st>>>(            \
-            rays, S, N, make_geom(ps, ks), dpp, fl, center, l_grid, both ? r_grid : nullptr,      \
-            (flags & SDIRT_PSF_NORMALIZE) ? 1 : 0);                                               \
-    } while (0)
-#define SDIRT_LAUNCH_FI_A(HR, BG, AC)                                                             \
-    do {                                                                                          \
-        if (strict) SDIRT_LAUNCH_FI_M(HR, BG, AC, Ieee); else SDIRT_LAUNCH_FI_M(HR, BG, AC, Lean); \
-    } while (0)
-#define SDIRT_LAUNCH_FI(HR, BG)                                                                   \
-    do {                                                                                          \
-        if (wide) SDIRT_LAUNCH_FI_A(HR, BG, double); else SDIRT_LAUNCH_FI_A(HR, BG, float);       \
-    } while (0)
-    if (both) {
-        if (dpp.big) SDIRT_LAUNCH_FI(true, true); else SDIRT_LAUNCH_FI(true, false);
-    } else {
-        if (dpp.big) SDIRT_LAUNCH_FI(false, true); else SDIRT_LAUNCH_FI(false, false);
-    }
-#undef SDIRT_LAUNCH_FI_A
-#undef SDIRT_LAUNCH_FI_M
-#undef SDIRT_LAUNCH_FI
+    const int rc = with_bool(both, [&](auto hr) { return with_bool(dpp.big, [&](auto bg) {
+        return with_bool(wide, [&](auto wd) { return with_math(flags, [&](auto m) -> int {
+            constexpr auto kernel = &k_forward_integral_tiles<decltype(hr)::value, decltype(bg)::value,
+                                                              std::conditional_t<decltype(wd)::value, double, float>, decltype(m)>;
+            if (lds_bytes > 48 * 1024)
+                if (int rc_ = allow_large_lds<kernel>()) return rc_;
+            kernel<<<grid, kFiThreads, lds_bytes, st>>>(rays, S, N, make_geom(ps, ks), dpp, fl, center, l_grid,
+                                                        both ? r_grid : nullptr, normalize ? 1 : 0);
+            return SDIRT_OK;
+        }); });
+    }); });
+    if (rc) return rc;
     if (normalize && fl.nsplit > 1) {          // the partial tiles have only just been added up in HBM
         launch_normalize(l_grid, N, ks * ks, st);
         if (both) launch_normalize(r_grid, N, ks * ks, st);
@@ -879,259 +1139,14 @@ int sdirt_chief_center(const sdirt_lens* lens, const float* point_obj, int64_t N
                        const int32_t* trips, uint32_t flags, float* center, int32_t* any_valid,
                        uint32_t* conv_mask, void* stream)
 {
-    if (!lens || !point_obj || !xc || !yc || !center || N < 0 || Sc < 0 || Sc > (1ll << 30))
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
-    TripTable tt;
-    if (int rc = make_trips(lens, trips, tt)) return rc;
+    PsfLaunch L;
+    if (int rc = check_psf_args(L, false, nullptr, 0, lens, point_obj, N, nullptr, nullptr, 0, xc, yc, Sc, pupil_z,
+                                d_sensor, 0, nullptr, nullptr, trips, center, nullptr))
+        return rc;
     if (N == 0) return SDIRT_OK;
-    if (!(flags & SDIRT_PSF_STRICT_IEEE))
-        k_chief_center<Lean><<<(int)N, kFused, 0, as_stream(stream)>>>(
-            tt, lens->dev, lens->n_surfaces, point_obj, xc, yc, (int)Sc, (float)pupil_z,
-            (float)d_sensor, center, any_valid, conv_mask, last_generation_from(N));
-    else
-        k_chief_center<Ieee><<<(int)N, kFused, 0, as_stream(stream)>>>(
-            tt, lens->dev, lens->n_surfaces, point_obj, xc, yc, (int)Sc, (float)pupil_z,
-            (float)d_sensor, center, any_valid, conv_mask, last_generation_from(N));
-    LAUNCH_CHECK();
-    return SDIRT_OK;
-}
-
-// Shared launcher of sdirt_psf_lr / sdirt_psf_lr_centered / sdirt_psf_rgb_centered.  `cen` != nullptr
-// requests the chief-ray pass: inside the same kernel when one workgroup owns a point (nsplit ==
-// 1), as a preceding k_chief_center launch otherwise.  W wavelength slots (W > 1 needs nsplit == 1):
-// lens[w], trips[w], x2 / y2 [W][S], outputs [N][W][ks][ks], masks [W][SDIRT_MAX_SURFACES].
-struct CenterRequest {
-    const sdirt_lens* lens_c;
-    const float* xc;              // [W][Sc]
-    const float* yc;
-    int64_t Sc;
-    TripSet trips_c;
-    float* center_out;            // [W][N][2]
-    int32_t* any_valid;           // [W]
-    uint32_t* conv_mask_c;        // [W][SDIRT_MAX_SURFACES]
-};
-
-constexpr size_t kWideTilesMax = 39 * 1024;
-
-
-static int spp_split(int64_t N, int64_t S, int* chunk_out, int n_cus = 0)
-{
-    // Fill the chip: at least ~4 workgroups per CU; split the spp axis when the
-    // number of points alone cannot (e.g. PSFNet training: N=64, S=20000).
-    int nsplit = 1;
-    const int64_t want_blocks = (int64_t)(n_cus > 0 ? n_cus : device_cus_or_default()) * 4;
-    if (N < want_blocks && S > 2 * kFused) {
-        nsplit = (int)((want_blocks + N - 1) / N);
-        const int max_split = (int)((S + 2 * kFused - 1) / (2 * kFused));
-        if (nsplit > max_split) nsplit = max_split;
-        if (nsplit < 1) nsplit = 1;
-    }
-    // slices of equal length up to a wave: a slice rounded up to whole workgroup passes (512) left the
-    // last slice nearly empty and the CUs unevenly loaded (20000 spp: 13 x 1536 + 32 -> 16 x 1280, 17 % faster)
-    int chunk = (int)((S + nsplit - 1) / nsplit);
-    chunk = ((chunk + 63) / 64) * 64;
-    nsplit = (int)((S + chunk - 1) / (chunk > 0 ? chunk : 1));
-    if (nsplit < 1) nsplit = 1;
-    if (chunk_out) *chunk_out = chunk;
-    return nsplit;
-}
-
-// Device scratch of a verified call: the control block, then the chief-ray partial sums.
-struct VerifiedRequest {
-    uint32_t* ctl;     // [SDIRT_CTL_WORDS], zeroed by the caller
-    double* part;      // [N][chief slices][3]
-};
-
-// The chief-ray pass of the split path in slices: enough workgroups to touch every CU, at least
-// one ray per lane and slice.
-static int chief_slices(int64_t N, int64_t Sc, int* chunk_out)
-{
-    int64_t ns = std::min<int64_t>((Sc + kFused - 1) / kFused,
-                                   (device_cus_or_default() + N - 1) / std::max<int64_t>(N, 1));
-    if (ns < 1) ns = 1;
-    int chunk = (int)((Sc + ns - 1) / ns);
-    chunk = (chunk + 63) / 64 * 64;
-    if (chunk < 64) chunk = 64;
-    ns = (Sc + chunk - 1) / chunk;
-    if (ns < 1) ns = 1;
-    if (chunk_out) *chunk_out = chunk;
-    return (int)ns;
-}
-
-static int launch_psf(const sdirt_lens* const* lens, int W, const float* point_obj, int64_t N,
-                      const float* x2, const float* y2, int64_t S, double pupil_z, double d_sensor,
-                      double ps, int32_t ks, const float* center, const CenterRequest* cen,
-                      const sdirt_dp_params* dp, const TripSet& tt, uint32_t flags, float* l_psf,
-                      float* r_psf, uint32_t* conv_mask, void* stream, const VerifiedRequest* vr = nullptr)
-{
-    const bool have_r = r_psf != nullptr;
-    const int tile = ks * ks;
-    // SDIRT_PSF_INTERLEAVED: l_psf / r_psf are the two halves of ONE [N, 2, ks, ks] array
-    const bool interleaved = (flags & SDIRT_PSF_INTERLEAVED) != 0;
-    if (interleaved && (W != 1 || !dp || !r_psf || r_psf != l_psf + tile))
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "SDIRT_PSF_INTERLEAVED: one wavelength, dp != NULL and r_psf == l_psf + ks * ks "
-                                                "(the two halves of one [N, 2, ks, ks] array)");
-    const int64_t pstride = interleaved ? 2 * (int64_t)tile : (int64_t)W * tile;
-    if ((int64_t)W * tile > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "grids too large");
-    // a multi-wavelength launch keeps one workgroup per (point, wavelength): the chief-ray pass
-    // stays fused and the whole of psf_rgb is one kernel, also for the few points of a psf_map
-    int chunk = ((int)S + kFused - 1) / kFused * kFused;
-    const int nsplit = W > 1 ? 1 : spp_split(N, S, &chunk);
-    const int K = lens[0]->n_surfaces;
-
-    hipStream_t st = as_stream(stream);
-    const bool lean = (flags & SDIRT_PSF_STRICT_IEEE) == 0;
-    const bool fuse_center = cen != nullptr && nsplit == 1;
-    if (vr && (!cen || nsplit == 1 || W != 1))
-        return fail(SDIRT_ERR_UNSUPPORTED, "verified call: one workgroup per point here (sdirt_psf_spp_slices == 1); "
-                                           "use sdirt_psf_lr_centered");
-    if (cen && !fuse_center && !vr) {                // split spp axis: centre as its own launch
-        if (lean)
-            k_chief_center<Lean><<<(int)N, kFused, 0, st>>>(
-                cen->trips_c.t[0], cen->lens_c->dev, K, point_obj, cen->xc, cen->yc, (int)cen->Sc,
-                (float)pupil_z, (float)d_sensor, cen->center_out, cen->any_valid, cen->conv_mask_c, last_generation_from(N));
-        else
-            k_chief_center<Ieee><<<(int)N, kFused, 0, st>>>(
-                cen->trips_c.t[0], cen->lens_c->dev, K, point_obj, cen->xc, cen->yc, (int)cen->Sc,
-                (float)pupil_z, (float)d_sensor, cen->center_out, cen->any_valid, cen->conv_mask_c, last_generation_from(N));
-        LAUNCH_CHECK();
-        center = cen->center_out;
-    }
-    if (nsplit > 1 && !vr) {
-        HIP_TRY(hipMemsetAsync(l_psf, 0, sizeof(float) * (size_t)N * tile * (interleaved ? 2 : 1), st));
-        if (have_r && !interleaved) HIP_TRY(hipMemsetAsync(r_psf, 0, sizeof(float) * (size_t)N * tile, st));
-    }
-    const SplatGeom gm = make_geom(ps, ks);
-    const DevDpParams dpp = make_dp(dp);
-    const SplatBlock sblk = make_splat_block(gm, dpp);
-    const dim3 grid((unsigned)(N * nsplit), (unsigned)W);
-    const bool both = have_r && dpp.have_r;
-    // double accumulators (ACC of k_psf_lr) whenever they leave room for four workgroups per CU, i.e. for the
-    // kernel's 8 waves per SIMD: 4 x (39 KiB + 0.4 KiB of static LDS) <= 160 KiB -- L + R up to ks 49, L alone up to 70
-    const size_t n_acc = (size_t)tile * (both ? 2 : 1);
-    bool wide = !dpp.big && sizeof(double) * n_acc <= kWideTilesMax;
-    // SDIRT_PSF_DETERMINISTIC: double tiles also where only TWO workgroups per CU have room for them (L + R up to ks 70)
-    // -- those then have 1024 threads; beyond that (or with the spp axis cut: partial grids meet in global float
-    // atomics) there is no order-independent sum to offer
-    bool wide1024 = false;
-    if ((flags & SDIRT_PSF_DETERMINISTIC) && !wide) {
-        if (dpp.big || nsplit > 1 || sizeof(double) * n_acc > 2 * kWideTilesMax)
-            return fail(SDIRT_ERR_UNSUPPORTED, "SDIRT_PSF_DETERMINISTIC: float64 tiles need ks <= 70 (L + R; L alone: 99), r <= 0.5 and "
-                                               "one workgroup per point (sdirt_psf_spp_slices == 1)");
-        wide = wide1024 = true;
-    }
-    if ((flags & SDIRT_PSF_DETERMINISTIC) && nsplit > 1)
-        return fail(SDIRT_ERR_UNSUPPORTED, "SDIRT_PSF_DETERMINISTIC: the spp axis is cut for this batch (sdirt_psf_spp_slices > 1): "
-                                           "partial grids are added with global float atomics");
-    const int threads = wide1024 ? 2 * kFused : kFused;
-    size_t lds_bytes = (wide ? sizeof(double) : sizeof(float)) * n_acc;
-    CenterArgs ca;
-    TripSet ttc;
-    LensSet ls;
-    std::memset(&ca, 0, sizeof(ca));
-    std::memset(&ttc, 0, sizeof(ttc));
-    std::memset(&ls, 0, sizeof(ls));
-    for (int w = 0; w < W; ++w) ls.p[w] = lens[w]->dev;
-    if (fuse_center) {
-        ca.lens_c = cen->lens_c->dev; ttc = cen->trips_c; ca.xc = cen->xc; ca.yc = cen->yc;
-        ca.Sc = (int)cen->Sc; ca.center_out = cen->center_out; ca.any_valid = cen->any_valid;
-        ca.conv_mask_c = cen->conv_mask_c;
-        lds_bytes = std::max(lds_bytes, sizeof(double) * 3 * threads);  // fp64 reduction scratch
-    }
-    SplitArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    // ---- verified call on the split path: round 1 with the speculated tables, the tables checked on
-    // the device by the round's last kernel, round 2 with the corrected tables enqueued right behind
-    // it -- its kernels return at once when round 1 was right.  No host round trip in between.
-    const int rounds = (vr && !(flags & SDIRT_PSF_ONE_ROUND)) ? 2 : 1;
-    int chunk_c = 0;
-    const int nslice_c = vr ? chief_slices(N, cen->Sc, &chunk_c) : 0;
-    for (int round = 0; round < rounds; ++round) {
-    if (vr) {
-        uint32_t* ctl = vr->ctl;
-        sa.gate = round ? ctl : nullptr;
-        sa.part = vr->part;
-        sa.nslice = nslice_c;
-        sa.trips_dev = round ? ctl + kCtlTrips2C : nullptr;
-        uint32_t* mask_c = ctl + (round ? kCtlMask2C : kCtlMask1C);
-        float* zr = (both && !interleaved) ? r_psf : nullptr;      // interleaved: one run of N * 2 * tile floats
-        const int64_t zn = (int64_t)N * tile * (interleaved ? 2 : 1);
-        if (lean)
-            k_chief_slices<Lean><<<(int)(N * nslice_c), kFused, 0, st>>>(
-                cen->trips_c.t[0], sa, cen->lens_c->dev, K, point_obj, cen->xc, cen->yc, (int)cen->Sc, chunk_c,
-                (float)pupil_z, (float)d_sensor, vr->part, ctl + kCtlAnyValid, mask_c, l_psf, zr, zn);
-        else
-            k_chief_slices<Ieee><<<(int)(N * nslice_c), kFused, 0, st>>>(
-                cen->trips_c.t[0], sa, cen->lens_c->dev, K, point_obj, cen->xc, cen->yc, (int)cen->Sc, chunk_c,
-                (float)pupil_z, (float)d_sensor, vr->part, ctl + kCtlAnyValid, mask_c, l_psf, zr, zn);
-        LAUNCH_CHECK();
-        sa.trips_dev = round ? ctl + kCtlTrips2P : nullptr;
-        conv_mask = ctl + (round ? kCtlMask2P : kCtlMask1P);
-        ca.center_out = cen->center_out;
-        center = nullptr;
-    }
-#define SDIRT_LAUNCH_PSF_T(HR, BG, MM, CT, AC, TH)                                                \
-    do {                                                                                          \
-        if (lds_bytes > 48 * 1024) /* large tiles: opt in to the full 160 KiB of LDS */           \
-            if (int rc_ = allow_large_lds<&k_psf_lr<HR, BG, MM, CT, AC, TH>>()) return rc_;       \
-        k_psf_lr<HR, BG, MM, CT, AC, TH><<<grid, TH, lds_bytes, st>>>(                            \
-            sblk, tt, ttc, ls, K, point_obj, x2, y2, (int)S, nsplit, chunk, (float)pupil_z,       \
-            (float)d_sensor, ks, (int)pstride, dpp.tr, dpp.tl, center, flags, l_psf,              \
-            both ? r_psf : nullptr,                                                               \
-            conv_mask, ca, sa, last_generation_from((int64_t)grid.x * grid.y));                   \
-    } while (0)
-#define SDIRT_LAUNCH_PSF(HR, BG, MM, CT, AC) SDIRT_LAUNCH_PSF_T(HR, BG, MM, CT, AC, kFused)
-#define SDIRT_LAUNCH_PSF_W(HR, MM)                                                                \
-    do {                                                                                          \
-        if (fuse_center) SDIRT_LAUNCH_PSF_T(HR, false, MM, true, double, 2 * kFused);             \
-        else SDIRT_LAUNCH_PSF_T(HR, false, MM, false, double, 2 * kFused);                        \
-    } while (0)
-#define SDIRT_LAUNCH_PSF_C(HR, BG, MM, AC)                                                        \
-    do {                                                                                          \
-        if (fuse_center) SDIRT_LAUNCH_PSF(HR, BG, MM, true, AC); else SDIRT_LAUNCH_PSF(HR, BG, MM, false, AC); \
-    } while (0)
-#define SDIRT_LAUNCH_PSF_M(HR, BG, AC)                                                            \
-    do {                                                                                          \
-        if (lean) SDIRT_LAUNCH_PSF_C(HR, BG, Lean, AC); else SDIRT_LAUNCH_PSF_C(HR, BG, Ieee, AC); \
-    } while (0)
-    // the corner-clipped microlens branch runs at 4 waves per SIMD whatever the tiles: float tiles only
-    if (wide1024) {
-        if (both) { if (lean) SDIRT_LAUNCH_PSF_W(true, Lean); else SDIRT_LAUNCH_PSF_W(true, Ieee); }
-        else { if (lean) SDIRT_LAUNCH_PSF_W(false, Lean); else SDIRT_LAUNCH_PSF_W(false, Ieee); }
-    } else if (both) {
-        if (dpp.big) SDIRT_LAUNCH_PSF_M(true, true, float);
-        else if (wide) SDIRT_LAUNCH_PSF_M(true, false, double);
-        else SDIRT_LAUNCH_PSF_M(true, false, float);
-    } else {
-        if (dpp.big) SDIRT_LAUNCH_PSF_M(false, true, float);
-        else if (wide) SDIRT_LAUNCH_PSF_M(false, false, double);
-        else SDIRT_LAUNCH_PSF_M(false, false, float);
-    }
-    LAUNCH_CHECK();
-    if (vr) {
-        FinishArgs fa;
-        std::memset(&fa, 0, sizeof(fa));
-        fa.gate = round ? vr->ctl : nullptr;
-        fa.ctl = round ? nullptr : vr->ctl;
-        fa.lens = lens[0]->dev; fa.K = K; fa.tp = tt.t[0]; fa.tc = cen->trips_c.t[0];
-        k_psf_finish<<<dim3((unsigned)N, both ? 2u : 1u), kBlock, 0, st>>>(
-            l_psf, r_psf, tile, pstride, (flags & SDIRT_PSF_NORMALIZE) ? 1 : 0, fa);
-        LAUNCH_CHECK();
-    }
-    }   // rounds
-#undef SDIRT_LAUNCH_PSF_M
-#undef SDIRT_LAUNCH_PSF_C
-#undef SDIRT_LAUNCH_PSF_W
-#undef SDIRT_LAUNCH_PSF
-#undef SDIRT_LAUNCH_PSF_T
-    // param_list=None leaves the R grid all-zero (monte_carlo.py:230-235)
-    if (!both && have_r) HIP_TRY(hipMemsetAsync(r_psf, 0, sizeof(float) * (size_t)N * W * tile, st));
-    if (!vr && nsplit > 1 && (flags & SDIRT_PSF_NORMALIZE)) {
-        launch_normalize(l_psf, N, tile, st, pstride);
-        if (have_r && dpp.have_r) launch_normalize(r_psf, N, tile, st, pstride);
-        LAUNCH_CHECK();
-    }
-    return SDIRT_OK;
+    L.flags = flags; L.st = as_stream(stream);
+    L.ca.center_out = center; L.ca.any_valid = any_valid; L.ca.conv_mask_c = conv_mask;
+    return launch_chief_center(L);
 }
 
 int sdirt_psf_lr(const sdirt_lens* lens, const float* point_obj, int64_t N, const float* x2,
@@ -1139,17 +1154,8 @@ int sdirt_psf_lr(const sdirt_lens* lens, const float* point_obj, int64_t N, cons
                  const float* center, const sdirt_dp_params* dp, const int32_t* trips,
                  uint32_t flags, float* l_psf, float* r_psf, uint32_t* conv_mask, void* stream)
 {
-    if (!lens || !point_obj || !x2 || !y2 || !center || !l_psf || N < 0 || S < 0 ||
-        S > (1ll << 30) || N > (1ll << 30))
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (int rc = check_ks(ks)) return rc;
-    if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
-    TripSet tt;
-    std::memset(&tt, 0, sizeof(tt));
-    if (int rc = make_trips(lens, trips, tt.t[0])) return rc;
-    if (N == 0) return SDIRT_OK;
-    return launch_psf(&lens, 1, point_obj, N, x2, y2, S, pupil_z, d_sensor, ps, ks, center, nullptr, dp,
-                      tt, flags, l_psf, r_psf, conv_mask, stream);
+    return sdirt_psf_rgb(&lens, 1, point_obj, N, x2, y2, S, pupil_z, d_sensor, ps, ks, center, dp, trips, flags,
+                         l_psf, r_psf, conv_mask, stream);
 }
 
 int sdirt_psf_rgb(const sdirt_lens* const* lens, int32_t W, const float* point_obj, int64_t N, const float* x2,
@@ -1157,22 +1163,13 @@ int sdirt_psf_rgb(const sdirt_lens* const* lens, int32_t W, const float* point_o
                   const float* center, const sdirt_dp_params* dp, const int32_t* trips, uint32_t flags,
                   float* l_psf, float* r_psf, uint32_t* conv_mask, void* stream)
 {
-    if (!lens || W < 1 || W > SDIRT_MAX_WAVELENGTHS || !point_obj || !x2 || !y2 || !center || !l_psf || N < 0 ||
-        S < 0 || S > (1ll << 30) || N > (1ll << 30))
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
-    for (int w = 0; w < W; ++w)
-        if (!lens[w] || lens[w]->n_surfaces != lens[0]->n_surfaces)
-            return fail(SDIRT_ERR_INVALID_ARGUMENT, "lens[%d] missing or surface count differs from lens[0]", w);
-    if (int rc = check_ks(ks)) return rc;
-    if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
-    const int K = lens[0]->n_surfaces;
-    TripSet tt;
-    std::memset(&tt, 0, sizeof(tt));
-    for (int w = 0; w < W; ++w)
-        if (int rc = make_trips(lens[w], trips ? trips + (size_t)w * K : nullptr, tt.t[w])) return rc;
+    PsfLaunch L;
+    if (int rc = check_psf_args(L, true, lens, W, nullptr, point_obj, N, x2, y2, S, nullptr, nullptr, 0, pupil_z,
+                                d_sensor, ks, dp, trips, nullptr, center, l_psf))
+        return rc;
     if (N == 0) return SDIRT_OK;
-    return launch_psf(lens, W, point_obj, N, x2, y2, S, pupil_z, d_sensor, ps, ks, center, nullptr, dp, tt, flags,
-                      l_psf, r_psf, conv_mask, stream);
+    if (int rc = plan_psf(L, ps, dp, flags, l_psf, r_psf, conv_mask, stream)) return rc;
+    return launch_psf(L);
 }
 
 int sdirt_psf_lr_centered(const sdirt_lens* lens, const sdirt_lens* lens_center,
@@ -1196,31 +1193,15 @@ int sdirt_psf_rgb_centered(const sdirt_lens* const* lens, int32_t W, const sdirt
                            float* center, int32_t* any_valid, float* l_psf, float* r_psf,
                            uint32_t* conv_mask, uint32_t* conv_mask_center, void* stream)
 {
-    if (!lens || W < 1 || W > SDIRT_MAX_WAVELENGTHS || !lens_center || !point_obj || !x2 || !y2 || !xc ||
-        !yc || !center || !l_psf || N < 0 || S < 0 || Sc < 0 || S > (1ll << 30) || Sc > (1ll << 30) ||
-        N > (1ll << 30))
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
-    for (int w = 0; w < W; ++w)
-        if (!lens[w] || lens[w]->n_surfaces != lens_center->n_surfaces)
-            return fail(SDIRT_ERR_INVALID_ARGUMENT, "lens[%d] missing or surface count differs from lens_center", w);
-    if (int rc = check_ks(ks)) return rc;
-    if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
-    const int K = lens_center->n_surfaces;
-    TripSet tt;
-    CenterRequest cr;
-    std::memset(&tt, 0, sizeof(tt));
-    std::memset(&cr.trips_c, 0, sizeof(cr.trips_c));
-    for (int w = 0; w < W; ++w) {
-        if (int rc = make_trips(lens[w], trips ? trips + (size_t)w * K : nullptr, tt.t[w])) return rc;
-        if (int rc = make_trips(lens_center, trips_center ? trips_center + (size_t)w * K : nullptr,
-                                cr.trips_c.t[w]))
-            return rc;
-    }
+    PsfLaunch L;
+    if (!lens_center) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (int rc = check_psf_args(L, true, lens, W, lens_center, point_obj, N, x2, y2, S, xc, yc, Sc, pupil_z, d_sensor,
+                                ks, dp, trips, trips_center, center, l_psf))
+        return rc;
     if (N == 0) return SDIRT_OK;
-    cr.lens_c = lens_center; cr.xc = xc; cr.yc = yc; cr.Sc = Sc; cr.center_out = center;
-    cr.any_valid = any_valid; cr.conv_mask_c = conv_mask_center;
-    return launch_psf(lens, W, point_obj, N, x2, y2, S, pupil_z, d_sensor, ps, ks, nullptr, &cr, dp, tt,
-                      flags, l_psf, r_psf, conv_mask, stream);
+    L.ca.center_out = center; L.ca.any_valid = any_valid; L.ca.conv_mask_c = conv_mask_center;
+    if (int rc = plan_psf(L, ps, dp, flags, l_psf, r_psf, conv_mask, stream)) return rc;
+    return launch_psf(L);
 }
 
 int32_t sdirt_psf_spp_slices(int64_t N, int64_t S, int32_t n_cus)
@@ -1244,32 +1225,21 @@ int sdirt_psf_lr_verified(const sdirt_lens* lens, const sdirt_lens* lens_center,
                           uint32_t flags, float* center, float* l_psf, float* r_psf, void* scratch,
                           void* stream)
 {
-    if (!lens || !lens_center || !point_obj || !x2 || !y2 || !xc || !yc || !center || !l_psf || !scratch ||
-        N < 0 || S < 0 || Sc < 0 || S > (1ll << 30) || Sc > (1ll << 30) || N > (1ll << 30))
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (!lens_center || !scratch) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (((uintptr_t)scratch) & 7) return fail(SDIRT_ERR_INVALID_ARGUMENT, "scratch must be 8-byte aligned");
-    if (lens->n_surfaces != lens_center->n_surfaces)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "surface count of lens and lens_center differ");
-    if (int rc = check_ks(ks)) return rc;
-    if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
     if (!trips || !trips_center) return fail(SDIRT_ERR_INVALID_ARGUMENT, "a verified call needs both speculated tables");
+    PsfLaunch L;
+    if (int rc = check_psf_args(L, true, &lens, 1, lens_center, point_obj, N, x2, y2, S, xc, yc, Sc, pupil_z, d_sensor,
+                                ks, dp, trips, trips_center, center, l_psf))
+        return rc;
     for (int k = 0; k < lens->n_surfaces; ++k)
         if (trips[k] < 0 || trips_center[k] < 0)
             return fail(SDIRT_ERR_INVALID_ARGUMENT, "a verified call runs the reference's batch-wide counts: no negative (per-wave) entries");
-    TripSet tt;
-    CenterRequest cr;
-    std::memset(&tt, 0, sizeof(tt));
-    std::memset(&cr.trips_c, 0, sizeof(cr.trips_c));
-    if (int rc = make_trips(lens, trips, tt.t[0])) return rc;
-    if (int rc = make_trips(lens_center, trips_center, cr.trips_c.t[0])) return rc;
     if (N == 0) return SDIRT_OK;
-    VerifiedRequest vr;
-    vr.ctl = static_cast<uint32_t*>(scratch);
-    vr.part = reinterpret_cast<double*>(static_cast<char*>(scratch) + ctl_bytes());
-    cr.lens_c = lens_center; cr.xc = xc; cr.yc = yc; cr.Sc = Sc; cr.center_out = center;
-    cr.any_valid = nullptr; cr.conv_mask_c = nullptr;
-    return launch_psf(&lens, 1, point_obj, N, x2, y2, S, pupil_z, d_sensor, ps, ks, nullptr, &cr, dp, tt, flags,
-                      l_psf, r_psf, nullptr, stream, &vr);
+    L.ca.center_out = center;
+    if (int rc = plan_psf(L, ps, dp, flags, l_psf, r_psf, nullptr, stream)) return rc;
+    return launch_psf_verified(L, static_cast<uint32_t*>(scratch),
+                               reinterpret_cast<double*>(static_cast<char*>(scratch) + ctl_bytes()));
 }
 
 static size_t align64(size_t n) { return (n + 63) / 64 * 64; }

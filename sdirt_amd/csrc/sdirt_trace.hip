@@ -471,26 +471,19 @@ static int launch_trace(const sdirt_lens* lens, int32_t first, int32_t last, int
         return to_sensor ? sdirt_propagate_to(z_sensor, out, M, stream) : SDIRT_OK;
     }
     const int grid = grid_for(M, kBlock);
-    const bool lean = (flags & SDIRT_PSF_STRICT_IEEE) == 0;
     const bool prefetch = (flags & SDIRT_TRACE_NO_PREFETCH) == 0;
     const float zs = (float)z_sensor;
-#define SDIRT_LAUNCH_TRACE_P(FW, MM, PF, TS)                                                        \
-    k_trace<FW, MM, PF, TS><<<grid, kBlock, 0, as_stream(stream)>>>(tt, lens->dev, lens->n_surfaces, \
-                                                                    first, last, rays, out, M, conv_mask, zs)
-#define SDIRT_LAUNCH_TRACE(FW, MM)                                                              \
-    do {                                                                                        \
-        if (prefetch) SDIRT_LAUNCH_TRACE_P(FW, MM, true, false); else SDIRT_LAUNCH_TRACE_P(FW, MM, false, false); \
-    } while (0)
-    if (to_sensor) {                           // forward, prefetching loop only (the self-test form has no use for it)
-        if (backward || !prefetch) return fail(SDIRT_ERR_UNSUPPORTED, "trace2sensor traces forward with the prefetching loop");
-        if (lean) SDIRT_LAUNCH_TRACE_P(true, Lean, true, true); else SDIRT_LAUNCH_TRACE_P(true, Ieee, true, true);
-    } else if (backward) {
-        if (lean) SDIRT_LAUNCH_TRACE(false, Lean); else SDIRT_LAUNCH_TRACE(false, Ieee);
-    } else {
-        if (lean) SDIRT_LAUNCH_TRACE(true, Lean); else SDIRT_LAUNCH_TRACE(true, Ieee);
-    }
-#undef SDIRT_LAUNCH_TRACE_P
-#undef SDIRT_LAUNCH_TRACE
+    // forward, prefetching loop only for trace2sensor (the self-test form has no use for it)
+    if (to_sensor && (backward || !prefetch)) return fail(SDIRT_ERR_UNSUPPORTED, "trace2sensor traces forward with the prefetching loop");
+    with_bool(!backward, [&](auto fw) { return with_bool(prefetch, [&](auto pf) { return with_bool(to_sensor, [&](auto ts) {
+        return with_math(flags, [&](auto m) {
+            // trace2sensor exists in the forward, prefetching form only (checked above): no other TS instantiation
+            constexpr bool FW = decltype(fw)::value, PF = decltype(pf)::value, TS = decltype(ts)::value && FW && PF;
+            k_trace<FW, decltype(m), PF, TS><<<grid, kBlock, 0, as_stream(stream)>>>(
+                tt, lens->dev, lens->n_surfaces, first, last, rays, out, M, conv_mask, zs);
+            return 0;
+        });
+    }); }); });
     LAUNCH_CHECK();
     return SDIRT_OK;
 }

@@ -7,7 +7,7 @@ root = sys.argv[1]
 p = root + "/sdirt_psf.hip"
 s = open(p).read()
 a = s.index("template <bool HAVE_R, bool BIG, class ACC, class M>")
-b = s.index("static void launch_normalize")
+b = s.index("template <bool LDS_TILE>")
 k = s[a:b]
 for name in ("tl_", "trr"):
     for tap in ("tl", "tr", "bl", "br"):
