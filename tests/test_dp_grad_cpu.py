@@ -1,6 +1,8 @@
 """Gradients of the dual-pixel splat without a GPU: the float64 restatement (tests/splat_f64.py) against the reference's
-own autograd gradients (computed afresh by tools/gen_golden_dp_grad.py where the reference checkout is present), and
-the rules that decide which psf_lr calls record gradients."""
+own autograd gradients (computed afresh by tools/gen_golden_dp_grad.py where the reference checkout is present) and, on
+every machine, against central differences of its own forward; what the backward fuzz of tests/test_gpu_dp_grad.py
+reaches (both states of every clamp gate, the fragile-ray cap); and the rules that decide which psf_lr calls record
+gradients."""
 import os
 import sys
 
@@ -8,8 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+import test_gpu_dp_grad as T           # the backward fuzz's case generator and tables; importing it needs no GPU
 from conftest import load_state
-from splat_f64 import max_normalise, splat_f64
+from splat_f64 import boundaries, fragile_rays, fragile_x, max_normalise, splat_f64, sub_pixel_areas
 
 from sdirt_amd import optics
 from sdirt_amd.optics import Lensgroup
@@ -61,6 +64,79 @@ def test_restatement_is_finite_where_the_segment_area_is_not_differentiable():
     L, R = splat_f64(0 * one, 0 * one, x_tan, one, one, torch.zeros(1, 2, dtype=torch.float64), 0.01, 5, h, f, w, 0.5)
     (L.sum() + 2 * R.sum()).backward()
     assert all(torch.isfinite(t.grad) for t in (h, f, w))
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_restatement_gradients_match_central_differences_of_its_own_forward(seed):
+    """sub_pixel_areas' autograd gradients in h, f, w (SegArea's hand-written chord, every clamp branch) against
+    central differences of its float64 forward, on random stacks with r drawn by thirds.  Dropped: the x_tan that
+    fragile_x flags (the derivative jumps there) -- with a band of 1e-3 instead of 1e-5, and around the edges where
+    the derivative is continuous but not smooth (|x| = r, |c| = sqrt(r^2 - 1/4): A' ~ sqrt(distance)) too, because a
+    central difference of step e is off by e^2 / 6 times the third derivative, which grows as distance^-1.5 there.
+    With e = 1e-7, distance >= 1e-3 and |dx/dh| <= f / (f - h)^2 <= 26 that is below 1e-6; a wrong sign or gate
+    is O(1)."""
+    rng = np.random.default_rng(300 + seed)
+    h = rng.uniform(0.4, 1.1)
+    f = h + rng.uniform(0.3, 1.2)
+    w = rng.uniform(0.1, 0.6)
+    lo, hi = T.R_THIRDS[seed % 3]
+    r = hi - (hi - lo) * rng.random() if seed % 3 == 1 else rng.uniform(lo, hi)
+    t = torch.from_numpy(rng.normal(0, 0.2, 400))
+    band = 1e-3
+    x1, x2 = boundaries(t, h, f, w)
+    edge = r if r <= 0.5 else float(np.sqrt(r * r - 0.25))
+    rough = torch.stack([((x.abs() - edge).abs() < band).any(0) for x in (x1, x2)]).any(0)
+    assert not (fragile_x(t, h, f, w, r) & ~fragile_x(t, h, f, w, r, band)).any()
+    t = t[~(fragile_x(t, h, f, w, r, band) | rough)]
+    assert t.numel() >= 300
+    leaves = [torch.tensor(v, dtype=torch.float64, requires_grad=True) for v in (h, f, w)]
+    fn = lambda h_, f_, w_: torch.cat(sub_pixel_areas(t, h_, f_, w_, r))
+    g = torch.autograd.grad((fn(*leaves) * torch.from_numpy(rng.normal(0, 1, 2 * t.numel()))).sum(), leaves)
+    assert all(abs(float(v)) > 1e-2 for v in g)
+    assert torch.autograd.gradcheck(fn, leaves, eps=1e-7, atol=1e-6, rtol=1e-6, check_undefined_grad=False)
+
+
+def test_backward_fuzz_reaches_both_states_of_every_gate_and_stays_under_the_fragile_cap():
+    """Over the default seeds of test_random_geometries_and_batch_shapes_against_the_float64_restatement: every clamp
+    gate of dz_boundaries (g1, g2, gi for small r; g1, g2 and the u gates of x1 and x2 for big r) is open on >= 5 %
+    and closed on >= 5 % of the live (ray, boundary) pairs in at least two cases; every value of the shape and ks
+    lists comes up, 78 and 79 with r on both sides of 0.5, each third of r three times; and no case has more fragile
+    rays than the cap.  ("small gi" shows where the rays went and no more: gi is redundant in the kernel, see
+    splat_f64.gate_states.)"""
+    cases = [T.fuzz_case(seed) for seed in range(12)]
+    both = {}
+    for c in cases:
+        assert T.fragile_within_cap(c), (c["S"], c["N"], c["ks"], c["n_fragile"], c["n_live"])
+        print(f"S {c['S']} N {c['N']} ks {c['ks']} r {c['r']:.3f}: fragile {c['n_fragile']} of {c['n_live']} live rays; "
+              f"gates (open, closed) {T.gate_shares(c)}")
+        for k, (a, b) in T.gate_shares(c).items():
+            key = ("big " if c["r"] > 0.5 else "small ") + k
+            both[key] = both.get(key, 0) + (a >= 0.05 and b >= 0.05)
+    assert set(both) == {"small g1", "small g2", "small gi", "big g1", "big g2", "big u1", "big u2"}
+    assert all(v >= 2 for v in both.values()), both
+    assert {(c["S"], c["N"]) for c in cases} == {(1, 5), (63, 5), (257, 1), (1500, 5), (4100, 3), (5000, 1), (40, 3000),
+                                                 (2048, 40)}
+    assert {c["ks"] for c in cases} == {2, 9, 21, 22, 65, 78, 79, 150}
+    for ks in (78, 79):
+        assert {c["r"] > 0.5 for c in cases if c["ks"] == ks} == {False, True}
+    thirds = [sum(lo <= c["r"] <= hi for c in cases) for lo, hi in T.R_THIRDS]
+    assert min(thirds) >= 3 and {c["precision"] for c in cases} == {"lean", "ieee"}
+    assert any(c["n_live"] < T.FEW_RAYS for c in cases) and any(c["ra"].sum() < 0.9 * c["ra"].size for c in cases)
+
+
+def test_fp32_fractions_are_the_float64_ones_to_rounding_and_carry_the_same_centre_derivative():
+    c = T.make_case(np.random.default_rng(1), 200, 3, 22, 0.00431, 0.78, 1.44, 0.3, 0.5)
+    G = torch.randn((3, 22, 22), generator=torch.Generator().manual_seed(1)).double()
+    out = []
+    for fd in (torch.float64, torch.float32):
+        cen = torch.from_numpy(c["cen"]).double().requires_grad_(True)
+        L, R = splat_f64(*c["rays"], cen, c["ps"], 22, c["h"], c["f"], c["w"], c["r"], frac_dtype=fd)
+        (G * L).sum().backward()
+        out.append((L.detach(), cen.grad))
+    assert not torch.equal(out[0][0], out[1][0])
+    assert float((out[0][0] - out[1][0]).abs().max()) <= 8 * 22 * 2.0 ** -23 * float(out[0][0].abs().max())
+    assert torch.allclose(out[0][1], out[1][1], rtol=1e-4, atol=0)
+    assert fragile_rays(*c["rays"], torch.from_numpy(c["cen"]), c["ps"], 22, c["h"], c["f"], c["w"], c["r"]).sum() == 0
 
 
 # ------------------------------------------------------------------ which calls record gradients
