@@ -40,6 +40,26 @@ def test_local_psf_render_against_reference():
     pad = (ks - 1) // 2
     exp = torch.nn.functional.pad(img[:1], (pad, pad, pad, pad), mode="replicate")[..., 2 * pad:, 2 * pad:]
     assert torch.allclose(rl, exp.half().float(), atol=0)
+    # the same check is exact in fp16 arithmetic on every dispatch path: ks 5 (8 pixels per LDS tile), 21 (C 3: the
+    # wave-per-pixel kernel), 33 (4 per tile), 49 (2 per tile), 65 (direct kernel), 1 / 3 / 4 channels each; images
+    # a little larger than pad so that the shifted image is not one replicated corner.  A one-hot at the first tap
+    # shifts by (+pad,+pad), one at the last tap (ks-1,ks-1) by (-pad,-pad): the last lanes of the tap tiling and
+    # the flip in the other direction.  Both sides get both taps (`kr` is the second half of a pixel's run).
+    gen = torch.Generator(device=DEV).manual_seed(7)
+    for ks in (5, 21, 33, 49, 65):
+        pad = (ks - 1) // 2
+        H, W = pad + 5, pad + 9
+        for C in (1, 3, 4):
+            x = torch.rand(1, C, H, W, device=DEV, generator=gen)
+            padded = torch.nn.functional.pad(x, (pad, pad, pad, pad), mode="replicate")
+            first, last = padded[..., 2 * pad:, 2 * pad:].half().float(), padded[..., :H, :W].half().float()
+            for tl, tr in ((0, ks - 1), (ks - 1, 0)):
+                d = torch.zeros(1, H, W, 2, ks, ks, device=DEV)
+                d[..., 0, tl, tl] = 1.0
+                d[..., 1, tr, tr] = 1.0
+                rl, rr = local_psf_render_fast(x, d, kernel_size=ks)
+                assert torch.allclose(rl, first if tl == 0 else last, atol=0), (ks, C, tl)
+                assert torch.allclose(rr, first if tr == 0 else last, atol=0), (ks, C, tr)
 
 
 def test_local_psf_render_high_res_against_reference_tiles():
@@ -60,12 +80,16 @@ def test_local_psf_render_high_res_against_reference_tiles():
 
 
 @pytest.mark.parametrize("shape", [(2, 3, 9, 13, 21), (1, 3, 5, 8, 21), (1, 3, 33, 70, 21), (1, 3, 4, 97, 21),
-                                   (1, 1, 7, 10, 21), (1, 3, 6, 11, 7), (1, 4, 5, 9, 33)])
+                                   (1, 1, 7, 10, 21), (1, 3, 6, 11, 7), (1, 4, 5, 9, 33), (1, 3, 5, 9, 49),
+                                   (1, 1, 4, 7, 65)])
 def test_render_kernels_equal_a_plain_torch_convolution(shape):
-    """Every dispatch path of sdirt_local_psf_render (software-pipelined ks 21 RGB kernel, row-mapped
-    LDS-tiled kernel for other sizes / channel counts) on ragged shapes -- rows shorter than a
-    pixel group, widths that are not a multiple of 8, odd run alignments, the tensor's last partial
-    16-byte vector -- against the definition: replicate padding, flipped per-pixel kernels, fp32."""
+    """The dispatch paths of sdirt_local_psf_render in fp32: the software-pipelined wave-per-pixel kernel
+    (ks 21 RGB), the row-mapped LDS-tiled kernel with 8 (ks 21 C 1, ks 7), 4 (ks 33) and 2 (ks 49) pixels
+    per tile, the direct kernel (ks 65) -- on ragged shapes: rows shorter than a pixel group, widths that
+    are not a multiple of 8, odd run alignments, the tensor's last partial 16-byte vector -- against the
+    definition: replicate padding, flipped per-pixel kernels, fp32.  Not reached: the direct kernel as
+    the fallback of ks <= 64 for images beyond 32-bit offsets (C*H*W >= 2^30 elements or B*H >= 65536),
+    which no small input selects."""
     from sdirt_amd import local_dp_psf_render
     B, C, H, W, ks = shape
     g = torch.Generator(device=DEV).manual_seed(sum(shape))
@@ -91,6 +115,29 @@ def test_render_production_size_runs_and_conserves_energy():
     rl, rr = local_psf_render_fast(img, psf, kernel_size=ks)
     assert rl.shape == (1, 3, H, W)
     assert (rl - 0.5).abs().max() < 2e-3 and (rr - 0.5).abs().max() < 2e-3
+
+
+@pytest.mark.parametrize("ks", [33, 49, 65])
+def test_render_fp16_arithmetic_stays_within_its_roundings_of_fp32(ks):
+    """fp16 arithmetic against fp32 on the tiled (4 and 2 pixels per tile) and direct kernels, 1 / 3 / 4 channels:
+    random kernels that sum to 1, image in [0,1)."""
+    from sdirt_amd import local_dp_psf_render, local_psf_render_fast
+    g = torch.Generator(device=DEV).manual_seed(ks)
+    # Image value, weight, product and result are each rounded to fp16 once (relative 2^-11 each, outputs
+    # <= 1), and a product below the fp16 normal range (weights ~ 1/ks^2 times values < 1) loses at most
+    # half a subnormal step, 2^-25, ks^2 times.  Both paths add in fp32 in the same lane-strided order
+    # (about ks^2/64 + 6 additions per partial sum, 2^-24 relative each: below 1e-5 at ks 65), which the
+    # first term's slack over the 5e-4 measured on fixture f7 covers.
+    bound = 4 * 2.0 ** -11 + ks * ks * 2.0 ** -25
+    for C in (1, 3, 4):
+        img = torch.rand(1, C, 5, 9, device=DEV, generator=g)
+        psf = torch.rand(1, 5, 9, 2, ks, ks, device=DEV, generator=g)
+        psf = psf / psf.sum((-1, -2), keepdim=True)
+        full = local_dp_psf_render(img, psf, kernel_size=ks)
+        half = torch.cat(local_psf_render_fast(img, psf, kernel_size=ks), dim=1)
+        err = float((half - full).abs().max())
+        print(f"ks {ks} C {C}: |half - fp32| max {err:.3e} (bound {bound:.3e})")
+        assert err <= bound, (ks, C, err)
 
 
 @pytest.mark.parametrize("name", ["rf50mm", "rf35mm"])

@@ -1,4 +1,4 @@
-"""Form experiment (round 5): the wave-per-pixel renderers with an occupancy target in __launch_bounds__ --
+"""Form experiment (round 5): the two __global__ wrappers of the wave-per-pixel body (render_wave) with an occupancy target in __launch_bounds__ --
 k_local_psf_render_wave at 8 waves per SIMD (<= 64 VGPRs; 68 today = 7 waves: 1792 workgroup slots for the 6144 workgroups of a
 512 x 768 frame = 3.43 generations; 8 waves = 2048 slots = 3.0), k_psfnet_render_wave at 6 (<= 80 VGPRs; 88 today = 5 waves)."""
 import sys
