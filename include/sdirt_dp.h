@@ -500,6 +500,34 @@ int sdirt_psfnet_render(const float* img /*dev [B,C,H,W]*/, const void* raw_l /*
                         int32_t height, int32_t width, int32_t ks, float* out_l /*dev [B,C,H,W]*/,
                         float* out_r /*dev [B,C,H,W]*/, void* stream);
 
+/* Backward pass of sdirt_local_psf_render(half_precision = 0), i.e. of local_dp_psf_render
+ * (deeplens/render_psf.py:157-188, which autograd differentiates through pad :172, flip :175, unfold :178,
+ * multiply and sum :183-184): grad_l, grad_r [B,C,H,W] are the upstream gradients of out_l, out_r.  fp32 sums,
+ * no atomics: two calls on the same operands give the same bits.  Odd ks <= 64, 1 / 3 / 4 channels, batch and
+ * height <= 65535.
+ *
+ * With respect to the kernels (the pad, unfold and multiply of :172-184 seen from the kernels' side):
+ *   grad_psf[b,y,x,s,i,j] = sum_c grad_s[b,c,y,x] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)],  pad = (ks-1)/2. */
+int sdirt_local_psf_render_grad_psf(const float* img /*dev [B,C,H,W]*/, const float* grad_l /*dev*/,
+                                    const float* grad_r /*dev*/, int32_t batch, int32_t channels, int32_t height,
+                                    int32_t width, int32_t ks, float* grad_psf /*dev [B,H,W,2,ks,ks]*/,
+                                    void* stream);
+
+/* With respect to the image (deeplens/render_psf.py:172-184 again: the backward of unfold :178 and of the
+ * replicate pad :172, so a border pixel collects what the padding read):
+ *   grad_img[b,c,v,u] = sum_s sum_{(y,x,i,j): clamp(y+pad-i) = v, clamp(x+pad-j) = u} grad_s[b,c,y,x] * psf[b,y,x,s,i,j].
+ * workspace: device memory of at least sdirt_local_psf_render_grad_img_workspace_bytes(...) bytes (per-tile
+ * partial sums; need not be initialised), 16-byte aligned as psf must be. */
+int sdirt_local_psf_render_grad_img(const float* psf /*dev [B,H,W,2,ks,ks]*/, const float* grad_l /*dev*/,
+                                    const float* grad_r /*dev*/, int32_t batch, int32_t channels, int32_t height,
+                                    int32_t width, int32_t ks, float* grad_img /*dev [B,C,H,W]*/,
+                                    void* workspace /*dev*/, int64_t workspace_bytes, void* stream);
+
+/* Bytes of workspace sdirt_local_psf_render_grad_img needs for this shape (render_psf.py:157-188 has no
+ * counterpart: its autograd keeps the [B,C*ks*ks,H*W] unfold buffer instead), or -1 for a shape it refuses. */
+int64_t sdirt_local_psf_render_grad_img_workspace_bytes(int32_t batch, int32_t channels, int32_t height,
+                                                        int32_t width, int32_t ks);
+
 /* ---- the PSF network itself ------------------------------------------------ */
 
 /* The network is described by its layer widths: widths[0..n_layers] = in, hidden..., out.  The

@@ -37,8 +37,53 @@ def local_psf_render_fast(input, psf, kernel_size=11, val=False):
     return _render(input, psf, kernel_size, half=True)
 
 
+class _LocalDpPsfRender(torch.autograd.Function):
+    """local_dp_psf_render under autograd: the forward is _render's kernel call on the same operands (bit-equal to
+    the no-grad call), the backward the two kernels of sdirt_render_grad.hip -- only those ctx.needs_input_grad asks
+    for."""
+
+    @staticmethod
+    def forward(ctx, input, dp_psf, kernel_size):
+        rl, rr = _render(input, dp_psf, kernel_size, half=False)
+        ctx.save_for_backward(input, dp_psf)
+        ctx.kernel_size = kernel_size
+        return torch.cat([rl, rr], dim=1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        input, dp_psf = ctx.saved_tensors
+        ks = ctx.kernel_size
+        b, c, h, w = input.shape if input.dim() == 4 else (1, *input.shape)
+        lib, stream = _lib.lib(), stream_ptr(input.device)
+        gl = grad[:, :c].to(torch.float32).contiguous()
+        gr = grad[:, c:].to(torch.float32).contiguous()
+        grad_input = grad_psf = None
+        if ctx.needs_input_grad[0]:
+            k = dp_psf.to(torch.float32).reshape(b, h, w, 2, ks, ks).contiguous()
+            nbytes = lib.sdirt_local_psf_render_grad_img_workspace_bytes(b, c, h, w, ks)
+            if nbytes < 0:
+                raise _lib.SdirtError(f"local_dp_psf_render has no backward for kernel_size={ks}")
+            work = torch.empty(nbytes // 4, dtype=torch.float32, device=input.device)
+            gi = torch.empty((b, c, h, w), dtype=torch.float32, device=input.device)
+            _lib.check(lib.sdirt_local_psf_render_grad_img(dptr(k), dptr(gl), dptr(gr), b, c, h, w, ks, dptr(gi),
+                                                           dptr(work), nbytes, stream))
+            grad_input = gi.to(input.dtype).reshape(input.shape)
+        if ctx.needs_input_grad[1]:
+            img = input.to(torch.float32).contiguous()
+            gk = torch.empty((b, h, w, 2, ks, ks), dtype=torch.float32, device=input.device)
+            _lib.check(lib.sdirt_local_psf_render_grad_psf(dptr(img), dptr(gl), dptr(gr), b, c, h, w, ks, dptr(gk),
+                                                           stream))
+            grad_psf = gk.to(dp_psf.dtype).reshape(dp_psf.shape)
+        return grad_input, grad_psf, None
+
+
 def local_dp_psf_render(input, dp_psf, kernel_size=21):
-    """render_psf.py:157-188 (fp32) -> [N, 2C, H, W] = cat(left, right)."""
+    """render_psf.py:157-188 (fp32) -> [N, 2C, H, W] = cat(left, right).  Differentiable in `input` and `dp_psf`,
+    as the reference's torch ops are: a call in grad mode on an operand that requires a gradient goes through
+    _LocalDpPsfRender (same forward kernel, same values); every other call is the plain kernel call."""
+    if torch.is_grad_enabled() and (input.requires_grad or dp_psf.requires_grad):
+        return _LocalDpPsfRender.apply(input, dp_psf, kernel_size)
     rl, rr = _render(input, dp_psf, kernel_size, half=False)
     return torch.cat([rl, rr], dim=1)
 
