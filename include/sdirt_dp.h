@@ -289,6 +289,44 @@ int sdirt_forward_integral_grad(sdirt_rays rays, int64_t spp, int64_t n_points, 
  * arithmetic only); 0 for a bad argument. */
 int32_t sdirt_forward_integral_grad_slices(int64_t n_points, int64_t spp, int32_t n_cus);
 
+/* sdirt_forward_integral_grad that ALSO stores every ray's own terms: ray_grad (dev fp32 [4, n_rays], SoA, point-major
+ * like the bundle, fully overwritten) = dLoss/d(o.x, o.y, d.x, d.z) of the sensor-plane rays -- o.x / o.y enter the splat
+ * as the centre does (points = -o.xy - centre, times ra), d.x / d.z through x_tan = -d.x / d.z (dx1/dt = -f h / (f - h),
+ * dx2/dt = -h, the chord-form area derivatives and clamp rule of the parameter terms).  A ray outside the window or
+ * with ra = 0 gets 0.  Every other argument and `partial` are those of sdirt_forward_integral_grad; partial = NULL: the
+ * rays' terms only. */
+int sdirt_forward_integral_grad_rays(sdirt_rays rays, int64_t spp, int64_t n_points, double ps, int32_t ks,
+                                     const float* center /*dev [N,2]*/, const sdirt_dp_params* dp /*host*/,
+                                     uint32_t flags /*SDIRT_PSF_STRICT_IEEE or 0*/, const float* grad_l /*dev or NULL*/,
+                                     const float* grad_r /*dev or NULL*/, double* partial /*dev [N,n_slices,5] or NULL*/,
+                                     int32_t n_slices, float* ray_grad /*dev [4,n_rays]*/, void* stream);
+
+/* ---- the backward pass of the staged trace: gradients in the prescription (d, c, k, ai of every surface) ----
+ * sdirt_trace2sensor_record is sdirt_trace2sensor (the same sensor-plane bundle, bit for bit, under the same trip
+ * table and math flag) that also stores each ray's (o, d) on entry to every surface and before the final propagation
+ * into `workspace` (dev, sdirt_trace2sensor_grad_workspace_bytes(n_rays, K) = 24 (K + 1) n_rays bytes). */
+int64_t sdirt_trace2sensor_grad_workspace_bytes(int64_t n_rays, int32_t n_surfaces);
+int sdirt_trace2sensor_record(const sdirt_lens* lens, const int32_t* trips /*host [K]*/,
+                              uint32_t flags /*SDIRT_PSF_STRICT_IEEE or 0*/, double d_sensor, sdirt_rays rays, sdirt_rays out,
+                              int64_t n_rays, uint32_t* conv_mask /*dev [K] or NULL*/, void* workspace /*dev*/,
+                              void* stream);
+
+/* Given ray_grad (dev fp32 [4, n_rays]: sdirt_forward_integral_grad_rays), the recorded `workspace`, the weights `ra`
+ * of the sensor-plane bundle (dev [n_rays]) and the trip table and flags of the recording call: the gradient the
+ * reference's autograd graph gives the surface parameters (deeplens/surfaces.py:523-679: the regain step
+ * t = t0 + t1 - clamp(ft / (dfdt + 1e-9), +-5) with t1 detached, _normal, _refract; every validity flag and mask is
+ * the forward's fp32 decision and carries no gradient; the stop's d through t = (d - o.z) / d.z).
+ * partial (dev float64 [n_workgroups, K, 3 + SDIRT_MAX_AI], fully overwritten): per workgroup the sums for the columns
+ * d, c, k, ai2, ai4, ... of every surface; the caller sums over the workgroups.  A column a surface does not own (c of
+ * a plane, k where k == 0 or the surface is a sphere, ai beyond ai_degree) is exactly 0.  n_workgroups must be
+ * sdirt_trace2sensor_grad_workgroups(n_rays, n_cus) of the current device.  Trip counts must be >= 0 (the per-wave
+ * counts of the speed mode are not recorded: SDIRT_ERR_UNSUPPORTED).  No atomics: the same bits every run. */
+int32_t sdirt_trace2sensor_grad_workgroups(int64_t n_rays, int32_t n_cus);
+int sdirt_trace2sensor_grad(const sdirt_lens* lens, const int32_t* trips /*host [K]*/, uint32_t flags, double d_sensor,
+                            const void* workspace /*dev*/, const float* ra /*dev [n_rays]*/,
+                            const float* ray_grad /*dev [4,n_rays]*/, int64_t n_rays,
+                            double* partial /*dev [n_workgroups,K,3+SDIRT_MAX_AI]*/, int32_t n_workgroups, void* stream);
+
 /* deeplens/optics.py:983-987: psf / (max + 1e-6), per point, in place. */
 int sdirt_psf_normalize(float* psf /*dev [N,ks,ks]*/, int64_t n_points, int32_t ks, void* stream);
 

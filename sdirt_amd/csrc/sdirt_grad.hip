@@ -228,6 +228,113 @@ k_forward_integral_grad(sdirt_rays R, int64_t S, SplatGeom gm, DevDpParams dp, D
     }
 }
 
+// d/dt of Z_a, t = x_tan, a = +1, 0, -1: dz_boundaries' clamp decisions (the forward's fp32 values) with
+// dx1/dt = -f h / (f - h) and dx2/dt = -h -- what a ray's direction gets through x_tan = -d.x / d.z.
+template <bool BIG, class M, class Div>
+__device__ __forceinline__ void dz_dt(const DevDpParams& p, const Div& div_fmh, const DpGrad& q, float x_tan, double dT[3])
+{
+    const float fx = p.f * x_tan, hx = p.h * x_tan;
+    float x1f[3], x2f[3];
+    if (BIG) {
+        x1f[0] = p.w - ((fx - p.w) * p.h) / p.fmh;
+        x1f[1] = ((-fx) * p.h) / p.fmh;
+        x1f[2] = (-p.w) - ((fx + p.w) * p.h) / p.fmh;
+    } else {
+        x1f[0] = p.w - div_fmh((fx - p.w) * p.h);
+        x1f[1] = div_fmh((-fx) * p.h);
+        x1f[2] = (-p.w) - div_fmh((fx + p.w) * p.h);
+    }
+    x2f[0] = p.w - hx; x2f[1] = 0.0f - hx; x2f[2] = (-p.w) - hx;
+    const double t = (double)x_tan, d1 = -q.f * q.h / q.fmh, d2 = -q.h;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double a = 1.0 - (double)k;
+        const double x1 = a * q.w - (q.f * t - a * q.w) * q.h / q.fmh;
+        const double x2 = a * q.w - q.h * t;
+        double c1, c2;
+        if (BIG) {
+            const bool g1 = in_range(x1f[k], -0.5f, 0.5f), g2 = in_range(x2f[k], -0.5f, 0.5f);
+            const float u1 = __ocml_acos_f32(clampf(x1f[k], -0.5f, 0.5f) / p.r);
+            const float u2 = __ocml_acos_f32(clampf(x2f[k], -0.5f, 0.5f) / p.r);
+            const bool gu1 = in_range(u1, p.tr, p.tl), gu2 = in_range(u2, p.tr, p.tl);
+            c1 = g1 ? (gu1 ? -1.0 : chord(q.r, x1)) : 0.0;
+            c2 = g2 ? -1.0 - (gu2 ? -1.0 : chord(q.r, x2)) : 0.0;
+        } else {
+            const bool g1 = in_range(x1f[k], -p.r, p.r), g2 = in_range(x2f[k], -0.5f, 0.5f);
+            const bool gi = in_range(clampf(x2f[k], -0.5f, 0.5f), -p.r, p.r);
+            c1 = g1 ? chord(q.r, x1) : 0.0;
+            c2 = g2 ? -1.0 - (gi ? chord(q.r, x2) : 0.0) : 0.0;
+        }
+        dT[k] = c1 * d1 + c2 * d2;
+    }
+}
+
+// The per-ray terms k_forward_integral_grad sums, stored instead: ray_grad [4, M] = dLoss/d(o.x, o.y, d.x, d.z) of the
+// sensor-plane rays (0 for a ray without weight or outside the window).  o.x / o.y enter as the centre does
+// (points = -o.xy - centre, times the weight): the centre terms of that kernel, ray by ray; d.x / d.z through
+// x_tan = -d.x / d.z.  The same launch geometry and LDS staging as k_forward_integral_grad; no reduction.
+template <bool BIG, class M, bool STAGE>
+__global__ void __launch_bounds__(kGradThreads)
+k_forward_integral_grad_rays(sdirt_rays R, int64_t S, int64_t Mtot, SplatGeom gm, DevDpParams dp, DpGrad q, GradLaunch gl_,
+                             const float* __restrict__ center, const float* __restrict__ gl, const float* __restrict__ gr,
+                             float* __restrict__ ray_grad)
+{
+    extern __shared__ __attribute__((aligned(16))) float g_lds[];
+    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
+    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
+    const int tile = gm.ks * gm.ks;
+    const float* GL = gl ? gl + n * tile : nullptr;
+    const float* GR = gr ? gr + n * tile : nullptr;
+    if (STAGE) {
+        for (int e = threadIdx.x; e < tile; e += kGradThreads) {
+            g_lds[e] = GL ? GL[e] : 0.0f;
+            g_lds[tile + e] = GR ? GR[e] : 0.0f;
+        }
+        __syncthreads();
+    }
+    const float cx = center[2 * n], cy = center[2 * n + 1];
+    const auto div_dy = UDiv<M>::make(gm.dy_rng), div_dx = UDiv<M>::make(gm.dx_rng);
+    const auto div_fmh = UDiv<M>::make(dp.fmh);
+    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
+    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
+        const int64_t i = n * S + s;
+        const float ox = R.ox[i], oy = R.oy[i], dx = R.dx[i], dz = R.dz[i], ra = R.ra[i];
+        float g_ox = 0.0f, g_oy = 0.0f, g_dx = 0.0f, g_dz = 0.0f;
+        GradTaps tp;
+        if (grad_taps(gm, div_dy, div_dx, ox, oy, cx, cy, ra, tp)) {
+            const float x_tan = (-dx) / dz;
+            float sl, sr;
+            if (BIG) dp_weights_big(dp, x_tan, sl, sr);
+            else dp_weights_small<M>(dp, div_fmh, x_tan, sl, sr);
+            double lt, lr_, lb, lbr, rt = 0.0, rr_ = 0.0, rb = 0.0, rbr = 0.0;
+            if (STAGE) {
+                lt = g_lds[tp.i_tl]; lr_ = g_lds[tp.i_tr]; lb = g_lds[tp.i_bl]; lbr = g_lds[tp.i_br];
+                rt = g_lds[tile + tp.i_tl]; rr_ = g_lds[tile + tp.i_tr]; rb = g_lds[tile + tp.i_bl];
+                rbr = g_lds[tile + tp.i_br];
+            } else {
+                lt = GL ? GL[tp.i_tl] : 0.0f; lr_ = GL ? GL[tp.i_tr] : 0.0f;
+                lb = GL ? GL[tp.i_bl] : 0.0f; lbr = GL ? GL[tp.i_br] : 0.0f;
+                if (GR) { rt = GR[tp.i_tl]; rr_ = GR[tp.i_tr]; rb = GR[tp.i_bl]; rbr = GR[tp.i_br]; }
+            }
+            const double wb = tp.wb, wr = tp.wr, w = tp.w;
+            const double bl = (1.0 - wb) * ((1.0 - wr) * lt + wr * lr_) + wb * ((1.0 - wr) * lb + wr * lbr);
+            const double br = (1.0 - wb) * ((1.0 - wr) * rt + wr * rr_) + wb * ((1.0 - wr) * rb + wr * rbr);
+            const double bl_wr = (1.0 - wb) * (lr_ - lt) + wb * (lbr - lb), bl_wb = (1.0 - wr) * (lb - lt) + wr * (lbr - lr_);
+            const double br_wr = (1.0 - wb) * (rr_ - rt) + wb * (rbr - rb), br_wb = (1.0 - wr) * (rb - rt) + wr * (rbr - rr_);
+            const double cs = w * ((double)sl * bl_wr + (double)sr * br_wr), cr = w * ((double)sl * bl_wb + (double)sr * br_wb);
+            double dT[3];
+            dz_dt<BIG, M>(dp, div_fmh, q, x_tan, dT);
+            const double dt = w * (bl * (dT[2] - dT[1]) + br * (dT[1] - dT[0]));          // dLoss/d(x_tan)
+            const double z = (double)dz;
+            g_ox = (float)(w * gl_.dwr_dcx * cs);
+            g_oy = (float)(w * gl_.dwb_dcy * cr);
+            g_dx = (float)(-dt / z);
+            g_dz = (float)(dt * (double)dx / (z * z));
+        }
+        ray_grad[i] = g_ox; ray_grad[Mtot + i] = g_oy; ray_grad[2 * Mtot + i] = g_dx; ray_grad[3 * Mtot + i] = g_dz;
+    }
+}
+
 GradLaunch plan_grad(int64_t N, int64_t S, int ncu)
 {
     GradLaunch g{};
@@ -249,13 +356,13 @@ int32_t sdirt_forward_integral_grad_slices(int64_t n_points, int64_t spp, int32_
     return plan_grad(n_points, spp, n_cus).nslices;
 }
 
-int sdirt_forward_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps, int32_t ks, const float* center,
+static int launch_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps, int32_t ks, const float* center,
                                 const sdirt_dp_params* dp, uint32_t flags, const float* grad_l, const float* grad_r,
-                                double* partial, int32_t n_slices, void* stream)
+                                double* partial, int32_t n_slices, float* ray_grad, void* stream)
 {
     if (int rc = check_rays(rays)) return rc;
     if (int rc = check_ks(ks, SDIRT_MAX_KS_STAGED)) return rc;
-    if (!center || !partial || S < 0 || N < 0 || N > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (!center || (!partial && !ray_grad) || S < 0 || N < 0 || N > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
     if (dp && !(dp->f != dp->h)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->f must differ from dp->h");
     if (N == 0) return SDIRT_OK;
@@ -279,12 +386,32 @@ int sdirt_forward_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps
     const unsigned grid = (unsigned)(N * gl.nslices);
     with_bool(dpp.big, [&](auto bg) { return with_bool(stage, [&](auto stg) { return with_math(flags, [&](auto m) {
         constexpr bool STG = decltype(stg)::value;
-        k_forward_integral_grad<decltype(bg)::value, decltype(m), STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(
-            rays, S, gm, dpp, q, gl, center, grad_l, gr, partial);
+        if (partial)
+            k_forward_integral_grad<decltype(bg)::value, decltype(m), STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(
+                rays, S, gm, dpp, q, gl, center, grad_l, gr, partial);
+        if (ray_grad)
+            k_forward_integral_grad_rays<decltype(bg)::value, decltype(m), STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(
+                rays, S, S * N, gm, dpp, q, gl, center, grad_l, gr, ray_grad);
         return 0;
     }); }); });
     LAUNCH_CHECK();
     return SDIRT_OK;
+}
+
+int sdirt_forward_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps, int32_t ks, const float* center,
+                                const sdirt_dp_params* dp, uint32_t flags, const float* grad_l, const float* grad_r,
+                                double* partial, int32_t n_slices, void* stream)
+{
+    return launch_integral_grad(rays, S, N, ps, ks, center, dp, flags, grad_l, grad_r, partial, n_slices, nullptr, stream);
+}
+
+int sdirt_forward_integral_grad_rays(sdirt_rays rays, int64_t S, int64_t N, double ps, int32_t ks, const float* center,
+                                     const sdirt_dp_params* dp, uint32_t flags, const float* grad_l,
+                                     const float* grad_r, double* partial, int32_t n_slices, float* ray_grad,
+                                     void* stream)
+{
+    if (!ray_grad) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null ray_grad");      // partial may be NULL: the rays' terms only
+    return launch_integral_grad(rays, S, N, ps, ks, center, dp, flags, grad_l, grad_r, partial, n_slices, ray_grad, stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@ keeps the speculated Newton trip tables (newton.py) and launches.
 There is no CPU fallback: every method that traces rays raises if
 libsdirt_dp.so is not built or no MI355X is visible.
 """
+import contextlib
 import ctypes as C
 import json
 import types
@@ -25,6 +26,7 @@ from .basics import DEFAULT_WAVE, DEPTH, GEO_SPP, WAVE_RGB, Ray, dptr, stream_pt
 from .monte_carlo import _requires_grad, splat_autograd
 from .newton import NEWTON_MAXITER, TripPlanner
 from .surfaces import Aspheric
+from .trace_grad import N_COLUMNS, SurfaceGradFunction, TraceRecord
 
 
 def _as_device(device):
@@ -271,6 +273,61 @@ class Lensgroup:
         self._dev.clear()
         self._pupil_cache.clear()
         self.__dict__.pop("_curved_cache", None)
+
+    # ------------------------------------------------------- surface parameters
+    def surface_parameters(self):
+        """The prescription as ONE tensor: a fresh float32 CPU tensor [K, 3 + MAX_AI], columns d, c, k, ai2, ai4, ...
+        holding the records' fp32 values, unused entries 0.  What `surface_params=` of psf_lr / psf_diff / psf_rgb
+        takes; which entries are parameters with a gradient is `Aspheric.owned_columns()` per surface."""
+        return torch.from_numpy(np.stack([s.parameter_row() for s in self.surfaces]))
+
+    def _surface_values(self, theta):
+        v = torch.as_tensor(theta).detach().to("cpu", torch.float32).numpy()
+        if v.shape != (len(self.surfaces), N_COLUMNS):
+            raise ValueError(f"surface parameters must have shape [{len(self.surfaces)}, {N_COLUMNS}]")
+        return v
+
+    def set_surface_parameters(self, theta):
+        """Write surface_parameters()-shaped values back into the Aspheric records.  ValueError (and no record changed)
+        when a write would change a surface's kind (c to or from 0, k of a sphere) or touch a column the surface does
+        not own.  The device tables, the cached pupils and the trip planners are dropped: the next call sees the new
+        lens and recomputes its entrance pupil, as the reference does on every call."""
+        values = self._surface_values(theta)
+        old = [s.parameter_row() for s in self.surfaces]
+        try:
+            for s, row in zip(self.surfaces, values):
+                s.set_parameter_row(row)
+        except ValueError:
+            for s, row in zip(self.surfaces, old):
+                s.set_parameter_row(row)
+            raise
+        self._invalidate()
+        self.trips = TripPlanner()
+        return self
+
+    @contextlib.contextmanager
+    def _surfaces_borrowed(self, theta):
+        """The lens as set_surface_parameters(theta) would make it, for the duration of one call: afterwards (also on
+        an exception) the records hold their old values and the device tables, pupils and planner are the old OBJECTS.
+        Nothing is touched when the values are already the records'."""
+        values = self._surface_values(theta)
+        old = [s.parameter_row() for s in self.surfaces]
+        if all(np.array_equal(a, b) for a, b in zip(old, values)):
+            yield
+            return
+        saved = (self._dev, self._pupil_cache, self.trips, self.__dict__.get("_curved_cache"))
+        try:
+            self._dev, self._pupil_cache = {}, {}
+            self.set_surface_parameters(values)
+            yield
+        finally:
+            for s, row in zip(self.surfaces, old):
+                s.d, s.c, s.k = np.float32(row[0]), np.float32(row[1]), np.float32(row[2])
+                if s.ai is not None:
+                    s.ai = row[3:3 + s.ai_degree].copy()
+            self._dev, self._pupil_cache, self.trips = saved[:3]
+            if saved[3] is not None:
+                self.__dict__["_curved_cache"] = saved[3]
 
     def find_aperture(self):
         """optics.py:193-201: first surface with air-like media on both sides."""
@@ -802,12 +859,12 @@ class Lensgroup:
         return self.psf_diff(points=points, wvln=wvln, ks=ks, spp=spp, center=center)
 
     def psf_diff(self, points, wvln=DEFAULT_WAVE, ks=31, spp=GEO_SPP, center=True,
-                 param_list=None, _defer=False):
+                 param_list=None, _defer=False, surface_params=None):
         """optics.py:934-996: normalised points [N,3] (or [3]) -> max-normalised
         PSF [N,ks,ks] (or [ks,ks]) of the left sub-pixel (right if param_list[4] != 'l')."""
         dp, right = _parse_param_list(param_list)
         res = self.psf_lr(points, ks=ks, wvln=wvln, spp=spp, center=center, dp=dp, want_r=right,
-                          _default_r_zero=(param_list is None), defer=_defer)
+                          _default_r_zero=(param_list is None), defer=_defer, surface_params=surface_params)
         pick = (lambda lr: lr[1]) if right else (lambda lr: lr[0])
         if _defer:
             return PendingPSF(lambda: pick(res.wait()))
@@ -883,7 +940,7 @@ class Lensgroup:
 
     def psf_lr(self, points, ks=31, wvln=DEFAULT_WAVE, spp=GEO_SPP, center=True,
                dp=(0.78, 1.44, 0.3, 0.5), normalize=True, want_r=True, _default_r_zero=False,
-               pupil_xy=None, center_pupil_xy=None, out=None, defer=False, center_out=None):
+               pupil_xy=None, center_pupil_xy=None, out=None, defer=False, center_out=None, surface_params=None):
         """Left AND right dual-pixel PSFs of one ray-traced batch: (L, R), each
         [N,ks,ks] (or [ks,ks] for a single point), max-normalised separately as
         optics.py:983-987 would normalise each of them.  dp = (h, f, w, r) of
@@ -912,8 +969,22 @@ class Lensgroup:
 
         Differentiable (optics.py:934-996 under autograd) when grad mode is on and h, f or w of dp -- or, with
         center=False, `points` -- require a gradient: the call then runs the staged chain and the splat through
-        monte_carlo.SplatFunction (_psf_lr_grad).  r, the wavelength, the lens, the rays and, with center=True,
-        the points get no gradient.  out=, center_out= and defer=True are refused there."""
+        monte_carlo.SplatFunction (_psf_lr_grad).  r, the wavelength, the rays and, with center=True,
+        the points get no gradient.  out=, center_out= and defer=True are refused there.
+
+        (trip_policy='adaptive' is refused with a theta that requires a gradient: its per-wave trip counts are not recorded.)
+        surface_params: a surface_parameters()-shaped tensor theta.  When it requires a gradient (and grad mode is on)
+        the PSFs are those of the lens set_surface_parameters(theta.detach()) would make -- the records are put back
+        afterwards -- and loss.backward() fills theta.grad with the gradient the reference's graph gives d, c, k and
+        ai of every surface (trace_grad.SurfaceGradFunction); h, f, w and the points get theirs in the
+        same call.  Otherwise the call is set_surface_parameters(theta) followed by the ordinary call."""
+        if surface_params is not None:
+            args = (points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy, center_pupil_xy,
+                    out, defer, center_out)
+            if _requires_grad(surface_params):
+                with self._surfaces_borrowed(surface_params):
+                    return self._psf_lr_grad(*args, surface_params=surface_params)
+            self.set_surface_parameters(surface_params)
         if _psf_needs_grad(dp if not _default_r_zero else None, points, center):
             return self._psf_lr_grad(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero,
                                      pupil_xy, center_pupil_xy, out, defer, center_out)
@@ -1198,9 +1269,10 @@ class Lensgroup:
                                                 dptr(L), dptr(R), st))
         return _epilogue(L, R, want_r, single_point)
 
-    def _staged_rays(self, points, po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen):
+    def _staged_rays(self, points, po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen, record=False):
         """The first stages of the staged chain: sample_from_points, psf_center (or the pinhole centres of
-        center=False) into `cen`, trace2sensor.  -> (the [spp, N] sensor-plane rays, spp)."""
+        center=False) into `cen`, trace2sensor.  -> (the [spp, N] sensor-plane rays, spp); record=True: the trace
+        keeps its checkpoints, -> (rays, spp, trace_grad.TraceRecord)."""
         pupilz, pupilr = self.entrance_pupil()
         # optics.py:963 (first two draws)
         x2, y2 = self._pupil_samples(spp, pupilr) if pupil_xy is None else map(self._on_device, pupil_xy)
@@ -1218,11 +1290,36 @@ class Lensgroup:
         else:
             self._pinhole_centres(points, cen)
         self.last_pupil_points = (x2, y2, xc, yc)
+        if record:
+            return ray, spp, self._trace2sensor_recorded(ray)
         self.trace(ray, forward=True, _to_sensor=self.d_sensor)        # trace2sensor, one pass
         return ray, spp
 
+    def _trace2sensor_recorded(self, ray):
+        """trace2sensor (forward, out of place, the same trip-table key and verification as trace()) through
+        sdirt_trace2sensor_record: the ray's storage is rebound to the sensor-plane bundle, -> the TraceRecord the
+        backward pass walks."""
+        if self.trip_policy == "adaptive":
+            raise ValueError("surface gradients need trip_policy 'reference' or 'max': the per-wave trip counts of "
+                             "'adaptive' are not recorded")
+        K = len(self.surfaces)
+        handle = self.dev_lens(ray.wvln)
+        dev_lens = self._dev[float(ray.wvln)]
+        nbytes = int(_lib.lib().sdirt_trace2sensor_grad_workspace_bytes(ray.numel, K))
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+        dst = Ray.empty(ray.shape, ray.wvln, self.device, obliq=ray.has_obliq)
+
+        def enqueue(trips, mask_ptr):
+            _lib.check(_lib.lib().sdirt_trace2sensor_record(handle, trips, self._math_flags(), float(self.d_sensor),
+                                                            ray.c_rays(), dst.c_rays(), ray.numel, mask_ptr, dptr(ws),
+                                                            stream_ptr(self.device)))
+        key = ("trace", round(float(ray.wvln), 6), 0, K, True, self.precision)
+        trips = self._run_with_trips(key, list(range(K)), enqueue)
+        ray._adopt(dst)
+        return TraceRecord(dev_lens, trips, self.precision, self.d_sensor, ws, ray, K)
+
     def _psf_lr_grad(self, points, ks, wvln, spp, center, dp, normalize, want_r, default_r_zero, pupil_xy,
-                     center_pupil_xy, out, defer, center_out):
+                     center_pupil_xy, out, defer, center_out, surface_params=None):
         """psf_lr under autograd: the staged chain's rays and centres (no gradient: optics.py:459, :888 are no_grad),
         then the RAW grids through monte_carlo.SplatFunction -- differentiable in h, f, w and, with center=False, in
         the pinhole centres points[:, :2] * sensor_size / 2 (optics.py:973-976) -- and the max-normalisation of
@@ -1241,13 +1338,21 @@ class Lensgroup:
         with torch.no_grad():
             po = self._points_to_object(points.detach())
             cen = torch.empty((N, 2), dtype=torch.float32, device=self.device)
-            ray, spp = self._staged_rays(points.detach(), po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen)
+            staged = self._staged_rays(points.detach(), po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen,
+                                       record=surface_params is not None)
+            ray, spp = staged[:2]
         if not center:
             # the pinhole centres of _pinhole_centres as torch ops on the caller's points: the same fp32 products
             pts = points.to(self.device, torch.float32)
             cen = torch.stack((pts[:, 0] * (self.sensor_size[1] / 2), pts[:, 1] * (self.sensor_size[0] / 2)), -1)
         param_list = None if (dp is None or default_r_zero) else (*dp[:4], "l")
         L, R = splat_autograd(ray, self.pixel_size, ks, cen, param_list, self.precision)
+        if surface_params is not None:
+            # the rays' share of the graph: dLoss/d(raw grids) -> the sensor-plane rays -> the recorded trace -> theta
+            dpp = None if param_list is None else _lib.DpParams(*[float(v) for v in param_list[:4]])
+            cen_c = cen.detach().to(self.device, torch.float32).reshape(N, 2).contiguous()
+            staged[2].center = cen_c
+            L, R = SurfaceGradFunction.apply(surface_params, L, R, staged[2], cen_c, self.pixel_size, ks, dpp)
         if normalize:
             L = L / (L.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
             R = R / (R.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
@@ -1256,7 +1361,7 @@ class Lensgroup:
         return _epilogue(L, R, want_r, single_point)
 
     def psf_rgb(self, points, ks=31, spp=GEO_SPP, center=True, param_list=None, pupil_xy=None,
-                center_pupil_xy=None):
+                center_pupil_xy=None, surface_params=None):
         """optics.py:999-1015: [N,3,ks,ks] (or [3,ks,ks]) -- the three wavelengths of WAVE_RGB, each an
         independent psf_diff (fresh pupil draws, in the reference's order; every chief-ray centre
         through the green lens).  The three calls are ONE kernel launch whatever the number of points
@@ -1270,8 +1375,11 @@ class Lensgroup:
             raise ValueError("center=False runs no chief-ray pass")
         n_points = points.shape[0] if points.dim() == 2 else 1
         dp, right = _parse_param_list(param_list)
+        surface_grad = surface_params is not None and _requires_grad(surface_params)
+        if surface_params is not None and not surface_grad:
+            self.set_surface_parameters(surface_params)
         if (n_points > 0 and self.device.type == "cuda" and self.mask_reduce is None and ks <= _lib.MAX_KS
-                and not _psf_needs_grad(dp, points, center)):
+                and not surface_grad and not _psf_needs_grad(dp, points, center)):
             return self._psf_rgb_fused(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy)
         # not one launch (grids above SDIRT_MAX_KS, a rank of a sharded run, or a call that records gradients: one
         # differentiable psf_diff per wavelength, stacked, as optics.py:1010-1014 does): wavelength by wavelength
@@ -1281,7 +1389,8 @@ class Lensgroup:
             lr = self.psf_lr(points, ks=ks, wvln=w, spp=spp, center=center, dp=dp, want_r=right,
                              _default_r_zero=(param_list is None),
                              pupil_xy=None if pupil_xy is None else (pupil_xy[0][i], pupil_xy[1][i]),
-                             center_pupil_xy=None if center_pupil_xy is None else (center_pupil_xy[0][i], center_pupil_xy[1][i]))
+                             center_pupil_xy=None if center_pupil_xy is None else (center_pupil_xy[0][i], center_pupil_xy[1][i]),
+                             surface_params=surface_params if surface_grad else None)
             psfs.append(lr[1] if right else lr[0])
         return torch.stack(psfs, dim=-3)
 

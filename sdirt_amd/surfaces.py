@@ -56,6 +56,44 @@ class Aspheric:
         s.n2 = float(self.mat2.ior(wvln))
         return s
 
+    def parameter_row(self):
+        """[d, c, k, ai2, ai4, ...] of this record as float32, unused entries 0 (Lensgroup.surface_parameters)."""
+        row = np.zeros(3 + _lib.MAX_AI, np.float32)
+        row[:3] = (self.d, self.c, self.k)
+        if self.ai is not None:
+            row[3:3 + self.ai_degree] = self.ai
+        return row
+
+    def owned_columns(self):
+        """Which entries of parameter_row() the reference's activate_grad (surfaces.py:837-860) makes parameters of
+        this surface with a gradient in its graph: d; c unless the surface is a plane; k of an asphere with k != 0;
+        the asphere's ai."""
+        own = np.zeros(3 + _lib.MAX_AI, bool)
+        kind = self.kind
+        own[0] = True
+        own[1] = kind != _lib.KIND_PLANE
+        own[2] = kind == _lib.KIND_ASPHERE and float(self.k) != 0.0
+        if kind == _lib.KIND_ASPHERE:
+            own[3:3 + self.ai_degree] = True
+        return own
+
+    def set_parameter_row(self, row):
+        """Write parameter_row() values back; ValueError when that would touch a column the surface does not own
+        or change its kind."""
+        row = np.asarray(row, np.float32)
+        changed = row != self.parameter_row()
+        if np.any(changed & ~self.owned_columns()):
+            raise ValueError(f"{KIND_NAMES[self.kind]} surface: column(s) {np.nonzero(changed & ~self.owned_columns())[0].tolist()} "
+                             "of (d, c, k, ai...) are not parameters of this surface")
+        kind = self.kind
+        old = (self.d, self.c, self.k, self.ai)
+        self.d, self.c, self.k = np.float32(row[0]), np.float32(row[1]), np.float32(row[2])
+        if self.ai is not None:
+            self.ai = row[3:3 + self.ai_degree].copy()
+        if self.kind != kind:
+            self.d, self.c, self.k, self.ai = old
+            raise ValueError(f"the write would turn a {KIND_NAMES[kind]} surface into another kind")
+
     def ray_reaction(self, ray):
         """surfaces.py:391-520: intersect `ray` with THIS surface and refract it; the ray object is updated and also
         returned, as in the reference (its storage is REBOUND to the traced bundle, like the reference's ray.o / d / ra:
