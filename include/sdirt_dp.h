@@ -566,6 +566,37 @@ int sdirt_local_psf_render_grad_img(const float* psf /*dev [B,H,W,2,ks,ks]*/, co
 int64_t sdirt_local_psf_render_grad_img_workspace_bytes(int32_t batch, int32_t channels, int32_t height,
                                                         int32_t width, int32_t ks);
 
+/* An RGB-D frame rendered into a dual-pixel pair straight from a ray-traced PSF volume: local_dp_psf_render
+ * (deeplens/render_psf.py:157-188: replicate padding, flipped kernels, fp32) with the kernel of every pixel
+ * interpolated trilinearly from the grid PSFs around it, inside the kernel -- no per-pixel kernel tensor exists.
+ * volume [Dz,Gy,Gx,2,ks,ks] fp32: z-major, then rows (y), then columns (x); [.,.,.,0] left, [.,.,.,1] right.
+ * Segment tables (dev): ix [W] int32, fx [W] fp32 per column; iy [H], fy [H] per row; iz, fz [B,H,W] per pixel.
+ * Segment i of an axis of n nodes lies between nodes i and min(i + 1, n - 1); i is clamped to [0, max(n - 2, 0)]
+ * on the device, so no table value makes the kernel read outside the volume.  Per pixel and side s
+ *   K = sum over the 8 corners of w * volume[corner],  w = (wz * wy) * wx, each factor f or 1 - f (fp32),
+ *   out_s[b,c,y,x] = sum_{i,j} K[s,i,j] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)],  pad = (ks-1)/2.
+ * Odd ks <= 63, 1 / 3 / 4 channels, batch and height <= 65535, any Dz, Gy, Gx >= 1.  batch == 0: SDIRT_OK, nothing
+ * to write. */
+int sdirt_render_psf_volume(const float* img /*dev [B,C,H,W]*/, const float* volume /*dev*/,
+                            const int32_t* ix /*dev*/, const float* fx /*dev*/, const int32_t* iy /*dev*/,
+                            const float* fy /*dev*/, const int32_t* iz /*dev*/, const float* fz /*dev*/,
+                            int32_t batch, int32_t channels, int32_t height, int32_t width, int32_t ks,
+                            int32_t depth_nodes, int32_t y_nodes, int32_t x_nodes, float* out_l /*dev [B,C,H,W]*/,
+                            float* out_r /*dev [B,C,H,W]*/, void* stream);
+
+/* Backward pass of sdirt_render_psf_volume with respect to the volume (what autograd gives
+ * deeplens/render_psf.py:157-188 applied to the interpolated kernels, passed back through the interpolation):
+ *   grad_volume[dz,gy,gx,s,i,j] = sum_{b,y,x} w(b,y,x; node) * sum_c grad_s[b,c,y,x] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)].
+ * EVERY element of grad_volume is written (it need not be initialised); a node no pixel touches gets exactly 0.
+ * fp32 sums in a fixed order, no atomics: two calls on the same operands give the same bits.  Same limits as the
+ * forward; no workspace.  batch == 0: SDIRT_OK as the forward, and grad_volume is still written, all 0. */
+int sdirt_render_psf_volume_grad(const float* img /*dev [B,C,H,W]*/, const float* grad_l /*dev [B,C,H,W]*/,
+                                 const float* grad_r /*dev [B,C,H,W]*/, const int32_t* ix /*dev*/,
+                                 const float* fx /*dev*/, const int32_t* iy /*dev*/, const float* fy /*dev*/,
+                                 const int32_t* iz /*dev*/, const float* fz /*dev*/, int32_t batch, int32_t channels,
+                                 int32_t height, int32_t width, int32_t ks, int32_t depth_nodes, int32_t y_nodes,
+                                 int32_t x_nodes, float* grad_volume /*dev [Dz,Gy,Gx,2,ks,ks]*/, void* stream);
+
 /* ---- the PSF network itself ------------------------------------------------ */
 
 /* The network is described by its layer widths: widths[0..n_layers] = in, hidden..., out.  The

@@ -1,0 +1,347 @@
+// sdirt_render_volume.hip -- an RGB-D frame rendered into a dual-pixel pair straight from a ray-traced PSF volume
+// (MI355X / gfx950 only), and the gradient of that render with respect to the volume.
+//
+// V [Dz,Gy,Gx,2,ks,ks] holds one L/R kernel pair per grid node.  The kernel of a pixel is the trilinear interpolation
+// of the eight nodes around it, K = sum_corners w * V[corner], w = (wz * wy) * wx with each factor f or 1 - f of the
+// segment tables (per column ix, fx; per row iy, fy; per pixel iz, fz), and the convolution is the one of
+// sdirt_local_psf_render (deeplens/render_psf.py:157-188: replicate padding, flipped taps):
+//   out_s[b,c,y,x]       = sum_{i,j} K[s,i,j] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)],       pad = (ks - 1) / 2
+//   dV[dz,gy,gx,s,i,j]   = sum_{b,y,x} w(y,x; node) * sum_c G_s[b,c,y,x] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)]
+// The per-pixel kernels exist in registers only.  fp32 operands and sums, no atomics: every sum is taken by one
+// thread (or one wave's butterfly) in a fixed order.  The tables are operands: an index outside [0, n-2] is clamped,
+// the upper node of a segment is min(i + 1, n - 1), so no table value can make a kernel read outside V.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "../../include/sdirt_dp.h"
+#include "sdirt_device.hpp"
+#include "sdirt_host.hpp"
+
+using namespace sdirt;
+
+namespace {
+
+constexpr int kMaxKsVolume = 63;
+constexpr int kPixChunk = 16;              // pixels of a row per workgroup of the forward (4 per wave)
+
+// the lower node of a segment of an axis of n nodes, whatever the table holds
+__device__ __forceinline__ int lower_node(int i, int n) { return min(max(i, 0), max(n - 2, 0)); }
+
+// The weight node g of an axis of n nodes has in the segment (i, f): 1 - f as the lower node, f as the upper; both
+// on an axis of one node, where the upper node is the lower.  `touches`: g is one of the segment's two nodes.
+__device__ __forceinline__ float node_weight(int i, float f, int g, int n, bool& touches)
+{
+    const int lo = lower_node(i, n), hi = min(lo + 1, n - 1);
+    touches = lo == g || hi == g;
+    const float a = lo == g ? 1.0f - f : 0.0f, b = hi == g ? f : 0.0f;
+    return lo == hi ? a + b : (lo == g ? a : b);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// forward
+// ---------------------------------------------------------------------------
+// One WAVE per output pixel, as k_local_psf_render: the lanes stride over the ks*ks taps; for its tap a lane reads the
+// eight corner values of each side (consecutive lanes, consecutive addresses: 256-B segments of a volume that stays in
+// L2 / Infinity Cache -- the pixels of a cell share their four (x, y) corners, and the workgroup's pixels are
+// neighbours in a row), forms K_l, K_r and multiplies the C image values at the flipped, clamped offset.  The segment
+// indices and weights are wave-uniform; the depth segment is read per pixel, nothing assumes a tile shares it.
+template <int C>
+__global__ void __launch_bounds__(kBlock)
+k_render_psf_volume(const float* __restrict__ img, const float* __restrict__ vol, const int* __restrict__ ix,
+                    const float* __restrict__ fx, const int* __restrict__ iy, const float* __restrict__ fy,
+                    const int* __restrict__ iz, const float* __restrict__ fz, int H, int W, int ks, int Dz, int Gy,
+                    int Gx, float* __restrict__ outl, float* __restrict__ outr)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int y = blockIdx.y, b = blockIdx.z;
+    const int pad = (ks - 1) / 2, kk = ks * ks;
+    const int64_t HW = (int64_t)H * W;
+    const float* __restrict__ img_b = img + (int64_t)b * C * HW;
+    // the lane's first tap and the step of 64 taps, as (row, column) of the kernel
+    const int fi0 = lane / ks, fj0 = lane - fi0 * ks, dfi = 64 / ks, dfj = 64 - dfi * ks;
+    const int y0 = lower_node(iy[y], Gy), y1 = min(y0 + 1, Gy - 1);
+    const float wy1 = fy[y], wy0 = 1.0f - wy1;
+    const int x_end = min(W, ((int)blockIdx.x + 1) * kPixChunk);
+    for (int x = blockIdx.x * kPixChunk + wave; x < x_end; x += kBlock / 64) {
+        const int64_t pixel = (int64_t)b * HW + (int64_t)y * W + x;
+        const int x0 = lower_node(ix[x], Gx), x1 = min(x0 + 1, Gx - 1);
+        const int z0 = lower_node(iz[pixel], Dz), z1 = min(z0 + 1, Dz - 1);
+        const float wx1 = fx[x], wx0 = 1.0f - wx1, wz1 = fz[pixel], wz0 = 1.0f - wz1;
+        // corner k = 4 * (z upper) + 2 * (y upper) + (x upper)
+        float w[8];
+        const float* v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int zz = k & 4 ? z1 : z0, yy = k & 2 ? y1 : y0, xx = k & 1 ? x1 : x0;
+            w[k] = ((k & 4 ? wz1 : wz0) * (k & 2 ? wy1 : wy0)) * (k & 1 ? wx1 : wx0);
+            v[k] = vol + (((int64_t)zz * Gy + yy) * Gx + xx) * 2 * kk;
+        }
+        float accl[C], accr[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) { accl[c] = 0.0f; accr[c] = 0.0f; }
+        int fi = fi0, fj = fj0;
+        for (int t = lane; t < kk; t += 64) {
+            float kl = 0.0f, kr = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                kl += w[k] * v[k][t];
+                kr += w[k] * v[k][kk + t];
+            }
+            // stored tap (fi, fj) multiplies the neighbour at the FLIPPED offset (render_psf.py:175)
+            const int yy = min(max(y + pad - fi, 0), H - 1), xx = min(max(x + pad - fj, 0), W - 1);
+            const float* px = img_b + ((int64_t)yy * W + xx);
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float p = px[c * HW];
+                accl[c] += kl * p;
+                accr[c] += kr * p;
+            }
+            fi += dfi;
+            fj += dfj;
+            if (fj >= ks) { fj -= ks; ++fi; }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            float a = accl[c], r = accr[c];
+            for (int off = 32; off > 0; off >>= 1) {
+                a += __shfl_xor(a, off);
+                r += __shfl_xor(r, off);
+            }
+            if (lane == 0) {
+                const int64_t o = ((int64_t)(b * C + c) * H + y) * W + x;
+                outl[o] = a;
+                outr[o] = r;
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// gradient with respect to the volume
+// ---------------------------------------------------------------------------
+// One workgroup per ((x, y) node, side, chunk of depth planes).  Thread t owns taps t, t + 256, ... of every plane of
+// the chunk; their sums live in LDS as acc[plane][tap] (each element is only ever touched by its owner, LDS is used
+// for its dynamic indexing by plane, so the sums need no barrier and no atomic).  The workgroup first finds the
+// columns and rows whose segment has this node as an end -- the smallest rectangle that holds them; with the monotone
+// tables axis_segments makes that is the at most four cells around the node -- then walks the rectangle's pixels,
+// batch by batch, image by image, in raster order.  A batch of 256 pixels is prepared by the 256 threads (weights,
+// planes, the C upstream values of this side) and left in LDS; then every thread adds, pixel after pixel,
+//   D = sum_c G[c] * img[c, clamp(y+pad-i), clamp(x+pad-j)]        acc[plane0][tap] += w0 * D, acc[plane1][tap] += w1 * D
+// for its taps.  Pixels whose weight at the node is 0, or whose planes lie in another chunk, are skipped.  At the end
+// the chunk's block of dV is written, every element once: nodes no pixel touches get the zeros acc started with.
+template <int C>
+__global__ void __launch_bounds__(kBlock)
+k_render_psf_volume_grad(const float* __restrict__ img, const float* __restrict__ gl, const float* __restrict__ gr,
+                         const int* __restrict__ ix, const float* __restrict__ fx, const int* __restrict__ iy,
+                         const float* __restrict__ fy, const int* __restrict__ iz, const float* __restrict__ fz, int B,
+                         int H, int W, int ks, int Dz, int Gy, int Gx, int planes, float* __restrict__ dvol)
+{
+    extern __shared__ __attribute__((aligned(16))) float acc[];          // [planes][ks*ks]
+    __shared__ float s_w0[kBlock], s_w1[kBlock], s_g[C][kBlock];
+    __shared__ int s_l0[kBlock], s_l1[kBlock], s_y[kBlock], s_x[kBlock];
+    __shared__ int s_range[4][kBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int gx = blockIdx.x % Gx, gy = blockIdx.x / Gx, side = blockIdx.y;
+    const int z_first = blockIdx.z * planes, nz = min(planes, Dz - z_first);
+    const int pad = (ks - 1) / 2, kk = ks * ks;
+    const int64_t HW = (int64_t)H * W;
+    const float* __restrict__ g = side ? gr : gl;
+    const int fi0 = tid / ks, fj0 = tid - fi0 * ks, dfi = kBlock / ks, dfj = kBlock - dfi * ks;
+
+    for (int l = 0; l < nz; ++l)
+        for (int t = tid; t < kk; t += kBlock) acc[l * kk + t] = 0.0f;
+
+    // the columns [x_lo, x_hi) and rows [y_lo, y_hi) that hold every pixel touching this node
+    int x_lo = W, x_hi = 0, y_lo = H, y_hi = 0;
+    for (int x = tid; x < W; x += kBlock) {
+        bool touches;
+        node_weight(ix[x], 0.0f, gx, Gx, touches);
+        if (touches) { x_lo = min(x_lo, x); x_hi = max(x_hi, x + 1); }
+    }
+    for (int y = tid; y < H; y += kBlock) {
+        bool touches;
+        node_weight(iy[y], 0.0f, gy, Gy, touches);
+        if (touches) { y_lo = min(y_lo, y); y_hi = max(y_hi, y + 1); }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        x_lo = min(x_lo, __shfl_xor(x_lo, off));
+        x_hi = max(x_hi, __shfl_xor(x_hi, off));
+        y_lo = min(y_lo, __shfl_xor(y_lo, off));
+        y_hi = max(y_hi, __shfl_xor(y_hi, off));
+    }
+    if (lane == 0) { s_range[0][wave] = x_lo; s_range[1][wave] = x_hi; s_range[2][wave] = y_lo; s_range[3][wave] = y_hi; }
+    __syncthreads();
+    for (int k = 0; k < kBlock / 64; ++k) {
+        x_lo = min(x_lo, s_range[0][k]);
+        x_hi = max(x_hi, s_range[1][k]);
+        y_lo = min(y_lo, s_range[2][k]);
+        y_hi = max(y_hi, s_range[3][k]);
+    }
+    const int nx = max(x_hi - x_lo, 0), ny = max(y_hi - y_lo, 0);
+    const int64_t npix = (int64_t)nx * ny;
+
+    for (int b = 0; b < B; ++b) {
+        const float* __restrict__ img_b = img + (int64_t)b * C * HW;
+        for (int64_t first = 0; first < npix; first += kBlock) {
+            __syncthreads();                                             // the previous batch has been consumed
+            const int64_t p = first + tid;
+            int l0 = -1, l1 = -1;
+            if (p < npix) {
+                const int y = y_lo + (int)(p / nx), x = x_lo + (int)(p - (p / nx) * nx);
+                bool ty, tx;
+                const float wy = node_weight(iy[y], fy[y], gy, Gy, ty), wx = node_weight(ix[x], fx[x], gx, Gx, tx);
+                const int64_t pixel = (int64_t)b * HW + (int64_t)y * W + x;
+                const int z0 = lower_node(iz[pixel], Dz), z1 = min(z0 + 1, Dz - 1);
+                const float f = fz[pixel];
+                const float w0 = ((1.0f - f) * wy) * wx, w1 = (f * wy) * wx;
+                if (ty && tx && w0 != 0.0f && z0 >= z_first && z0 < z_first + nz) l0 = z0 - z_first;
+                if (ty && tx && w1 != 0.0f && z1 >= z_first && z1 < z_first + nz) l1 = z1 - z_first;
+                s_w0[tid] = w0;
+                s_w1[tid] = w1;
+                s_y[tid] = y + pad;
+                s_x[tid] = x + pad;
+#pragma unroll
+                for (int c = 0; c < C; ++c) s_g[c][tid] = g[(int64_t)b * C * HW + c * HW + (int64_t)y * W + x];
+            }
+            s_l0[tid] = l0;
+            s_l1[tid] = l1;
+            __syncthreads();
+            const int n = (int)min((int64_t)kBlock, npix - first);
+            for (int q = 0; q < n; ++q) {
+                const int q0 = __builtin_amdgcn_readfirstlane(s_l0[q]), q1 = __builtin_amdgcn_readfirstlane(s_l1[q]);
+                if (q0 < 0 && q1 < 0) continue;
+                const float w0 = s_w0[q], w1 = s_w1[q];
+                const int yb = s_y[q], xb = s_x[q];
+                float u[C];
+#pragma unroll
+                for (int c = 0; c < C; ++c) u[c] = s_g[c][q];
+                int fi = fi0, fj = fj0;
+                for (int t = tid; t < kk; t += kBlock) {
+                    const int yy = min(max(yb - fi, 0), H - 1), xx = min(max(xb - fj, 0), W - 1);
+                    const float* px = img_b + ((int64_t)yy * W + xx);
+                    float d = u[0] * px[0];
+#pragma unroll
+                    for (int c = 1; c < C; ++c) d += u[c] * px[c * HW];
+                    if (q0 >= 0) acc[q0 * kk + t] += w0 * d;
+                    if (q1 >= 0) acc[q1 * kk + t] += w1 * d;
+                    fi += dfi;
+                    fj += dfj;
+                    if (fj >= ks) { fj -= ks; ++fi; }
+                }
+            }
+        }
+    }
+    for (int l = 0; l < nz; ++l) {
+        float* __restrict__ out = dvol + ((((int64_t)(z_first + l) * Gy + gy) * Gx + gx) * 2 + side) * kk;
+        for (int t = tid; t < kk; t += kBlock) out[t] = acc[l * kk + t];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------
+namespace {
+
+// depth planes whose [ks*ks] sums fit in the 64 KiB of LDS a workgroup of the gradient asks for at most
+constexpr int kGradLds = 64 * 1024;
+int planes_per_chunk(int Dz, int ks) { return std::min(Dz, kGradLds / (int)(sizeof(float) * ks * ks)); }
+
+int check_volume_render(const void* img, const void* a, const void* b, const int32_t* ix, const float* fx,
+                        const int32_t* iy, const float* fy, const int32_t* iz, const float* fz, int B, int C, int H,
+                        int W, int ks, int Dz, int Gy, int Gx)
+{
+    if (!img || !a || !b || !ix || !fx || !iy || !fy || !iz || !fz)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (B < 0 || H < 1 || W < 1 || Dz < 1 || Gy < 1 || Gx < 1 || ks < 1 || (ks & 1) == 0)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad shape (ks must be odd, every extent >= 1)");
+    if (C != 1 && C != 3 && C != 4) return fail(SDIRT_ERR_UNSUPPORTED, "channels=%d (supported: 1, 3, 4)", C);
+    if (ks > kMaxKsVolume)
+        return fail(SDIRT_ERR_UNSUPPORTED, "ks=%d: the volume render supports ks <= %d", ks, kMaxKsVolume);
+    if (B > 65535 || H > 65535) return fail(SDIRT_ERR_UNSUPPORTED, "batch=%d height=%d (supported: <= 65535)", B, H);
+    if ((int64_t)Gy * Gx > INT32_MAX) return fail(SDIRT_ERR_UNSUPPORTED, "%d x %d nodes per plane", Gy, Gx);
+    return SDIRT_OK;
+}
+
+template <int C>
+int launch_volume_grad(dim3 grid, size_t lds, hipStream_t st, const float* img, const float* gl, const float* gr,
+                       const int32_t* ix, const float* fx, const int32_t* iy, const float* fy, const int32_t* iz,
+                       const float* fz, int B, int H, int W, int ks, int Dz, int Gy, int Gx, int planes, float* dvol)
+{
+    if (lds > 32 * 1024)
+        if (int rc = allow_large_lds<&k_render_psf_volume_grad<C>>(kGradLds)) return rc;
+    k_render_psf_volume_grad<C><<<grid, kBlock, lds, st>>>(img, gl, gr, ix, fx, iy, fy, iz, fz, B, H, W, ks, Dz, Gy,
+                                                           Gx, planes, dvol);
+    return SDIRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdirt_render_psf_volume(const float* img, const float* volume, const int32_t* ix, const float* fx,
+                            const int32_t* iy, const float* fy, const int32_t* iz, const float* fz, int32_t B,
+                            int32_t C, int32_t H, int32_t W, int32_t ks, int32_t Dz, int32_t Gy, int32_t Gx,
+                            float* out_l, float* out_r, void* stream)
+{
+    if (!volume) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = check_volume_render(img, out_l, out_r, ix, fx, iy, fy, iz, fz, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
+    if (B == 0) return SDIRT_OK;
+    const dim3 grid((unsigned)((W + kPixChunk - 1) / kPixChunk), (unsigned)H, (unsigned)B);
+    hipStream_t st = as_stream(stream);
+    switch (C) {
+    case 1:
+        k_render_psf_volume<1><<<grid, kBlock, 0, st>>>(img, volume, ix, fx, iy, fy, iz, fz, H, W, ks, Dz, Gy, Gx,
+                                                        out_l, out_r);
+        break;
+    case 3:
+        k_render_psf_volume<3><<<grid, kBlock, 0, st>>>(img, volume, ix, fx, iy, fy, iz, fz, H, W, ks, Dz, Gy, Gx,
+                                                        out_l, out_r);
+        break;
+    default:
+        k_render_psf_volume<4><<<grid, kBlock, 0, st>>>(img, volume, ix, fx, iy, fy, iz, fz, H, W, ks, Dz, Gy, Gx,
+                                                        out_l, out_r);
+        break;
+    }
+    LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+
+int sdirt_render_psf_volume_grad(const float* img, const float* grad_l, const float* grad_r, const int32_t* ix,
+                                 const float* fx, const int32_t* iy, const float* fy, const int32_t* iz,
+                                 const float* fz, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ks, int32_t Dz,
+                                 int32_t Gy, int32_t Gx, float* grad_volume, void* stream)
+{
+    if (!grad_volume) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int rc = check_volume_render(img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, C, H, W, ks, Dz, Gy, Gx))
+        return rc;
+    // (an empty batch is launched like any other: every element of grad_volume is written, all 0)
+    const int planes = planes_per_chunk(Dz, ks), chunks = (Dz + planes - 1) / planes;
+    if (chunks > 65535) return fail(SDIRT_ERR_UNSUPPORTED, "%d depth planes at ks=%d", Dz, ks);
+    const dim3 grid((unsigned)(Gy * Gx), 2u, (unsigned)chunks);
+    const size_t lds = sizeof(float) * (size_t)planes * ks * ks;
+    hipStream_t st = as_stream(stream);
+    int rc;
+    switch (C) {
+    case 1:
+        rc = launch_volume_grad<1>(grid, lds, st, img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, H, W, ks, Dz, Gy, Gx,
+                                   planes, grad_volume);
+        break;
+    case 3:
+        rc = launch_volume_grad<3>(grid, lds, st, img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, H, W, ks, Dz, Gy, Gx,
+                                   planes, grad_volume);
+        break;
+    default:
+        rc = launch_volume_grad<4>(grid, lds, st, img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, H, W, ks, Dz, Gy, Gx,
+                                   planes, grad_volume);
+        break;
+    }
+    if (rc) return rc;
+    LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+
+}  // extern "C"

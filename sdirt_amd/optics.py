@@ -1360,6 +1360,33 @@ class Lensgroup:
             R = None
         return _epilogue(L, R, want_r, single_point)
 
+    def psf_volume(self, grid=(32, 32), z=16, ks=21, spp=GEO_SPP, dp=(0.78, 1.44, 0.3, 0.5), wvln=DEFAULT_WAVE,
+                   surface_params=None, pupil_xy=None, center_pupil_xy=None):
+        """The ray-traced PSF grid of the whole field and depth range as a render_psf.PSFVolume, for
+        local_dp_psf_render_volume / PSFNet.render_volume: grid = (rows, columns) of cell-centred sensor nodes
+        (psfnet.py:220-226: x from -1 + 1/(2 gx) to 1 - 1/(2 gx), y from 1 - 1/(2 gy) down), z = a number of depth
+        nodes spread evenly over the normalised depth [0, 1], or a 1-D tensor of strictly monotone normalised depths;
+        depth = z (d_max - d_min) + d_min with the lens's d_min / d_max (PSFNet's; -200 / -20000 mm on a plain
+        Lensgroup, psfnet.py:15-16).
+
+        ONE psf_lr call on the Dz*Gy*Gx points, so it is differentiable exactly where psf_lr is (h, f, w of dp,
+        surface_params); L and R are stacked and each divided by its own sum with torch ops, which keeps the graph."""
+        from .render_psf import PSFVolume
+        gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
+        z_nodes = (z.detach().to(torch.float32).reshape(-1).cpu() if torch.is_tensor(z)
+                   else torch.linspace(0, 1, int(z)) if int(z) > 1 else torch.zeros(1))
+        d_min, d_max = float(getattr(self, "d_min", -200.0)), float(getattr(self, "d_max", -20000.0))
+        vol = PSFVolume(None, torch.linspace(-1 + 1 / (2 * gx), 1 - 1 / (2 * gx), gx),
+                        torch.linspace(1 - 1 / (2 * gy), -1 + 1 / (2 * gy), gy), z_nodes, d_min, d_max)
+        L, R = self.psf_lr(vol.points(), ks=ks, wvln=wvln, spp=spp, dp=dp, pupil_xy=pupil_xy,
+                           center_pupil_xy=center_pupil_xy, surface_params=surface_params)
+        psf = torch.stack((L, R), -3)                                              # [N, 2, ks, ks]
+        psf = psf / psf.sum((-1, -2), keepdim=True).clamp_min(1e-30)               # (a node no ray reaches stays 0)
+        vol.psf = psf.reshape(len(z_nodes), gy, gx, 2, ks, ks)
+        dev = vol.psf.device
+        vol.x_nodes, vol.y_nodes, vol.z_nodes = vol.x_nodes.to(dev), vol.y_nodes.to(dev), vol.z_nodes.to(dev)
+        return vol
+
     def psf_rgb(self, points, ks=31, spp=GEO_SPP, center=True, param_list=None, pupil_xy=None,
                 center_pupil_xy=None, surface_params=None):
         """optics.py:999-1015: [N,3,ks,ks] (or [3,ks,ks]) -- the three wavelengths of WAVE_RGB, each an

@@ -21,7 +21,7 @@ import torch
 
 from .optics import Lensgroup
 from .psfnet_arch import MLP, MLPConv, initialize_weights
-from .render_psf import local_psf_render_fast, psfnet_render
+from .render_psf import local_dp_psf_render_volume, local_psf_render_fast, psfnet_render
 
 DMIN = 200      # [mm]  psfnet.py:15
 DMAX = 20000    # [mm]  psfnet.py:16
@@ -429,6 +429,22 @@ class PSFNet(Lensgroup):
         render = torch.cat(render_lr, dim=1)
         if not train and render.is_cuda and render.dtype == torch.float32:
             return self._tone(render, 1)                      # gamma + clip in one pass
+        render = self.gamma(render)
+        if train:
+            render = self.noise(render, img.shape)
+        return torch.clip(render, 0.0, 1.0)
+
+    def render_volume(self, img, depth, volume, train=False):
+        """render()'s batched branch (psfnet.py:676-714) with the per-pixel kernels taken from a ray-traced
+        render_psf.PSFVolume (Lensgroup.psf_volume) instead of the network: depth + d_sensor -> depth2z, degamma,
+        local_dp_psf_render_volume in fp32, gamma, noise when `train`, clip.  img [N,C,H,W], depth [N,1,H,W] (mm,
+        negative) -> [N,2C,H,W].  Not under no_grad: a volume that requires a gradient gets one (torch ops for the
+        tone curve); the same call without gradients is the ground truth a fitted network is judged against."""
+        if img.dim() != 4:
+            raise ValueError("render_volume expects img [N,C,H,W] and depth [N,1,H,W]")
+        z = self.depth2z(depth + self.d_sensor).squeeze(1)
+        render = local_dp_psf_render_volume(self.degamma(img), volume.psf, volume.x_nodes, volume.y_nodes,
+                                            volume.z_nodes, z, volume.psf.shape[-1])
         render = self.gamma(render)
         if train:
             render = self.noise(render, img.shape)

@@ -5,6 +5,8 @@ an unfold buffer [B, C*ks*ks, H*W] (1 GB at 512x768, ks 21) and multiplies it
 with the per-pixel kernels; here one HIP kernel gathers the ks*ks neighbourhood
 of every output pixel and reads each per-pixel kernel exactly once.
 """
+import dataclasses
+
 import torch
 
 from . import _lib
@@ -86,6 +88,152 @@ def local_dp_psf_render(input, dp_psf, kernel_size=21):
         return _LocalDpPsfRender.apply(input, dp_psf, kernel_size)
     rl, rr = _render(input, dp_psf, kernel_size, half=False)
     return torch.cat([rl, rr], dim=1)
+
+
+def axis_segments(nodes, t):
+    """Where the coordinates `t` (any shape) fall on a 1-D axis of strictly monotone `nodes` (increasing or
+    decreasing), in fp32 -> (i int32, f fp32), each shaped like t: t lies between nodes[i] and nodes[i + 1], i clamped
+    to [0, n - 2], and f = clamp((t - nodes[i]) / (nodes[i + 1] - nodes[i]), 0, 1) -- outside the node range the end
+    node alone counts (constant extrapolation).  A t exactly on the last node gives (n - 2, 1).  An axis of one node
+    gives i = 0, f = 0."""
+    nodes = nodes.to(torch.float32).reshape(-1)
+    t = t.to(device=nodes.device, dtype=torch.float32)
+    n = nodes.numel()
+    if n < 1:
+        raise ValueError("axis_segments needs at least one node")
+    if n == 1:
+        return torch.zeros(t.shape, dtype=torch.int32, device=t.device), torch.zeros_like(t)
+    ascending = bool(nodes[-1] > nodes[0])
+    steps = nodes[1:] - nodes[:-1]
+    if not bool(((steps > 0) if ascending else (steps < 0)).all()):
+        raise ValueError("axis_segments needs strictly monotone nodes")
+    # decreasing nodes: the same search on the negated axis (negation is exact)
+    key, val = (nodes, t) if ascending else (-nodes, -t)
+    i = (torch.searchsorted(key.contiguous(), val.contiguous(), right=True) - 1).clamp(0, n - 2)
+    lo, hi = nodes[i], nodes[i + 1]
+    f = ((t - lo) / (hi - lo)).clamp(0.0, 1.0) + 0.0                      # (+ 0.0: a -0 of a decreasing axis becomes 0)
+    return i.to(torch.int32), f
+
+
+def volume_segment_tables(x_nodes, y_nodes, z_nodes, z, height, width):
+    """The six segment tables of local_dp_psf_render_volume for an image of height x width pixels and the normalised
+    depth map z [B,H,W]: pixel x = linspace(-1, 1, W), pixel y = linspace(1, -1, H) (the render grid of
+    psfnet.py:684-688) -> (ix [W], fx [W], iy [H], fy [H], iz [B,H,W], fz [B,H,W]) on z's device."""
+    dev = z.device
+    ix, fx = axis_segments(x_nodes.to(dev), torch.linspace(-1, 1, width, device=dev))
+    iy, fy = axis_segments(y_nodes.to(dev), torch.linspace(1, -1, height, device=dev))
+    iz, fz = axis_segments(z_nodes.to(dev), z)
+    return tuple(t.contiguous() for t in (ix, fx, iy, fy, iz, fz))
+
+
+def _volume_shape(img, volume, tables, ks):
+    b, c, h, w = img.shape
+    dz, gy, gx = volume.shape[:3]
+    if tuple(volume.shape) != (dz, gy, gx, 2, ks, ks):
+        raise ValueError(f"volume must be [Dz, Gy, Gx, 2, {ks}, {ks}], got {tuple(volume.shape)}")
+    want = ((w,), (w,), (h,), (h,), (b, h, w), (b, h, w))
+    for t, shape, dtype in zip(tables, want, (torch.int32, torch.float32) * 3):
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != img.device or not t.is_contiguous():
+            raise ValueError(f"segment tables must be contiguous (int32, float32) pairs of shapes {want} on the image's device")
+    return b, c, h, w, dz, gy, gx
+
+
+def _render_volume(img, volume, tables, ks):
+    """img [B,C,H,W] and volume [Dz,Gy,Gx,2,ks,ks], fp32 contiguous on the GPU -> (left, right) [B,C,H,W]."""
+    if img.device.type != "cuda":
+        raise _lib.SdirtError("sdirt_amd renders on the GPU only (no CPU fallback)")
+    b, c, h, w, dz, gy, gx = _volume_shape(img, volume, tables, ks)
+    rl = torch.empty((b, c, h, w), dtype=torch.float32, device=img.device)
+    rr = torch.empty_like(rl)
+    _lib.check(_lib.lib().sdirt_render_psf_volume(dptr(img), dptr(volume), *(dptr(t) for t in tables), b, c, h, w, ks,
+                                                  dz, gy, gx, dptr(rl), dptr(rr), stream_ptr(img.device)))
+    return rl, rr
+
+
+class _RenderPsfVolume(torch.autograd.Function):
+    """local_dp_psf_render_volume under autograd: the forward is _render_volume's kernel call on the same operands
+    (bit-equal to the no-grad call), the backward sdirt_render_psf_volume_grad."""
+
+    @staticmethod
+    def forward(ctx, volume, img, ks, *tables):
+        vol = volume.to(torch.float32).contiguous()
+        rl, rr = _render_volume(img, vol, tables, ks)
+        ctx.save_for_backward(img, *tables)
+        ctx.kernel_size, ctx.volume_shape, ctx.volume_dtype = ks, vol.shape, volume.dtype
+        return torch.cat([rl, rr], dim=1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        img, *tables = ctx.saved_tensors
+        b, c, h, w = img.shape
+        dz, gy, gx = ctx.volume_shape[:3]
+        gl = grad[:, :c].to(torch.float32).contiguous()
+        gr = grad[:, c:].to(torch.float32).contiguous()
+        dvol = torch.empty(ctx.volume_shape, dtype=torch.float32, device=img.device)
+        _lib.check(_lib.lib().sdirt_render_psf_volume_grad(dptr(img), dptr(gl), dptr(gr), *(dptr(t) for t in tables),
+                                                           b, c, h, w, ctx.kernel_size, dz, gy, gx, dptr(dvol),
+                                                           stream_ptr(img.device)))
+        return (dvol.to(ctx.volume_dtype), None, None) + (None,) * len(tables)
+
+
+def local_dp_psf_render_volume(input, volume, x_nodes, y_nodes, z_nodes, z, kernel_size=21):
+    """An image and its normalised depth map rendered into a dual-pixel pair straight from a PSF volume:
+    local_dp_psf_render (render_psf.py:157-188) with the kernel of every pixel interpolated trilinearly in (x, y, z)
+    from the eight grid PSFs around it, inside the HIP kernel -- the [B,H,W,2,ks,ks] tensor never exists.
+    -> [B, 2C, H, W] = cat(left, right).
+
+    input [B,C,H,W]; volume [Dz,Gy,Gx,2,ks,ks] (z-major, then rows, then columns: the order of a VolumeStepper block);
+    x_nodes [Gx], y_nodes [Gy], z_nodes [Dz] strictly monotone (axis_segments); z [B,H,W] in the units of z_nodes.
+    Pixel x = linspace(-1, 1, W), pixel y = linspace(1, -1, H).  Outside the nodes the end PSF is used.  The kernel
+    does no normalisation: sum-normalised node PSFs give sum-normalised per-pixel kernels.
+
+    Differentiable in `volume` (a call in grad mode on a volume that requires a gradient goes through _RenderPsfVolume:
+    same forward kernel, same values).  Gradients in the image and in the depth are not built: asking for them raises."""
+    if input.dim() < 4:
+        input = input.unsqueeze(0)
+    grad_mode = torch.is_grad_enabled()
+    if grad_mode and input.requires_grad:
+        raise ValueError("local_dp_psf_render_volume: the gradient with respect to the image is not built "
+                         "(detach the image; local_dp_psf_render has one)")
+    if grad_mode and z.requires_grad:
+        raise ValueError("local_dp_psf_render_volume: the gradient with respect to the depth is not built (detach z)")
+    b, _, h, w = input.shape
+    img = input.detach().to(torch.float32).contiguous()
+    zz = z.detach().to(img.device).reshape(b, h, w)
+    tables = volume_segment_tables(x_nodes.detach(), y_nodes.detach(), z_nodes.detach(), zz, h, w)
+    volume = volume.to(img.device)
+    if grad_mode and volume.requires_grad:
+        return _RenderPsfVolume.apply(volume, img, kernel_size, *tables).to(input.dtype)
+    rl, rr = _render_volume(img, volume.detach().to(torch.float32).contiguous(), tables, kernel_size)
+    return torch.cat([rl, rr], dim=1).to(input.dtype)
+
+
+@dataclasses.dataclass
+class PSFVolume:
+    """A ray-traced PSF grid as local_dp_psf_render_volume consumes it (Lensgroup.psf_volume makes one).
+    psf [Dz,Gy,Gx,2,ks,ks]: left and right PSF of every node, each sum-normalised; x_nodes [Gx], y_nodes [Gy]:
+    normalised sensor coordinates (y decreases, as the image's rows do); z_nodes [Dz]: normalised depth
+    z = (depth - d_min) / (d_max - d_min) (PSFNet.depth2z), depth in mm."""
+    psf: torch.Tensor
+    x_nodes: torch.Tensor
+    y_nodes: torch.Tensor
+    z_nodes: torch.Tensor
+    d_min: float
+    d_max: float
+
+    def points(self):
+        """[Dz*Gy*Gx, 3] points (x, y normalised, depth in mm) in the volume's order: what psf_lr is given."""
+        depth = self.z_nodes.to(torch.float32) * (self.d_max - self.d_min) + self.d_min
+        dz, gy, gx = len(self.z_nodes), len(self.y_nodes), len(self.x_nodes)
+        x = self.x_nodes.to(torch.float32).reshape(1, 1, gx).expand(dz, gy, gx)
+        y = self.y_nodes.to(torch.float32).reshape(1, gy, 1).expand(dz, gy, gx)
+        return torch.stack((x, y, depth.reshape(dz, 1, 1).expand(dz, gy, gx)), -1).reshape(-1, 3).contiguous()
+
+    def render(self, input, z):
+        """local_dp_psf_render_volume of this volume."""
+        return local_dp_psf_render_volume(input, self.psf, self.x_nodes, self.y_nodes, self.z_nodes, z,
+                                          self.psf.shape[-1])
 
 
 def psfnet_render(input, raw_l, raw_r, kernel_size):
