@@ -514,6 +514,21 @@ int sdirt_host_uniform_fill(void* th_state /*host, in/out*/, int64_t state_bytes
 int sdirt_selftest_math(int32_t mode, uint64_t first, uint64_t count, int32_t exp_span,
                         uint64_t* out /*dev [9]*/, void* stream);
 
+/* The fused PSF kernel reads the dual-pixel weights (sl, sr) of a ray from a table over x_tan that belongs to the
+ * SENSOR (h, f, w, r): built in float64 once per parameter set on the stream of the first call that needs it, kept in
+ * the lens handle the call renders through (lens[0] of a multi-wavelength call) and rebuilt, in stream order and without
+ * a host synchronisation, when a call brings other parameters.  SDIRT_PSF_STRICT_IEEE, r > 0.5, the staged entry points
+ * and the backward passes evaluate the closed form, as does a call on a stream that is being captured.  (Setting
+ * SDIRT_DP_WEIGHT_TABLE=0 in the environment makes every call evaluate the closed form: a test hook.)
+ * This entry evaluates BOTH forms, exactly as the kernel does, at n abscissae: lr_table / lr_closed [n][2] = (sl, sr)
+ * interpolated in the handle's table for `dp` (built here if need be) / from the closed form.  info (host, may be
+ * NULL): [0] entries of the table, [1] log2 of its cells per unit of x_tan.  SDIRT_ERR_UNSUPPORTED when these
+ * parameters have no table (r > 0.5; a sensor so steep, f h / (f - h) large, that linear interpolation in the largest
+ * table would miss its error bound). */
+int sdirt_dp_weight_table_selftest(const sdirt_lens* lens, const sdirt_dp_params* dp, const float* x_tan /*dev [n]*/,
+                                   int64_t n, float* lr_table /*dev [n][2]*/, float* lr_closed /*dev [n][2]*/,
+                                   int32_t* info /*host [2]*/, void* stream);
+
 /* ---- image-space consumer of the PSFs ------------------------------------ */
 
 /* local_psf_render_fast / local_psf_render / local_dp_psf_render,

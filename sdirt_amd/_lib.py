@@ -137,6 +137,7 @@ SIGNATURES = {
     "sdirt_ctl_from_lanes": (C.c_int, [_P, _P, C.POINTER(_I32), C.POINTER(_I32), _P, _P, _P]),
     "sdirt_host_uniform_fill": (C.c_int, [_P, _I64, _I64, _P]),
     "sdirt_selftest_math": (C.c_int, [_I32, C.c_uint64, C.c_uint64, _I32, _P, _P]),
+    "sdirt_dp_weight_table_selftest": (C.c_int, [_P, C.POINTER(DpParams), _P, _I64, _P, _P, C.POINTER(_I32), _P]),
     "sdirt_local_psf_render": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "sdirt_psfnet_render": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "sdirt_local_psf_render_grad_psf": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),

@@ -761,6 +761,48 @@ __device__ __forceinline__ void dp_weights_small(const DevDpParams& p, float x_t
     dp_weights_small<Lean>(p, UDiv<Ieee>::make(p.fmh), x_tan, sl, sr);
 }
 
+// The same weights from the sensor's table (host side: DpWeightTable, sdirt_psf.hip).  The closed form is
+//     sl = [sl_ml - sl_in] + (xm - xl),   sr = [sr_ml - sr_in] + (xr - xm)
+// with xr, xm, xl = w - h x, -h x, -w - h x clamped to +-0.5: the brackets hold the twelve circle-segment areas -- all of
+// the expensive arithmetic, and C1 in x_tan (each area ends like (1 - z)^(3/2)) -- and go into the table; the two strip
+// widths are piecewise LINEAR with a kink at each clamp, which no table interpolates, and cost three clamps: they are
+// evaluated as before.  Entry i holds the brackets at x_tan = (i - half) / scale, evaluated in float64 and rounded once.
+// scale is a power of two, so x_tan * scale is EXACT and the interpolation fraction carries no rounding of its own;
+// outside the table -- where every clamped argument of a segment area is saturated and the brackets are constant --
+// the index is clamped (NaN goes to the first entry).  The buffer has one entry more than any index reaches:
+// i0 + 1 <= 2 * half.
+struct DpTableRef {
+    const float2* tab;
+    float scale;         // 2^k cells per unit of x_tan
+    float lo, hi;        // -half, half - 1
+    int32_t half;
+    float h, w;          // DevDpParams' h and w, for the strip widths
+};
+typedef float DpTablePair __attribute__((ext_vector_type(4), aligned(8)));     // entry i0 (left, right), entry i0 + 1
+// fetch: issued as soon as x_tan is known, so that the load's latency lies under the tap arithmetic.  One 16-byte
+// vector load from global memory (the pointer arrives as two words of a kernel-argument block: without the address
+// space the compiler issues a flat load, whose wait also covers the LDS atomics in flight).  The empty statement
+// behind it keeps the compiler from sinking the load into the branch that uses it.
+__device__ __forceinline__ DpTablePair dp_table_fetch(const DpTableRef& t, float x_tan, float& frac)
+{
+    typedef const DpTablePair __attribute__((address_space(1))) * GlobalPair;
+    const float c = __builtin_fminf(__builtin_fmaxf(x_tan * t.scale, t.lo), t.hi);
+    const float fl = __builtin_floorf(c);
+    frac = c - fl;
+    const DpTablePair q = *(GlobalPair)(uintptr_t)(t.tab + ((int)fl + t.half));
+    asm volatile("" ::: "memory");
+    return q;
+}
+__device__ __forceinline__ void dp_table_weights(const DpTableRef& t, const DpTablePair& q, float frac, float x_tan,
+                                                 float& sl, float& sr)
+{
+    const float hx = t.h * x_tan;
+    const float xr = clamp_finite(t.w - hx, -0.5f, 0.5f), xm = clamp_finite(0.0f - hx, -0.5f, 0.5f),
+                xl = clamp_finite((-t.w) - hx, -0.5f, 0.5f);
+    sl = __builtin_fmaf(frac, q.z - q.x, q.x) + (xm - xl);
+    sr = __builtin_fmaf(frac, q.w - q.y, q.y) + (xr - xm);
+}
+
 // monte_carlo.py:274-338 (r > 0.5)
 __device__ __forceinline__ void dp_weights_big(const DevDpParams& p, float x_tan, float& sl,
                                                float& sr)

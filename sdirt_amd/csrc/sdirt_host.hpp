@@ -9,6 +9,7 @@
 #include <cstdio>
 
 #include <cstdint>
+#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -88,11 +89,28 @@ inline int device_cus_or_default()
 }
 
 
+// The dual-pixel sub-pixel weights (sl, sr) of k_psf_lr as a table over x_tan (sdirt_psf.hip: dp_table_for): a
+// property of the SENSOR (h, f, w, r), built once per parameter set and kept with the lens handle the call renders
+// through.  The device buffer is allocated with the handle (data-path calls never allocate) and holds
+// kDpTableEntries + 1 float2 whatever the parameters, so that no index the kernel can form leaves it.
+constexpr int kDpTableEntries = 1 << 18;          // capacity: 2 MiB; a parameter set uses 2 * half + 1 entries of it
+struct DpWeightTable {
+    float2* dev = nullptr;                        // [kDpTableEntries + 1] (sl, sr) at x_tan = (i - half) / scale
+    bool built = false;
+    uint64_t key[4] = {};                         // bit patterns of the doubles (h, f, w, r) the entries were built from
+    int half = 0;                                 // entries on either side of x_tan = 0
+    int log2_scale = 0;                           // cells per unit of x_tan: a power of two, the index is exact in fp32
+    hipEvent_t ready = nullptr;                   // recorded behind the build on the stream that ran it
+    std::vector<hipStream_t> synced;              // streams already ordered behind `ready`
+    std::mutex lock;
+};
+
 // A prescription at one wavelength: the device table the kernels read and its host mirror.
 struct sdirt_lens {
     int32_t n_surfaces;
     sdirt::DevSurface* dev;               // device table [n_surfaces]
     std::vector<sdirt::DevSurface> host;  // host mirror
+    mutable DpWeightTable dp_table;       // filled by the PSF calls that render through this handle
 };
 
 // Newton trip counts of one launch, one signed byte per surface, passed by value at a FIXED

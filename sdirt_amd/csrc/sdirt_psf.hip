@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <type_traits>
@@ -22,23 +23,181 @@ using namespace sdirt;
 // 64-byte block at offset 0 of k_psf_lr's kernel-argument segment: the kernel fetches it with one
 // scalar load per RAY, right before the splat, instead of keeping ~20 SGPRs alive through the
 // trace (where round 1's build parked them in VGPR lanes: v_writelane / v_readlane traffic).
+// Words 7..14 are the dual-pixel parameters of the closed form -- or, in the TAB instantiations, which never
+// evaluate it, the reference to the sensor's weight table (DpTableRef): the pointer travels in the block the
+// kernel re-reads per ray and costs no SGPR across the trace.
 struct alignas(64) SplatBlock {
     float lim, x_min, y_max, dx_rng, dy_rng, ksm1;
     int32_t ks;
-    float h, f, w, r, fmh, rr, inv_r;
-    int32_t r_pow2;
+    union {
+        struct { float h, f, w, r, fmh, rr, inv_r; int32_t r_pow2; } dp;                    // words 7..14
+        struct { float scale; uint32_t tab_lo, tab_hi; float lo, hi; int32_t half; float h, w; } tb;   // 7, 8-9 (pointer), 10 .. 14
+    };
     int32_t pad;
 };
 static_assert(sizeof(SplatBlock) == 64, "layout");
+static_assert(offsetof(SplatBlock, dp.h) == 28 && offsetof(SplatBlock, dp.r_pow2) == 56, "layout");
+static_assert(offsetof(SplatBlock, tb.scale) == 28 && offsetof(SplatBlock, tb.tab_lo) == 32 && offsetof(SplatBlock, tb.half) == 48, "layout");
 
-static SplatBlock make_splat_block(const SplatGeom& g, const DevDpParams& p)
+static SplatBlock make_splat_block(const SplatGeom& g, const DevDpParams& p, const DpTableRef* t)
 {
     SplatBlock b;
+    std::memset(&b, 0, sizeof(b));
     b.lim = g.lim; b.x_min = g.x_min; b.y_max = g.y_max; b.dx_rng = g.dx_rng; b.dy_rng = g.dy_rng;
     b.ksm1 = g.ksm1; b.ks = g.ks;
-    b.h = p.h; b.f = p.f; b.w = p.w; b.r = p.r; b.fmh = p.fmh; b.rr = p.rr; b.inv_r = p.inv_r;
-    b.r_pow2 = p.r_pow2; b.pad = 0;
+    if (t) {
+        b.tb.scale = t->scale; b.tb.tab_lo = (uint32_t)(uintptr_t)t->tab; b.tb.tab_hi = (uint32_t)((uintptr_t)t->tab >> 32); b.tb.lo = t->lo; b.tb.hi = t->hi; b.tb.half = t->half;
+        b.tb.h = t->h; b.tb.w = t->w;
+    } else {
+        b.dp.h = p.h; b.dp.f = p.f; b.dp.w = p.w; b.dp.r = p.r; b.dp.fmh = p.fmh; b.dp.rr = p.rr; b.dp.inv_r = p.inv_r;
+        b.dp.r_pow2 = p.r_pow2;
+    }
     return b;
+}
+
+// ---------------------------------------------------------------------------
+// the sensor's dual-pixel weight table
+// ---------------------------------------------------------------------------
+// (sl, sr) of monte_carlo.py:169-206 (r <= 0.5) are a function of ONE scalar per ray, x_tan, and of the sensor's
+// (h, f, w, r): k_psf_lr's Lean instantiations read their segment-area part (DpTableRef, sdirt_device.hpp) from a
+// table of that function instead of evaluating six segment areas per ray (dp_weights_small: ~140 vector
+// instructions, six square roots).
+//   entries  float64 evaluation of the reference's literal sequence (clamp, acos, u - sin(2u) / 2), rounded to fp32 once
+//   spacing  2^-k in x_tan, the largest k whose table fits kDpTableEntries: 2^-16 for the default sensor (134 439
+//            entries, 1.03 MiB, L2-resident); a power of two makes x_tan * 2^k exact, so the fraction has no rounding
+//   extent   |x_tan| <= X = the point beyond which all six clamped arguments are saturated and the areas are
+//            constant, plus two cells; the kernel clamps the index, the end entries ARE the saturated values
+//   error    linear interpolation of a C1 function that behaves like (1 - z)^(3/2) at each of its twelve saturation
+//            points: a segment area is r^2 S(z) with S -> 1.886 (1 - z)^1.5, and a chord of s^1.5 over a cell d is off
+//            by at most 0.148 d^1.5, so the worst error is 0.148 * 1.886 r^2 (z' 2^-k)^1.5 with z' = d z / d x_tan of the
+//            steepest abscissa (f h / (f - h) / r through the microlens); a sensor so steep that this exceeds
+//            kDpTableErrMax gets no table (2.6e-8 for the default sensor).  Measured against float64 on 2e5 points per
+//            parameter set (tests/test_gpu_dp_weight_table.py), with the closed form's own error beside it: see
+//            docs/KERNEL_NOTES.md
+constexpr double kDpTableErrMax = 1e-7;      // a third of seg_acos's 3.1e-7: entry and interpolation roundings add ~1e-7
+struct DpTablePlan {
+    double h, f, w, r;
+    int half, k;
+};
+static bool plan_dp_table(const sdirt_dp_params* dp, DpTablePlan& pl)
+{
+    pl.h = dp ? dp->h : 0.78; pl.f = dp ? dp->f : 1.44; pl.w = dp ? dp->w : 0.3; pl.r = dp ? dp->r : 0.5;
+    const double fmh = pl.f - pl.h, rc = std::min(pl.r, 0.5);
+    // x_ml: |f h / fmh x| >= r + |w f / fmh| saturates the microlens trio; x_in: |h x| >= |w| + rc the pixel trio
+    const double x_ml = (pl.r + std::fabs(pl.w * pl.f / fmh)) / std::fabs(pl.f * pl.h / fmh);
+    const double x_in = (std::fabs(pl.w) + rc) / std::fabs(pl.h);
+    const double X = std::max(x_ml, x_in);
+    if (!(pl.r > 0.0) || pl.r > 0.5 || !std::isfinite(X) || !(X > 0.0)) return false;
+    int e = 0;
+    (void)std::frexp((kDpTableEntries / 2 - 2) / X, &e);       // (cap - 2) / X in [2^(e-1), 2^e)
+    pl.k = e - 1;
+    if (pl.k < -24 || pl.k > 24) return false;                  // a sensor outside anything the splat can resolve
+    pl.half = (int)std::ceil(std::ldexp(X, pl.k)) + 2;
+    const double steep = std::max(std::fabs(pl.f * pl.h / fmh), std::fabs(pl.h)) / pl.r;
+    if (!(0.148 * 1.886 * pl.r * pl.r * std::pow(std::ldexp(steep, -pl.k), 1.5) <= kDpTableErrMax)) return false;
+    return pl.half >= 2 && pl.half <= kDpTableEntries / 2;
+}
+
+__device__ __forceinline__ double seg64(double x, double r)    // rr-less segment area of a clamped abscissa
+{
+    const double u = acos(x / r);
+    return u - 0.5 * sin(2.0 * u);
+}
+__device__ __forceinline__ double clamp64(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+
+__global__ void __launch_bounds__(kBlock) k_dp_table_build(float2* __restrict__ tab, int half, double cell, double h, double f,
+                                                           double w, double r)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > 2 * half) return;
+    const double x = (double)(i - half) * cell, rr = r * r, fmh = f - h;
+    const double fx = f * x, hx = h * x;
+    double xr = clamp64(w - (fx - w) * h / fmh, -r, r), xm = clamp64((-fx) * h / fmh, -r, r),
+           xl = clamp64((-w) - (fx + w) * h / fmh, -r, r);
+    double sm = seg64(xm, r);
+    const double sr_ml = rr * (sm - seg64(xr, r)), sl_ml = rr * (seg64(xl, r) - sm);
+    xr = clamp64(w - hx, -0.5, 0.5); xm = clamp64(-hx, -0.5, 0.5); xl = clamp64((-w) - hx, -0.5, 0.5);
+    sm = seg64(clamp64(xm, -r, r), r);
+    const double sr_in = rr * (sm - seg64(clamp64(xr, -r, r), r)), sl_in = rr * (seg64(clamp64(xl, -r, r), r) - sm);
+    tab[i] = make_float2((float)(sl_ml - sl_in), (float)(sr_ml - sr_in));     // the strip widths xm - xl, xr - xm: in the kernel
+}
+
+// The table of `dp` on `lens`, ready for a kernel enqueued on `st` behind this call: the handle's entries when they
+// were built from the same bit patterns, else rebuilt on `st` first -- build, then use, in stream order; no host
+// synchronisation.  Other streams are ordered by an event: a stream that has not used this build yet waits for it, a
+// rebuild waits for every stream that used the entries it overwrites.  false: no table for this call (r > 0.5, a
+// degenerate or very steep sensor, a stream that is being captured -- a graph would replay the use without the build) and the
+// kernel evaluates the closed form.
+// What the caller owes, as for every other field of the handle: calls that render through ONE handle with DIFFERENT
+// sensors come from one thread at a time (the lock covers the bookkeeping, not the launch that follows it), and a
+// stream that has rendered through the handle outlives it or the next rebuild (the list keeps its handle).
+static bool dp_table_for(const sdirt_lens* lens, const sdirt_dp_params* dp, hipStream_t st, DpTableRef& ref)
+{
+    DpWeightTable& T = lens->dp_table;
+    DpTablePlan pl;
+    if (!T.dev || !T.ready || !plan_dp_table(dp, pl)) return false;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return false;
+    }
+    uint64_t key[4];
+    const double v[4] = {pl.h, pl.f, pl.w, pl.r};
+    std::memcpy(key, v, sizeof(key));
+    std::lock_guard<std::mutex> guard(T.lock);
+    bool ok = true;
+    if (!T.built || std::memcmp(key, T.key, sizeof(key)) != 0) {
+        for (hipStream_t u : T.synced)
+            if (u != st) ok = ok && hipEventRecord(T.ready, u) == hipSuccess && hipStreamWaitEvent(st, T.ready, 0) == hipSuccess;
+        T.synced.clear();
+        T.built = false;
+        if (ok) {
+            k_dp_table_build<<<(2 * pl.half + kBlock) / kBlock, kBlock, 0, st>>>(T.dev, pl.half, std::ldexp(1.0, -pl.k), pl.h,
+                                                                                 pl.f, pl.w, pl.r);
+            ok = hipGetLastError() == hipSuccess && hipEventRecord(T.ready, st) == hipSuccess;
+        }
+        if (ok) {
+            std::memcpy(T.key, key, sizeof(key));
+            T.half = pl.half; T.log2_scale = pl.k; T.built = true;
+            T.synced.push_back(st);
+        }
+    } else if (std::find(T.synced.begin(), T.synced.end(), st) == T.synced.end()) {
+        // a reader is never forgotten -- a rebuild has to wait for it --: the 65th stream of one build gets no table
+        ok = T.synced.size() < 64 && hipStreamWaitEvent(st, T.ready, 0) == hipSuccess;
+        if (ok) T.synced.push_back(st);
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        return false;
+    }
+    ref.tab = T.dev; ref.scale = (float)std::ldexp(1.0, T.log2_scale);
+    ref.lo = (float)(-T.half); ref.hi = (float)(T.half - 1); ref.half = T.half;
+    ref.h = (float)pl.h; ref.w = (float)pl.w;                   // make_dp's roundings
+    return true;
+}
+
+// SDIRT_DP_WEIGHT_TABLE=0 in the environment: every call evaluates the closed form (a test hook: the A/B of
+// tests/test_gpu_dp_weight_table.py and of the profiles; read per call, so a test can flip it in one process)
+static bool dp_table_enabled()
+{
+    const char* e = std::getenv("SDIRT_DP_WEIGHT_TABLE");
+    return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+// sdirt_dp_weight_table_selftest: both forms of the weights on the same abscissae, as k_psf_lr evaluates them
+__global__ void __launch_bounds__(kBlock) k_dp_weights_both(DpTableRef t, DevDpParams dp, const float* __restrict__ x_tan, int64_t n,
+                                                            float2* __restrict__ lr_table, float2* __restrict__ lr_closed)
+{
+    const auto div_fmh = UDiv<Lean>::make(dp.fmh);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float x = x_tan[i];
+        float frac, sl, sr;
+        const DpTablePair q = dp_table_fetch(t, x, frac);
+        dp_table_weights(t, q, frac, x, sl, sr);
+        lr_table[i] = make_float2(sl, sr);
+        dp_weights_small<Lean>(dp, div_fmh, x, sl, sr);
+        lr_closed[i] = make_float2(sl, sr);
+    }
 }
 
 // forward_integral on a point-major SoA bundle, grids too large for LDS (ks > SDIRT_MAX_KS; the one caller is a
@@ -545,7 +704,9 @@ struct TripSet {
 // plan_psf whenever the double tiles still leave room for four workgroups per CU (L + R: ks <= 49).
 // THREADS = 1024 (SDIRT_PSF_DETERMINISTIC on grids of 50 to 70 pixels): double tiles in workgroups of 16 waves, two per
 // CU -- the same 8 waves per SIMD; a workgroup waits at its barriers for the slowest of 16 waves: +0.5 % (profiles/r05/ab_tiles.txt).
-template <bool HAVE_R, bool BIG, class HotMath, bool CENTER, class ACC, int THREADS = kFused>
+// TAB (Lean, r <= 0.5 only): the dual-pixel weights come from the sensor's table (dp_table_for) -- words 7..14 of
+// the splat block are its DpTableRef -- instead of dp_weights_small.
+template <bool HAVE_R, bool BIG, class HotMath, bool CENTER, class ACC, int THREADS = kFused, bool TAB = false>
 __global__ void __launch_bounds__(THREADS, BIG ? 4 : 8)
 k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet trips_c /* 64 + 64 W */,
          LensSet lens_set, int K, const float* __restrict__ po, const float* __restrict__ x2,
@@ -657,17 +818,32 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet t
         SplatGeom gm;
         gm.lim = F(0); gm.x_min = F(1); gm.y_max = F(2); gm.dx_rng = F(3); gm.dy_rng = F(4);
         gm.ksm1 = F(5); gm.ks = (int)q[6];
-        DevDpParams dp;
-        dp.h = F(7); dp.f = F(8); dp.w = F(9); dp.r = F(10); dp.fmh = F(11); dp.rr = F(12);
-        dp.inv_r = F(13); dp.r_pow2 = (int)q[14]; dp.tr = tr; dp.tl = tl; dp.big = BIG; dp.have_r = HAVE_R;
         SplatTaps tp;
-        if (!splat_taps<HotMath::kFused>(gm, UDiv<HotMath>::make(gm.dy_rng), UDiv<HotMath>::make(gm.dx_rng), sx, sy, cx,
-                                         cy, ra, tp))
-            return;
-        const float x_tan = HotMath::div(-dx, dz);
         float sl, sr;
-        if (BIG) dp_weights_big(dp, x_tan, sl, sr);      // separate instantiation: the rarely
-        else dp_weights_small<HotMath>(dp, UDiv<HotMath>::make(dp.fmh), x_tan, sl, sr);   // used r > 0.5 branch costs registers
+        if constexpr (TAB) {
+            static_assert(!BIG && HotMath::kFused, "the weight table stands in for dp_weights_small<Lean> only");
+            // the two table entries around x_tan: the load is in flight while the taps are computed (every lane loads,
+            // also one whose ray misses the window: the index is clamped into the table whatever x_tan is)
+            DpTableRef t;
+            t.scale = F(7); t.tab = reinterpret_cast<const float2*>((uint64_t)q[8] | ((uint64_t)q[9] << 32));
+            t.lo = F(10); t.hi = F(11); t.half = (int)q[12]; t.h = F(13); t.w = F(14);
+            const float x_tan = HotMath::div(-dx, dz);
+            float frac;
+            const DpTablePair e = dp_table_fetch(t, x_tan, frac);
+            if (!splat_taps<true>(gm, UDiv<HotMath>::make(gm.dy_rng), UDiv<HotMath>::make(gm.dx_rng), sx, sy, cx, cy, ra, tp))
+                return;
+            dp_table_weights(t, e, frac, x_tan, sl, sr);
+        } else {
+            DevDpParams dp;
+            dp.h = F(7); dp.f = F(8); dp.w = F(9); dp.r = F(10); dp.fmh = F(11); dp.rr = F(12);
+            dp.inv_r = F(13); dp.r_pow2 = (int)q[14]; dp.tr = tr; dp.tl = tl; dp.big = BIG; dp.have_r = HAVE_R;
+            if (!splat_taps<HotMath::kFused>(gm, UDiv<HotMath>::make(gm.dy_rng), UDiv<HotMath>::make(gm.dx_rng), sx, sy, cx,
+                                             cy, ra, tp))
+                return;
+            const float x_tan = HotMath::div(-dx, dz);
+            if (BIG) dp_weights_big(dp, x_tan, sl, sr);      // separate instantiation: the rarely
+            else dp_weights_small<HotMath>(dp, UDiv<HotMath>::make(dp.fmh), x_tan, sl, sr);   // used r > 0.5 branch costs registers
+        }
         atomicAdd(&tl_[tp.i_tl], (ACC)(tp.w_tl * sl));
         atomicAdd(&tl_[tp.i_tr], (ACC)(tp.w_tr * sl));
         atomicAdd(&tl_[tp.i_bl], (ACC)(tp.w_bl * sl));
@@ -811,10 +987,12 @@ struct PsfLaunch {
     uint32_t* conv_mask;
     SplitArgs sa;
     hipStream_t st;
+    const sdirt_lens* table_owner;   // the handle whose dual-pixel weight table the call may use: lens[0]
     // the plan
     SplatBlock sblk;
     DevDpParams dpp;
     bool both, interleaved, fused;
+    bool tabbed;                     // the TAB instantiation: sblk carries the table's reference
     int nsplit, chunk, threads;
     Tiles tiles;
     size_t lds_bytes;
@@ -845,6 +1023,7 @@ static int check_psf_args(PsfLaunch& L, bool primary, const sdirt_lens* const* l
     }
     const int K = ref->n_surfaces;
     L = PsfLaunch{};
+    if (primary) L.table_owner = lens[0];
     for (int w = 0; primary && w < W; ++w) {
         L.ls.p[w] = lens[w]->dev;
         if (int rc = make_trips(lens[w], trips ? trips + (size_t)w * K : nullptr, L.tt.t[w])) return rc;
@@ -880,7 +1059,11 @@ static int plan_psf(PsfLaunch& L, double ps, const sdirt_dp_params* dp, uint32_t
     L.nsplit = L.W > 1 ? 1 : spp_split(L.N, L.S, &L.chunk);
     L.fused = L.centered && L.nsplit == 1;
     L.dpp = make_dp(dp);
-    L.sblk = make_splat_block(make_geom(ps, L.ks), L.dpp);
+    // the weights from the sensor's table: the fused Lean small-radius case only (built or rebuilt on this stream, ahead
+    // of the launch, when the handle's entries are another sensor's); else the closed form, as before
+    DpTableRef tref;
+    L.tabbed = !L.dpp.big && !(flags & SDIRT_PSF_STRICT_IEEE) && dp_table_enabled() && dp_table_for(L.table_owner, dp, L.st, tref);
+    L.sblk = make_splat_block(make_geom(ps, L.ks), L.dpp, L.tabbed ? &tref : nullptr);
     L.both = r_psf != nullptr && L.dpp.have_r;
     // double accumulators (ACC of k_psf_lr) whenever they leave room for four workgroups per CU, i.e. for the
     // kernel's 8 waves per SIMD: 4 x (39 KiB + 0.4 KiB of static LDS) <= 160 KiB -- L + R up to ks 49, L alone up to 70
@@ -905,10 +1088,10 @@ static int plan_psf(PsfLaunch& L, double ps, const sdirt_dp_params* dp, uint32_t
     return SDIRT_OK;
 }
 
-template <bool HAVE_R, bool BIG, class M, bool CENTER, class ACC, int THREADS>
+template <bool HAVE_R, bool BIG, class M, bool CENTER, class ACC, int THREADS, bool TAB = false>
 static int launch_psf_lr_as(const PsfLaunch& L)
 {
-    constexpr auto kernel = &k_psf_lr<HAVE_R, BIG, M, CENTER, ACC, THREADS>;
+    constexpr auto kernel = &k_psf_lr<HAVE_R, BIG, M, CENTER, ACC, THREADS, TAB>;
     if (L.lds_bytes > 48 * 1024)        // large tiles: opt in to the full 160 KiB of LDS
         if (int rc = allow_large_lds<kernel>()) return rc;
     const dim3 grid((unsigned)(L.N * L.nsplit), (unsigned)L.W);
@@ -919,12 +1102,21 @@ static int launch_psf_lr_as(const PsfLaunch& L)
     return SDIRT_OK;
 }
 
-// The one of k_psf_lr's 32 instantiations the plan asks for: tile form x HAVE_R x math x CENTER
+// The one of k_psf_lr's 44 instantiations the plan asks for: tile form x HAVE_R x math x CENTER, and the twelve Lean
+// small-radius ones once more with the weights from the table
 static int launch_psf_lr(const PsfLaunch& L)
 {
     return with_bool(L.both, [&](auto hr) { return with_bool(L.fused, [&](auto ct) { return with_math(L.flags, [&](auto m) {
         constexpr bool HR = decltype(hr)::value, CT = decltype(ct)::value;
         using M = decltype(m);
+        if constexpr (M::kFused) {
+            if (L.tabbed) switch (L.tiles) {
+            case Tiles::Float: return launch_psf_lr_as<HR, false, M, CT, float, kFused, true>(L);
+            case Tiles::Double: return launch_psf_lr_as<HR, false, M, CT, double, kFused, true>(L);
+            case Tiles::Double1024: return launch_psf_lr_as<HR, false, M, CT, double, 2 * kFused, true>(L);
+            case Tiles::BigFloat: return fail(SDIRT_ERR_UNSUPPORTED, "no weight table for r > 0.5");
+            }
+        }
         switch (L.tiles) {
         case Tiles::Float: return launch_psf_lr_as<HR, false, M, CT, float, kFused>(L);
         case Tiles::Double: return launch_psf_lr_as<HR, false, M, CT, double, kFused>(L);
@@ -1120,6 +1312,23 @@ int sdirt_forward_integral(sdirt_rays rays, int64_t S, int64_t N, double ps, int
         launch_normalize(l_grid, N, ks * ks, st);
         if (both) launch_normalize(r_grid, N, ks * ks, st);
     }
+    LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+
+int sdirt_dp_weight_table_selftest(const sdirt_lens* lens, const sdirt_dp_params* dp, const float* x_tan, int64_t n,
+                                   float* lr_table, float* lr_closed, int32_t* info, void* stream)
+{
+    if (!lens || !x_tan || !lr_table || !lr_closed || n < 0) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
+    hipStream_t st = as_stream(stream);
+    DpTableRef t;
+    if (!dp_table_for(lens, dp, st, t))
+        return fail(SDIRT_ERR_UNSUPPORTED, "no weight table for these parameters (r > 0.5, a degenerate or very steep sensor, or a capturing stream)");
+    if (info) { info[0] = 2 * t.half + 1; info[1] = lens->dp_table.log2_scale; }
+    if (n == 0) return SDIRT_OK;
+    k_dp_weights_both<<<grid_for(n, kBlock), kBlock, 0, st>>>(t, make_dp(dp), x_tan, n, reinterpret_cast<float2*>(lr_table),
+                                                              reinterpret_cast<float2*>(lr_closed));
     LAUNCH_CHECK();
     return SDIRT_OK;
 }

@@ -354,7 +354,12 @@ int sdirt_lens_create(const sdirt_surface_desc* surfaces, int32_t n_surfaces, sd
     if (e == hipSuccess)
         e = hipMemcpy(L->dev, L->host.data(), sizeof(DevSurface) * n_surfaces,
                       hipMemcpyHostToDevice);
+    // the dual-pixel weight table of the fused PSF kernel: room for it now, its entries on the first call that uses it
+    if (e == hipSuccess) e = hipMalloc(&L->dp_table.dev, sizeof(float2) * (kDpTableEntries + 1));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&L->dp_table.ready, hipEventDisableTiming);
     if (e != hipSuccess) {
+        if (L->dp_table.ready) (void)hipEventDestroy(L->dp_table.ready);
+        if (L->dp_table.dev) (void)hipFree(L->dp_table.dev);
         if (L->dev) (void)hipFree(L->dev);
         delete L;
         return fail(e == hipErrorNoDevice ? SDIRT_ERR_NO_DEVICE : SDIRT_ERR_HIP,
@@ -367,6 +372,8 @@ int sdirt_lens_create(const sdirt_surface_desc* surfaces, int32_t n_surfaces, sd
 void sdirt_lens_destroy(sdirt_lens* lens)
 {
     if (!lens) return;
+    if (lens->dp_table.ready) (void)hipEventDestroy(lens->dp_table.ready);
+    if (lens->dp_table.dev) (void)hipFree(lens->dp_table.dev);
     if (lens->dev) (void)hipFree(lens->dev);
     delete lens;
 }
