@@ -69,10 +69,12 @@ typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 
 // One 64-byte block through the scalar cache into 16 consecutive SGPRs, waited for on the spot.
 // The address is wave-uniform by construction.
+// OFF: a constant byte offset, part of the instruction (no address arithmetic, no second pointer).
+template <int OFF = 0>
 __device__ __forceinline__ u32x16 sload_block(const void* p)
 {
     u32x16 r;
-    asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(p) : "memory");
+    asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(p), "i"(OFF) : "memory");
     return r;
 }
 
@@ -321,6 +323,15 @@ template <> struct UDiv<Lean> {
     __device__ __forceinline__ float operator()(float a) const { return Lean::div_y(a, b, y); }
 };
 
+// UDiv<M>::make(b) with the reciprocal already at hand: y == Lean::recip(b), computed once where b is known
+// (k_psf_lr: once per workgroup instead of once per ray).  Ieee has nothing to hoist and ignores y.
+template <class M>
+__device__ __forceinline__ UDiv<M> udiv_by(float b, float y)
+{
+    if constexpr (M::kFused) return UDiv<M>{b, y};
+    else return UDiv<M>{b};
+}
+
 __device__ __forceinline__ float clampf(float v, float lo, float hi)
 {
     // torch.clamp semantics: NaN propagates
@@ -399,6 +410,12 @@ __device__ __forceinline__ void sag_g_dgd(const C& k, const NoPoly&, int, float 
 template <class M, bool INSIDE, class C, bool UNITK = false, class P = Poly>
 __device__ __forceinline__ void sag_g_dgd(const C& k, const P& pol, int deg, float r2, float& g, float& dgd)
 {
+    // `deg` is compared where it is branched on, once per evaluation: s_cmp + s_cbranch_scc.  Left alone, the compiler
+    // hoists the seven comparisons of the unrolled loop below (and `deg > 3`) out of the Newton loops as seven 64-bit
+    // condition masks -- 14 SGPRs held across every trip of an asphere, at the very place where the kernels that trace
+    // are at their SGPR limit, paid for with values parked in VGPR lanes (v_readlane / v_writelane) all around it;
+    // the branch on a mask is s_andn2 + s_cbranch_vcc, so the scalar unit has the same two instructions either way
+    asm volatile("" : "+s"(deg));
     sag_g_dgd<M, INSIDE, C, UNITK>(k, NoPoly{}, 0, r2, g, dgd);
     dgd = dgd + pol.ai(0);
     g = g + pol.ai(0) * r2;

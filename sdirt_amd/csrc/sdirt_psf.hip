@@ -55,6 +55,53 @@ static SplatBlock make_splat_block(const SplatGeom& g, const DevDpParams& p, con
     return b;
 }
 
+// What k_psf_lr's prologue and epilogue need of the launch -- sample arrays, sizes, planes, strides --, as a SECOND
+// 64-byte block, at offset 64 of the kernel-argument segment: one scalar load where the workgroup starts, one more where
+// it ends, and nothing of it held in an SGPR across the sample loops.  What a ray needs of it at its ends (its sample
+// addresses, the point, the planes, the last sample) is wave-uniform but only ever a VECTOR operand and lives in VGPRs
+// (in_vgpr), of which the Lean kernels have ten to spare.  As plain kernel arguments these were SGPRs that the register
+// allocator, out of its 80 inside the Newton loops, parked in VGPR lanes: some 65 v_readlane / v_writelane per traced
+// ray that compute nothing (docs/KERNEL_NOTES.md, "Lane moves"; `make lanes` counts them).
+struct alignas(64) LoopBlock {
+    const float* x2;
+    const float* y2;
+    const float* po;
+    int32_t S, chunk, nsplit, K;
+    float pz, zs;
+    int32_t ks, pstride, prio_from, pad;
+};
+static_assert(sizeof(LoopBlock) == 64, "layout");
+static_assert(offsetof(LoopBlock, x2) == 0 && offsetof(LoopBlock, y2) == 8 && offsetof(LoopBlock, po) == 16, "layout");
+static_assert(offsetof(LoopBlock, S) == 24 && offsetof(LoopBlock, K) == 36 && offsetof(LoopBlock, pz) == 40, "layout");
+static_assert(offsetof(LoopBlock, ks) == 48 && offsetof(LoopBlock, prio_from) == 56, "layout");
+
+// A wave-uniform value that is only ever a vector operand (an address base, a bound a lane index is compared with, a
+// coordinate) in a VGPR: behind this the compiler treats it as a per-lane value and never asks an SGPR for it.
+template <class T>
+__device__ __forceinline__ T in_vgpr(T v)
+{
+    asm("" : "+v"(v));
+    return v;
+}
+// ... where the kernel has the VGPRs for it (ON): the strict-IEEE and the big-radius instantiations of k_psf_lr are at
+// their VGPR budget and would pay with scratch
+template <bool ON, class T>
+__device__ __forceinline__ T in_vgpr_if(T v)
+{
+    if constexpr (ON) return in_vgpr(v);
+    else return v;
+}
+typedef const __attribute__((address_space(1))) float* GlobalF;    // behind in_vgpr the compiler cannot tell any more
+
+// One word of a block that sload_block fetched, as a value of its own: the register allocator otherwise keeps -- and
+// parks, and brings back -- all sixteen registers of the block for as long as one of them is in use.
+__device__ __forceinline__ uint32_t in_sgpr(uint32_t v)
+{
+    uint32_t o;
+    asm("s_mov_b32 %0, %1" : "=s"(o) : "s"(v));
+    return o;
+}
+
 // ---------------------------------------------------------------------------
 // the sensor's dual-pixel weight table
 // ---------------------------------------------------------------------------
@@ -450,20 +497,27 @@ k_chief_center(TripTable trips /* kernarg offset 0 */, const DevSurface* __restr
     if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
     if (threadIdx.x == 0) red_any = 0;
     __syncthreads();
-    const float px = po[3 * n], py = po[3 * n + 1], pzo = po[3 * n + 2];
+    // what is wave-uniform but only ever a vector operand -- the point, the planes, this lane's sample addresses and
+    // the end of its loop -- in VGPRs, as in k_psf_lr; the launch is kFused wide
+    const float px = in_vgpr(po[3 * n]), py = in_vgpr(po[3 * n + 1]), pzo = in_vgpr(po[3 * n + 2]);
+    const float pzv = in_vgpr(pz), zsv = in_vgpr(zs);
+    GlobalF xcp = in_vgpr((GlobalF)xc + threadIdx.x);
+    GlobalF ycp = in_vgpr((GlobalF)yc + threadIdx.x);
+    const int sc_end = in_vgpr(Sc);
     double sx = 0.0, sy = 0.0, sr = 0.0;
     int any = 0;
-    for (int s = threadIdx.x, pass = 0; s < Sc; s += blockDim.x, ++pass) {
-        if (by_work_left) prio_by_work_left(passes - pass);
-        Ray r = make_ray<HotMath>(px, py, pzo, xc[s], yc[s], pz);
-        trace_ray<true, HotMath>(lens, 0, K, kernarg_at(0), r, conv_mask ? lds_mask : nullptr);
-        propagate_to<HotMath>(r, zs);
+    int left = by_work_left ? passes : INT32_MIN / 2;
+    for (int s = threadIdx.x; s < sc_end; s += kFused, xcp += kFused, ycp += kFused, --left) {
+        if (left > 0) prio_by_work_left(left);
+        Ray r = make_ray<HotMath>(px, py, pzo, *xcp, *ycp, pzv);
+        trace_ray<true, HotMath>(lens, 0, K, kernarg_at(0), r, lds_mask);
+        propagate_to<HotMath>(r, zsv);
         sx += (double)(r.ox * r.ra);
         sy += (double)(r.oy * r.ra);
         sr += (double)r.ra;
         any |= (r.ra == 1.0f);
     }
-    if (by_work_left) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy; red[2][threadIdx.x] = sr;
     if (any) red_any = 1;
     reduce_centroid<kFused>(&red[0][0]);
@@ -522,14 +576,18 @@ k_chief_slices(TripTable trips /* kernarg offset 0 */, SplitArgs sa, const DevSu
     if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
     if (threadIdx.x == 0) red_any = 0;
     __syncthreads();
-    const float px = po[3 * n], py = po[3 * n + 1], pzo = po[3 * n + 2];
+    const float px = in_vgpr(po[3 * n]), py = in_vgpr(po[3 * n + 1]), pzo = in_vgpr(po[3 * n + 2]);
+    const float pzv = in_vgpr(pz), zsv = in_vgpr(zs);
     double sx = 0.0, sy = 0.0, sr = 0.0;
     int any = 0;
-    const int s_end = min(Sc, (j + 1) * chunk);
-    for (int s = j * chunk + threadIdx.x; s < s_end; s += blockDim.x) {
-        Ray r = make_ray<HotMath>(px, py, pzo, xc[s], yc[s], pz);
+    const int s_end = in_vgpr(min(Sc, (j + 1) * chunk));
+    const int s0 = j * chunk + (int)threadIdx.x;
+    GlobalF xcp = in_vgpr((GlobalF)xc + s0);
+    GlobalF ycp = in_vgpr((GlobalF)yc + s0);
+    for (int s = s0; s < s_end; s += kFused, xcp += kFused, ycp += kFused) {
+        Ray r = make_ray<HotMath>(px, py, pzo, *xcp, *ycp, pzv);
         trace_ray<true, HotMath>(lens, 0, K, trip_words, r, lds_mask);
-        propagate_to<HotMath>(r, zs);
+        propagate_to<HotMath>(r, zsv);
         sx += (double)(r.ox * r.ra);
         sy += (double)(r.oy * r.ra);
         sr += (double)r.ra;
@@ -687,8 +745,9 @@ struct CenterArgs {
 // __launch_bounds__(512, 8): four workgroups per CU = 8 waves per SIMD (<= 80 SGPRs, <= 64 VGPRs).
 // The big-radius microlens branch (corner-clipped areas, monte_carlo.py:242-372) needs ~90 VGPRs:
 // capped at 64 it would spill 60 of them to scratch, so it runs at 4 waves per SIMD instead.
-// `sb` MUST stay the first parameter: the kernel reads it as a 64-byte block at offset 0 of its
-// kernel-argument segment (see SplatBlock) and never through the parameter itself.
+// `sb`, `lb`, `prim` and `trips_c` MUST stay the first four parameters: the kernel reads them as 64-byte blocks at fixed
+// offsets of its kernel-argument segment (0, 64, 128, 128 + 128 W: SplatBlock, LoopBlock, PrimarySet, TripSet) and never
+// through the parameters themselves.
 // blockIdx.y = wavelength slot w of a multi-wavelength launch (psf_rgb: gridDim.y = 3, one lens
 // table, pupil sample set, trip table and mask row per slot; a plain call has gridDim.y = 1): the
 // output is [N, gridDim.y, ks, ks], the reference's psf_rgb layout (optics.py:1015).
@@ -698,6 +757,16 @@ struct LensSet {
 struct TripSet {
     TripTable t[SDIRT_MAX_WAVELENGTHS];
 };
+// The primary trip table of each wavelength slot with a copy of the splat block right behind it: the address of its
+// trip table is the one pointer into the argument segment a primary ray holds while it is traced, and the splat's
+// constants are found 64 bytes behind it -- no second pointer to keep (or park) for the end of the ray.
+struct PrimarySet {
+    struct Slot {
+        TripTable t;
+        SplatBlock sb;
+    } s[SDIRT_MAX_WAVELENGTHS];
+};
+static_assert(sizeof(PrimarySet::Slot) == 128 && offsetof(PrimarySet::Slot, sb) == 64, "layout");
 // ACC = the accumulator type of the LDS tiles.  float: ds_add_f32, which gfx950 executes lane by lane (~193 cycles
 // of the CU's LDS per wave instruction whatever the addresses, profiles/r04/lds_atomic_bench.txt); double:
 // ds_add_f64 (17-33 cycles), the sum rounded to fp32 once on the way out like k_forward_integral_tiles -- chosen by
@@ -708,11 +777,9 @@ struct TripSet {
 // the splat block are its DpTableRef -- instead of dp_weights_small.
 template <bool HAVE_R, bool BIG, class HotMath, bool CENTER, class ACC, int THREADS = kFused, bool TAB = false>
 __global__ void __launch_bounds__(THREADS, BIG ? 4 : 8)
-k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet trips_c /* 64 + 64 W */,
-         LensSet lens_set, int K, const float* __restrict__ po, const float* __restrict__ x2,
-         const float* __restrict__ y2, int S, int nsplit, int chunk, float pz, float zs, int ks, int pstride, float tr,
-         float tl, const float* __restrict__ center, uint32_t flags, float* __restrict__ lout,
-         float* __restrict__ rout, uint32_t* __restrict__ conv_mask, CenterArgs ca, SplitArgs sa, int prio_from)
+k_psf_lr(SplatBlock sb /* kernarg offset 0 */, LoopBlock lb /* 64 */, PrimarySet prim /* 128 */, TripSet trips_c /* 128 + 128 W */,
+         LensSet lens_set, float tr, float tl, const float* __restrict__ center, uint32_t flags, float* __restrict__ lout,
+         float* __restrict__ rout, uint32_t* __restrict__ conv_mask, CenterArgs ca, SplitArgs sa)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char tiles_raw[];
     ACC* __restrict__ tiles = reinterpret_cast<ACC*>(tiles_raw);    // [L | R] ks*ks each
@@ -720,9 +787,22 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet t
     __shared__ uint32_t lds_mask[SDIRT_MAX_SURFACES];
     __shared__ float red[THREADS / 64];
     __shared__ float c_sh[2];
+    constexpr bool kPin = HotMath::kFused && !BIG;
+    const auto pin = [](auto v) { return in_vgpr_if<kPin>(v); };
+    constexpr int kLoopAt = 64, kTripsAt = 128, kTripsCAt = 128 + 128 * SDIRT_MAX_WAVELENGTHS;
+    // the loop block (LoopBlock): read once, here; the launch is THREADS wide, so the loops step by the constant
+    const u32x16 lq = sload_block(kernarg_at(kLoopAt));
+    const auto lw = [&](int i) { return in_sgpr(lq[i]); };         // a word of it, on its own: the sixteen are dead behind this
+    const auto lptr = [&](int i) { return reinterpret_cast<GlobalF>((uint64_t)lw(i) | ((uint64_t)lw(i + 1) << 32)); };
+    GlobalF x2 = lptr(0);
+    GlobalF y2 = lptr(2);
+    GlobalF po = lptr(4);
+    const int S = (int)lw(6), chunk = (int)lw(7), nsplit = (int)lw(8), K = (int)lw(9);
+    const float pz = pin(__uint_as_float(lw(10))), zs_s = __uint_as_float(lw(11));
+    const int ks = (int)lw(12), prio_from = (int)lw(14);
+    __builtin_assume(K >= 1);                     // sdirt_lens_create takes no lens without a surface
     const int tile = ks * ks;
     ACC* tl_ = tiles;
-    ACC* trr = tiles + tile;
     const int n = blockIdx.x / nsplit;
     const int j = blockIdx.x - n * nsplit;
     const int w = blockIdx.y;
@@ -732,7 +812,6 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet t
     const int passes_p = (min(S, (j + 1) * chunk) - j * chunk + THREADS - 1) / THREADS;
     const int passes_c = CENTER ? (ca.Sc + THREADS - 1) / THREADS : 0;
     const DevSurface* __restrict__ lens = lens_set.p[w];
-    constexpr int kTripsAt = 64, kTripsCAt = 64 + 64 * SDIRT_MAX_WAVELENGTHS;
     x2 += (int64_t)w * S; y2 += (int64_t)w * S;
     if (conv_mask) conv_mask += w * SDIRT_MAX_SURFACES;
     if (CENTER) {
@@ -743,7 +822,12 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet t
     } else if (center) {
         center += (int64_t)w * N * 2;
     }
-    const float px = po[3 * n], py = po[3 * n + 1], pzo = po[3 * n + 2];
+    // the point, the pupil plane's distance from it and the sensor plane: vector operands of every ray
+    const float px = pin(po[3 * n]), py = pin(po[3 * n + 1]), pzo = pin(po[3 * n + 2]);
+    const float zs = pin(zs_s);
+    // the issue priority of the last generation counts DOWN the passes that are left; every other workgroup starts so
+    // far below zero that it never gets there
+    constexpr int kNoPrio = INT32_MIN / 2;
 
     if (CENTER) {
         // ---- chief-ray centre of this point (same arithmetic and reduction order as
@@ -754,11 +838,17 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet t
         __syncthreads();
         double sx = 0.0, sy = 0.0, sr = 0.0;
         int any = 0;
-        for (int s = threadIdx.x, pass = 0; s < ca.Sc; s += blockDim.x, ++pass) {
-            if (by_work_left) prio_by_work_left(passes_c + passes_p - pass);
-            Ray r = make_ray<HotMath>(px, py, pzo, ca.xc[s], ca.yc[s], pz);
-            trace_ray<true, HotMath>(ca.lens_c, 0, K, kernarg_at(kTripsCAt + 64 * w), r,
-                                     ca.conv_mask_c ? lds_mask : nullptr);
+        // this lane's samples: addresses and the end of the loop per lane, in VGPRs
+        GlobalF xcp = pin((GlobalF)(ca.xc + threadIdx.x));
+        GlobalF ycp = pin((GlobalF)(ca.yc + threadIdx.x));
+        const int sc_end = pin(ca.Sc);
+        int left = by_work_left ? passes_c + passes_p : kNoPrio;
+        for (int s = threadIdx.x; s < sc_end; s += THREADS, --left) {
+            if (left > 0) prio_by_work_left(left);
+            Ray r = make_ray<HotMath>(px, py, pzo, kPin ? *xcp : ca.xc[s], kPin ? *ycp : ca.yc[s], pz);
+            if constexpr (kPin) { xcp += THREADS; ycp += THREADS; }
+            // (the masks of a call that asks for none are gathered all the same and dropped below: one flag less to keep)
+            trace_ray<true, HotMath>(ca.lens_c, 0, K, kernarg_at(kTripsCAt + 64 * w), r, lds_mask);
             propagate_to<HotMath>(r, zs);
             sx += (double)(r.ox * r.ra);
             sy += (double)(r.oy * r.ra);
@@ -807,17 +897,32 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet t
     if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
     __syncthreads();
 
-    const float cx = (CENTER || from_parts) ? c_sh[0] : center[2 * n], cy = (CENTER || from_parts) ? c_sh[1] : center[2 * n + 1];
-    const int s_end = min(S, (j + 1) * chunk);
+    const float cx = pin((CENTER || from_parts) ? c_sh[0] : center[2 * n]);
+    const float cy = pin((CENTER || from_parts) ? c_sh[1] : center[2 * n + 1]);
+    const int s_end = pin(min(S, (j + 1) * chunk));
     const void* kernarg = kernarg_at(0);
-    const void* primary_trips = (!CENTER && sa.trips_dev) ? (const void*)sa.trips_dev : kernarg_at(kTripsAt + 64 * w);
+    // the reciprocals of the window's extent, the same for every ray of the launch: once per workgroup (Lean; the
+    // quotient of a ray stays Lean::div_y with this y -- the same bits; Ieee divides by the extent itself)
+    float rcp_dy = 0.0f, rcp_dx = 0.0f;
+    if constexpr (HotMath::kFused) {
+        const u32x16 q = sload_block(kernarg);
+        rcp_dy = pin(Lean::recip(__uint_as_float(q[4])));
+        rcp_dx = pin(Lean::recip(__uint_as_float(q[3])));
+    }
+    // the primary trip table: in the argument segment, found from the segment's own address like the splat block, or
+    // (round 2 of a verified call) the corrected one in device memory
+    const bool trips_in_mem = !CENTER && sa.trips_dev;
+    const void* primary_trips = trips_in_mem ? (const void*)sa.trips_dev : kernarg_at(kTripsAt + 128 * w);
     auto splat = [&](float sx, float sy, float dx, float dz, float ra) {
         // the splat constants: one 64-byte scalar load per ray, dead again after the splat
-        const u32x16 q = sload_block(kernarg);
+        // (behind the trip table where that is known to stand in the argument segment, else the copy at offset 0)
+        const u32x16 q = CENTER ? sload_block<64>(primary_trips) : sload_block(kernarg);
         const auto F = [&](int i) { return __uint_as_float(q[i]); };
         SplatGeom gm;
         gm.lim = F(0); gm.x_min = F(1); gm.y_max = F(2); gm.dx_rng = F(3); gm.dy_rng = F(4);
         gm.ksm1 = F(5); gm.ks = (int)q[6];
+        const auto div_dy = udiv_by<HotMath>(gm.dy_rng, rcp_dy), div_dx = udiv_by<HotMath>(gm.dx_rng, rcp_dx);
+        ACC* trr = tl_ + gm.ks * gm.ks;          // the R tile, from the block's ks
         SplatTaps tp;
         float sl, sr;
         if constexpr (TAB) {
@@ -830,16 +935,13 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet t
             const float x_tan = HotMath::div(-dx, dz);
             float frac;
             const DpTablePair e = dp_table_fetch(t, x_tan, frac);
-            if (!splat_taps<true>(gm, UDiv<HotMath>::make(gm.dy_rng), UDiv<HotMath>::make(gm.dx_rng), sx, sy, cx, cy, ra, tp))
-                return;
+            if (!splat_taps<true>(gm, div_dy, div_dx, sx, sy, cx, cy, ra, tp)) return;
             dp_table_weights(t, e, frac, x_tan, sl, sr);
         } else {
             DevDpParams dp;
             dp.h = F(7); dp.f = F(8); dp.w = F(9); dp.r = F(10); dp.fmh = F(11); dp.rr = F(12);
             dp.inv_r = F(13); dp.r_pow2 = (int)q[14]; dp.tr = tr; dp.tl = tl; dp.big = BIG; dp.have_r = HAVE_R;
-            if (!splat_taps<HotMath::kFused>(gm, UDiv<HotMath>::make(gm.dy_rng), UDiv<HotMath>::make(gm.dx_rng), sx, sy, cx,
-                                             cy, ra, tp))
-                return;
+            if (!splat_taps<HotMath::kFused>(gm, div_dy, div_dx, sx, sy, cx, cy, ra, tp)) return;
             const float x_tan = HotMath::div(-dx, dz);
             if (BIG) dp_weights_big(dp, x_tan, sl, sr);      // separate instantiation: the rarely
             else dp_weights_small<HotMath>(dp, UDiv<HotMath>::make(dp.fmh), x_tan, sl, sr);   // used r > 0.5 branch costs registers
@@ -855,44 +957,56 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet t
             atomicAdd(&trr[tp.i_br], (ACC)(tp.w_br * sr));
         }
     };
-    for (int s = j * chunk + threadIdx.x, pass = 0; s < s_end; s += blockDim.x, ++pass) {
-        if (by_work_left) prio_by_work_left(passes_p - pass);
-        Ray r = make_ray<HotMath>(px, py, pzo, x2[s], y2[s], pz);
-        trace_ray<true, HotMath>(lens, 0, K, primary_trips, r, conv_mask ? lds_mask : nullptr);
-        propagate_to<HotMath>(r, zs);
-        splat(r.ox, r.oy, r.dx, r.dz, r.ra);
+    {
+        const int s0 = j * chunk + (int)threadIdx.x;
+        GlobalF x2p = pin(x2 + s0);
+        GlobalF y2p = pin(y2 + s0);
+        int left = by_work_left ? passes_p : kNoPrio;
+        for (int s = s0; s < s_end; s += THREADS, --left) {
+            if (left > 0) prio_by_work_left(left);
+            Ray r = make_ray<HotMath>(px, py, pzo, kPin ? *x2p : x2[s], kPin ? *y2p : y2[s], pz);
+            if constexpr (kPin) { x2p += THREADS; y2p += THREADS; }
+            trace_ray<true, HotMath>(lens, 0, K, primary_trips, r, lds_mask);
+            propagate_to<HotMath>(r, zs);
+            splat(r.ox, r.oy, r.dx, r.dz, r.ra);
+        }
     }
-    if (by_work_left) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);               // (it is 0 already in a workgroup that never raised it)
     __syncthreads();
 
     // pstride: floats from one point's grid(s) to the next -- W * tile, or 2 * tile for SDIRT_PSF_INTERLEAVED
-    float* Lg = lout + (int64_t)n * pstride + w * tile;
-    float* Rg = HAVE_R ? rout + (int64_t)n * pstride + w * tile : nullptr;
+    // what the end of the workgroup needs of the loop block, read again: nothing of it was kept across the loops
+    const u32x16 eq = sload_block(kernarg_at(kLoopAt));
+    const int nsplit_e = (int)in_sgpr(eq[8]), K_e = (int)in_sgpr(eq[9]), ks_e = (int)in_sgpr(eq[12]), pstride = (int)in_sgpr(eq[13]);
+    const int tile_e = ks_e * ks_e;
+    ACC* trr = tiles + tile_e;
+    float* Lg = lout + (int64_t)n * pstride + w * tile_e;
+    float* Rg = HAVE_R ? rout + (int64_t)n * pstride + w * tile_e : nullptr;
     // (double tiles: every sum is rounded to fp32 ONCE here; the maximum and the quotients are taken of the rounded
     // values, i.e. of exactly what k_psf_normalize would read back)
-    if (nsplit == 1) {
+    if (nsplit_e == 1) {
         if (flags & SDIRT_PSF_NORMALIZE) {
             float mx = -INFINITY;
-            for (int i = threadIdx.x; i < tile; i += blockDim.x) mx = fmaxf(mx, (float)tl_[i]);
+            for (int i = threadIdx.x; i < tile_e; i += blockDim.x) mx = fmaxf(mx, (float)tl_[i]);
             const auto div_l = UDiv<HotMath>::make(block_max(mx, red) + 1e-6f);
             auto div_r = div_l;
             if (HAVE_R) {
                 mx = -INFINITY;
-                for (int i = threadIdx.x; i < tile; i += blockDim.x) mx = fmaxf(mx, (float)trr[i]);
+                for (int i = threadIdx.x; i < tile_e; i += blockDim.x) mx = fmaxf(mx, (float)trr[i]);
                 div_r = UDiv<HotMath>::make(block_max(mx, red) + 1e-6f);
             }
-            for (int i = threadIdx.x; i < tile; i += blockDim.x) {
+            for (int i = threadIdx.x; i < tile_e; i += blockDim.x) {
                 Lg[i] = div_l((float)tl_[i]);
                 if (HAVE_R) Rg[i] = div_r((float)trr[i]);
             }
         } else {
-            for (int i = threadIdx.x; i < tile; i += blockDim.x) {
+            for (int i = threadIdx.x; i < tile_e; i += blockDim.x) {
                 Lg[i] = (float)tl_[i];
                 if (HAVE_R) Rg[i] = (float)trr[i];
             }
         }
     } else {
-        for (int i = threadIdx.x; i < tile; i += blockDim.x) {
+        for (int i = threadIdx.x; i < tile_e; i += blockDim.x) {
             const float a = (float)tl_[i];
             if (a != 0.0f) atomicAdd(&Lg[i], a);
             if (HAVE_R) {
@@ -901,7 +1015,7 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, TripSet trips /* 64 */, TripSet t
             }
         }
     }
-    if (conv_mask && (int)threadIdx.x < K && lds_mask[threadIdx.x])
+    if (conv_mask && (int)threadIdx.x < K_e && lds_mask[threadIdx.x])
         atomicOr(&conv_mask[threadIdx.x], lds_mask[threadIdx.x]);
 }
 
@@ -1088,6 +1202,28 @@ static int plan_psf(PsfLaunch& L, double ps, const sdirt_dp_params* dp, uint32_t
     return SDIRT_OK;
 }
 
+static LoopBlock make_loop_block(const PsfLaunch& L, int prio_from)
+{
+    LoopBlock b;
+    std::memset(&b, 0, sizeof(b));
+    b.x2 = L.x2; b.y2 = L.y2; b.po = L.po;
+    b.S = (int32_t)L.S; b.chunk = L.chunk; b.nsplit = L.nsplit; b.K = L.K;
+    b.pz = L.pz; b.zs = L.zs;
+    b.ks = L.ks; b.pstride = (int32_t)L.pstride; b.prio_from = prio_from;
+    return b;
+}
+
+static PrimarySet make_primary_set(const PsfLaunch& L)
+{
+    PrimarySet p;
+    std::memset(&p, 0, sizeof(p));
+    for (int w = 0; w < L.W; ++w) {
+        p.s[w].t = L.tt.t[w];
+        p.s[w].sb = L.sblk;
+    }
+    return p;
+}
+
 template <bool HAVE_R, bool BIG, class M, bool CENTER, class ACC, int THREADS, bool TAB = false>
 static int launch_psf_lr_as(const PsfLaunch& L)
 {
@@ -1096,9 +1232,8 @@ static int launch_psf_lr_as(const PsfLaunch& L)
         if (int rc = allow_large_lds<kernel>()) return rc;
     const dim3 grid((unsigned)(L.N * L.nsplit), (unsigned)L.W);
     kernel<<<grid, THREADS, L.lds_bytes, L.st>>>(
-        L.sblk, L.tt, L.ttc, L.ls, L.K, L.po, L.x2, L.y2, (int)L.S, L.nsplit, L.chunk, L.pz,
-        L.zs, L.ks, (int)L.pstride, L.dpp.tr, L.dpp.tl, L.center, L.flags, L.l, L.both ? L.r : nullptr, L.conv_mask,
-        L.ca, L.sa, last_generation_from((int64_t)grid.x * grid.y));
+        L.sblk, make_loop_block(L, last_generation_from((int64_t)grid.x * grid.y)), make_primary_set(L), L.ttc, L.ls, L.dpp.tr, L.dpp.tl,
+        L.center, L.flags, L.l, L.both ? L.r : nullptr, L.conv_mask, L.ca, L.sa);
     return SDIRT_OK;
 }
 
