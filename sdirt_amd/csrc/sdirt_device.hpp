@@ -385,9 +385,11 @@ __device__ __forceinline__ float to_vgpr(float s)
     asm volatile("v_mov_b32 %0, %1" : "=v"(v) : "s"(s));
     return v;
 }
-template <class S>
+// UNITK: 1 + k == 1 and nothing reads onepk (sag_g_dgd leaves the product out): it gets no register and no move
+template <bool UNITK = false, class S>
 __device__ __forceinline__ ConicV conic_v(const S& s)
 {
+    if (UNITK) return ConicV{to_vgpr(s.c()), to_vgpr(s.c2()), 1.0f, to_vgpr(s.d())};
     return ConicV{to_vgpr(s.c()), to_vgpr(s.c2()), to_vgpr(s.onepk()), to_vgpr(s.d())};
 }
 struct ConicS {      // the same constants straight from SGPRs (cold paths)
@@ -407,28 +409,42 @@ __device__ __forceinline__ void sag_g_dgd(const C& k, const NoPoly&, int, float 
     dgd = M::div(M::add_half_quot(onesf, a, sf) * k.c, onesf * onesf);   // (onesf + (a/2)/sf) * c / onesf^2
 }
 
-template <class M, bool INSIDE, class C, bool UNITK = false, class P = Poly>
+// WANT_G = false: only dgd is asked for (the surface normal, refract()): the terms of g are left out and the powers
+// stop at r2 ** (deg - 1), the highest one dgd has.
+template <class M, bool INSIDE, class C, bool UNITK = false, class P = Poly, bool WANT_G = true>
 __device__ __forceinline__ void sag_g_dgd(const C& k, const P& pol, int deg, float r2, float& g, float& dgd)
 {
     // `deg` is compared where it is branched on, once per evaluation: s_cmp + s_cbranch_scc.  Left alone, the compiler
-    // hoists the seven comparisons of the unrolled loop below (and `deg > 3`) out of the Newton loops as seven 64-bit
+    // hoists the seven comparisons of the unrolled loop below out of the Newton loops as seven 64-bit
     // condition masks -- 14 SGPRs held across every trip of an asphere, at the very place where the kernels that trace
     // are at their SGPR limit, paid for with values parked in VGPR lanes (v_readlane / v_writelane) all around it;
     // the branch on a mask is s_andn2 + s_cbranch_vcc, so the scalar unit has the same two instructions either way
     asm volatile("" : "+s"(deg));
     sag_g_dgd<M, INSIDE, C, UNITK>(k, NoPoly{}, 0, r2, g, dgd);
     dgd = dgd + pol.ai(0);
-    g = g + pol.ai(0) * r2;
-    float pw = r2;                        // r2 ** i
+    if (WANT_G) g = g + pol.ai(0) * r2;
+    // The terms are a chain of wave-uniform BRANCHES, one per term, each left at the first term the surface does not
+    // have.  (The empty statement is what keeps them branches: where no loop surrounds the evaluation the compiler
+    // otherwise runs all seven terms, the fp64 products included, and picks the results with v_cndmask on seven
+    // wave-uniform masks.)  The fp64 running product starts at the first power that reads it, r2 ** 4, with the
+    // same three roundings ((x*x)*x)*x it had when it was carried from r2 ** 2 on: no `deg > 3` select on a
+    // 64-bit value, and no fp64 product at all on surfaces of degree <= 3.
     const double xd = (double)r2;
     double accd = xd;                     // r2 ** n in fp64: ((x*x)*x)*...
+    float pw = r2;                        // r2 ** i
 #pragma unroll
     for (int i = 1; i < kMaxAi; ++i) {
-        if (i < deg) {
-            dgd = dgd + pol.kai(i) * pw;
-            const int n = i + 1;
-            if (deg > 3) accd = accd * xd;
+        if (i >= deg) break;
+        asm volatile("");
+        auto raise_to = [&](int n) __attribute__((always_inline)) {     // pw = r2 ** n, n = 2, 3, ... in turn
+            if (n == 4) accd = ((xd * xd) * xd) * xd;
+            if (n > 4) accd = accd * xd;
             pw = n == 2 ? r2 * r2 : n == 3 ? (r2 * r2) * r2 : (float)accd;
+        };
+        if (!WANT_G && i > 1) raise_to(i);      // dgd's term i reads r2 ** i, g's reads r2 ** (i + 1)
+        dgd = dgd + pol.kai(i) * pw;
+        if (WANT_G) {
+            raise_to(i + 1);
             g = g + pol.ai(i) * pw;
         }
     }
@@ -440,19 +456,19 @@ __device__ __forceinline__ void sag_g_dgd(const C& k, const P& pol, int deg, flo
 // the wave had |f(t)| > 50e-6 in trip j -- the per-wave share of the reference's
 // batch-wide `.any()` loop condition (surfaces.py:547).
 template <class M, bool KGT, class P, bool UNITK = false, class S = Surf>
-__device__ __forceinline__ bool newton_k(const S& s, const P& pol, const Ray& r, int trips, float& t_out,
-                                         uint32_t& mask_out)
+__device__ __forceinline__ bool newton_k(const S& s, const P& pol, const Ray& r, const bool alive, int trips,
+                                         float& t_out, uint32_t& mask_out)
 {
     using CV = ConicV;
     const bool adaptive = trips < 0;
     const int cap = adaptive ? -trips : trips;
     const float tol_loose = (float)50e-6, tol_tight = (float)10e-6, eps = (float)1e-9;
-    const ConicV k = conic_v(s);
+    const ConicV k = conic_v<UNITK>(s);
     const int deg = s.ai_degree();
     const float t0 = M::div(k.d - r.oz, r.dz);
     const float dd = r.dx * r.dx + r.dy * r.dy;
     const float dox = r.dx * r.ox + r.dy * r.oy;
-    const bool alive = r.ra > 0.0f;
+    // alive = r.ra > 0, compared once per surface visit by the caller.
     // `valid_loose && ra > 0` as ONE comparison per trip: a dead ray compares against a bound no
     // squared radius can pass (k > -1: rr < lim_loose; k <= -1: rr > 0, surfaces.py:736-743)
     const float bound = KGT ? (alive ? s.lim_loose() : -1.0f) : (alive ? 0.0f : __builtin_inff());
@@ -567,90 +583,105 @@ __device__ __forceinline__ bool newton_k(const S& s, const P& pol, const Ray& r,
 }
 
 // surfaces.py:633-679 with _normal (:589-630).  FWD: rays travel +z (n negated,
-// eta = n1/n2); !FWD: backward tracing.
+// eta = n1/n2); !FWD: backward tracing.  live = r.ra > 0, as the caller's validity test left it.
+//
+// The sign of the normal (Lean policy).  The reference's normal is n = sgn * m, where m is what is normalised below
+// and sgn = +-1 is wave-uniform: -1 when tracing forward (surfaces.py:650), times the sign of c on a sphere, whose
+// m = normalize(o - centre) leaves out the +-2 of :607-615 (exact, and it commutes with every rounding of the
+// normalisation).  Negation commutes with every rounding too, so
+//     cosi = d . n = sgn (d . m),   cosi * n = (d . m) m,   cosi^2 = (d . m)^2,   sr * n = (sgn sr) * m
+// bit for bit: the sign survives in one place only, and is applied there as ONE product of sr with +-1, computed on
+// the scalar unit -- no negation of the normal and no select on the kind.  Signed zeros: every product above has the
+// sign bit the reference's has (the xor of its factors' signs is the same), so a component that is zero -- the on-axis
+// ray, or nx == 0 with dx == 0 -- gets the same zero from the same sum.  The one sum that can differ is cosi itself,
+// +0 here where the reference has -0, when it cancels exactly: such a ray fails cosi^2 > 0.1 and keeps its direction.
 template <bool FWD, class M, class P, class S>
-__device__ __forceinline__ void refract(const S& s, const P& pol, Ray& r)
+__device__ __forceinline__ void refract(const S& s, const P& pol, Ray& r, const bool live)
 {
+    // Snell's law on the normal sgn * normalize(nx, ny, nz), sgn = neg ? -1 : +1 (Lean) or the normal as it stands (Ieee).
+    // A surface normal never vanishes on a ray that sits on the surface; the radicand of `sr` is
+    // >= 2^-24 by the validity test (sqrt_pos; a dead ray's garbage stays confined to the
+    // discarded candidate direction)
+    auto snell = [&](float nx, float ny, float nz, const bool neg) __attribute__((always_inline)) {
+        normalize3<M, true>(nx, ny, nz);
+        if (!M::kFused && FWD) { nx = -nx; ny = -ny; nz = -nz; }
+        const float eta = s.eta(), eta2 = s.eta2();
+        const float cosi = (r.dx * nx + r.dy * ny) + r.dz * nz;     // up to the pending sign
+        const float c2i = cosi * cosi;
+        const float omc = 1.0f - c2i;
+        const bool v = c2i > 0.1f && eta2 * omc < 1.0f && live;
+        const float vf = v ? 1.0f : 0.0f;
+        float sr = M::sqrt_pos(M::one_minus_flagged(eta2 * omc, vf));
+        if (M::kFused) sr = sr * (neg ? -1.0f : 1.0f);
+        float ndx = sr * nx + eta * (r.dx - cosi * nx);
+        float ndy = sr * ny + eta * (r.dy - cosi * ny);
+        float ndz = sr * nz + eta * (r.dz - cosi * nz);
+        ndx = v ? ndx : r.dx; ndy = v ? ndy : r.dy; ndz = v ? ndz : r.dz;
+        r.ob = r.ob * ((ndx * r.dx + ndy * r.dy) + ndz * r.dz);
+        r.dx = ndx; r.dy = ndy; r.dz = ndz;
+        r.ra = r.ra * vf;
+    };
     float nx, ny, nz;
-    float sgn = 1.0f;              // sign of the normal still to be applied (spheres under the Lean policy)
-    bool flip_fwd = FWD;
-    if (!std::is_same<P, NoPoly>::value) {
-        const float vf = r.ra > 0.0f ? 1.0f : 0.0f;
+    if constexpr (!std::is_same<P, NoPoly>::value) {
+        const float vf = live ? 1.0f : 0.0f;
         const float xv = r.ox * vf, yv = r.oy * vf;
         float g, ds;
         // _dsdr2 is evaluated at whatever (x, y) the ray holds (surfaces.py:600): general sqrt
-        sag_g_dgd<M, false>(conic_s(s), pol, s.ai_degree(), xv * xv + yv * yv, g, ds);
+        sag_g_dgd<M, false, ConicS, false, P, false>(conic_s(s), pol, s.ai_degree(), xv * xv + yv * yv, g, ds);
         nx = (ds * 2.0f) * xv; ny = (ds * 2.0f) * yv; nz = -1.0f;
     } else if (s.kind() == 0) {
         nx = 0.0f; ny = 0.0f; nz = -1.0f;
     } else if (s.kind() == 1 && M::kFused) {
-        // sphere: n = normalize(+-2 (o - centre)), negated when tracing forward (surfaces.py:607-615, 650).
-        // Scaling by +-2 is exact and commutes with every rounding of the normalisation, so
-        // n = sgn * m with m = normalize(o - centre) -- and the sign only survives in the sr * n term
-        // below (cosi * n = (sgn cm)(sgn m) = cm m): three multiplications by +-2 and the negation
-        // become one multiplication of sr by +-1.
-        nx = r.ox; ny = r.oy; nz = r.oz - s.d_plus_R();
-        sgn = (s.c_pos() != FWD) ? 1.0f : -1.0f;
-        flip_fwd = false;
+        // the sphere has its own copy of what follows: its normal is read where the position lies (no moves into
+        // registers shared with the other kinds), and its sign is the only one that is not a constant
+        snell(r.ox, r.oy, r.oz - s.d_plus_R(), s.c_pos() == FWD);
+        return;
     } else if (s.kind() == 1) {
         const float sg = s.c_pos() ? 2.0f : -2.0f;       // (+-2) * x is exact either way
         nx = sg * r.ox; ny = sg * r.oy; nz = sg * r.oz - sg * s.d_plus_R();
     } else {                                              // conic without polynomial terms
-        const float vf = r.ra > 0.0f ? 1.0f : 0.0f;
+        const float vf = live ? 1.0f : 0.0f;
         const float xv = r.ox * vf, yv = r.oy * vf;
         float g, ds;
         sag_g_dgd<M, false>(conic_s(s), pol, 0, xv * xv + yv * yv, g, ds);
         nx = (ds * 2.0f) * xv; ny = (ds * 2.0f) * yv; nz = -1.0f;
     }
-    // a surface normal never vanishes on a ray that sits on the surface; the radicand of `sr` is
-    // >= 2^-24 by the validity test (sqrt_pos; a dead ray's garbage stays confined to the
-    // discarded candidate direction)
-    normalize3<M, true>(nx, ny, nz);
-    if (flip_fwd) { nx = -nx; ny = -ny; nz = -nz; }
-    const float eta = s.eta(), eta2 = s.eta2();
-    const float cosi = (r.dx * nx + r.dy * ny) + r.dz * nz;     // up to the pending sign
-    const float c2i = cosi * cosi;
-    const float omc = 1.0f - c2i;
-    const bool v = c2i > 0.1f && eta2 * omc < 1.0f && r.ra > 0.0f;
-    const float vf = v ? 1.0f : 0.0f;
-    float sr = M::sqrt_pos(M::one_minus_flagged(eta2 * omc, vf));
-    if (M::kFused && s.kind() == 1) sr = sr * sgn;
-    float ndx = sr * nx + eta * (r.dx - cosi * nx);
-    float ndy = sr * ny + eta * (r.dy - cosi * ny);
-    float ndz = sr * nz + eta * (r.dz - cosi * nz);
-    ndx = v ? ndx : r.dx; ndy = v ? ndy : r.dy; ndz = v ? ndz : r.dz;
-    r.ob = r.ob * ((ndx * r.dx + ndy * r.dy) + ndz * r.dz);
-    r.dx = ndx; r.dy = ndy; r.dz = ndz;
-    r.ra = r.ra * vf;
+    snell(nx, ny, nz, FWD);
 }
 
 // Curved surface: Newton intersection, validity, refraction (surfaces.py:456-520).  `between` runs
 // after the intersection and before the refraction (the trace loop's prefetch of the next surface).
+// r.ra > 0 is compared ONCE per visit: `alive` serves the Newton solve and the sphere's validity test, and the
+// validity v -- which implies it, and is all that is left of it once ra = keep_if(ra, v) -- serves the refraction.
 template <bool FWD, class M, class P, class F, class S>
 __device__ __forceinline__ uint32_t curved_reaction(const S& s, const P& pol, Ray& r, int trips, F between)
 {
     uint32_t mask = 0;
     float t;
+    const bool alive = r.ra > 0.0f;
     // k > -1 (every sphere, ellipsoid, mild asphere) and k <= -1 differ only in the domain test
     // (surfaces.py:727-743); the branch is wave-uniform and taken once, outside the loop
     // (and, for pure conics, a copy for 1 + k == 1: every sphere)
     bool vn;
     if (std::is_same<P, NoPoly>::value && s.unit_k())
-        vn = newton_k<M, true, P, true>(s, pol, r, trips, t, mask);
+        vn = newton_k<M, true, P, true>(s, pol, r, alive, trips, t, mask);
     else
-        vn = s.k_gt_m1() ? newton_k<M, true>(s, pol, r, trips, t, mask)
-                         : newton_k<M, false>(s, pol, r, trips, t, mask);
+        vn = s.k_gt_m1() ? newton_k<M, true>(s, pol, r, alive, trips, t, mask)
+                         : newton_k<M, false>(s, pol, r, alive, trips, t, mask);
     between();
     const float nx = r.ox + t * r.dx, ny = r.oy + t * r.dy, nz = r.oz + t * r.dz;
     bool v;
     if (s.kind() == 1) {                                                                  // :464
-        v = nx * nx + ny * ny <= s.r2_lim() && t >= 0.0f && r.ra > 0.0f;
+        // (the empty statement keeps the two kinds' lane masks a branch merged on the scalar unit: with no compare
+        // of ra left in here the compiler otherwise picks between them per lane, five vector instructions)
+        asm volatile("");
+        v = nx * nx + ny * ny <= s.r2_lim() && t >= 0.0f && alive;
     } else {
-        v = vn;                                                                           // :495
+        v = vn;                                                                           // :495 (false on a dead ray)
     }
     r.ox = v ? nx : r.ox; r.oy = v ? ny : r.oy; r.oz = v ? nz : r.oz;
     r.ra = M::keep_if(r.ra, v);
-    refract<FWD, M>(s, pol, r);
+    refract<FWD, M>(s, pol, r, v);
     return mask;
 }
 
@@ -667,7 +698,7 @@ __device__ __forceinline__ uint32_t surface_reaction(const S& s, const DevSurfac
         r.ox = v ? nx : r.ox; r.oy = v ? ny : r.oy; r.oz = v ? nz : r.oz;
         r.ra = M::keep_if(r.ra, v);
         between();
-        if (s.do_refract()) refract<FWD, M>(s, NoPoly{}, r);
+        if (s.do_refract()) refract<FWD, M>(s, NoPoly{}, r, v);
         return 0;
     }
     if (s.ai_degree() > 0)                        // wave-uniform: the polynomial block is fetched

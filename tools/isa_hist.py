@@ -116,7 +116,8 @@ def histogram(body):
             d = re.search(r"Loop Header: Depth=(\d+)", l)          # the label line names the parents
             cur = (last_label, int(d.group(1)))
             continue
-        if l.startswith(";") and "in Loop: Header=" in l:          # "; %bb.N:  ; in Loop: Header=..."
+        if t.startswith(";") and "in Loop: Header=" in l:          # "; %bb.N:  ; in Loop: Header=...", or the line
+                                                                   # under a label that carries the block's IR name
             i = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", l)
             cur = (i.group(1), int(i.group(2)))
             continue
