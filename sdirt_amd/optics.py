@@ -1664,13 +1664,22 @@ for _name in ("sample_parallel_2D", "sample_point_source_2D", "sample_pupil", "s
 def intersect_lines_2d_lstsq_fp32(origins, directions):
     """optics.py:1470-1515 as the reference evaluates it: all pairs, the 2x2 systems
     [Di, -Dj] x = Oj - Oi solved in fp32 by torch.linalg.lstsq (CPU: LAPACK gelsy),
-    both evaluations of the intersection averaged.  Host-side, 120 tiny systems."""
+    both evaluations of the intersection averaged.  Host-side, 120 tiny systems.
+
+    The batched gelsy call does not return the same bits for the FIRST system of a batch from one call to the next, on
+    identical operands in one process, also alone and on one thread (observed with torch 2.10 on MKL: two or three
+    outcomes for it, every later system reproducible).  The first pair's lines are adjacent and nearly parallel, so
+    the outcomes differ in the fourth digit and move the pupil radius by 1.4e-4 relative.  A well-conditioned dummy
+    system therefore takes the first place and is dropped: every real system is solved as the later ones always are,
+    which is also what the first one gets in most plain calls."""
     n = origins.shape[0]
     idx_i, idx_j = torch.combinations(torch.arange(n), r=2).unbind(1)
     Oi, Oj, Di, Dj = origins[idx_i], origins[idx_j], directions[idx_i], directions[idx_j]
     b = Oj - Oi
     A = torch.stack([Di, -Dj], dim=-1)
-    x = torch.linalg.lstsq(A, b.unsqueeze(-1))[0].squeeze(-1)
+    A = torch.cat((torch.eye(2, dtype=A.dtype).unsqueeze(0), A))
+    b = torch.cat((torch.ones((1, 2), dtype=b.dtype), b))
+    x = torch.linalg.lstsq(A, b.unsqueeze(-1))[0].squeeze(-1)[1:]
     P_i = Oi + x[:, 0].unsqueeze(-1) * Di
     P_j = Oj + x[:, 1].unsqueeze(-1) * Dj
     return (P_i + P_j) / 2

@@ -117,10 +117,10 @@ def test_render_production_size_runs_and_conserves_energy():
     assert (rl - 0.5).abs().max() < 2e-3 and (rr - 0.5).abs().max() < 2e-3
 
 
-@pytest.mark.parametrize("ks", [33, 49, 65])
+@pytest.mark.parametrize("ks", [7, 21, 33, 49, 65])
 def test_render_fp16_arithmetic_stays_within_its_roundings_of_fp32(ks):
-    """fp16 arithmetic against fp32 on the tiled (4 and 2 pixels per tile) and direct kernels, 1 / 3 / 4 channels:
-    random kernels that sum to 1, image in [0,1)."""
+    """fp16 arithmetic against fp32 on the tiled (8, 4 and 2 pixels per tile), wave-per-pixel (ks 21 RGB, on a row of
+    70 pixels: two chunks) and direct kernels, 1 / 3 / 4 channels: random kernels that sum to 1, image in [0,1)."""
     from sdirt_amd import local_dp_psf_render, local_psf_render_fast
     g = torch.Generator(device=DEV).manual_seed(ks)
     # Image value, weight, product and result are each rounded to fp16 once (relative 2^-11 each, outputs
@@ -129,9 +129,10 @@ def test_render_fp16_arithmetic_stays_within_its_roundings_of_fp32(ks):
     # (about ks^2/64 + 6 additions per partial sum, 2^-24 relative each: below 1e-5 at ks 65), which the
     # first term's slack over the 5e-4 measured on fixture f7 covers.
     bound = 4 * 2.0 ** -11 + ks * ks * 2.0 ** -25
+    H, W = (5, 70) if ks == 21 else (5, 9)
     for C in (1, 3, 4):
-        img = torch.rand(1, C, 5, 9, device=DEV, generator=g)
-        psf = torch.rand(1, 5, 9, 2, ks, ks, device=DEV, generator=g)
+        img = torch.rand(1, C, H, W, device=DEV, generator=g)
+        psf = torch.rand(1, H, W, 2, ks, ks, device=DEV, generator=g)
         psf = psf / psf.sum((-1, -2), keepdim=True)
         full = local_dp_psf_render(img, psf, kernel_size=ks)
         half = torch.cat(local_psf_render_fast(img, psf, kernel_size=ks), dim=1)
@@ -305,7 +306,8 @@ def test_pipelined_training_loop_equals_the_plain_loop(tmp_path):
 @pytest.mark.parametrize("shape", [(1, 3, 40, 56, 21), (2, 1, 9, 13, 5), (1, 4, 7, 33, 9), (1, 3, 5, 7, 31)])
 def test_psfnet_render_kernel_equals_pred_then_render(shape):
     """sdirt_psfnet_render on random raw outputs == stack / fliplr / normalise in torch (fp16,
-    as PSFNet.pred does on the GPU) followed by the fp16 convolution kernel."""
+    as PSFNet.pred does on the GPU) followed by the fp16 convolution kernel.  At ks 21, C 3 both sides run the same
+    wave-per-pixel body (render_wave): the independent float64 reference is in tests/test_gpu_lattice.py."""
     from sdirt_amd.render_psf import local_psf_render_fast, psfnet_render
     B, C, H, W, ks = shape
     g = torch.Generator(device=DEV).manual_seed(ks)

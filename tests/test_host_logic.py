@@ -90,6 +90,28 @@ def test_intersect_lines_2d():
     assert len(intersect_lines_2d(o[:2], np.array([[1.0, 0.0], [2.0, 0.0]]))) == 0   # parallel
 
 
+def test_fp32_lstsq_pupil_intersections_are_reproducible():
+    """intersect_lines_2d_lstsq_fp32 on a paraxial fan (16 nearly parallel lines through one point, as the pupil
+    estimator traces them): the same bits on every call -- the plain batched gelsy call returns two or three different
+    solutions for the first pair -- and every pair but the first exactly as the plain call solves it."""
+    from sdirt_amd.optics import intersect_lines_2d_lstsq_fp32
+    phi = torch.linspace(-0.1, 0.1, 16) / 180 * torch.pi * 1.7
+    D = torch.stack((torch.sin(phi), -torch.cos(phi)), -1)
+    O = (torch.tensor([0.0016, 22.5]) + D * torch.linspace(20, 21, 16).unsqueeze(-1)).float()
+    D = D.float()
+    first = intersect_lines_2d_lstsq_fp32(O, D)
+    assert first.shape == (120, 2) and first.dtype == torch.float32
+    scratch = []
+    for k in range(40):
+        scratch.append(torch.full((3 + 5 * k,), float(k)))             # vary what the allocator hands out
+        assert torch.equal(intersect_lines_2d_lstsq_fp32(O, D), first), k
+        scratch = scratch[-3:]
+    i, j = torch.combinations(torch.arange(16), r=2).unbind(1)
+    x = torch.linalg.lstsq(torch.stack([D[i], -D[j]], dim=-1), (O[j] - O[i]).unsqueeze(-1))[0].squeeze(-1)
+    plain = ((O[i] + x[:, :1] * D[i]) + (O[j] + x[:, 1:] * D[j])) / 2
+    assert torch.equal(plain[1:], first[1:])
+
+
 # ------------------------------------------------------------------ newton.py
 def masks_for(trips, need):
     """Mask a kernel would report: bit j set while the slowest ray has not converged."""
