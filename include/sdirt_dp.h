@@ -612,6 +612,26 @@ int sdirt_render_psf_volume_grad(const float* img /*dev [B,C,H,W]*/, const float
                                  int32_t height, int32_t width, int32_t ks, int32_t depth_nodes, int32_t y_nodes,
                                  int32_t x_nodes, float* grad_volume /*dev [Dz,Gy,Gx,2,ks,ks]*/, void* stream);
 
+/* Backward pass of sdirt_render_psf_volume with respect to the scene: the image and the depth table value fz (what
+ * autograd gives deeplens/render_psf.py:157-188 applied to the interpolated kernels, in the image and, through the
+ * interpolation weights, in fz):
+ *   grad_img[b,c,v,u] = sum_s sum_{(y,x,i,j): clamp(y+pad-i) = v, clamp(x+pad-j) = u} grad_s[b,c,y,x] * K_s(b,y,x)[i,j]
+ *   grad_fz[b,y,x]    = sum_s sum_c grad_s[b,c,y,x] * sum_{i,j} (dK_s/dfz)[i,j] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)]
+ *   dK_s/dfz          = sum over the 8 corners of +-(wy * wx) * volume[corner]   (+ upper depth plane, - lower)
+ * so a border position of the image collects what the replicate padding read.  grad_fz is the gradient in the TABLE
+ * VALUE fz, not in the depth; where the two depth planes are the same node (an axis of one node) it is exactly 0.
+ * Either output may be NULL and is then not computed; both NULL is SDIRT_ERR_INVALID_ARGUMENT.  Every element of an
+ * output is written once (it need not be initialised); fp32 sums in a fixed order, no atomics: two calls on the same
+ * operands give the same bits.  Same limits as the forward; no workspace.  batch == 0: SDIRT_OK, nothing to write. */
+int sdirt_render_psf_volume_grad_scene(const float* img /*dev [B,C,H,W]*/, const float* volume /*dev*/,
+                                       const float* grad_l /*dev [B,C,H,W]*/, const float* grad_r /*dev [B,C,H,W]*/,
+                                       const int32_t* ix /*dev*/, const float* fx /*dev*/, const int32_t* iy /*dev*/,
+                                       const float* fy /*dev*/, const int32_t* iz /*dev*/, const float* fz /*dev*/,
+                                       int32_t batch, int32_t channels, int32_t height, int32_t width, int32_t ks,
+                                       int32_t depth_nodes, int32_t y_nodes, int32_t x_nodes,
+                                       float* grad_img /*dev [B,C,H,W] or NULL*/, float* grad_fz /*dev [B,H,W] or NULL*/,
+                                       void* stream);
+
 /* ---- the PSF network itself ------------------------------------------------ */
 
 /* The network is described by its layer widths: widths[0..n_layers] = in, hidden..., out.  The

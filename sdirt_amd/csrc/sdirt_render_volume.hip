@@ -1,5 +1,6 @@
 // sdirt_render_volume.hip -- an RGB-D frame rendered into a dual-pixel pair straight from a ray-traced PSF volume
-// (MI355X / gfx950 only), and the gradient of that render with respect to the volume.
+// (MI355X / gfx950 only), and the gradients of that render with respect to the volume, the image and the depth table
+// value fz.
 //
 // V [Dz,Gy,Gx,2,ks,ks] holds one L/R kernel pair per grid node.  The kernel of a pixel is the trilinear interpolation
 // of the eight nodes around it, K = sum_corners w * V[corner], w = (wz * wy) * wx with each factor f or 1 - f of the
@@ -242,6 +243,167 @@ k_render_psf_volume_grad(const float* __restrict__ img, const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------
+// gradients with respect to the scene: the depth table value fz and the image
+// ---------------------------------------------------------------------------
+// dfz[b,y,x] = sum_s sum_c G_s[b,c,y,x] * sum_{i,j} (dK_s/dfz)[i,j] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)], where
+// dK_s/dfz = sum_corners +-(wy * wx) * V[corner]: + for the upper depth plane, - for the lower (K is linear in fz, so
+// fz itself is not an operand).  The forward's geometry: one wave per pixel, the lanes stride over the taps, the
+// corner pointers and weights are wave-uniform.  Per tap the 2C upstream values are folded into
+// D_s = sum_c G_s[c] * img[c, .] first; a butterfly sums the lanes, one store per pixel.  A pixel whose two depth
+// planes are the same node (an axis of one node) gets exactly 0, not the rounded difference of equal sums.
+template <int C>
+__global__ void __launch_bounds__(kBlock)
+k_render_psf_volume_grad_depth(const float* __restrict__ img, const float* __restrict__ vol,
+                               const float* __restrict__ gl, const float* __restrict__ gr,
+                               const int* __restrict__ ix, const float* __restrict__ fx, const int* __restrict__ iy,
+                               const float* __restrict__ fy, const int* __restrict__ iz, int H, int W, int ks, int Dz,
+                               int Gy, int Gx, float* __restrict__ dfz)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int y = blockIdx.y, b = blockIdx.z;
+    const int pad = (ks - 1) / 2, kk = ks * ks;
+    const int64_t HW = (int64_t)H * W;
+    const float* __restrict__ img_b = img + (int64_t)b * C * HW;
+    const int fi0 = lane / ks, fj0 = lane - fi0 * ks, dfi = 64 / ks, dfj = 64 - dfi * ks;
+    const int y0 = lower_node(iy[y], Gy), y1 = min(y0 + 1, Gy - 1);
+    const float wy1 = fy[y], wy0 = 1.0f - wy1;
+    const int x_end = min(W, ((int)blockIdx.x + 1) * kPixChunk);
+    for (int x = blockIdx.x * kPixChunk + wave; x < x_end; x += kBlock / 64) {
+        const int64_t pixel = (int64_t)b * HW + (int64_t)y * W + x;
+        const int z0 = lower_node(iz[pixel], Dz), z1 = min(z0 + 1, Dz - 1);
+        if (z0 == z1) {
+            if (lane == 0) dfz[pixel] = 0.0f;
+            continue;
+        }
+        const int x0 = lower_node(ix[x], Gx), x1 = min(x0 + 1, Gx - 1);
+        const float wx1 = fx[x], wx0 = 1.0f - wx1;
+        // corner k = 4 * (z upper) + 2 * (y upper) + (x upper)
+        float w[8];
+        const float* v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int zz = k & 4 ? z1 : z0, yy = k & 2 ? y1 : y0, xx = k & 1 ? x1 : x0;
+            const float wyx = (k & 2 ? wy1 : wy0) * (k & 1 ? wx1 : wx0);
+            w[k] = k & 4 ? wyx : -wyx;
+            v[k] = vol + (((int64_t)zz * Gy + yy) * Gx + xx) * 2 * kk;
+        }
+        float ul[C], ur[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int64_t o = (int64_t)b * C * HW + c * HW + (int64_t)y * W + x;
+            ul[c] = gl[o];
+            ur[c] = gr[o];
+        }
+        float acc = 0.0f;
+        int fi = fi0, fj = fj0;
+        for (int t = lane; t < kk; t += 64) {
+            float kl = 0.0f, kr = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                kl += w[k] * v[k][t];
+                kr += w[k] * v[k][kk + t];
+            }
+            const int yy = min(max(y + pad - fi, 0), H - 1), xx = min(max(x + pad - fj, 0), W - 1);
+            const float* px = img_b + ((int64_t)yy * W + xx);
+            float dl = 0.0f, dr = 0.0f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float p = px[c * HW];
+                dl += ul[c] * p;
+                dr += ur[c] * p;
+            }
+            acc += kl * dl + kr * dr;
+            fi += dfi;
+            fj += dfj;
+            if (fj >= ks) { fj -= ks; ++fi; }
+        }
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        if (lane == 0) dfz[pixel] = acc;
+    }
+}
+
+// dImg[b,c,v,u] = sum_s sum_{(y,x,i,j): clamp(y+pad-i) = v, clamp(x+pad-j) = u} G_s[b,c,y,x] * K_s(b,y,x)[i,j]: a gather,
+// one wave per image position (v, u), all C channels.  The lanes stride over the ks*ks output pixels
+// (y, x) = (v - pad + yr, u - pad + xr) whose kernels reach the position; those outside the image have no term.  Inside
+// the image pixel (y, x) reaches (v, u) with the one tap (i, j) = (yr, xr) -- consecutive lanes are consecutive pixels
+// and consecutive taps, so with a smooth depth they read consecutive addresses of the same corners.  On a border the
+// position also collects every padded position that clamps onto it (k_render_grad_img_gather, sdirt_render_grad.hip):
+// on the first row the taps i >= yr, on the last the taps i <= yr, on an image of one row all of them; columns
+// likewise.  The upstream values do not depend on the tap, so a lane first sums its pixel's kernel over the tap
+// range, S_s = sum_{i,j} K_s[i,j], then adds G_l[c] * S_l + G_r[c] * S_r.  Unlike the forward, the segment, the eight
+// weights and the corner offsets vary per lane.  Fixed order throughout, a butterfly at the end, one store per channel.
+template <int C>
+__global__ void __launch_bounds__(kBlock)
+k_render_psf_volume_grad_img(const float* __restrict__ vol, const float* __restrict__ gl, const float* __restrict__ gr,
+                             const int* __restrict__ ix, const float* __restrict__ fx, const int* __restrict__ iy,
+                             const float* __restrict__ fy, const int* __restrict__ iz, const float* __restrict__ fz,
+                             int H, int W, int ks, int Dz, int Gy, int Gx, float* __restrict__ dimg)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int v = blockIdx.y, b = blockIdx.z;
+    const int pad = (ks - 1) / 2, kk = ks * ks;
+    const int64_t HW = (int64_t)H * W;
+    const float* __restrict__ gl_b = gl + (int64_t)b * C * HW;
+    const float* __restrict__ gr_b = gr + (int64_t)b * C * HW;
+    const int r0 = lane / ks, c0 = lane - r0 * ks, dr = 64 / ks, dc = 64 - dr * ks;
+    const int u_end = min(W, ((int)blockIdx.x + 1) * kPixChunk);
+    for (int u = blockIdx.x * kPixChunk + wave; u < u_end; u += kBlock / 64) {
+        float acc[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = 0.0f;
+        int yr = r0, xr = c0;
+        for (int p = lane; p < kk; p += 64) {
+            const int y = v - pad + yr, x = u - pad + xr;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                // the taps of pixel (y, x) that read a padded position clamping onto (v, u)
+                const int i_lo = v == H - 1 ? 0 : yr, i_hi = v == 0 ? ks - 1 : yr;
+                const int j_lo = u == W - 1 ? 0 : xr, j_hi = u == 0 ? ks - 1 : xr;
+                const int64_t pixel = (int64_t)y * W + x;
+                const int x0 = lower_node(ix[x], Gx), x1 = min(x0 + 1, Gx - 1);
+                const int y0 = lower_node(iy[y], Gy), y1 = min(y0 + 1, Gy - 1);
+                const int z0 = lower_node(iz[(int64_t)b * HW + pixel], Dz), z1 = min(z0 + 1, Dz - 1);
+                const float wx1 = fx[x], wx0 = 1.0f - wx1, wy1 = fy[y], wy0 = 1.0f - wy1;
+                const float wz1 = fz[(int64_t)b * HW + pixel], wz0 = 1.0f - wz1;
+                float w[8];
+                const float* vk[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int zz = k & 4 ? z1 : z0, yy = k & 2 ? y1 : y0, xx = k & 1 ? x1 : x0;
+                    w[k] = ((k & 4 ? wz1 : wz0) * (k & 2 ? wy1 : wy0)) * (k & 1 ? wx1 : wx0);
+                    vk[k] = vol + (((int64_t)zz * Gy + yy) * Gx + xx) * 2 * kk;
+                }
+                float sl = 0.0f, sr = 0.0f;
+                for (int i = i_lo; i <= i_hi; ++i)
+                    for (int j = j_lo; j <= j_hi; ++j) {
+                        const int t = i * ks + j;
+                        float kl = 0.0f, kr = 0.0f;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) {
+                            kl += w[k] * vk[k][t];
+                            kr += w[k] * vk[k][kk + t];
+                        }
+                        sl += kl;
+                        sr += kr;
+                    }
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[c] += gl_b[c * HW + pixel] * sl + gr_b[c * HW + pixel] * sr;
+            }
+            yr += dr;
+            xr += dc;
+            if (xr >= ks) { xr -= ks; ++yr; }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            float a = acc[c];
+            for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+            if (lane == 0) dimg[((int64_t)(b * C + c) * H + v) * W + u] = a;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
 namespace {
@@ -341,6 +503,56 @@ int sdirt_render_psf_volume_grad(const float* img, const float* grad_l, const fl
     }
     if (rc) return rc;
     LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+
+int sdirt_render_psf_volume_grad_scene(const float* img, const float* volume, const float* grad_l,
+                                       const float* grad_r, const int32_t* ix, const float* fx, const int32_t* iy,
+                                       const float* fy, const int32_t* iz, const float* fz, int32_t B, int32_t C,
+                                       int32_t H, int32_t W, int32_t ks, int32_t Dz, int32_t Gy, int32_t Gx,
+                                       float* grad_img, float* grad_fz, void* stream)
+{
+    if (!volume) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (!grad_img && !grad_fz) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer (neither gradient is asked for)");
+    if (int rc = check_volume_render(img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, C, H, W, ks, Dz, Gy, Gx))
+        return rc;
+    if (B == 0) return SDIRT_OK;
+    const dim3 grid((unsigned)((W + kPixChunk - 1) / kPixChunk), (unsigned)H, (unsigned)B);
+    hipStream_t st = as_stream(stream);
+    if (grad_fz) {
+        switch (C) {
+        case 1:
+            k_render_psf_volume_grad_depth<1><<<grid, kBlock, 0, st>>>(img, volume, grad_l, grad_r, ix, fx, iy, fy, iz,
+                                                                       H, W, ks, Dz, Gy, Gx, grad_fz);
+            break;
+        case 3:
+            k_render_psf_volume_grad_depth<3><<<grid, kBlock, 0, st>>>(img, volume, grad_l, grad_r, ix, fx, iy, fy, iz,
+                                                                       H, W, ks, Dz, Gy, Gx, grad_fz);
+            break;
+        default:
+            k_render_psf_volume_grad_depth<4><<<grid, kBlock, 0, st>>>(img, volume, grad_l, grad_r, ix, fx, iy, fy, iz,
+                                                                       H, W, ks, Dz, Gy, Gx, grad_fz);
+            break;
+        }
+        LAUNCH_CHECK();
+    }
+    if (grad_img) {
+        switch (C) {
+        case 1:
+            k_render_psf_volume_grad_img<1><<<grid, kBlock, 0, st>>>(volume, grad_l, grad_r, ix, fx, iy, fy, iz, fz, H,
+                                                                     W, ks, Dz, Gy, Gx, grad_img);
+            break;
+        case 3:
+            k_render_psf_volume_grad_img<3><<<grid, kBlock, 0, st>>>(volume, grad_l, grad_r, ix, fx, iy, fy, iz, fz, H,
+                                                                     W, ks, Dz, Gy, Gx, grad_img);
+            break;
+        default:
+            k_render_psf_volume_grad_img<4><<<grid, kBlock, 0, st>>>(volume, grad_l, grad_r, ix, fx, iy, fy, iz, fz, H,
+                                                                     W, ks, Dz, Gy, Gx, grad_img);
+            break;
+        }
+        LAUNCH_CHECK();
+    }
     return SDIRT_OK;
 }
 

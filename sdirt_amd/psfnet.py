@@ -434,17 +434,19 @@ class PSFNet(Lensgroup):
             render = self.noise(render, img.shape)
         return torch.clip(render, 0.0, 1.0)
 
-    def render_volume(self, img, depth, volume, train=False):
+    def render_volume(self, img, depth, volume, train=False, scene_grad=False):
         """render()'s batched branch (psfnet.py:676-714) with the per-pixel kernels taken from a ray-traced
         render_psf.PSFVolume (Lensgroup.psf_volume) instead of the network: depth + d_sensor -> depth2z, degamma,
         local_dp_psf_render_volume in fp32, gamma, noise when `train`, clip.  img [N,C,H,W], depth [N,1,H,W] (mm,
         negative) -> [N,2C,H,W].  Not under no_grad: a volume that requires a gradient gets one (torch ops for the
-        tone curve); the same call without gradients is the ground truth a fitted network is judged against."""
+        tone curve); the same call without gradients is the ground truth a fitted network is judged against.
+        scene_grad=True: an `img` or a `depth` that requires a gradient gets one as well (depth2z and degamma are torch
+        ops; local_dp_psf_render_volume's scene_grad)."""
         if img.dim() != 4:
             raise ValueError("render_volume expects img [N,C,H,W] and depth [N,1,H,W]")
         z = self.depth2z(depth + self.d_sensor).squeeze(1)
         render = local_dp_psf_render_volume(self.degamma(img), volume.psf, volume.x_nodes, volume.y_nodes,
-                                            volume.z_nodes, z, volume.psf.shape[-1])
+                                            volume.z_nodes, z, volume.psf.shape[-1], scene_grad=scene_grad)
         render = self.gamma(render)
         if train:
             render = self.noise(render, img.shape)

@@ -177,7 +177,50 @@ class _RenderPsfVolume(torch.autograd.Function):
         return (dvol.to(ctx.volume_dtype), None, None) + (None,) * len(tables)
 
 
-def local_dp_psf_render_volume(input, volume, x_nodes, y_nodes, z_nodes, z, kernel_size=21):
+class _RenderPsfVolumeScene(torch.autograd.Function):
+    """local_dp_psf_render_volume(..., scene_grad=True) under autograd: the forward is _render_volume's kernel call on
+    the same operands (bit-equal to the plain call); the backward calls only what ctx.needs_input_grad asks for --
+    sdirt_render_psf_volume_grad for the volume, sdirt_render_psf_volume_grad_scene for the image, the depth table
+    value fz or both, with NULL for the one that is not wanted.  The step from fz to z is
+    axis_segments' torch ops, outside this Function."""
+
+    @staticmethod
+    def forward(ctx, volume, img, fz, ks, ix, fx, iy, fy, iz):
+        vol = volume.to(torch.float32).contiguous()
+        rl, rr = _render_volume(img, vol, (ix, fx, iy, fy, iz, fz), ks)
+        ctx.save_for_backward(vol, img, fz, ix, fx, iy, fy, iz)
+        ctx.kernel_size, ctx.volume_dtype = ks, volume.dtype
+        return torch.cat([rl, rr], dim=1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        vol, img, fz, ix, fx, iy, fy, iz = ctx.saved_tensors
+        tables = (ix, fx, iy, fy, iz, fz)
+        b, c, h, w = img.shape
+        dz, gy, gx = vol.shape[:3]
+        shape = (b, c, h, w, ctx.kernel_size, dz, gy, gx)
+        lib, stream = _lib.lib(), stream_ptr(img.device)
+        gl = grad[:, :c].to(torch.float32).contiguous()
+        gr = grad[:, c:].to(torch.float32).contiguous()
+        dvol = dimg = dfz = None
+        if ctx.needs_input_grad[0]:
+            dvol = torch.empty(vol.shape, dtype=torch.float32, device=img.device)
+            _lib.check(lib.sdirt_render_psf_volume_grad(dptr(img), dptr(gl), dptr(gr), *(dptr(t) for t in tables),
+                                                        *shape, dptr(dvol), stream))
+            dvol = dvol.to(ctx.volume_dtype)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            if ctx.needs_input_grad[1]:
+                dimg = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+            if ctx.needs_input_grad[2]:
+                dfz = torch.empty(fz.shape, dtype=torch.float32, device=img.device)
+            _lib.check(lib.sdirt_render_psf_volume_grad_scene(dptr(img), dptr(vol), dptr(gl), dptr(gr),
+                                                              *(dptr(t) for t in tables), *shape, dptr(dimg),
+                                                              dptr(dfz), stream))
+        return dvol, dimg, dfz, None, None, None, None, None, None
+
+
+def local_dp_psf_render_volume(input, volume, x_nodes, y_nodes, z_nodes, z, kernel_size=21, scene_grad=False):
     """An image and its normalised depth map rendered into a dual-pixel pair straight from a PSF volume:
     local_dp_psf_render (render_psf.py:157-188) with the kernel of every pixel interpolated trilinearly in (x, y, z)
     from the eight grid PSFs around it, inside the HIP kernel -- the [B,H,W,2,ks,ks] tensor never exists.
@@ -189,10 +232,31 @@ def local_dp_psf_render_volume(input, volume, x_nodes, y_nodes, z_nodes, z, kern
     does no normalisation: sum-normalised node PSFs give sum-normalised per-pixel kernels.
 
     Differentiable in `volume` (a call in grad mode on a volume that requires a gradient goes through _RenderPsfVolume:
-    same forward kernel, same values).  Gradients in the image and in the depth are not built: asking for them raises."""
+    same forward kernel, same values).  By default gradients in the image and in the depth are not taken: asking for
+    them raises.
+
+    scene_grad=True opts in to them: a call in grad mode with `input`, `z` or `volume` requiring a gradient goes through
+    _RenderPsfVolumeScene (same forward kernel, same values) and is differentiable in all three.  The kernel gives the
+    gradient in the table value fz; from there to z it is axis_segments' torch ops, so torch's rules hold at the kinks:
+    slope 1 / (nodes[i+1] - nodes[i]) of the segment the table names, also for a z exactly on a node, and exactly 0
+    outside the node range.  `input.grad` comes back in the input's dtype.  Under no_grad, or with nothing requiring a
+    gradient, scene_grad=True is the plain call."""
     if input.dim() < 4:
         input = input.unsqueeze(0)
     grad_mode = torch.is_grad_enabled()
+    if scene_grad and grad_mode and (input.requires_grad or z.requires_grad or volume.requires_grad):
+        b, _, h, w = input.shape
+        img = input.to(torch.float32).contiguous()
+        # volume_segment_tables' ops on a z that is NOT detached: bit-equal table values, fz differentiable in z
+        dev = img.device
+        ix, fx = axis_segments(x_nodes.detach().to(dev), torch.linspace(-1, 1, w, device=dev))
+        iy, fy = axis_segments(y_nodes.detach().to(dev), torch.linspace(1, -1, h, device=dev))
+        zz = z.to(dev).reshape(b, h, w)
+        iz, fz = axis_segments(z_nodes.detach().to(dev), zz)
+        if zz.requires_grad and not fz.requires_grad:
+            fz = fz + 0.0 * zz.to(torch.float32)               # an axis of one node: fz = 0 for every z, z.grad = 0
+        ix, fx, iy, fy, iz, fz = (t.contiguous() for t in (ix, fx, iy, fy, iz, fz))
+        return _RenderPsfVolumeScene.apply(volume.to(dev), img, fz, kernel_size, ix, fx, iy, fy, iz).to(input.dtype)
     if grad_mode and input.requires_grad:
         raise ValueError("local_dp_psf_render_volume: the gradient with respect to the image is not built "
                          "(detach the image; local_dp_psf_render has one)")
@@ -230,10 +294,10 @@ class PSFVolume:
         y = self.y_nodes.to(torch.float32).reshape(1, gy, 1).expand(dz, gy, gx)
         return torch.stack((x, y, depth.reshape(dz, 1, 1).expand(dz, gy, gx)), -1).reshape(-1, 3).contiguous()
 
-    def render(self, input, z):
-        """local_dp_psf_render_volume of this volume."""
+    def render(self, input, z, scene_grad=False):
+        """local_dp_psf_render_volume of this volume (scene_grad=True: differentiable in `input` and `z` as well)."""
         return local_dp_psf_render_volume(input, self.psf, self.x_nodes, self.y_nodes, self.z_nodes, z,
-                                          self.psf.shape[-1])
+                                          self.psf.shape[-1], scene_grad=scene_grad)
 
 
 def psfnet_render(input, raw_l, raw_r, kernel_size):

@@ -11,6 +11,10 @@ operands for both paths:
     fused      local_dp_psf_render_volume (sdirt_render_psf_volume) and its backward (sdirt_render_psf_volume_grad)
     composed   the per-pixel kernels [B,H,W,2,ks,ks] (1.39 GB) interpolated with torch ops from the same segment tables,
                then local_dp_psf_render, and torch autograd through both for the backward
+    scene      scene_grad=True: the backward in the image alone and in the depth alone
+               (sdirt_render_psf_volume_grad_scene with the other output NULL), against the composed path's -- the
+               image through local_dp_psf_render's backward on the materialised kernels, the depth back through the
+               materialisation (torch autograd through the interpolation weights and axis_segments)
 
 Device-event times around `steps` calls after `warmup` calls, the two paths alternating round by round (--rounds), the
 median round reported; the backward times are those of backward() alone (the forward that builds the graph is outside
@@ -24,7 +28,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from sdirt_amd.render_psf import (local_dp_psf_render, local_dp_psf_render_volume,      # noqa: E402
+from sdirt_amd.render_psf import (axis_segments, local_dp_psf_render, local_dp_psf_render_volume,      # noqa: E402
                                   volume_segment_tables)
 
 
@@ -67,7 +71,7 @@ def main():
     ap.add_argument("--width", type=int, default=768)
     ap.add_argument("--ks", type=int, default=21)
     ap.add_argument("--grid", type=int, nargs=3, default=[16, 32, 32], metavar=("DZ", "GY", "GX"))
-    ap.add_argument("--fused-only", action="store_true", help="for a profiler run: the two HIP kernels alone")
+    ap.add_argument("--fused-only", action="store_true", help="for a profiler run: the HIP kernels alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("render_volume_bench needs a GPU: nothing is timed without one")
@@ -91,15 +95,27 @@ def main():
         with torch.no_grad():
             return local_dp_psf_render(img, interpolate_kernels(vol, tables), ks)
 
+    img_leaf, z_leaf = img.clone().requires_grad_(True), z.clone().requires_grad_(True)
+
     def backward(out):
-        leaf.grad = None
+        leaf.grad = img_leaf.grad = z_leaf.grad = None
         out.backward(G)
+
+    def composed_in_depth():
+        iz, fz = axis_segments(zn, z_leaf)
+        return local_dp_psf_render(img, interpolate_kernels(vol, (*tables[:4], iz, fz)), ks)
 
     paths = {
         "fused_forward": (fused_forward, None),
         "fused_backward": (backward, lambda: local_dp_psf_render_volume(img, leaf, xn, yn, zn, z, ks)),
         "composed_forward": (composed_forward, None),
         "composed_backward": (backward, lambda: local_dp_psf_render(img, interpolate_kernels(leaf, tables), ks)),
+        "fused_backward_image": (backward, lambda: local_dp_psf_render_volume(img_leaf, vol, xn, yn, zn, z, ks,
+                                                                              scene_grad=True)),
+        "composed_backward_image": (backward, lambda: local_dp_psf_render(img_leaf, interpolate_kernels(vol, tables), ks)),
+        "fused_backward_depth": (backward, lambda: local_dp_psf_render_volume(img, vol, xn, yn, zn, z_leaf, ks,
+                                                                              scene_grad=True)),
+        "composed_backward_depth": (backward, composed_in_depth),
     }
     if a.fused_only:
         paths = {k: v for k, v in paths.items() if k.startswith("fused")}
@@ -112,7 +128,7 @@ def main():
     for name, us in rounds.items():
         res[name] = {"event_us_median": round(statistics.median(us), 1), "event_us_rounds": [round(u, 1) for u in us]}
     if not a.fused_only:
-        for stage in ("forward", "backward"):
+        for stage in ("forward", "backward", "backward_image", "backward_depth"):
             res[f"composed_over_fused_{stage}"] = round(res[f"composed_{stage}"]["event_us_median"]
                                                         / res[f"fused_{stage}"]["event_us_median"], 2)
         same = torch.allclose(fused_forward(None), composed_forward(None), rtol=0, atol=1e-3)
