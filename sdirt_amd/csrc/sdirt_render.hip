@@ -14,6 +14,7 @@
 #include "../../include/sdirt_dp.h"
 #include "sdirt_device.hpp"
 #include "sdirt_host.hpp"
+#include "sdirt_render.hpp"
 
 using namespace sdirt;
 
@@ -682,8 +683,8 @@ int sdirt_local_psf_render(const float* img, const float* psf, int32_t B, int32_
                            int32_t W, int32_t ks, int32_t half_precision, float* out_l, float* out_r,
                            void* stream)
 {
-    if (!img || !psf || !out_l || !out_r || B < 0 || H < 1 || W < 1 || ks < 1 || (ks & 1) == 0)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument (ks must be odd)");
+    // no limit on ks, B or H here (the direct kernel takes any), C is refused at the dispatch
+    if (int rc = check_image_call({img, psf, out_l, out_r}, B, C, H, W, ks, 0, false)) return rc;
     if (B == 0) return SDIRT_OK;
     const RenderCall r{img, B, H, W, ks, out_l, out_r, as_stream(stream)};
     // row-mapped LDS-tiled kernel whenever 8 (or 4, or 2) pixels' kernels fit in 64 KB of LDS and the
@@ -692,13 +693,11 @@ int sdirt_local_psf_render(const float* img, const float* psf, int32_t B, int32_
     const bool small = ks <= 64 && (int64_t)C * H * W < (1ll << 30) && (int64_t)B * H < 65536;
     const int pix = !small ? 0 : per_pixel * 8 + 16 <= 64 * 1024 ? 8 : per_pixel * 4 + 16 <= 64 * 1024 ? 4
                     : per_pixel * 2 + 16 <= 64 * 1024 ? 2 : 0;
-    int rc;
-    switch (C) {
-    case 1: rc = half_precision ? launch_render<1, true>(r, psf, per_pixel, pix) : launch_render<1, false>(r, psf, per_pixel, pix); break;
-    case 3: rc = half_precision ? launch_render<3, true>(r, psf, per_pixel, pix) : launch_render<3, false>(r, psf, per_pixel, pix); break;
-    case 4: rc = half_precision ? launch_render<4, true>(r, psf, per_pixel, pix) : launch_render<4, false>(r, psf, per_pixel, pix); break;
-    default: return fail(SDIRT_ERR_UNSUPPORTED, "channels=%d (supported: 1, 3, 4)", C);
-    }
+    const int rc = with_channels(C, [&](auto c) {
+        return with_bool(half_precision != 0, [&](auto half) {
+            return launch_render<decltype(c)::value, decltype(half)::value>(r, psf, per_pixel, pix);
+        });
+    });
     if (rc) return rc;
     LAUNCH_CHECK();
     return SDIRT_OK;
@@ -707,9 +706,7 @@ int sdirt_local_psf_render(const float* img, const float* psf, int32_t B, int32_
 int sdirt_psfnet_render(const float* img, const void* raw_l, const void* raw_r, int32_t B, int32_t C,
                         int32_t H, int32_t W, int32_t ks, float* out_l, float* out_r, void* stream)
 {
-    if (!img || !raw_l || !raw_r || !out_l || !out_r || B < 0 || H < 1 || W < 1 || ks < 1 ||
-        (ks & 1) == 0)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument (ks must be odd)");
+    if (int rc = check_image_call({img, raw_l, raw_r, out_l, out_r}, B, C, H, W, ks, 0, false)) return rc;
     if (((uintptr_t)raw_l | (uintptr_t)raw_r) & 15)
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "raw_l / raw_r must be 16-byte aligned");
     if (B == 0) return SDIRT_OK;
@@ -719,13 +716,7 @@ int sdirt_psfnet_render(const float* img, const void* raw_l, const void* raw_r, 
         return fail(SDIRT_ERR_UNSUPPORTED, "ks=%d: eight pixels' kernels exceed 64 KB of LDS", ks);
     const _Float16* rl = static_cast<const _Float16*>(raw_l);
     const _Float16* rr = static_cast<const _Float16*>(raw_r);
-    int rc;
-    switch (C) {
-    case 1: rc = launch_psfnet<1>(r, rl, rr, per_pixel); break;
-    case 3: rc = launch_psfnet<3>(r, rl, rr, per_pixel); break;
-    case 4: rc = launch_psfnet<4>(r, rl, rr, per_pixel); break;
-    default: return fail(SDIRT_ERR_UNSUPPORTED, "channels=%d (supported: 1, 3, 4)", C);
-    }
+    const int rc = with_channels(C, [&](auto c) { return launch_psfnet<decltype(c)::value>(r, rl, rr, per_pixel); });
     if (rc) return rc;
     LAUNCH_CHECK();
     return SDIRT_OK;

@@ -14,6 +14,7 @@
 #include "../../include/sdirt_dp.h"
 #include "sdirt_device.hpp"
 #include "sdirt_host.hpp"
+#include "sdirt_render.hpp"
 
 using namespace sdirt;
 
@@ -207,16 +208,9 @@ k_render_grad_img_gather(const float* __restrict__ partial, int B, int C, int H,
 // ---------------------------------------------------------------------------
 namespace {
 
-// the argument rules of sdirt_local_psf_render, and the limits of these kernels' launch geometry
-int check_render_grad(const void* a, const void* b, const void* c, const void* d, int B, int C, int H, int W, int ks)
-{
-    if (!a || !b || !c || !d || B < 0 || H < 1 || W < 1 || ks < 1 || (ks & 1) == 0)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument (ks must be odd)");
-    if (C != 1 && C != 3 && C != 4) return fail(SDIRT_ERR_UNSUPPORTED, "channels=%d (supported: 1, 3, 4)", C);
-    if (ks > 64) return fail(SDIRT_ERR_UNSUPPORTED, "ks=%d: the render gradients support ks <= 64", ks);
-    if (B > 65535 || H > 65535) return fail(SDIRT_ERR_UNSUPPORTED, "batch=%d height=%d (supported: <= 65535)", B, H);
-    return SDIRT_OK;
-}
+// the argument rules of sdirt_local_psf_render (check_image_call) with the limits of these kernels' launch geometry:
+// ks <= 64 (a kernel row per 64 lanes, the tile's kernels in 64 KB of LDS), B and H in a grid dimension
+constexpr int kMaxKsGrad = 64;
 
 dim3 tile_grid(int B, int H, int W)
 {
@@ -254,22 +248,21 @@ extern "C" {
 int sdirt_local_psf_render_grad_psf(const float* img, const float* grad_l, const float* grad_r, int32_t B, int32_t C,
                                     int32_t H, int32_t W, int32_t ks, float* grad_psf, void* stream)
 {
-    if (int rc = check_render_grad(img, grad_l, grad_r, grad_psf, B, C, H, W, ks)) return rc;
+    if (int rc = check_image_call({img, grad_l, grad_r, grad_psf}, B, C, H, W, ks, kMaxKsGrad, true)) return rc;
     if (B == 0) return SDIRT_OK;
     const dim3 grid((unsigned)((W + kGradChunk - 1) / kGradChunk), (unsigned)H, (unsigned)B);
     hipStream_t st = as_stream(stream);
-    switch (C) {
-    case 1: k_render_grad_psf<1><<<grid, kBlock, 0, st>>>(img, grad_l, grad_r, H, W, ks, grad_psf); break;
-    case 3: k_render_grad_psf<3><<<grid, kBlock, 0, st>>>(img, grad_l, grad_r, H, W, ks, grad_psf); break;
-    case 4: k_render_grad_psf<4><<<grid, kBlock, 0, st>>>(img, grad_l, grad_r, H, W, ks, grad_psf); break;
-    }
+    with_channels(C, [&](auto c) {                                    // C is one of them: checked above
+        k_render_grad_psf<decltype(c)::value><<<grid, kBlock, 0, st>>>(img, grad_l, grad_r, H, W, ks, grad_psf);
+        return SDIRT_OK;
+    });
     LAUNCH_CHECK();
     return SDIRT_OK;
 }
 
 int64_t sdirt_local_psf_render_grad_img_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t ks)
 {
-    if (B < 0 || C < 1 || H < 1 || W < 1 || ks < 1 || ks > 64 || (ks & 1) == 0) return -1;
+    if (B < 0 || C < 1 || H < 1 || W < 1 || ks < 1 || ks > kMaxKsGrad || (ks & 1) == 0) return -1;
     const dim3 g = tile_grid(B, H, W);
     return (int64_t)sizeof(float) * B * g.y * g.x * C * halo_side(ks) * halo_side(ks);
 }
@@ -278,7 +271,7 @@ int sdirt_local_psf_render_grad_img(const float* psf, const float* grad_l, const
                                     int32_t H, int32_t W, int32_t ks, float* grad_img, void* workspace,
                                     int64_t workspace_bytes, void* stream)
 {
-    if (int rc = check_render_grad(psf, grad_l, grad_r, grad_img, B, C, H, W, ks)) return rc;
+    if (int rc = check_image_call({psf, grad_l, grad_r, grad_img}, B, C, H, W, ks, kMaxKsGrad, true)) return rc;
     if (B == 0) return SDIRT_OK;
     const int64_t need = sdirt_local_psf_render_grad_img_workspace_bytes(B, C, H, W, ks);
     if (!workspace || workspace_bytes < need)
@@ -286,12 +279,9 @@ int sdirt_local_psf_render_grad_img(const float* psf, const float* grad_l, const
                     (long long)need);
     hipStream_t st = as_stream(stream);
     float* partial = static_cast<float*>(workspace);
-    int rc;
-    switch (C) {
-    case 1: rc = launch_img<1>(psf, grad_l, grad_r, B, H, W, ks, partial, st); break;
-    case 3: rc = launch_img<3>(psf, grad_l, grad_r, B, H, W, ks, partial, st); break;
-    default: rc = launch_img<4>(psf, grad_l, grad_r, B, H, W, ks, partial, st); break;
-    }
+    const int rc = with_channels(C, [&](auto c) {
+        return launch_img<decltype(c)::value>(psf, grad_l, grad_r, B, H, W, ks, partial, st);
+    });
     if (rc) return rc;
     LAUNCH_CHECK();
     const int grid = grid_for((int64_t)B * C * H * W, kBlock, 256 * 32);

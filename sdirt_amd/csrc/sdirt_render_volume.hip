@@ -18,6 +18,7 @@
 #include "../../include/sdirt_dp.h"
 #include "sdirt_device.hpp"
 #include "sdirt_host.hpp"
+#include "sdirt_render.hpp"
 
 using namespace sdirt;
 
@@ -26,17 +27,90 @@ namespace {
 constexpr int kMaxKsVolume = 63;
 constexpr int kPixChunk = 16;              // pixels of a row per workgroup of the forward (4 per wave)
 
-// the lower node of a segment of an axis of n nodes, whatever the table holds
-__device__ __forceinline__ int lower_node(int i, int n) { return min(max(i, 0), max(n - 2, 0)); }
+// The six segment tables, which every kernel reads and none writes: one kernel parameter, by value.  (The six
+// extents stay plain int parameters: as members of a by-value struct they change the forward's register allocation
+// -- 35 VGPRs for 66 at C = 3, the sixteen corner loads of a tap no longer in flight together.)
+struct SegmentTables {
+    const int* ix; const float* fx;        // [W]
+    const int* iy; const float* fy;        // [H]
+    const int* iz; const float* fz;        // [B,H,W]
+};
 
-// The weight node g of an axis of n nodes has in the segment (i, f): 1 - f as the lower node, f as the upper; both
-// on an axis of one node, where the upper node is the lower.  `touches`: g is one of the segment's two nodes.
-__device__ __forceinline__ float node_weight(int i, float f, int g, int n, bool& touches)
+// The segment (i, f) of a table on an axis of n nodes: its two nodes, whatever the table holds -- the lower clamped
+// to [0, n - 2], the upper min(lo + 1, n - 1), the lower again on an axis of one node -- and their weights 1 - f, f.
+struct Segment {
+    int lo, hi;
+    float w_lo, w_hi;
+    __device__ __forceinline__ Segment(int i, float f, int n)
+        : lo(min(max(i, 0), max(n - 2, 0))), hi(min(lo + 1, n - 1)), w_lo(1.0f - f), w_hi(f) {}
+    // g is one of the segment's two nodes
+    __device__ __forceinline__ bool touches(int g) const { return lo == g || hi == g; }
+};
+
+// The weight of node g in the segment: 1 - f as the lower node, f as the upper; both on an axis of one node.
+__device__ __forceinline__ float node_weight(const Segment& s, int g)
 {
-    const int lo = lower_node(i, n), hi = min(lo + 1, n - 1);
-    touches = lo == g || hi == g;
-    const float a = lo == g ? 1.0f - f : 0.0f, b = hi == g ? f : 0.0f;
-    return lo == hi ? a + b : (lo == g ? a : b);
+    const float a = s.lo == g ? s.w_lo : 0.0f, b = s.hi == g ? s.w_hi : 0.0f;
+    return s.lo == s.hi ? a + b : (s.lo == g ? a : b);
+}
+
+// The eight nodes around a pixel, corner k = 4 * (z upper) + 2 * (y upper) + (x upper): the L kernel of each (its R
+// kernel follows kk = ks*ks floats on) and its weight (wz * wy) * wx -- or, d_fz, the weight's derivative in fz,
+// +-(wy * wx): + for the upper depth plane, - for the lower, each product formed once and used with both signs.
+struct Corners {
+    float w[8];
+    const float* v[8];
+    __device__ __forceinline__ Corners(const float* vol, int Gy, int Gx, int kk, const Segment& z, const Segment& y,
+                                       const Segment& x, bool d_fz = false)
+    {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int zz = k & 4 ? z.hi : z.lo, yy = k & 2 ? y.hi : y.lo, xx = k & 1 ? x.hi : x.lo;
+            w[k] = ((k & 4 ? z.w_hi : z.w_lo) * (k & 2 ? y.w_hi : y.w_lo)) * (k & 1 ? x.w_hi : x.w_lo);
+            v[k] = vol + (((int64_t)zz * Gy + yy) * Gx + xx) * 2 * kk;
+        }
+        if (d_fz) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float wyx = (k & 2 ? y.w_hi : y.w_lo) * (k & 1 ? x.w_hi : x.w_lo);
+                w[k] = -wyx;
+                w[k + 4] = wyx;
+            }
+        }
+    }
+};
+
+// tap t of the interpolated L and R kernels, the corners added in order
+__device__ __forceinline__ void kernel_tap(const Corners& cn, int t, int kk, float& kl, float& kr)
+{
+    kl = 0.0f;
+    kr = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        kl += cn.w[k] * cn.v[k][t];
+        kr += cn.w[k] * cn.v[k][kk + t];
+    }
+}
+
+// Taps first, first + stride, ... of a ks x ks kernel as (row i, column j), without a division per step.  The two
+// divisions are the constructor's: build the start state once, outside the loops, and copy it.
+struct TapWalker {
+    int i, j, di, dj, ks;
+    __device__ __forceinline__ TapWalker(int first, int stride, int ks_)
+        : i(first / ks_), j(first - i * ks_), di(stride / ks_), dj(stride - di * ks_), ks(ks_) {}
+    __device__ __forceinline__ void next()
+    {
+        i += di;
+        j += dj;
+        if (j >= ks) { j -= ks; ++i; }
+    }
+};
+
+// Channel 0 of the image at (yy, xx), clamped into the image (replicate padding).  Stored tap (i, j) of the kernel of
+// pixel (y, x) multiplies the neighbour at the FLIPPED offset (render_psf.py:175): yy = y + pad - i, xx = x + pad - j.
+__device__ __forceinline__ const float* clamped_pixel(const float* img_b, int yy, int xx, int H, int W)
+{
+    return img_b + ((int64_t)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1));
 }
 
 }  // namespace
@@ -51,67 +125,40 @@ __device__ __forceinline__ float node_weight(int i, float f, int g, int n, bool&
 // indices and weights are wave-uniform; the depth segment is read per pixel, nothing assumes a tile shares it.
 template <int C>
 __global__ void __launch_bounds__(kBlock)
-k_render_psf_volume(const float* __restrict__ img, const float* __restrict__ vol, const int* __restrict__ ix,
-                    const float* __restrict__ fx, const int* __restrict__ iy, const float* __restrict__ fy,
-                    const int* __restrict__ iz, const float* __restrict__ fz, int H, int W, int ks, int Dz, int Gy,
-                    int Gx, float* __restrict__ outl, float* __restrict__ outr)
+k_render_psf_volume(const float* __restrict__ img, const float* __restrict__ vol, const SegmentTables tb, int H, int W,
+                    int ks, int Dz, int Gy, int Gx, float* __restrict__ outl, float* __restrict__ outr)
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int y = blockIdx.y, b = blockIdx.z;
-    const int pad = (ks - 1) / 2, kk = ks * ks;
+    const int y = blockIdx.y, b = blockIdx.z, pad = (ks - 1) / 2, kk = ks * ks;
     const int64_t HW = (int64_t)H * W;
     const float* __restrict__ img_b = img + (int64_t)b * C * HW;
-    // the lane's first tap and the step of 64 taps, as (row, column) of the kernel
-    const int fi0 = lane / ks, fj0 = lane - fi0 * ks, dfi = 64 / ks, dfj = 64 - dfi * ks;
-    const int y0 = lower_node(iy[y], Gy), y1 = min(y0 + 1, Gy - 1);
-    const float wy1 = fy[y], wy0 = 1.0f - wy1;
+    const TapWalker tap0(lane, 64, ks);
+    const Segment sy(tb.iy[y], tb.fy[y], Gy);
     const int x_end = min(W, ((int)blockIdx.x + 1) * kPixChunk);
     for (int x = blockIdx.x * kPixChunk + wave; x < x_end; x += kBlock / 64) {
         const int64_t pixel = (int64_t)b * HW + (int64_t)y * W + x;
-        const int x0 = lower_node(ix[x], Gx), x1 = min(x0 + 1, Gx - 1);
-        const int z0 = lower_node(iz[pixel], Dz), z1 = min(z0 + 1, Dz - 1);
-        const float wx1 = fx[x], wx0 = 1.0f - wx1, wz1 = fz[pixel], wz0 = 1.0f - wz1;
-        // corner k = 4 * (z upper) + 2 * (y upper) + (x upper)
-        float w[8];
-        const float* v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int zz = k & 4 ? z1 : z0, yy = k & 2 ? y1 : y0, xx = k & 1 ? x1 : x0;
-            w[k] = ((k & 4 ? wz1 : wz0) * (k & 2 ? wy1 : wy0)) * (k & 1 ? wx1 : wx0);
-            v[k] = vol + (((int64_t)zz * Gy + yy) * Gx + xx) * 2 * kk;
-        }
+        const Corners cn(vol, Gy, Gx, kk, Segment(tb.iz[pixel], tb.fz[pixel], Dz), sy, Segment(tb.ix[x], tb.fx[x], Gx));
         float accl[C], accr[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) { accl[c] = 0.0f; accr[c] = 0.0f; }
-        int fi = fi0, fj = fj0;
+        TapWalker tap = tap0;
         for (int t = lane; t < kk; t += 64) {
-            float kl = 0.0f, kr = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                kl += w[k] * v[k][t];
-                kr += w[k] * v[k][kk + t];
-            }
-            // stored tap (fi, fj) multiplies the neighbour at the FLIPPED offset (render_psf.py:175)
-            const int yy = min(max(y + pad - fi, 0), H - 1), xx = min(max(x + pad - fj, 0), W - 1);
-            const float* px = img_b + ((int64_t)yy * W + xx);
+            float kl, kr;
+            kernel_tap(cn, t, kk, kl, kr);
+            const float* px = clamped_pixel(img_b, y + pad - tap.i, x + pad - tap.j, H, W);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 const float p = px[c * HW];
                 accl[c] += kl * p;
                 accr[c] += kr * p;
             }
-            fi += dfi;
-            fj += dfj;
-            if (fj >= ks) { fj -= ks; ++fi; }
+            tap.next();
         }
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             float a = accl[c], r = accr[c];
-            for (int off = 32; off > 0; off >>= 1) {
-                a += __shfl_xor(a, off);
-                r += __shfl_xor(r, off);
-            }
+            shuffle_sum(a, r);
             if (lane == 0) {
                 const int64_t o = ((int64_t)(b * C + c) * H + y) * W + x;
                 outl[o] = a;
@@ -137,9 +184,8 @@ k_render_psf_volume(const float* __restrict__ img, const float* __restrict__ vol
 template <int C>
 __global__ void __launch_bounds__(kBlock)
 k_render_psf_volume_grad(const float* __restrict__ img, const float* __restrict__ gl, const float* __restrict__ gr,
-                         const int* __restrict__ ix, const float* __restrict__ fx, const int* __restrict__ iy,
-                         const float* __restrict__ fy, const int* __restrict__ iz, const float* __restrict__ fz, int B,
-                         int H, int W, int ks, int Dz, int Gy, int Gx, int planes, float* __restrict__ dvol)
+                         const SegmentTables tb, int B, int H, int W, int ks, int Dz, int Gy, int Gx, int planes,
+                         float* __restrict__ dvol)
 {
     extern __shared__ __attribute__((aligned(16))) float acc[];          // [planes][ks*ks]
     __shared__ float s_w0[kBlock], s_w1[kBlock], s_g[C][kBlock];
@@ -150,24 +196,18 @@ k_render_psf_volume_grad(const float* __restrict__ img, const float* __restrict_
     const int z_first = blockIdx.z * planes, nz = min(planes, Dz - z_first);
     const int pad = (ks - 1) / 2, kk = ks * ks;
     const int64_t HW = (int64_t)H * W;
-    const float* __restrict__ g = side ? gr : gl;
-    const int fi0 = tid / ks, fj0 = tid - fi0 * ks, dfi = kBlock / ks, dfj = kBlock - dfi * ks;
+    const float* __restrict__ gs = side ? gr : gl;
+    const TapWalker tap0(tid, kBlock, ks);
 
     for (int l = 0; l < nz; ++l)
         for (int t = tid; t < kk; t += kBlock) acc[l * kk + t] = 0.0f;
 
     // the columns [x_lo, x_hi) and rows [y_lo, y_hi) that hold every pixel touching this node
     int x_lo = W, x_hi = 0, y_lo = H, y_hi = 0;
-    for (int x = tid; x < W; x += kBlock) {
-        bool touches;
-        node_weight(ix[x], 0.0f, gx, Gx, touches);
-        if (touches) { x_lo = min(x_lo, x); x_hi = max(x_hi, x + 1); }
-    }
-    for (int y = tid; y < H; y += kBlock) {
-        bool touches;
-        node_weight(iy[y], 0.0f, gy, Gy, touches);
-        if (touches) { y_lo = min(y_lo, y); y_hi = max(y_hi, y + 1); }
-    }
+    for (int x = tid; x < W; x += kBlock)
+        if (Segment(tb.ix[x], 0.0f, Gx).touches(gx)) { x_lo = min(x_lo, x); x_hi = max(x_hi, x + 1); }
+    for (int y = tid; y < H; y += kBlock)
+        if (Segment(tb.iy[y], 0.0f, Gy).touches(gy)) { y_lo = min(y_lo, y); y_hi = max(y_hi, y + 1); }
     for (int off = 32; off > 0; off >>= 1) {
         x_lo = min(x_lo, __shfl_xor(x_lo, off));
         x_hi = max(x_hi, __shfl_xor(x_hi, off));
@@ -193,20 +233,20 @@ k_render_psf_volume_grad(const float* __restrict__ img, const float* __restrict_
             int l0 = -1, l1 = -1;
             if (p < npix) {
                 const int y = y_lo + (int)(p / nx), x = x_lo + (int)(p - (p / nx) * nx);
-                bool ty, tx;
-                const float wy = node_weight(iy[y], fy[y], gy, Gy, ty), wx = node_weight(ix[x], fx[x], gx, Gx, tx);
+                const Segment sy(tb.iy[y], tb.fy[y], Gy), sx(tb.ix[x], tb.fx[x], Gx);
+                const bool touches = sy.touches(gy) && sx.touches(gx);
+                const float wy = node_weight(sy, gy), wx = node_weight(sx, gx);
                 const int64_t pixel = (int64_t)b * HW + (int64_t)y * W + x;
-                const int z0 = lower_node(iz[pixel], Dz), z1 = min(z0 + 1, Dz - 1);
-                const float f = fz[pixel];
-                const float w0 = ((1.0f - f) * wy) * wx, w1 = (f * wy) * wx;
-                if (ty && tx && w0 != 0.0f && z0 >= z_first && z0 < z_first + nz) l0 = z0 - z_first;
-                if (ty && tx && w1 != 0.0f && z1 >= z_first && z1 < z_first + nz) l1 = z1 - z_first;
+                const Segment sz(tb.iz[pixel], tb.fz[pixel], Dz);
+                const float w0 = (sz.w_lo * wy) * wx, w1 = (sz.w_hi * wy) * wx;
+                if (touches && w0 != 0.0f && sz.lo >= z_first && sz.lo < z_first + nz) l0 = sz.lo - z_first;
+                if (touches && w1 != 0.0f && sz.hi >= z_first && sz.hi < z_first + nz) l1 = sz.hi - z_first;
                 s_w0[tid] = w0;
                 s_w1[tid] = w1;
                 s_y[tid] = y + pad;
                 s_x[tid] = x + pad;
 #pragma unroll
-                for (int c = 0; c < C; ++c) s_g[c][tid] = g[(int64_t)b * C * HW + c * HW + (int64_t)y * W + x];
+                for (int c = 0; c < C; ++c) s_g[c][tid] = gs[(int64_t)b * C * HW + c * HW + (int64_t)y * W + x];
             }
             s_l0[tid] = l0;
             s_l1[tid] = l1;
@@ -220,18 +260,15 @@ k_render_psf_volume_grad(const float* __restrict__ img, const float* __restrict_
                 float u[C];
 #pragma unroll
                 for (int c = 0; c < C; ++c) u[c] = s_g[c][q];
-                int fi = fi0, fj = fj0;
+                TapWalker tap = tap0;
                 for (int t = tid; t < kk; t += kBlock) {
-                    const int yy = min(max(yb - fi, 0), H - 1), xx = min(max(xb - fj, 0), W - 1);
-                    const float* px = img_b + ((int64_t)yy * W + xx);
+                    const float* px = clamped_pixel(img_b, yb - tap.i, xb - tap.j, H, W);
                     float d = u[0] * px[0];
 #pragma unroll
                     for (int c = 1; c < C; ++c) d += u[c] * px[c * HW];
                     if (q0 >= 0) acc[q0 * kk + t] += w0 * d;
                     if (q1 >= 0) acc[q1 * kk + t] += w1 * d;
-                    fi += dfi;
-                    fj += dfj;
-                    if (fj >= ks) { fj -= ks; ++fi; }
+                    tap.next();
                 }
             }
         }
@@ -254,71 +291,47 @@ k_render_psf_volume_grad(const float* __restrict__ img, const float* __restrict_
 template <int C>
 __global__ void __launch_bounds__(kBlock)
 k_render_psf_volume_grad_depth(const float* __restrict__ img, const float* __restrict__ vol,
-                               const float* __restrict__ gl, const float* __restrict__ gr,
-                               const int* __restrict__ ix, const float* __restrict__ fx, const int* __restrict__ iy,
-                               const float* __restrict__ fy, const int* __restrict__ iz, int H, int W, int ks, int Dz,
-                               int Gy, int Gx, float* __restrict__ dfz)
+                               const float* __restrict__ gl, const float* __restrict__ gr, const SegmentTables tb,
+                               int H, int W, int ks, int Dz, int Gy, int Gx, float* __restrict__ dfz)
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int y = blockIdx.y, b = blockIdx.z;
-    const int pad = (ks - 1) / 2, kk = ks * ks;
+    const int y = blockIdx.y, b = blockIdx.z, pad = (ks - 1) / 2, kk = ks * ks;
     const int64_t HW = (int64_t)H * W;
     const float* __restrict__ img_b = img + (int64_t)b * C * HW;
-    const int fi0 = lane / ks, fj0 = lane - fi0 * ks, dfi = 64 / ks, dfj = 64 - dfi * ks;
-    const int y0 = lower_node(iy[y], Gy), y1 = min(y0 + 1, Gy - 1);
-    const float wy1 = fy[y], wy0 = 1.0f - wy1;
+    const TapWalker tap0(lane, 64, ks);
+    const Segment sy(tb.iy[y], tb.fy[y], Gy);
     const int x_end = min(W, ((int)blockIdx.x + 1) * kPixChunk);
     for (int x = blockIdx.x * kPixChunk + wave; x < x_end; x += kBlock / 64) {
         const int64_t pixel = (int64_t)b * HW + (int64_t)y * W + x;
-        const int z0 = lower_node(iz[pixel], Dz), z1 = min(z0 + 1, Dz - 1);
-        if (z0 == z1) {
-            if (lane == 0) dfz[pixel] = 0.0f;
-            continue;
-        }
-        const int x0 = lower_node(ix[x], Gx), x1 = min(x0 + 1, Gx - 1);
-        const float wx1 = fx[x], wx0 = 1.0f - wx1;
-        // corner k = 4 * (z upper) + 2 * (y upper) + (x upper)
-        float w[8];
-        const float* v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int zz = k & 4 ? z1 : z0, yy = k & 2 ? y1 : y0, xx = k & 1 ? x1 : x0;
-            const float wyx = (k & 2 ? wy1 : wy0) * (k & 1 ? wx1 : wx0);
-            w[k] = k & 4 ? wyx : -wyx;
-            v[k] = vol + (((int64_t)zz * Gy + yy) * Gx + xx) * 2 * kk;
-        }
-        float ul[C], ur[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int64_t o = (int64_t)b * C * HW + c * HW + (int64_t)y * W + x;
-            ul[c] = gl[o];
-            ur[c] = gr[o];
-        }
+        const Segment sz(tb.iz[pixel], 0.0f, Dz);                        // K is linear in fz: its value is no operand
         float acc = 0.0f;
-        int fi = fi0, fj = fj0;
-        for (int t = lane; t < kk; t += 64) {
-            float kl = 0.0f, kr = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                kl += w[k] * v[k][t];
-                kr += w[k] * v[k][kk + t];
-            }
-            const int yy = min(max(y + pad - fi, 0), H - 1), xx = min(max(x + pad - fj, 0), W - 1);
-            const float* px = img_b + ((int64_t)yy * W + xx);
-            float dl = 0.0f, dr = 0.0f;
+        if (sz.lo != sz.hi) {
+            const Corners cn(vol, Gy, Gx, kk, sz, sy, Segment(tb.ix[x], tb.fx[x], Gx), true);
+            float ul[C], ur[C];
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                const float p = px[c * HW];
-                dl += ul[c] * p;
-                dr += ur[c] * p;
+                const int64_t o = (int64_t)b * C * HW + c * HW + (int64_t)y * W + x;
+                ul[c] = gl[o];
+                ur[c] = gr[o];
             }
-            acc += kl * dl + kr * dr;
-            fi += dfi;
-            fj += dfj;
-            if (fj >= ks) { fj -= ks; ++fi; }
+            TapWalker tap = tap0;
+            for (int t = lane; t < kk; t += 64) {
+                float kl, kr;
+                kernel_tap(cn, t, kk, kl, kr);
+                const float* px = clamped_pixel(img_b, y + pad - tap.i, x + pad - tap.j, H, W);
+                float dl = 0.0f, dr = 0.0f;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const float p = px[c * HW];
+                    dl += ul[c] * p;
+                    dr += ur[c] * p;
+                }
+                acc += kl * dl + kr * dr;
+                tap.next();
+            }
+            acc = shuffle_sum(acc);
         }
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
         if (lane == 0) dfz[pixel] = acc;
     }
 }
@@ -336,9 +349,8 @@ k_render_psf_volume_grad_depth(const float* __restrict__ img, const float* __res
 template <int C>
 __global__ void __launch_bounds__(kBlock)
 k_render_psf_volume_grad_img(const float* __restrict__ vol, const float* __restrict__ gl, const float* __restrict__ gr,
-                             const int* __restrict__ ix, const float* __restrict__ fx, const int* __restrict__ iy,
-                             const float* __restrict__ fy, const int* __restrict__ iz, const float* __restrict__ fz,
-                             int H, int W, int ks, int Dz, int Gy, int Gx, float* __restrict__ dimg)
+                             const SegmentTables tb, int H, int W, int ks, int Dz, int Gy, int Gx,
+                             float* __restrict__ dimg)
 {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -347,57 +359,39 @@ k_render_psf_volume_grad_img(const float* __restrict__ vol, const float* __restr
     const int64_t HW = (int64_t)H * W;
     const float* __restrict__ gl_b = gl + (int64_t)b * C * HW;
     const float* __restrict__ gr_b = gr + (int64_t)b * C * HW;
-    const int r0 = lane / ks, c0 = lane - r0 * ks, dr = 64 / ks, dc = 64 - dr * ks;
+    const TapWalker rel0(lane, 64, ks);                                 // (yr, xr) = (rel.i, rel.j)
     const int u_end = min(W, ((int)blockIdx.x + 1) * kPixChunk);
     for (int u = blockIdx.x * kPixChunk + wave; u < u_end; u += kBlock / 64) {
         float acc[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = 0.0f;
-        int yr = r0, xr = c0;
+        TapWalker rel = rel0;
         for (int p = lane; p < kk; p += 64) {
-            const int y = v - pad + yr, x = u - pad + xr;
+            const int y = v - pad + rel.i, x = u - pad + rel.j;
             if (y >= 0 && y < H && x >= 0 && x < W) {
                 // the taps of pixel (y, x) that read a padded position clamping onto (v, u)
-                const int i_lo = v == H - 1 ? 0 : yr, i_hi = v == 0 ? ks - 1 : yr;
-                const int j_lo = u == W - 1 ? 0 : xr, j_hi = u == 0 ? ks - 1 : xr;
+                const int i_lo = v == H - 1 ? 0 : rel.i, i_hi = v == 0 ? ks - 1 : rel.i;
+                const int j_lo = u == W - 1 ? 0 : rel.j, j_hi = u == 0 ? ks - 1 : rel.j;
                 const int64_t pixel = (int64_t)y * W + x;
-                const int x0 = lower_node(ix[x], Gx), x1 = min(x0 + 1, Gx - 1);
-                const int y0 = lower_node(iy[y], Gy), y1 = min(y0 + 1, Gy - 1);
-                const int z0 = lower_node(iz[(int64_t)b * HW + pixel], Dz), z1 = min(z0 + 1, Dz - 1);
-                const float wx1 = fx[x], wx0 = 1.0f - wx1, wy1 = fy[y], wy0 = 1.0f - wy1;
-                const float wz1 = fz[(int64_t)b * HW + pixel], wz0 = 1.0f - wz1;
-                float w[8];
-                const float* vk[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int zz = k & 4 ? z1 : z0, yy = k & 2 ? y1 : y0, xx = k & 1 ? x1 : x0;
-                    w[k] = ((k & 4 ? wz1 : wz0) * (k & 2 ? wy1 : wy0)) * (k & 1 ? wx1 : wx0);
-                    vk[k] = vol + (((int64_t)zz * Gy + yy) * Gx + xx) * 2 * kk;
-                }
+                const Corners cn(vol, Gy, Gx, kk,
+                                 Segment(tb.iz[(int64_t)b * HW + pixel], tb.fz[(int64_t)b * HW + pixel], Dz),
+                                 Segment(tb.iy[y], tb.fy[y], Gy), Segment(tb.ix[x], tb.fx[x], Gx));
                 float sl = 0.0f, sr = 0.0f;
                 for (int i = i_lo; i <= i_hi; ++i)
                     for (int j = j_lo; j <= j_hi; ++j) {
-                        const int t = i * ks + j;
-                        float kl = 0.0f, kr = 0.0f;
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) {
-                            kl += w[k] * vk[k][t];
-                            kr += w[k] * vk[k][kk + t];
-                        }
+                        float kl, kr;
+                        kernel_tap(cn, i * ks + j, kk, kl, kr);
                         sl += kl;
                         sr += kr;
                     }
 #pragma unroll
                 for (int c = 0; c < C; ++c) acc[c] += gl_b[c * HW + pixel] * sl + gr_b[c * HW + pixel] * sr;
             }
-            yr += dr;
-            xr += dc;
-            if (xr >= ks) { xr -= ks; ++yr; }
+            rel.next();
         }
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-            float a = acc[c];
-            for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+            const float a = shuffle_sum(acc[c]);
             if (lane == 0) dimg[((int64_t)(b * C + c) * H + v) * W + u] = a;
         }
     }
@@ -412,31 +406,32 @@ namespace {
 constexpr int kGradLds = 64 * 1024;
 int planes_per_chunk(int Dz, int ks) { return std::min(Dz, kGradLds / (int)(sizeof(float) * ks * ks)); }
 
-int check_volume_render(const void* img, const void* a, const void* b, const int32_t* ix, const float* fx,
-                        const int32_t* iy, const float* fy, const int32_t* iz, const float* fz, int B, int C, int H,
-                        int W, int ks, int Dz, int Gy, int Gx)
+// the shared shape rules, and the volume's own: every extent >= 1, a plane's nodes fit int32
+int check_volume_render(const void* a, const void* b, const void* c, const void* d, const SegmentTables& tb, int B,
+                        int C, int H, int W, int ks, int Dz, int Gy, int Gx)
 {
-    if (!img || !a || !b || !ix || !fx || !iy || !fy || !iz || !fz)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (B < 0 || H < 1 || W < 1 || Dz < 1 || Gy < 1 || Gx < 1 || ks < 1 || (ks & 1) == 0)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad shape (ks must be odd, every extent >= 1)");
-    if (C != 1 && C != 3 && C != 4) return fail(SDIRT_ERR_UNSUPPORTED, "channels=%d (supported: 1, 3, 4)", C);
-    if (ks > kMaxKsVolume)
-        return fail(SDIRT_ERR_UNSUPPORTED, "ks=%d: the volume render supports ks <= %d", ks, kMaxKsVolume);
-    if (B > 65535 || H > 65535) return fail(SDIRT_ERR_UNSUPPORTED, "batch=%d height=%d (supported: <= 65535)", B, H);
+    if (Dz < 1 || Gy < 1 || Gx < 1) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad shape (Dz, Gy, Gx must be >= 1)");
+    if (int rc = check_image_call({a, b, c, d, tb.ix, tb.fx, tb.iy, tb.fy, tb.iz, tb.fz}, B, C, H, W, ks, kMaxKsVolume,
+                                  true))
+        return rc;
     if ((int64_t)Gy * Gx > INT32_MAX) return fail(SDIRT_ERR_UNSUPPORTED, "%d x %d nodes per plane", Gy, Gx);
     return SDIRT_OK;
 }
 
+// one wave per pixel (forward, depth gradient) or image position (image gradient)
+dim3 pixel_grid(int B, int H, int W)
+{
+    return dim3((unsigned)((W + kPixChunk - 1) / kPixChunk), (unsigned)H, (unsigned)B);
+}
+
 template <int C>
 int launch_volume_grad(dim3 grid, size_t lds, hipStream_t st, const float* img, const float* gl, const float* gr,
-                       const int32_t* ix, const float* fx, const int32_t* iy, const float* fy, const int32_t* iz,
-                       const float* fz, int B, int H, int W, int ks, int Dz, int Gy, int Gx, int planes, float* dvol)
+                       const SegmentTables& tb, int B, int H, int W, int ks, int Dz, int Gy, int Gx, int planes,
+                       float* dvol)
 {
     if (lds > 32 * 1024)
         if (int rc = allow_large_lds<&k_render_psf_volume_grad<C>>(kGradLds)) return rc;
-    k_render_psf_volume_grad<C><<<grid, kBlock, lds, st>>>(img, gl, gr, ix, fx, iy, fy, iz, fz, B, H, W, ks, Dz, Gy,
-                                                           Gx, planes, dvol);
+    k_render_psf_volume_grad<C><<<grid, kBlock, lds, st>>>(img, gl, gr, tb, B, H, W, ks, Dz, Gy, Gx, planes, dvol);
     return SDIRT_OK;
 }
 
@@ -449,25 +444,16 @@ int sdirt_render_psf_volume(const float* img, const float* volume, const int32_t
                             int32_t C, int32_t H, int32_t W, int32_t ks, int32_t Dz, int32_t Gy, int32_t Gx,
                             float* out_l, float* out_r, void* stream)
 {
-    if (!volume) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (int rc = check_volume_render(img, out_l, out_r, ix, fx, iy, fy, iz, fz, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
+    const SegmentTables tb{ix, fx, iy, fy, iz, fz};
+    if (int rc = check_volume_render(img, volume, out_l, out_r, tb, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
     if (B == 0) return SDIRT_OK;
-    const dim3 grid((unsigned)((W + kPixChunk - 1) / kPixChunk), (unsigned)H, (unsigned)B);
+    const dim3 grid = pixel_grid(B, H, W);
     hipStream_t st = as_stream(stream);
-    switch (C) {
-    case 1:
-        k_render_psf_volume<1><<<grid, kBlock, 0, st>>>(img, volume, ix, fx, iy, fy, iz, fz, H, W, ks, Dz, Gy, Gx,
-                                                        out_l, out_r);
-        break;
-    case 3:
-        k_render_psf_volume<3><<<grid, kBlock, 0, st>>>(img, volume, ix, fx, iy, fy, iz, fz, H, W, ks, Dz, Gy, Gx,
-                                                        out_l, out_r);
-        break;
-    default:
-        k_render_psf_volume<4><<<grid, kBlock, 0, st>>>(img, volume, ix, fx, iy, fy, iz, fz, H, W, ks, Dz, Gy, Gx,
-                                                        out_l, out_r);
-        break;
-    }
+    with_channels(C, [&](auto c) {
+        k_render_psf_volume<decltype(c)::value><<<grid, kBlock, 0, st>>>(img, volume, tb, H, W, ks, Dz, Gy, Gx, out_l,
+                                                                       out_r);
+        return SDIRT_OK;
+    });
     LAUNCH_CHECK();
     return SDIRT_OK;
 }
@@ -477,31 +463,19 @@ int sdirt_render_psf_volume_grad(const float* img, const float* grad_l, const fl
                                  const float* fz, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ks, int32_t Dz,
                                  int32_t Gy, int32_t Gx, float* grad_volume, void* stream)
 {
-    if (!grad_volume) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (int rc = check_volume_render(img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, C, H, W, ks, Dz, Gy, Gx))
-        return rc;
+    const SegmentTables tb{ix, fx, iy, fy, iz, fz};
+    if (int rc = check_volume_render(img, grad_l, grad_r, grad_volume, tb, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
     // (an empty batch is launched like any other: every element of grad_volume is written, all 0)
     const int planes = planes_per_chunk(Dz, ks), chunks = (Dz + planes - 1) / planes;
     if (chunks > 65535) return fail(SDIRT_ERR_UNSUPPORTED, "%d depth planes at ks=%d", Dz, ks);
     const dim3 grid((unsigned)(Gy * Gx), 2u, (unsigned)chunks);
     const size_t lds = sizeof(float) * (size_t)planes * ks * ks;
     hipStream_t st = as_stream(stream);
-    int rc;
-    switch (C) {
-    case 1:
-        rc = launch_volume_grad<1>(grid, lds, st, img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, H, W, ks, Dz, Gy, Gx,
-                                   planes, grad_volume);
-        break;
-    case 3:
-        rc = launch_volume_grad<3>(grid, lds, st, img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, H, W, ks, Dz, Gy, Gx,
-                                   planes, grad_volume);
-        break;
-    default:
-        rc = launch_volume_grad<4>(grid, lds, st, img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, H, W, ks, Dz, Gy, Gx,
-                                   planes, grad_volume);
-        break;
-    }
-    if (rc) return rc;
+    if (int rc = with_channels(C, [&](auto c) {
+            return launch_volume_grad<decltype(c)::value>(grid, lds, st, img, grad_l, grad_r, tb, B, H, W, ks, Dz, Gy,
+                                                          Gx, planes, grad_volume);
+        }))
+        return rc;
     LAUNCH_CHECK();
     return SDIRT_OK;
 }
@@ -512,45 +486,26 @@ int sdirt_render_psf_volume_grad_scene(const float* img, const float* volume, co
                                        int32_t H, int32_t W, int32_t ks, int32_t Dz, int32_t Gy, int32_t Gx,
                                        float* grad_img, float* grad_fz, void* stream)
 {
-    if (!volume) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer");
+    const SegmentTables tb{ix, fx, iy, fy, iz, fz};
     if (!grad_img && !grad_fz) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer (neither gradient is asked for)");
-    if (int rc = check_volume_render(img, grad_l, grad_r, ix, fx, iy, fy, iz, fz, B, C, H, W, ks, Dz, Gy, Gx))
-        return rc;
+    if (int rc = check_volume_render(img, volume, grad_l, grad_r, tb, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
     if (B == 0) return SDIRT_OK;
-    const dim3 grid((unsigned)((W + kPixChunk - 1) / kPixChunk), (unsigned)H, (unsigned)B);
+    const dim3 grid = pixel_grid(B, H, W);
     hipStream_t st = as_stream(stream);
     if (grad_fz) {
-        switch (C) {
-        case 1:
-            k_render_psf_volume_grad_depth<1><<<grid, kBlock, 0, st>>>(img, volume, grad_l, grad_r, ix, fx, iy, fy, iz,
-                                                                       H, W, ks, Dz, Gy, Gx, grad_fz);
-            break;
-        case 3:
-            k_render_psf_volume_grad_depth<3><<<grid, kBlock, 0, st>>>(img, volume, grad_l, grad_r, ix, fx, iy, fy, iz,
-                                                                       H, W, ks, Dz, Gy, Gx, grad_fz);
-            break;
-        default:
-            k_render_psf_volume_grad_depth<4><<<grid, kBlock, 0, st>>>(img, volume, grad_l, grad_r, ix, fx, iy, fy, iz,
-                                                                       H, W, ks, Dz, Gy, Gx, grad_fz);
-            break;
-        }
+        with_channels(C, [&](auto c) {
+            k_render_psf_volume_grad_depth<decltype(c)::value><<<grid, kBlock, 0, st>>>(
+                img, volume, grad_l, grad_r, tb, H, W, ks, Dz, Gy, Gx, grad_fz);
+            return SDIRT_OK;
+        });
         LAUNCH_CHECK();
     }
     if (grad_img) {
-        switch (C) {
-        case 1:
-            k_render_psf_volume_grad_img<1><<<grid, kBlock, 0, st>>>(volume, grad_l, grad_r, ix, fx, iy, fy, iz, fz, H,
-                                                                     W, ks, Dz, Gy, Gx, grad_img);
-            break;
-        case 3:
-            k_render_psf_volume_grad_img<3><<<grid, kBlock, 0, st>>>(volume, grad_l, grad_r, ix, fx, iy, fy, iz, fz, H,
-                                                                     W, ks, Dz, Gy, Gx, grad_img);
-            break;
-        default:
-            k_render_psf_volume_grad_img<4><<<grid, kBlock, 0, st>>>(volume, grad_l, grad_r, ix, fx, iy, fy, iz, fz, H,
-                                                                     W, ks, Dz, Gy, Gx, grad_img);
-            break;
-        }
+        with_channels(C, [&](auto c) {
+            k_render_psf_volume_grad_img<decltype(c)::value><<<grid, kBlock, 0, st>>>(
+                volume, grad_l, grad_r, tb, H, W, ks, Dz, Gy, Gx, grad_img);
+            return SDIRT_OK;
+        });
         LAUNCH_CHECK();
     }
     return SDIRT_OK;

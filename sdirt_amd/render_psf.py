@@ -39,6 +39,12 @@ def local_psf_render_fast(input, psf, kernel_size=11, val=False):
     return _render(input, psf, kernel_size, half=True)
 
 
+def _grad_halves(grad, c):
+    """The upstream gradient of cat(left, right) [B,2C,H,W] -> its two halves, fp32 and contiguous, as the kernels
+    read them."""
+    return grad[:, :c].to(torch.float32).contiguous(), grad[:, c:].to(torch.float32).contiguous()
+
+
 class _LocalDpPsfRender(torch.autograd.Function):
     """local_dp_psf_render under autograd: the forward is _render's kernel call on the same operands (bit-equal to
     the no-grad call), the backward the two kernels of sdirt_render_grad.hip -- only those ctx.needs_input_grad asks
@@ -58,8 +64,7 @@ class _LocalDpPsfRender(torch.autograd.Function):
         ks = ctx.kernel_size
         b, c, h, w = input.shape if input.dim() == 4 else (1, *input.shape)
         lib, stream = _lib.lib(), stream_ptr(input.device)
-        gl = grad[:, :c].to(torch.float32).contiguous()
-        gr = grad[:, c:].to(torch.float32).contiguous()
+        gl, gr = _grad_halves(grad, c)
         grad_input = grad_psf = None
         if ctx.needs_input_grad[0]:
             k = dp_psf.to(torch.float32).reshape(b, h, w, 2, ks, ks).contiguous()
@@ -168,8 +173,7 @@ class _RenderPsfVolume(torch.autograd.Function):
         img, *tables = ctx.saved_tensors
         b, c, h, w = img.shape
         dz, gy, gx = ctx.volume_shape[:3]
-        gl = grad[:, :c].to(torch.float32).contiguous()
-        gr = grad[:, c:].to(torch.float32).contiguous()
+        gl, gr = _grad_halves(grad, c)
         dvol = torch.empty(ctx.volume_shape, dtype=torch.float32, device=img.device)
         _lib.check(_lib.lib().sdirt_render_psf_volume_grad(dptr(img), dptr(gl), dptr(gr), *(dptr(t) for t in tables),
                                                            b, c, h, w, ctx.kernel_size, dz, gy, gx, dptr(dvol),
@@ -201,8 +205,7 @@ class _RenderPsfVolumeScene(torch.autograd.Function):
         dz, gy, gx = vol.shape[:3]
         shape = (b, c, h, w, ctx.kernel_size, dz, gy, gx)
         lib, stream = _lib.lib(), stream_ptr(img.device)
-        gl = grad[:, :c].to(torch.float32).contiguous()
-        gr = grad[:, c:].to(torch.float32).contiguous()
+        gl, gr = _grad_halves(grad, c)
         dvol = dimg = dfz = None
         if ctx.needs_input_grad[0]:
             dvol = torch.empty(vol.shape, dtype=torch.float32, device=img.device)
@@ -247,16 +250,13 @@ def local_dp_psf_render_volume(input, volume, x_nodes, y_nodes, z_nodes, z, kern
     if scene_grad and grad_mode and (input.requires_grad or z.requires_grad or volume.requires_grad):
         b, _, h, w = input.shape
         img = input.to(torch.float32).contiguous()
-        # volume_segment_tables' ops on a z that is NOT detached: bit-equal table values, fz differentiable in z
-        dev = img.device
-        ix, fx = axis_segments(x_nodes.detach().to(dev), torch.linspace(-1, 1, w, device=dev))
-        iy, fy = axis_segments(y_nodes.detach().to(dev), torch.linspace(1, -1, h, device=dev))
-        zz = z.to(dev).reshape(b, h, w)
-        iz, fz = axis_segments(z_nodes.detach().to(dev), zz)
+        # volume_segment_tables on a z that is NOT detached: the plain call's table values, fz differentiable in z
+        zz = z.to(img.device).reshape(b, h, w)
+        ix, fx, iy, fy, iz, fz = volume_segment_tables(x_nodes.detach(), y_nodes.detach(), z_nodes.detach(), zz, h, w)
         if zz.requires_grad and not fz.requires_grad:
-            fz = fz + 0.0 * zz.to(torch.float32)               # an axis of one node: fz = 0 for every z, z.grad = 0
-        ix, fx, iy, fy, iz, fz = (t.contiguous() for t in (ix, fx, iy, fy, iz, fz))
-        return _RenderPsfVolumeScene.apply(volume.to(dev), img, fz, kernel_size, ix, fx, iy, fy, iz).to(input.dtype)
+            fz = (fz + 0.0 * zz.to(torch.float32)).contiguous()  # an axis of one node: fz = 0 for every z, z.grad = 0
+        out = _RenderPsfVolumeScene.apply(volume.to(img.device), img, fz, kernel_size, ix, fx, iy, fy, iz)
+        return out.to(input.dtype)
     if grad_mode and input.requires_grad:
         raise ValueError("local_dp_psf_render_volume: the gradient with respect to the image is not built "
                          "(detach the image; local_dp_psf_render has one)")
