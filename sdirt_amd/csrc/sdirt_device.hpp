@@ -39,7 +39,8 @@ struct alignas(64) SurfHot {
     float c2;            // c*c (fp32)
     float onepk;         // 1 + k
     float lim_loose;     // ((1/c2) * fp32(1-1e-9)) / (1+k)   surfaces.py:728,739
-    float r2_lim;        // fp32(r*r in double)               surfaces.py:464,728
+    float r2_lim;        // fp32(r*r in double)               surfaces.py:464,728; planes: the largest x with
+                         // sqrtf(x) <= fp32(r), the aperture test without the root (surface_reaction)
     float lim_tight;     // curved: min(r2_lim, lim_loose) when k > -1, else r2_lim -- the two domain
                          // tests of _valid (surfaces.py:727-733) as one; planes: fp32(r) (surfaces.py:421)
     // dwords 8-11: what refraction needs when tracing forward; 12-15: the same for backward
@@ -365,8 +366,9 @@ __device__ __forceinline__ void normalize3(float& x, float& y, float& z)
 }
 
 // Even-asphere sag g(r2) and dg/d(r2), surfaces.py:787-808 and 811-830 evaluated together
-// (they share sqrt(1-a)).  INSIDE: r2 is known to lie inside the conic's domain with k > -1
-// (0 < 1 - a <= 1), so sqrt_pos applies.  P = Poly: the surface has polynomial terms (deg of
+// (they share sqrt(1-a)).  INSIDE: the radicand 1 - a is known to be positive, finite and normal -- r2 inside the
+// conic's domain with k > -1 (0 < 1 - a <= 1: the Newton trips), or any r2 with k <= -1 (a <= 0) -- so sqrt_pos
+// applies.  P = Poly: the surface has polynomial terms (deg of
 // them, wave-uniform); P = NoPoly: pure conic (every sphere).
 // r2 ** n as torch evaluates it on CPU: n == 2 -> x*x, n == 3 -> (x*x)*x, n >= 4 a <= 1-ulp
 // vector pow, for which the correctly rounded exact power stands here (running product in
@@ -450,19 +452,32 @@ __device__ __forceinline__ void sag_g_dgd(const C& k, const P& pol, int deg, flo
     }
 }
 
+// What Newton's own validity (surfaces.py:580-586) is made of: the final t, the residual of the differentiable step
+// and the squared radius at the final position, with the bound it is held against.  The three compares are made by
+// whoever asks (NewtonEnd::valid): a sphere's validity is its own test (surfaces.py:464) and never does.
+struct NewtonEnd {
+    float t, ft, rr, tight;
+    __device__ __forceinline__ bool valid() const
+    {
+        bool v = rr < tight;                                   // false on a dead ray (tight = -1)
+        v = v && __builtin_fabsf(ft) < (float)10e-6;
+        return v && t > 0.0f;
+    }
+};
+
 // surfaces.py:523-586.  `trips` loop iterations (wave-uniform), then the extra
-// differentiable step and the validity test.  Returns Newton's own validity;
+// differentiable step; the validity test is left to the caller (NewtonEnd).
 // mask_out (wave-uniform, lives in SGPRs) gets bit j set when ANY active lane of
 // the wave had |f(t)| > 50e-6 in trip j -- the per-wave share of the reference's
 // batch-wide `.any()` loop condition (surfaces.py:547).
 template <class M, bool KGT, class P, bool UNITK = false, class S = Surf>
-__device__ __forceinline__ bool newton_k(const S& s, const P& pol, const Ray& r, const bool alive, int trips,
-                                         float& t_out, uint32_t& mask_out)
+__device__ __forceinline__ NewtonEnd newton_k(const S& s, const P& pol, const Ray& r, const bool alive, int trips,
+                                              uint32_t& mask_out)
 {
     using CV = ConicV;
     const bool adaptive = trips < 0;
     const int cap = adaptive ? -trips : trips;
-    const float tol_loose = (float)50e-6, tol_tight = (float)10e-6, eps = (float)1e-9;
+    const float tol_loose = (float)50e-6, eps = (float)1e-9;
     const ConicV k = conic_v<UNITK>(s);
     const int deg = s.ai_degree();
     const float t0 = M::div(k.d - r.oz, r.dz);
@@ -503,8 +518,14 @@ __device__ __forceinline__ bool newton_k(const S& s, const P& pol, const Ray& r,
         // g(x*valid, y*valid) (surfaces.py:694-696): (x*1)^2 + (y*1)^2 is rr bit for bit, and
         // (x*0)^2 + (y*0)^2 is 0 for every finite position
         const float r2 = (KGT ? rr < bound : rr > bound) ? rr : 0.0f;
+        // sqrt_pos on either side of k = -1.  k > -1: r2 < lim_loose, the radicand 1 - a lies in (0, 1].  k <= -1:
+        // a <= 0, the radicand is >= 1 -- and where r2 or a overflows (radicand +inf: sqrt gives inf, sqrt_pos NaN)
+        // g and dgd are NaN under either form, because Lean::div by an infinite 1 + sf is NaN.  sqrt_pos is verified
+        // exhaustively on [2^-100, 2^100] (selftest mode 3); a finite radicand above that needs r2 beyond 1e25 mm^2,
+        // which only a ray whose Newton iteration has diverged holds -- it fails |ft| < 10e-6 and is dead under
+        // either root.
         float g, dgd;
-        sag_g_dgd<M, KGT, CV, UNITK>(k, pol, deg, r2, g, dgd);
+        sag_g_dgd<M, true, CV, UNITK>(k, pol, deg, r2, g, dgd);
         const float ft = (g + k.d) - nz;
         const float dfdt = M::dfdt(dgd, dd * t + dox, r.dz);            // dgd * dr2dt - dz, dr2dt = 2((dx^2+dy^2) t + (dx ox + dy oy))
         const unsigned long long open = __ballot(__builtin_fabsf(ft) > tol_loose);
@@ -568,18 +589,24 @@ __device__ __forceinline__ bool newton_k(const S& s, const P& pol, const Ray& r,
     const float tight = alive ? s.lim_tight() : -1.0f;
     const float r2 = rr < tight ? rr : 0.0f;
     float g, dgd;
-    sag_g_dgd<M, KGT, CV, UNITK>(k, pol, deg, r2, g, dgd);
+    sag_g_dgd<M, true, CV, UNITK>(k, pol, deg, r2, g, dgd);
     const float ft = (g + k.d) - nz;
     const float dfdt = M::dfdt(dgd, dd * t + dox, r.dz);
     t = t - M::newton_step(ft, dfdt + eps);
     nx = r.ox + r.dx * t;
     ny = r.oy + r.dy * t;
     rr = nx * nx + ny * ny;
-    bool v = rr < tight;
-    v = v && __builtin_fabsf(ft) < tol_tight;
-    v = v && t > 0.0f;
-    t_out = t;
-    return v;
+    return NewtonEnd{t, ft, rr, tight};
+}
+
+// The kinds' paths are `if (A) {...} if (B) {...}` with B the complement of A behind an empty statement, not
+// `if (A) {...} else {...}`: each path then updates the ray in place and merges with "the ray as it was" only.  Of an
+// if / else the compiler makes one merge of two fresh sets of registers, which start undefined on the other path
+// while the old ray is still live there -- that overlap is what kept old and new ray in separate registers.
+__device__ __forceinline__ uint32_t apart(uint32_t flags)        // the surface's flags word, read "once more"
+{
+    asm volatile("" : "+s"(flags));
+    return flags;
 }
 
 // surfaces.py:633-679 with _normal (:589-630).  FWD: rays travel +z (n negated,
@@ -595,7 +622,21 @@ __device__ __forceinline__ bool newton_k(const S& s, const P& pol, const Ray& r,
 // sign bit the reference's has (the xor of its factors' signs is the same), so a component that is zero -- the on-axis
 // ray, or nx == 0 with dx == 0 -- gets the same zero from the same sum.  The one sum that can differ is cosi itself,
 // +0 here where the reference has -0, when it cancels exactly: such a ray fails cosi^2 > 0.1 and keeps its direction.
-template <bool FWD, class M, class P, class S>
+//
+// UNIT_W (the fused kernels, Lean): every weight is exactly 0 or 1 (ra starts at 1 and is only ever multiplied by 0/1
+// flags), and the caller has NOT applied its validity to ra: (live ? ra : 0) * vf is vf itself, because vf implies
+// live and live implies ra == 1 -- the visit's one weight update.  The staged k_trace carries arbitrary weights
+// and keeps the two products.
+//
+// The asphere's normal under Lean: sqrt_pos.  _dsdr2 is evaluated at whatever (x, y) the ray holds (surfaces.py:600),
+// and the radicand 1 - a, a = ((1 + k) r2) c2, is positive and normal there:
+//   a dead ray evaluates at r2 = 0 (x, y times 0), where the radicand is 1;
+//   a live ray has passed rr < lim_tight <= lim_loose at this very position (k > -1: a < 1 up to its rounding);
+//   for k <= -1, 1 + k <= 0 gives a <= 0 and a radicand >= 1.
+// Where a ROUNDS to 1 (k > -1, rr one or two floats under lim_loose: the host's fp32(1 - 1e-9) is 1.0f) the radicand
+// is 0 and both forms give a NaN normal -- the general one through (a / 2) / 0, whose Lean::div is NaN, this one
+// through 0 * rsq(0): the ray fails c2i > 0.1, keeps its direction and dies either way.  Ieee: the literal sqrt.
+template <bool FWD, class M, bool UNIT_W = false, bool PLANE = false, class P, class S>
 __device__ __forceinline__ void refract(const S& s, const P& pol, Ray& r, const bool live)
 {
     // Snell's law on the normal sgn * normalize(nx, ny, nz), sgn = neg ? -1 : +1 (Lean) or the normal as it stands (Ieee).
@@ -619,22 +660,28 @@ __device__ __forceinline__ void refract(const S& s, const P& pol, Ray& r, const 
         ndx = v ? ndx : r.dx; ndy = v ? ndy : r.dy; ndz = v ? ndz : r.dz;
         r.ob = r.ob * ((ndx * r.dx + ndy * r.dy) + ndz * r.dz);
         r.dx = ndx; r.dy = ndy; r.dz = ndz;
-        r.ra = r.ra * vf;
+        r.ra = M::kFused && UNIT_W ? vf : r.ra * vf;
     };
     float nx, ny, nz;
     if constexpr (!std::is_same<P, NoPoly>::value) {
         const float vf = live ? 1.0f : 0.0f;
         const float xv = r.ox * vf, yv = r.oy * vf;
         float g, ds;
-        // _dsdr2 is evaluated at whatever (x, y) the ray holds (surfaces.py:600): general sqrt
-        sag_g_dgd<M, false, ConicS, false, P, false>(conic_s(s), pol, s.ai_degree(), xv * xv + yv * yv, g, ds);
+        sag_g_dgd<M, true, ConicS, false, P, false>(conic_s(s), pol, s.ai_degree(), xv * xv + yv * yv, g, ds);
         nx = (ds * 2.0f) * xv; ny = (ds * 2.0f) * yv; nz = -1.0f;
-    } else if (s.kind() == 0) {
+    } else if (PLANE) {
         nx = 0.0f; ny = 0.0f; nz = -1.0f;
-    } else if (s.kind() == 1 && M::kFused) {
+    } else if (M::kFused) {
         // the sphere has its own copy of what follows: its normal is read where the position lies (no moves into
         // registers shared with the other kinds), and its sign is the only one that is not a constant
-        snell(r.ox, r.oy, r.oz - s.d_plus_R(), s.c_pos() == FWD);
+        if (s.kind() == 1) snell(r.ox, r.oy, r.oz - s.d_plus_R(), s.c_pos() == FWD);
+        if ((apart(s.a[0]) & 3u) != 1u) {                         // conic without polynomial terms
+            const float vf = live ? 1.0f : 0.0f;
+            const float xv = r.ox * vf, yv = r.oy * vf;
+            float g, ds;
+            sag_g_dgd<M, true>(conic_s(s), pol, 0, xv * xv + yv * yv, g, ds);
+            snell((ds * 2.0f) * xv, (ds * 2.0f) * yv, -1.0f, FWD);
+        }
         return;
     } else if (s.kind() == 1) {
         const float sg = s.c_pos() ? 2.0f : -2.0f;       // (+-2) * x is exact either way
@@ -643,32 +690,31 @@ __device__ __forceinline__ void refract(const S& s, const P& pol, Ray& r, const 
         const float vf = live ? 1.0f : 0.0f;
         const float xv = r.ox * vf, yv = r.oy * vf;
         float g, ds;
-        sag_g_dgd<M, false>(conic_s(s), pol, 0, xv * xv + yv * yv, g, ds);
+        sag_g_dgd<M, true>(conic_s(s), pol, 0, xv * xv + yv * yv, g, ds);
         nx = (ds * 2.0f) * xv; ny = (ds * 2.0f) * yv; nz = -1.0f;
     }
     snell(nx, ny, nz, FWD);
 }
 
-// Curved surface: Newton intersection, validity, refraction (surfaces.py:456-520).  `between` runs
-// after the intersection and before the refraction (the trace loop's prefetch of the next surface).
+// Curved surface, first half: Newton intersection and validity (surfaces.py:456-495); the position is committed where
+// it stands and the validity v returned for the refraction.
 // r.ra > 0 is compared ONCE per visit: `alive` serves the Newton solve and the sphere's validity test, and the
 // validity v -- which implies it, and is all that is left of it once ra = keep_if(ra, v) -- serves the refraction.
-template <bool FWD, class M, class P, class F, class S>
-__device__ __forceinline__ uint32_t curved_reaction(const S& s, const P& pol, Ray& r, int trips, F between)
+// Newton's own validity is asked for on the non-sphere branch only (NewtonEnd::valid): a sphere's is its own test.
+template <class M, bool UNIT_W = false, class P, class S>
+__device__ __forceinline__ bool curved_hit(const S& s, const P& pol, Ray& r, int trips, uint32_t& mask)
 {
-    uint32_t mask = 0;
-    float t;
     const bool alive = r.ra > 0.0f;
     // k > -1 (every sphere, ellipsoid, mild asphere) and k <= -1 differ only in the domain test
     // (surfaces.py:727-743); the branch is wave-uniform and taken once, outside the loop
     // (and, for pure conics, a copy for 1 + k == 1: every sphere)
-    bool vn;
+    NewtonEnd e;
     if (std::is_same<P, NoPoly>::value && s.unit_k())
-        vn = newton_k<M, true, P, true>(s, pol, r, alive, trips, t, mask);
+        e = newton_k<M, true, P, true>(s, pol, r, alive, trips, mask);
     else
-        vn = s.k_gt_m1() ? newton_k<M, true>(s, pol, r, alive, trips, t, mask)
-                         : newton_k<M, false>(s, pol, r, alive, trips, t, mask);
-    between();
+        e = s.k_gt_m1() ? newton_k<M, true>(s, pol, r, alive, trips, mask)
+                        : newton_k<M, false>(s, pol, r, alive, trips, mask);
+    const float t = e.t;
     const float nx = r.ox + t * r.dx, ny = r.oy + t * r.dy, nz = r.oz + t * r.dz;
     bool v;
     if (s.kind() == 1) {                                                                  // :464
@@ -677,33 +723,62 @@ __device__ __forceinline__ uint32_t curved_reaction(const S& s, const P& pol, Ra
         asm volatile("");
         v = nx * nx + ny * ny <= s.r2_lim() && t >= 0.0f && alive;
     } else {
-        v = vn;                                                                           // :495 (false on a dead ray)
+        v = e.valid();                                                                    // :495 (false on a dead ray)
     }
     r.ox = v ? nx : r.ox; r.oy = v ? ny : r.oy; r.oz = v ? nz : r.oz;
-    r.ra = M::keep_if(r.ra, v);
-    refract<FWD, M>(s, pol, r, v);
-    return mask;
+    if (!(M::kFused && UNIT_W)) r.ra = M::keep_if(r.ra, v);           // UNIT_W: refract()'s update is the visit's only one
+    return v;
 }
 
 // Aspheric.ray_reaction, surfaces.py:391-520, on surface `blk` whose constants `s` are already in
 // registers.  Returns the Newton convergence mask of this wave on this surface (0 for planes).
-template <bool FWD, class M, class F, class S>
+// `between` runs ONCE, after the intersection and before the refraction (the trace loop's prefetch of the next
+// surface): the three kinds -- plane, curved without polynomial terms, asphere with terms -- are three `if`s in a row
+// before it (intersection, validity, position) and three after it (refraction), each updating the ray in place (see
+// apart() for why they are no if / else chain).  The asphere's halves stand next to `between`, so that its polynomial
+// block is live across nothing else.
+//
+// The plane's aperture test (surfaces.py:421), sqrt(x^2 + y^2) <= r.  A correctly rounded square root is monotone, so
+// the test holds exactly when x^2 + y^2 <= X, X the largest fp32 whose rounded root is <= r; the host finds X once
+// (make_dev_surface: plane_r2_max) and puts it in the r2_lim word, which no kernel reads for a plane otherwise.  NaN
+// and +inf fail both forms.  Lean compares against X -- one v_cmp for v_sqrt + 10; Ieee keeps the literal root.
+template <bool FWD, class M, bool UNIT_W = false, class F, class S>
 __device__ __forceinline__ uint32_t surface_reaction(const S& s, const DevSurface* __restrict__ blk,
                                                      int trips, Ray& r, F between)
 {
-    if (s.kind() == 0) {
+    uint32_t mask = 0;
+    bool v = false;
+    const uint32_t f0 = s.a[0], f1 = apart(f0), f2 = apart(f0);
+    // wave-uniform, all three, and ONE scalar compare each (a conjunction of two comes out as two 64-bit masks, an
+    // s_and_b64 and a branch on vcc: ten scalar instructions per test, six tests per visit).  Only an asphere has
+    // a degree (make_dev_surface), so "has terms" is the degree field alone.
+    const bool plane = (f0 & 3u) == 0u;
+    const bool conic = (f1 & 0xf03u) - 1u < 2u;                    // kind 1 or 2, degree 0: sphere, or conic without terms
+    const bool terms = (f2 & 0xf00u) != 0u;
+    if (plane) {
         const float t = M::div(s.d() - r.oz, r.dz);
         const float nx = r.ox + t * r.dx, ny = r.oy + t * r.dy, nz = r.oz + t * r.dz;
-        const bool v = M::sqrt(nx * nx + ny * ny) <= s.r_lim() && r.ra > 0.0f;
+        const float rr = nx * nx + ny * ny;
+        const bool inside = M::kFused ? rr <= s.r2_lim() : M::sqrt(rr) <= s.r_lim();
+        v = inside && r.ra > 0.0f;
         r.ox = v ? nx : r.ox; r.oy = v ? ny : r.oy; r.oz = v ? nz : r.oz;
         r.ra = M::keep_if(r.ra, v);
-        between();
-        if (s.do_refract()) refract<FWD, M>(s, NoPoly{}, r, v);
-        return 0;
     }
-    if (s.ai_degree() > 0)                        // wave-uniform: the polynomial block is fetched
-        return curved_reaction<FWD, M>(s, s.poly(blk), r, trips, between);   // (one more round trip) on aspheres only
-    return curved_reaction<FWD, M>(s, NoPoly{}, r, trips, between);
+    if (conic) v = curved_hit<M, UNIT_W>(s, NoPoly{}, r, trips, mask);
+    Poly pol;
+    if (terms) {
+        pol = s.poly(blk);                        // the polynomial block is fetched (one more round trip) on aspheres only
+        v = curved_hit<M, UNIT_W>(s, pol, r, trips, mask);
+    }
+    between();
+    // (the kinds are decoded again: a condition carried across `between` comes back as a lane mask, a v_cndmask and a
+    // v_cmp per visit)
+    const uint32_t g1 = apart(f0), g2 = apart(f0);
+    if ((g2 & 0xf00u) != 0u) refract<FWD, M, UNIT_W>(s, pol, r, v);
+    if ((g1 & 0xf03u) - 1u < 2u) refract<FWD, M, UNIT_W>(s, NoPoly{}, r, v);
+    if ((f0 & (3u | kFlagRefract)) == kFlagRefract)
+        refract<FWD, M, false, true>(s, NoPoly{}, r, v);            // a refracting plane (rare: it keeps both weight updates)
+    return mask;
 }
 
 // Ray.propagate_to, basics.py:256-264

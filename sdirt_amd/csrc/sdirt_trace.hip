@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <type_traits>
 #include <vector>
@@ -17,6 +18,21 @@
 #include "sdirt_trace.hpp"
 
 using namespace sdirt;
+
+// The largest fp32 X with sqrtf(X) <= r: a plane's aperture test sqrt(x^2 + y^2) <= r (surfaces.py:421) as
+// x^2 + y^2 <= X, exactly, because the correctly rounded root is monotone.  X is NOT fl(r * r) in general (r = 5:
+// one float above 25); it is found by stepping from there with the host's correctly rounded sqrtf.
+static float plane_r2_max(float r)
+{
+    if (!(r >= 0.0f)) return r != r ? r : -1.0f;                 // NaN stays NaN; nothing passes a negative radius
+    if (std::isinf(r)) return r;
+    float x = r * r;
+    if (std::isinf(x)) x = std::numeric_limits<float>::max();
+    while (x > 0.0f && std::sqrt(x) > r) x = std::nextafter(x, 0.0f);
+    for (float up = std::nextafter(x, INFINITY); !std::isinf(up) && std::sqrt(up) <= r; up = std::nextafter(x, INFINITY))
+        x = up;
+    return x;
+}
 
 // Per-surface constant block; every double->float rounding happens here, at the
 // same place the reference's torch scalar handling performs it.
@@ -38,7 +54,8 @@ static DevSurface make_dev_surface(const sdirt_surface_desc& in)
         h.d_plus_R_b = h.d_plus_R;
         h.lim_tight = in.k > -1.0f ? std::min(h.r2_lim, h.lim_loose) : h.r2_lim;
     } else {
-        h.lim_tight = (float)in.r;                    // planes: the aperture radius itself
+        h.lim_tight = (float)in.r;                    // planes: the aperture radius itself ...
+        h.r2_lim = plane_r2_max(h.lim_tight);         // ... and the largest x^2 + y^2 whose root passes it
     }
     const double eta_f = in.n1 / in.n2, eta_b = in.n2 / in.n1;
     h.eta_f = (float)eta_f;  h.eta2_f = (float)(eta_f * eta_f);

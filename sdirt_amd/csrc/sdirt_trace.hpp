@@ -44,7 +44,9 @@ __device__ __forceinline__ void lds_or_first_lane(uint32_t* p, uint32_t m)
 // per-wave convergence masks are OR-ed into lds_mask[k] by the first active lane.
 // PREFETCH = false: every surface's constants are loaded and waited for on the spot (the
 // reference form the load-time selftest compares the prefetching loop against).
-template <bool FWD, class M = Ieee, bool PREFETCH = true>
+// UNIT_W: every ray's weight is exactly 0 or 1 (the fused kernels: make_ray's 1, then 0/1 flags only) -- one weight
+// update per visit (refract()).
+template <bool FWD, class M = Ieee, bool PREFETCH = true, bool UNIT_W = false>
 __device__ __forceinline__ void trace_ray(const DevSurface* __restrict__ lens, int first, int last,
                                           const void* trip_words, Ray& r, uint32_t* lds_mask)
 {
@@ -60,7 +62,7 @@ __device__ __forceinline__ void trace_ray(const DevSurface* __restrict__ lens, i
         SurfRaw nxt;
         Surf s;
         s.a = cur.a; s.b = cur.b;
-        const uint32_t m = surface_reaction<FWD, M>(s, lens + k, surf_trips(cur, k), r, [&] {
+        const uint32_t m = surface_reaction<FWD, M, UNIT_W>(s, lens + k, surf_trips(cur, k), r, [&] {
             if (PREFETCH) surf_issue<FWD>(nxt, lens + kn, trip_words, kn);
         });
         if (lds_mask && m != 0u) lds_or_first_lane(&lds_mask[k], m);
