@@ -285,6 +285,19 @@ int sdirt_forward_integral_grad(sdirt_rays rays, int64_t spp, int64_t n_points, 
                                 const float* grad_r /*dev or NULL*/, double* partial /*dev [N,n_slices,5]*/,
                                 int32_t n_slices, void* stream);
 
+/* sdirt_forward_integral_grad with a sixth component, the sensor position s (the focus setting): a ray meets the
+ * sensor plane at o = o' + d (s - o'.z) / d.z, so d(o.xy)/ds = d.xy / d.z, and o enters the splat as the centre does.
+ * partial (dev float64 [N, n_slices, 6], fully overwritten) = (dh, df, dw, dcx, dcy, ds), ds = the sum over the rays of
+ * g_x d.x / d.z + g_y d.y / d.z with g_x, g_y the ray's own terms of dcx, dcy; the slopes are float64 from the fp32 d
+ * (d.y is read as well: 24 bytes per ray).  Components 0 to 4 are sdirt_forward_integral_grad's, bit for bit.  The
+ * centres' own dependence on s (the chief-ray centres: sdirt_chief_center_slope) is the caller's to add:
+ * dLoss/ds = sum_n (ds_n + dcx_n dcx_n/ds + dcy_n dcy_n/ds).  Same arguments, slicing and n_slices otherwise. */
+int sdirt_forward_integral_grad_focus(sdirt_rays rays, int64_t spp, int64_t n_points, double ps, int32_t ks,
+                                      const float* center /*dev [N,2]*/, const sdirt_dp_params* dp /*host*/,
+                                      uint32_t flags /*SDIRT_PSF_STRICT_IEEE or 0*/, const float* grad_l /*dev or NULL*/,
+                                      const float* grad_r /*dev or NULL*/, double* partial /*dev [N,n_slices,6]*/,
+                                      int32_t n_slices, void* stream);
+
 /* Slices of the spp axis sdirt_forward_integral_grad cuts a batch into on a device of n_cus compute units (host
  * arithmetic only); 0 for a bad argument. */
 int32_t sdirt_forward_integral_grad_slices(int64_t n_points, int64_t spp, int32_t n_cus);
@@ -342,6 +355,16 @@ int sdirt_chief_center(const sdirt_lens* lens, const float* point_obj /*dev [N,3
                        float* center /*dev [N,2]*/, int32_t* any_valid /*dev or NULL*/,
                        uint32_t* conv_mask /*dev [K] or NULL*/, void* stream);
 
+/* sdirt_chief_center that ALSO returns how the centre moves with the sensor plane: a ray meets the plane z = d_sensor at
+ * o = o' + d (d_sensor - o'.z) / d.z, so slope (dev float64 [N,2], fully overwritten) =
+ * d(center)/d(d_sensor) = -sum_s(ra d.xy / d.z) / (sum_s ra + 1e-9), d the direction after the last surface; float64
+ * terms from the fp32 rays, summed in a fixed order.  `center` is sdirt_chief_center's, bit for bit. */
+int sdirt_chief_center_slope(const sdirt_lens* lens, const float* point_obj /*dev [N,3]*/,
+                             int64_t n_points, const float* xc /*dev [Sc]*/, const float* yc /*dev [Sc]*/,
+                             int64_t spp_center, double pupil_z, double d_sensor,
+                             const int32_t* trips /*host [K]*/, uint32_t flags /*SDIRT_PSF_STRICT_IEEE or 0*/,
+                             float* center /*dev [N,2]*/, double* slope /*dev [N,2]*/,
+                             int32_t* any_valid /*dev or NULL*/, uint32_t* conv_mask /*dev [K] or NULL*/, void* stream);
 
 
 /* Lensgroup.psf_diff, deeplens/optics.py:934-996, fused from sampling to the

@@ -105,6 +105,8 @@ SIGNATURES = {
     "sdirt_forward_integral_plan": (C.c_int, [_I64, _I64, _I32, _I32, _I32, C.POINTER(_I64)]),
     "sdirt_forward_integral_grad": (C.c_int, [Rays, _I64, _I64, _D, _I32, _P, C.POINTER(DpParams), _U32,
                                               _P, _P, _P, _I32, _P]),
+    "sdirt_forward_integral_grad_focus": (C.c_int, [Rays, _I64, _I64, _D, _I32, _P, C.POINTER(DpParams), _U32,
+                                                    _P, _P, _P, _I32, _P]),
     "sdirt_forward_integral_grad_slices": (_I32, [_I64, _I64, _I32]),
     "sdirt_forward_integral_grad_rays": (C.c_int, [Rays, _I64, _I64, _D, _I32, _P, C.POINTER(DpParams), _U32,
                                                    _P, _P, _P, _I32, _P, _P]),
@@ -115,6 +117,8 @@ SIGNATURES = {
     "sdirt_psf_normalize": (C.c_int, [_P, _I64, _I32, _P]),
     "sdirt_chief_center": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _D, _D, C.POINTER(_I32), _U32,
                                      _P, _P, _P, _P]),
+    "sdirt_chief_center_slope": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _D, _D, C.POINTER(_I32), _U32,
+                                           _P, _P, _P, _P, _P]),
     "sdirt_psf_lr": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _D, _D, _D, _I32, _P,
                                C.POINTER(DpParams), C.POINTER(_I32), _U32, _P, _P, _P, _P]),
     "sdirt_psf_lr_centered": (C.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _P, _P, _I64, _D, _D, _D, _I32,

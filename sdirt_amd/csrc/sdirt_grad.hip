@@ -28,6 +28,7 @@ namespace {
 
 constexpr int kGradThreads = 256;
 constexpr int kGradComps = 5;                       // h, f, w, cx, cy
+constexpr int kFocusComps = 6;                      // ... and the sensor position (k_forward_integral_grad_focus)
 constexpr int kGradLdsBytes = 48 * 1024;            // both grids staged in LDS up to ks 78
 
 // The float64 copies of the parameters the derivatives are evaluated at.
@@ -228,6 +229,94 @@ k_forward_integral_grad(sdirt_rays R, int64_t S, SplatGeom gm, DevDpParams dp, D
     }
 }
 
+// k_forward_integral_grad with a SIXTH component, the sensor position s (the focus setting): the sensor-plane point of a
+// ray is o = o' + d (s - o'.z) / d.z, so d(o.xy)/ds = d.xy / d.z, and o enters the splat as the centre does (the shift is
+// -o - c): component 5 = sum over the rays of g_x d.x / d.z + g_y d.y / d.z, g_x and g_y the ray's own terms of
+// components 3 and 4.  The slopes and the sum are float64, from the forward's fp32 d; the window, the taps and the clamp
+// decisions are the forward's and carry no gradient; x_tan = -d.x / d.z and ra do not depend on s.  24 bytes per ray (d.y
+// as well).  A kernel of its own, the body restated: k_forward_integral_grad keeps its registers and its ISA.  Components
+// 0 to 4 are the same operations in the same order: the same bits.
+template <bool BIG, class M, bool STAGE>
+__global__ void __launch_bounds__(kGradThreads)
+k_forward_integral_grad_focus(sdirt_rays R, int64_t S, SplatGeom gm, DevDpParams dp, DpGrad q, GradLaunch gl_,
+                              const float* __restrict__ center, const float* __restrict__ gl, const float* __restrict__ gr,
+                              double* __restrict__ partial)
+{
+    extern __shared__ __attribute__((aligned(16))) float g_lds[];
+    __shared__ double red[kGradThreads / 64][kFocusComps];
+    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
+    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
+    const int tile = gm.ks * gm.ks;
+    const float* GL = gl ? gl + n * tile : nullptr;
+    const float* GR = gr ? gr + n * tile : nullptr;
+    if (STAGE) {
+        for (int e = threadIdx.x; e < tile; e += kGradThreads) {
+            g_lds[e] = GL ? GL[e] : 0.0f;
+            g_lds[tile + e] = GR ? GR[e] : 0.0f;
+        }
+        __syncthreads();
+    }
+    const float cx = center[2 * n], cy = center[2 * n + 1];
+    const auto div_dy = UDiv<M>::make(gm.dy_rng), div_dx = UDiv<M>::make(gm.dx_rng);
+    const auto div_fmh = UDiv<M>::make(dp.fmh);
+    double acc[kFocusComps] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
+    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
+        const int64_t i = n * S + s;
+        const float ox = R.ox[i], oy = R.oy[i], dx = R.dx[i], dy = R.dy[i], dz = R.dz[i], ra = R.ra[i];
+        GradTaps tp;
+        if (!grad_taps(gm, div_dy, div_dx, ox, oy, cx, cy, ra, tp)) continue;
+        const float x_tan = (-dx) / dz;                   // monte_carlo.py:48
+        float sl, sr;
+        if (BIG) dp_weights_big(dp, x_tan, sl, sr);
+        else dp_weights_small<M>(dp, div_fmh, x_tan, sl, sr);
+        // upstream gradients at the four taps
+        double lt, lr_, lb, lbr, rt = 0.0, rr_ = 0.0, rb = 0.0, rbr = 0.0;
+        if (STAGE) {
+            lt = g_lds[tp.i_tl]; lr_ = g_lds[tp.i_tr]; lb = g_lds[tp.i_bl]; lbr = g_lds[tp.i_br];
+            rt = g_lds[tile + tp.i_tl]; rr_ = g_lds[tile + tp.i_tr]; rb = g_lds[tile + tp.i_bl];
+            rbr = g_lds[tile + tp.i_br];
+        } else {
+            lt = GL ? GL[tp.i_tl] : 0.0f; lr_ = GL ? GL[tp.i_tr] : 0.0f;
+            lb = GL ? GL[tp.i_bl] : 0.0f; lbr = GL ? GL[tp.i_br] : 0.0f;
+            if (GR) { rt = GR[tp.i_tl]; rr_ = GR[tp.i_tr]; rb = GR[tp.i_bl]; rbr = GR[tp.i_br]; }
+        }
+        const double wb = tp.wb, wr = tp.wr, w = tp.w;
+        // g . bilinear weights, and its derivatives by the column (wr) and row (wb) fractions
+        const double bl = (1.0 - wb) * ((1.0 - wr) * lt + wr * lr_) + wb * ((1.0 - wr) * lb + wr * lbr);
+        const double br = (1.0 - wb) * ((1.0 - wr) * rt + wr * rr_) + wb * ((1.0 - wr) * rb + wr * rbr);
+        const double bl_wr = (1.0 - wb) * (lr_ - lt) + wb * (lbr - lb), bl_wb = (1.0 - wr) * (lb - lt) + wr * (lbr - lr_);
+        const double br_wr = (1.0 - wb) * (rr_ - rt) + wb * (rbr - rb), br_wb = (1.0 - wr) * (rb - rt) + wr * (rbr - rr_);
+        double dZ[3][3];
+        dz_boundaries<BIG, M>(dp, div_fmh, q, x_tan, dZ);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double dsr = dZ[1][c] - dZ[0][c], dsl = dZ[2][c] - dZ[1][c];
+            acc[c] += w * (bl * dsl + br * dsr);
+        }
+        // the centre moves the shifted point (times the weight, :38) and so the bilinear fractions
+        const double cs = w * ((double)sl * bl_wr + (double)sr * br_wr), cr = w * ((double)sl * bl_wb + (double)sr * br_wb);
+        const double g_x = w * gl_.dwr_dcx * cs, g_y = w * gl_.dwb_dcy * cr;
+        acc[3] += g_x;
+        acc[4] += g_y;
+        // the sensor plane moves the ray's point along the ray: d(o.xy)/ds = d.xy / d.z
+        const double z = (double)dz;
+        acc[5] += g_x * ((double)dx / z) + g_y * ((double)dy / z);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < kFocusComps; ++c) {
+        const double v = wave_sum(acc[c]);
+        if (lane == 0) red[wave][c] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kFocusComps) {
+        double v = 0.0;
+        for (int k = 0; k < kGradThreads / 64; ++k) v += red[k][threadIdx.x];
+        partial[(n * gl_.nslices + j) * kFocusComps + threadIdx.x] = v;
+    }
+}
+
 // d/dt of Z_a, t = x_tan, a = +1, 0, -1: dz_boundaries' clamp decisions (the forward's fp32 values) with
 // dx1/dt = -f h / (f - h) and dx2/dt = -h -- what a ray's direction gets through x_tan = -d.x / d.z.
 template <bool BIG, class M, class Div>
@@ -358,7 +447,7 @@ int32_t sdirt_forward_integral_grad_slices(int64_t n_points, int64_t spp, int32_
 
 static int launch_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps, int32_t ks, const float* center,
                                 const sdirt_dp_params* dp, uint32_t flags, const float* grad_l, const float* grad_r,
-                                double* partial, int32_t n_slices, float* ray_grad, void* stream)
+                                double* partial, int32_t n_slices, float* ray_grad, bool focus, void* stream)
 {
     if (int rc = check_rays(rays)) return rc;
     if (int rc = check_ks(ks, SDIRT_MAX_KS_STAGED)) return rc;
@@ -386,7 +475,10 @@ static int launch_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps
     const unsigned grid = (unsigned)(N * gl.nslices);
     with_bool(dpp.big, [&](auto bg) { return with_bool(stage, [&](auto stg) { return with_math(flags, [&](auto m) {
         constexpr bool STG = decltype(stg)::value;
-        if (partial)
+        if (partial && focus)        // [N, n_slices, 6]
+            k_forward_integral_grad_focus<decltype(bg)::value, decltype(m), STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(
+                rays, S, gm, dpp, q, gl, center, grad_l, gr, partial);
+        else if (partial)
             k_forward_integral_grad<decltype(bg)::value, decltype(m), STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(
                 rays, S, gm, dpp, q, gl, center, grad_l, gr, partial);
         if (ray_grad)
@@ -402,7 +494,15 @@ int sdirt_forward_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps
                                 const sdirt_dp_params* dp, uint32_t flags, const float* grad_l, const float* grad_r,
                                 double* partial, int32_t n_slices, void* stream)
 {
-    return launch_integral_grad(rays, S, N, ps, ks, center, dp, flags, grad_l, grad_r, partial, n_slices, nullptr, stream);
+    return launch_integral_grad(rays, S, N, ps, ks, center, dp, flags, grad_l, grad_r, partial, n_slices, nullptr, false, stream);
+}
+
+int sdirt_forward_integral_grad_focus(sdirt_rays rays, int64_t S, int64_t N, double ps, int32_t ks, const float* center,
+                                      const sdirt_dp_params* dp, uint32_t flags, const float* grad_l, const float* grad_r,
+                                      double* partial, int32_t n_slices, void* stream)
+{
+    if (!partial) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null partial");
+    return launch_integral_grad(rays, S, N, ps, ks, center, dp, flags, grad_l, grad_r, partial, n_slices, nullptr, true, stream);
 }
 
 int sdirt_forward_integral_grad_rays(sdirt_rays rays, int64_t S, int64_t N, double ps, int32_t ks, const float* center,
@@ -411,7 +511,7 @@ int sdirt_forward_integral_grad_rays(sdirt_rays rays, int64_t S, int64_t N, doub
                                      void* stream)
 {
     if (!ray_grad) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null ray_grad");      // partial may be NULL: the rays' terms only
-    return launch_integral_grad(rays, S, N, ps, ks, center, dp, flags, grad_l, grad_r, partial, n_slices, ray_grad, stream);
+    return launch_integral_grad(rays, S, N, ps, ks, center, dp, flags, grad_l, grad_r, partial, n_slices, ray_grad, false, stream);
 }
 
 }  // extern "C"

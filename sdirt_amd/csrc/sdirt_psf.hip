@@ -531,6 +531,72 @@ k_chief_center(TripTable trips /* kernarg offset 0 */, const DevSurface* __restr
         atomicOr(&conv_mask[threadIdx.x], lds_mask[threadIdx.x]);
 }
 
+// k_chief_center that also returns how the centre moves with the sensor plane (sdirt_chief_center_slope): the
+// sensor-plane point of a ray is o = o' + d (zs - o'.z) / d.z, so with c = -sum(ra o.xy) / (sum(ra) + 1e-9)
+//   dc/dzs = -sum(ra d.xy / d.z) / (sum(ra) + 1e-9).
+// The same rays and the same centroid sums in the same order (the centre is k_chief_center's, bit for bit); the slope
+// terms are float64 from the fp32 direction after the last surface, summed per lane and then over the workgroup in
+// reduce_centroid's fixed tree order, through the same LDS block once the centroid's totals have been read.  A kernel
+// of its own: k_chief_center keeps its registers and its ISA.  No work-left priorities: the pass runs once per
+// gradient call, beside a staged trace.
+template <class HotMath>
+__global__ void __launch_bounds__(kFused, 8)
+k_chief_center_slope(TripTable trips /* kernarg offset 0 */, const DevSurface* __restrict__ lens, int K,
+                     const float* __restrict__ po, const float* __restrict__ xc,
+                     const float* __restrict__ yc, int Sc, float pz, float zs,
+                     float* __restrict__ center, double* __restrict__ slope, int32_t* __restrict__ any_valid,
+                     uint32_t* __restrict__ conv_mask)
+{
+    __shared__ uint32_t lds_mask[SDIRT_MAX_SURFACES];
+    __shared__ double red[3][kFused];
+    __shared__ int red_any;
+    const int n = blockIdx.x;
+    if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
+    if (threadIdx.x == 0) red_any = 0;
+    __syncthreads();
+    const float px = in_vgpr(po[3 * n]), py = in_vgpr(po[3 * n + 1]), pzo = in_vgpr(po[3 * n + 2]);
+    const float pzv = in_vgpr(pz), zsv = in_vgpr(zs);
+    GlobalF xcp = in_vgpr((GlobalF)xc + threadIdx.x);
+    GlobalF ycp = in_vgpr((GlobalF)yc + threadIdx.x);
+    const int sc_end = in_vgpr(Sc);
+    double sx = 0.0, sy = 0.0, sr = 0.0, tx = 0.0, ty = 0.0;
+    int any = 0;
+    for (int s = threadIdx.x; s < sc_end; s += kFused, xcp += kFused, ycp += kFused) {
+        Ray r = make_ray<HotMath>(px, py, pzo, *xcp, *ycp, pzv);
+        trace_ray<true, HotMath, true, true>(lens, 0, K, kernarg_at(0), r, lds_mask);
+        propagate_to<HotMath>(r, zsv);
+        sx += (double)(r.ox * r.ra);
+        sy += (double)(r.oy * r.ra);
+        sr += (double)r.ra;
+        any |= (r.ra == 1.0f);
+        if (r.ra != 0.0f) {                       // a dead ray's direction is whatever the trace left
+            const double z = (double)r.dz;
+            tx += (double)r.ra * ((double)r.dx / z);
+            ty += (double)r.ra * ((double)r.dy / z);
+        }
+    }
+    red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy; red[2][threadIdx.x] = sr;
+    if (any) red_any = 1;
+    reduce_centroid<kFused>(&red[0][0]);
+    const double sum_ra = red[2][0];
+    if (threadIdx.x == 0) {
+        const float den = (float)red[2][0] + (float)1e-9;
+        center[2 * n] = -((float)red[0][0] / den);
+        center[2 * n + 1] = -((float)red[1][0] / den);
+        if (any_valid && red_any) atomicOr(any_valid, 1);
+    }
+    __syncthreads();                              // everyone has read the centroid's totals: the block is free again
+    red[0][threadIdx.x] = tx; red[1][threadIdx.x] = ty; red[2][threadIdx.x] = 0.0;
+    reduce_centroid<kFused>(&red[0][0]);
+    if (threadIdx.x == 0) {
+        const double den = sum_ra + 1e-9;
+        slope[2 * n] = -(red[0][0] / den);
+        slope[2 * n + 1] = -(red[1][0] / den);
+    }
+    if (conv_mask && (int)threadIdx.x < K && lds_mask[threadIdx.x])
+        atomicOr(&conv_mask[threadIdx.x], lds_mask[threadIdx.x]);
+}
+
 // ---------------------------------------------------------------------------
 // speculate -> verify ON THE DEVICE -> re-render once (sdirt_psf_lr_verified)
 // ---------------------------------------------------------------------------
@@ -1491,6 +1557,26 @@ int sdirt_chief_center(const sdirt_lens* lens, const float* point_obj, int64_t N
     L.flags = flags; L.st = as_stream(stream);
     L.ca.center_out = center; L.ca.any_valid = any_valid; L.ca.conv_mask_c = conv_mask;
     return launch_chief_center(L);
+}
+
+int sdirt_chief_center_slope(const sdirt_lens* lens, const float* point_obj, int64_t N, const float* xc,
+                             const float* yc, int64_t Sc, double pupil_z, double d_sensor,
+                             const int32_t* trips, uint32_t flags, float* center, double* slope, int32_t* any_valid,
+                             uint32_t* conv_mask, void* stream)
+{
+    if (!slope) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null slope");
+    PsfLaunch L;
+    if (int rc = check_psf_args(L, false, nullptr, 0, lens, point_obj, N, nullptr, nullptr, 0, xc, yc, Sc, pupil_z,
+                                d_sensor, 0, nullptr, nullptr, trips, center, nullptr))
+        return rc;
+    if (N == 0) return SDIRT_OK;
+    with_math(flags, [&](auto m) {
+        k_chief_center_slope<decltype(m)><<<(int)N, kFused, 0, as_stream(stream)>>>(
+            L.ttc.t[0], L.ca.lens_c, L.K, L.po, L.ca.xc, L.ca.yc, L.ca.Sc, L.pz, L.zs, center, slope, any_valid, conv_mask);
+        return 0;
+    });
+    LAUNCH_CHECK();
+    return SDIRT_OK;
 }
 
 int sdirt_psf_lr(const sdirt_lens* lens, const float* point_obj, int64_t N, const float* x2,

@@ -31,10 +31,16 @@ class SplatFunction(torch.autograd.Function):
     centres [N, 2] (pointc_ref).  The rays, r and the precision are constants, as in the reference (its rays are
     sampled under no_grad, r is re-wrapped by torch.tensor(r) at monte_carlo.py:167, :274).  The backward is one
     kernel, sdirt_forward_integral_grad, on the same rays, centres and parameters: the forward's window, taps and
-    clamp decisions, float64 sums, no atomics."""
+    clamp decisions, float64 sums, no atomics.
+
+    d_sensor (a 0-d tensor, or None): the sensor position the rays were propagated to.  When it requires a gradient the
+    backward is sdirt_forward_integral_grad_focus instead -- the same five sums and a sixth, the rays' own share
+    sum(g_x d.x / d.z + g_y d.y / d.z) -- and center_slope ([N, 2] float64 d(centre)/d(d_sensor) of the chief-ray
+    centres, sdirt_chief_center_slope; None for centres that do not move with the sensor) adds the centres' share:
+    dLoss/ds = sum_n (ds_n + dcx_n slope_n,x + dcy_n slope_n,y).  The value of d_sensor is not used here."""
 
     @staticmethod
-    def forward(ctx, h, f, w, center, ray, ps, ks, r, have_dp, precision):
+    def forward(ctx, h, f, w, center, ray, ps, ks, r, have_dp, precision, d_sensor=None, center_slope=None):
         S, N = ray.shape
         dev = ray.device
         center = center.detach().to(dev, torch.float32).reshape(N, 2).contiguous()
@@ -45,7 +51,8 @@ class SplatFunction(torch.autograd.Function):
             ray.c_rays(), S, N, float(ps), int(ks), dptr(center), C.byref(dp) if dp is not None else None,
             _flags(precision), dptr(lg), dptr(rg), stream_ptr(dev)))
         ctx.ray, ctx.dp, ctx.geom, ctx.precision = ray, dp, (S, N, float(ps), int(ks)), precision
-        ctx.meta = [(v.dtype, v.device) if torch.is_tensor(v) else None for v in (h, f, w)]
+        ctx.meta = [(v.dtype, v.device) if torch.is_tensor(v) else None for v in (h, f, w, d_sensor)]
+        ctx.center_slope = center_slope
         ctx.save_for_backward(center)
         return lg, rg
 
@@ -56,19 +63,27 @@ class SplatFunction(torch.autograd.Function):
         dev = center.device
         ncu = int(torch.cuda.get_device_properties(dev).multi_processor_count)
         ns = int(_lib.lib().sdirt_forward_integral_grad_slices(N, S, ncu))
-        partial = torch.empty((N, ns, 5), dtype=torch.float64, device=dev)
+        focus = ctx.needs_input_grad[10]
+        partial = torch.empty((N, ns, 6 if focus else 5), dtype=torch.float64, device=dev)
         gl = gl.to(torch.float32).contiguous() if gl is not None else None
         gr = gr.to(torch.float32).contiguous() if gr is not None else None
         dp = ctx.dp
-        _lib.check(_lib.lib().sdirt_forward_integral_grad(
+        entry = _lib.lib().sdirt_forward_integral_grad_focus if focus else _lib.lib().sdirt_forward_integral_grad
+        _lib.check(entry(
             ctx.ray.c_rays(), S, N, ps, ks, dptr(center), C.byref(dp) if dp is not None else None,
             _flags(ctx.precision), dptr(gl), dptr(gr), dptr(partial), ns, stream_ptr(dev)))
-        tot = partial.sum(1)                                   # [N, 5] float64: the slices in a fixed order
+        tot = partial.sum(1)                                   # [N, 5 or 6] float64: the slices in a fixed order
         theta = tot[:, :3].sum(0)
         grads = [theta[i].to(device=ctx.meta[i][1], dtype=ctx.meta[i][0]) if ctx.needs_input_grad[i] else None
                  for i in range(3)]
-        gc = tot[:, 3:].to(torch.float32) if ctx.needs_input_grad[3] else None
-        return (*grads, gc, None, None, None, None, None, None)
+        gc = tot[:, 3:5].to(torch.float32) if ctx.needs_input_grad[3] else None
+        gs = None
+        if focus:
+            per_point = tot[:, 5]
+            if ctx.center_slope is not None:                   # the chief-ray centres move with the sensor
+                per_point = per_point + (tot[:, 3:5] * ctx.center_slope.to(dev, torch.float64)).sum(1)
+            gs = per_point.sum(0).to(device=ctx.meta[3][1], dtype=ctx.meta[3][0])
+        return (*grads, gc, None, None, None, None, None, None, gs, None)
 
 
 def _as_scalar(v):
@@ -77,13 +92,17 @@ def _as_scalar(v):
     return v.reshape(()) if torch.is_tensor(v) and v.requires_grad else float(v)
 
 
-def splat_autograd(ray, ps, ks, center, param_list, precision="lean"):
+def splat_autograd(ray, ps, ks, center, param_list, precision="lean", d_sensor=None, center_slope=None):
     """RAW (l_grid, r_grid) through SplatFunction: param_list = (h, f, w, r, direct) or None (the reference's
-    defaults, R all zero); r and direct get no gradient.  The grids are NOT swapped for direct != 'l'."""
+    defaults, R all zero); r and direct get no gradient.  The grids are NOT swapped for direct != 'l'.
+    d_sensor / center_slope: the sensor position as a 0-d tensor that requires a gradient and the slope of the
+    chief-ray centres in it (SplatFunction); None: the sensor position is a constant."""
     have_dp = param_list is not None
     h, f, w, r = (param_list[:4] if have_dp else (0.78, 1.44, 0.3, 0.5))
     h, f, w = (_as_scalar(v) for v in (h, f, w))
-    return SplatFunction.apply(h, f, w, center, ray, ps, ks, float(r), have_dp, precision)
+    if d_sensor is not None:
+        d_sensor = d_sensor.reshape(())
+    return SplatFunction.apply(h, f, w, center, ray, ps, ks, float(r), have_dp, precision, d_sensor, center_slope)
 
 
 def _flags(precision):

@@ -116,10 +116,11 @@ def _parse_param_list(param_list):
     return (h, f, w, r), direct != "l"
 
 
-def _psf_needs_grad(dp, points, center):
+def _psf_needs_grad(dp, points, center, d_sensor=None):
     """Whether a psf call records gradients: grad mode is on and h, f or w of dp -- or, with center=False (the
-    pinhole centres, optics.py:973-976), the points -- require one.  r never gets a gradient (monte_carlo.py:167)."""
-    vals = list(dp[:3]) if dp is not None else []
+    pinhole centres, optics.py:973-976), the points, or the call's own sensor position d_sensor -- require one.
+    r never gets a gradient (monte_carlo.py:167)."""
+    vals = (list(dp[:3]) if dp is not None else []) + [d_sensor]
     if not center:
         vals.append(points)
     return _requires_grad(*vals)
@@ -328,6 +329,24 @@ class Lensgroup:
             self._dev, self._pupil_cache, self.trips = saved[:3]
             if saved[3] is not None:
                 self.__dict__["_curved_cache"] = saved[3]
+
+    @contextlib.contextmanager
+    def _sensor_borrowed(self, d_sensor):
+        """The lens with its sensor at `d_sensor` (a number or a one-element tensor; None: as it is) for the duration of
+        one call: afterwards, also on an exception, lens.d_sensor is the old object.  Every path reads self.d_sensor
+        when it launches (the fused kernels, _psf_rgb_fused, the staged chain, TraceRecord), and nothing cached on
+        the lens depends on it: the pupils are traced from the stop, the trip tables are verified per call, and the
+        object-space points use hfov and r_last, which stay constants of the lens state."""
+        if d_sensor is None:
+            yield
+            return
+        value = float(d_sensor.detach()) if torch.is_tensor(d_sensor) else float(d_sensor)
+        old = self.d_sensor
+        try:
+            self.d_sensor = value
+            yield
+        finally:
+            self.d_sensor = old
 
     def find_aperture(self):
         """optics.py:193-201: first surface with air-like media on both sides."""
@@ -839,12 +858,20 @@ class Lensgroup:
         self._chief_center(po, xc, yc, pupilz, center)
         return center
 
-    def _chief_center(self, po, xc, yc, pupilz, center):
+    def _chief_center(self, po, xc, yc, pupilz, center, slope=None):
+        """The chief-ray centres of `po` into `center`; slope (float64 [N, 2]): d(centre)/d(d_sensor) as well
+        (sdirt_chief_center_slope: the same centres, bit for bit)."""
         anyv = torch.zeros(1, dtype=torch.int32, device=self.device)
         handle = self.dev_lens(DEFAULT_WAVE)                      # optics.py:900: always green
 
         def enqueue(trips, mask_ptr):
             with self._timed("chief_center"):
+                if slope is not None:
+                    _lib.check(_lib.lib().sdirt_chief_center_slope(
+                        handle, dptr(po), po.shape[0], dptr(xc), dptr(yc), xc.shape[0], float(pupilz),
+                        float(self.d_sensor), trips, self._math_flags(), dptr(center), dptr(slope), dptr(anyv),
+                        mask_ptr, stream_ptr(self.device)))
+                    return
                 _lib.check(_lib.lib().sdirt_chief_center(
                     handle, dptr(po), po.shape[0], dptr(xc), dptr(yc), xc.shape[0], float(pupilz),
                     float(self.d_sensor), trips, self._math_flags(), dptr(center), dptr(anyv),
@@ -859,12 +886,14 @@ class Lensgroup:
         return self.psf_diff(points=points, wvln=wvln, ks=ks, spp=spp, center=center)
 
     def psf_diff(self, points, wvln=DEFAULT_WAVE, ks=31, spp=GEO_SPP, center=True,
-                 param_list=None, _defer=False, surface_params=None):
+                 param_list=None, _defer=False, surface_params=None, d_sensor=None):
         """optics.py:934-996: normalised points [N,3] (or [3]) -> max-normalised
-        PSF [N,ks,ks] (or [ks,ks]) of the left sub-pixel (right if param_list[4] != 'l')."""
+        PSF [N,ks,ks] (or [ks,ks]) of the left sub-pixel (right if param_list[4] != 'l').
+        d_sensor: the sensor position of this call (psf_lr)."""
         dp, right = _parse_param_list(param_list)
         res = self.psf_lr(points, ks=ks, wvln=wvln, spp=spp, center=center, dp=dp, want_r=right,
-                          _default_r_zero=(param_list is None), defer=_defer, surface_params=surface_params)
+                          _default_r_zero=(param_list is None), defer=_defer, surface_params=surface_params,
+                          d_sensor=d_sensor)
         pick = (lambda lr: lr[1]) if right else (lambda lr: lr[0])
         if _defer:
             return PendingPSF(lambda: pick(res.wait()))
@@ -940,7 +969,8 @@ class Lensgroup:
 
     def psf_lr(self, points, ks=31, wvln=DEFAULT_WAVE, spp=GEO_SPP, center=True,
                dp=(0.78, 1.44, 0.3, 0.5), normalize=True, want_r=True, _default_r_zero=False,
-               pupil_xy=None, center_pupil_xy=None, out=None, defer=False, center_out=None, surface_params=None):
+               pupil_xy=None, center_pupil_xy=None, out=None, defer=False, center_out=None, surface_params=None,
+               d_sensor=None, _focus=None):
         """Left AND right dual-pixel PSFs of one ray-traced batch: (L, R), each
         [N,ks,ks] (or [ks,ks] for a single point), max-normalised separately as
         optics.py:983-987 would normalise each of them.  dp = (h, f, w, r) of
@@ -977,17 +1007,40 @@ class Lensgroup:
         the PSFs are those of the lens set_surface_parameters(theta.detach()) would make -- the records are put back
         afterwards -- and loss.backward() fills theta.grad with the gradient the reference's graph gives d, c, k and
         ai of every surface (trace_grad.SurfaceGradFunction); h, f, w and the points get theirs in the
-        same call.  Otherwise the call is set_surface_parameters(theta) followed by the ordinary call."""
+        same call.  Otherwise the call is set_surface_parameters(theta) followed by the ordinary call.
+
+        d_sensor: the sensor position (the focus setting) of THIS call, a number or a one-element tensor; None: the
+        lens's.  The call renders with it on every path and leaves lens.d_sensor as it was, also when it raises.  A
+        0-d tensor that requires a gradient (in grad mode) makes it a grad call, and loss.backward() fills its .grad:
+        a ray meets the sensor plane at o' + d (s - o'.z) / d.z, so the splat shifts by d.xy / d.z per unit of s, and
+        with center=True the chief-ray centre moves with the sensor as well, which is part of the derivative (the
+        reference keeps that centre out of its graph).  The points' z are positions in the lens frame
+        and do not move with the sensor; hfov, r_last and the pinhole scale stay constants."""
+        if d_sensor is not None:
+            focus = d_sensor if _requires_grad(d_sensor) else None
+            if focus is not None and focus.numel() != 1:
+                raise ValueError("d_sensor must be a 0-d (one-element) tensor to get a gradient")
+            with self._sensor_borrowed(d_sensor):
+                res = self.psf_lr(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
+                                  center_pupil_xy, out, defer, center_out, surface_params, None, focus)
+            if isinstance(res, PendingPSF):
+                # the trip check of a deferred call may launch again: with this call's sensor position
+                def finish(pending=res):
+                    with self._sensor_borrowed(d_sensor):
+                        return pending.wait()
+                return PendingPSF(finish)
+            return res
+        focus_kw = {} if _focus is None else {"focus": _focus}
         if surface_params is not None:
             args = (points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy, center_pupil_xy,
                     out, defer, center_out)
             if _requires_grad(surface_params):
                 with self._surfaces_borrowed(surface_params):
-                    return self._psf_lr_grad(*args, surface_params=surface_params)
+                    return self._psf_lr_grad(*args, surface_params=surface_params, **focus_kw)
             self.set_surface_parameters(surface_params)
-        if _psf_needs_grad(dp if not _default_r_zero else None, points, center):
+        if _psf_needs_grad(dp if not _default_r_zero else None, points, center, _focus):
             return self._psf_lr_grad(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero,
-                                     pupil_xy, center_pupil_xy, out, defer, center_out)
+                                     pupil_xy, center_pupil_xy, out, defer, center_out, **focus_kw)
         return self._psf_lr(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
                             center_pupil_xy, out, defer, center_out)
 
@@ -1269,10 +1322,12 @@ class Lensgroup:
                                                 dptr(L), dptr(R), st))
         return _epilogue(L, R, want_r, single_point)
 
-    def _staged_rays(self, points, po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen, record=False):
+    def _staged_rays(self, points, po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen, record=False,
+                     cen_slope=None):
         """The first stages of the staged chain: sample_from_points, psf_center (or the pinhole centres of
         center=False) into `cen`, trace2sensor.  -> (the [spp, N] sensor-plane rays, spp); record=True: the trace
-        keeps its checkpoints, -> (rays, spp, trace_grad.TraceRecord)."""
+        keeps its checkpoints, -> (rays, spp, trace_grad.TraceRecord).  cen_slope (float64 [N, 2], center=True):
+        the chief-ray pass also writes d(centre)/d(d_sensor) there."""
         pupilz, pupilr = self.entrance_pupil()
         # optics.py:963 (first two draws)
         x2, y2 = self._pupil_samples(spp, pupilr) if pupil_xy is None else map(self._on_device, pupil_xy)
@@ -1286,7 +1341,7 @@ class Lensgroup:
             # optics.py:969 (draws three and four)
             xc, yc = (self._pupil_samples(GEO_SPP, pupilr_c) if center_pupil_xy is None
                       else map(self._on_device, center_pupil_xy))
-            self._chief_center(po, xc, yc, pupilz_c, cen)
+            self._chief_center(po, xc, yc, pupilz_c, cen, cen_slope)
         else:
             self._pinhole_centres(points, cen)
         self.last_pupil_points = (x2, y2, xc, yc)
@@ -1319,11 +1374,13 @@ class Lensgroup:
         return TraceRecord(dev_lens, trips, self.precision, self.d_sensor, ws, ray, K)
 
     def _psf_lr_grad(self, points, ks, wvln, spp, center, dp, normalize, want_r, default_r_zero, pupil_xy,
-                     center_pupil_xy, out, defer, center_out, surface_params=None):
+                     center_pupil_xy, out, defer, center_out, surface_params=None, focus=None):
         """psf_lr under autograd: the staged chain's rays and centres (no gradient: optics.py:459, :888 are no_grad),
         then the RAW grids through monte_carlo.SplatFunction -- differentiable in h, f, w and, with center=False, in
         the pinhole centres points[:, :2] * sensor_size / 2 (optics.py:973-976) -- and the max-normalisation of
-        optics.py:983-987 as torch ops, so that its gradient goes to the arg-max pixel as in the reference."""
+        optics.py:983-987 as torch ops, so that its gradient goes to the arg-max pixel as in the reference.
+        focus: the call's sensor position as a 0-d tensor that requires a gradient (the lens is already set to its
+        value): the chief-ray pass also returns the centres' slope in it, and SplatFunction takes both."""
         if defer or out is not None or center_out is not None:
             raise ValueError("defer=True, out= and center_out= are not supported when psf_lr records gradients")
         self._require_gpu()
@@ -1338,15 +1395,17 @@ class Lensgroup:
         with torch.no_grad():
             po = self._points_to_object(points.detach())
             cen = torch.empty((N, 2), dtype=torch.float32, device=self.device)
+            cen_slope = (torch.empty((N, 2), dtype=torch.float64, device=self.device)
+                         if focus is not None and center else None)
             staged = self._staged_rays(points.detach(), po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen,
-                                       record=surface_params is not None)
+                                       record=surface_params is not None, cen_slope=cen_slope)
             ray, spp = staged[:2]
         if not center:
             # the pinhole centres of _pinhole_centres as torch ops on the caller's points: the same fp32 products
             pts = points.to(self.device, torch.float32)
             cen = torch.stack((pts[:, 0] * (self.sensor_size[1] / 2), pts[:, 1] * (self.sensor_size[0] / 2)), -1)
         param_list = None if (dp is None or default_r_zero) else (*dp[:4], "l")
-        L, R = splat_autograd(ray, self.pixel_size, ks, cen, param_list, self.precision)
+        L, R = splat_autograd(ray, self.pixel_size, ks, cen, param_list, self.precision, focus, cen_slope)
         if surface_params is not None:
             # the rays' share of the graph: dLoss/d(raw grids) -> the sensor-plane rays -> the recorded trace -> theta
             dpp = None if param_list is None else _lib.DpParams(*[float(v) for v in param_list[:4]])
@@ -1361,7 +1420,7 @@ class Lensgroup:
         return _epilogue(L, R, want_r, single_point)
 
     def psf_volume(self, grid=(32, 32), z=16, ks=21, spp=GEO_SPP, dp=(0.78, 1.44, 0.3, 0.5), wvln=DEFAULT_WAVE,
-                   surface_params=None, pupil_xy=None, center_pupil_xy=None):
+                   surface_params=None, pupil_xy=None, center_pupil_xy=None, d_sensor=None):
         """The ray-traced PSF grid of the whole field and depth range as a render_psf.PSFVolume, for
         local_dp_psf_render_volume / PSFNet.render_volume: grid = (rows, columns) of cell-centred sensor nodes
         (psfnet.py:220-226: x from -1 + 1/(2 gx) to 1 - 1/(2 gx), y from 1 - 1/(2 gy) down), z = a number of depth
@@ -1370,7 +1429,7 @@ class Lensgroup:
         Lensgroup, psfnet.py:15-16).
 
         ONE psf_lr call on the Dz*Gy*Gx points, so it is differentiable exactly where psf_lr is (h, f, w of dp,
-        surface_params); L and R are stacked and each divided by its own sum with torch ops, which keeps the graph."""
+        surface_params, the call's sensor position d_sensor); L and R are stacked and each divided by its own sum with torch ops, which keeps the graph."""
         from .render_psf import PSFVolume
         gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
         z_nodes = (z.detach().to(torch.float32).reshape(-1).cpu() if torch.is_tensor(z)
@@ -1379,7 +1438,7 @@ class Lensgroup:
         vol = PSFVolume(None, torch.linspace(-1 + 1 / (2 * gx), 1 - 1 / (2 * gx), gx),
                         torch.linspace(1 - 1 / (2 * gy), -1 + 1 / (2 * gy), gy), z_nodes, d_min, d_max)
         L, R = self.psf_lr(vol.points(), ks=ks, wvln=wvln, spp=spp, dp=dp, pupil_xy=pupil_xy,
-                           center_pupil_xy=center_pupil_xy, surface_params=surface_params)
+                           center_pupil_xy=center_pupil_xy, surface_params=surface_params, d_sensor=d_sensor)
         psf = torch.stack((L, R), -3)                                              # [N, 2, ks, ks]
         psf = psf / psf.sum((-1, -2), keepdim=True).clamp_min(1e-30)               # (a node no ray reaches stays 0)
         vol.psf = psf.reshape(len(z_nodes), gy, gx, 2, ks, ks)
@@ -1388,25 +1447,31 @@ class Lensgroup:
         return vol
 
     def psf_rgb(self, points, ks=31, spp=GEO_SPP, center=True, param_list=None, pupil_xy=None,
-                center_pupil_xy=None, surface_params=None):
+                center_pupil_xy=None, surface_params=None, d_sensor=None):
         """optics.py:999-1015: [N,3,ks,ks] (or [3,ks,ks]) -- the three wavelengths of WAVE_RGB, each an
         independent psf_diff (fresh pupil draws, in the reference's order; every chief-ray centre
         through the green lens).  The three calls are ONE kernel launch whatever the number of points
         (center=True: sdirt_psf_rgb_centered; center=False: sdirt_psf_rgb -- lens table, pupil sets, trip
         tables and mask rows indexed by blockIdx.y) and one control-block readback.
         pupil_xy [2, 3, spp] / center_pupil_xy [2, 3, 2048]: explicit pupil sample points per
-        wavelength instead of random draws (ray-level parity hand-off)."""
+        wavelength instead of random draws (ray-level parity hand-off).
+        d_sensor: the sensor position of this call (psf_lr).  When it requires a gradient the three wavelengths are
+        three differentiable psf_lr calls, each centred through the green lens, and its gradient is their sum."""
         if not torch.is_tensor(points):
             points = torch.tensor(points)
         if center_pupil_xy is not None and not center:
             raise ValueError("center=False runs no chief-ray pass")
+        focus_grad = d_sensor is not None and _requires_grad(d_sensor)
+        if d_sensor is not None and not focus_grad:
+            with self._sensor_borrowed(d_sensor):
+                return self.psf_rgb(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy, surface_params)
         n_points = points.shape[0] if points.dim() == 2 else 1
         dp, right = _parse_param_list(param_list)
         surface_grad = surface_params is not None and _requires_grad(surface_params)
         if surface_params is not None and not surface_grad:
             self.set_surface_parameters(surface_params)
         if (n_points > 0 and self.device.type == "cuda" and self.mask_reduce is None and ks <= _lib.MAX_KS
-                and not surface_grad and not _psf_needs_grad(dp, points, center)):
+                and not surface_grad and not focus_grad and not _psf_needs_grad(dp, points, center)):
             return self._psf_rgb_fused(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy)
         # not one launch (grids above SDIRT_MAX_KS, a rank of a sharded run, or a call that records gradients: one
         # differentiable psf_diff per wavelength, stacked, as optics.py:1010-1014 does): wavelength by wavelength
@@ -1417,7 +1482,8 @@ class Lensgroup:
                              _default_r_zero=(param_list is None),
                              pupil_xy=None if pupil_xy is None else (pupil_xy[0][i], pupil_xy[1][i]),
                              center_pupil_xy=None if center_pupil_xy is None else (center_pupil_xy[0][i], center_pupil_xy[1][i]),
-                             surface_params=surface_params if surface_grad else None)
+                             surface_params=surface_params if surface_grad else None,
+                             d_sensor=d_sensor if focus_grad else None)
             psfs.append(lr[1] if right else lr[0])
         return torch.stack(psfs, dim=-3)
 

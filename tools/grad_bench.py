@@ -6,8 +6,10 @@ samples, ks 21).  Synthetic sensor-plane rays (spread over the PSF window, |x_ta
 upstream gradients; the DP parameters are the reference's defaults with r = 0.5 (small-r model) unless --big.
 Counted bytes: the five ray arrays the kernel reads (o.x, o.y, d.x, d.z, ra: 20 B per ray), the two upstream grids
 (8 B per pixel, once per workgroup that stages them) and the float64 partials it stores.
+--focus: the six-component entry instead (sdirt_forward_integral_grad_focus: the sensor position as well; it reads d.y
+too, 24 B per ray, and stores six partials), on the same rays with d.y spread like d.x.
 
-Usage:  python tools/grad_bench.py [--iters 50] [--big] [--ieee]
+Usage:  python tools/grad_bench.py [--iters 50] [--big] [--ieee] [--focus]
 """
 import argparse
 import ctypes as C
@@ -24,7 +26,7 @@ from sdirt_amd.basics import Ray, dptr, stream_ptr  # noqa: E402
 PS = 0.005
 
 
-def bench(N, S, ks, iters, r, flags):
+def bench(N, S, ks, iters, r, flags, focus=False):
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     ray = Ray.empty((S, N), device=dev)
@@ -34,7 +36,7 @@ def bench(N, S, ks, iters, r, flags):
     ray.soa[1, :M] = (torch.rand(M, device=dev, generator=g) * 2 - 1) * half
     ray.soa[2, :M] = 0.0
     ray.soa[3, :M] = (torch.rand(M, device=dev, generator=g) * 2 - 1) * 0.3
-    ray.soa[4, :M] = 0.0
+    ray.soa[4, :M] = (torch.rand(M, device=dev, generator=g) * 2 - 1) * 0.3 if focus else 0.0
     ray.soa[5, :M] = 1.0
     ray.soa[6, :M] = 1.0
     center = torch.zeros((N, 2), dtype=torch.float32, device=dev)
@@ -43,12 +45,14 @@ def bench(N, S, ks, iters, r, flags):
     ncu = torch.cuda.get_device_properties(dev).multi_processor_count
     h = _lib.lib()
     ns = int(h.sdirt_forward_integral_grad_slices(N, S, ncu))
-    partial = torch.empty((N, ns, 5), dtype=torch.float64, device=dev)
+    comps = 6 if focus else 5
+    partial = torch.empty((N, ns, comps), dtype=torch.float64, device=dev)
     dp = _lib.DpParams(0.78, 1.44, 0.3, r)
+    entry = h.sdirt_forward_integral_grad_focus if focus else h.sdirt_forward_integral_grad
 
     def launch():
-        _lib.check(h.sdirt_forward_integral_grad(ray.c_rays(), S, N, PS, ks, dptr(center), C.byref(dp), flags,
-                                                 dptr(gl), dptr(gr), dptr(partial), ns, stream_ptr(dev)))
+        _lib.check(entry(ray.c_rays(), S, N, PS, ks, dptr(center), C.byref(dp), flags,
+                         dptr(gl), dptr(gr), dptr(partial), ns, stream_ptr(dev)))
     for _ in range(3):
         launch()
     torch.cuda.synchronize()
@@ -61,7 +65,7 @@ def bench(N, S, ks, iters, r, flags):
     torch.cuda.synchronize()
     ms = a.elapsed_time(b) / iters
     assert torch.equal(first, partial), "the backward kernel is not run-to-run identical"
-    nbytes = 20 * M + 8 * ks * ks * N * ns + 8 * 5 * N * ns
+    nbytes = (24 if focus else 20) * M + 8 * ks * ks * N * ns + 8 * comps * N * ns
     return dict(points=N, spp=S, ks=ks, slices=ns, ms=round(ms, 4), gbytes=round(nbytes / 1e9, 4),
                 gb_per_s=round(nbytes / ms / 1e6, 1), frac_of_8tbs=round(nbytes / ms / 1e6 / 8000, 3))
 
@@ -71,12 +75,13 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--big", action="store_true", help="r = 0.65 (big-r model)")
     ap.add_argument("--ieee", action="store_true", help="SDIRT_PSF_STRICT_IEEE")
+    ap.add_argument("--focus", action="store_true", help="the six-component entry sdirt_forward_integral_grad_focus")
     args = ap.parse_args()
     r = 0.65 if args.big else 0.5
     flags = _lib.PSF_STRICT_IEEE if args.ieee else 0
     for N, S, ks in ((4096, 4096, 65), (64, 65536, 21)):
-        res = bench(N, S, ks, args.iters, r, flags)
-        res.update(r=r, precision="ieee" if args.ieee else "lean")
+        res = bench(N, S, ks, args.iters, r, flags, args.focus)
+        res.update(r=r, precision="ieee" if args.ieee else "lean", entry="focus" if args.focus else "grad")
         print(json.dumps(res))
 
 
