@@ -655,6 +655,54 @@ int sdirt_render_psf_volume_grad_scene(const float* img /*dev [B,C,H,W]*/, const
                                        float* grad_img /*dev [B,C,H,W] or NULL*/, float* grad_fz /*dev [B,H,W] or NULL*/,
                                        void* stream);
 
+/* sdirt_render_psf_volume from a CHROMATIC volume [C,Dz,Gy,Gx,2,ks,ks], one PSF volume per image channel, channel-
+ * major: local_dp_psf_render (deeplens/render_psf.py:157-188) channel by channel, channel c with the kernels
+ * interpolated from volume[c] -- the per-wavelength PSFs of psf_rgb (deeplens/optics.py:999-1015) in the render, so
+ * that lateral and axial colour reach the image.
+ *   K[c] = sum over the 8 corners of w * volume[c][corner]      (the weights do not depend on c)
+ *   out_s[b,c,y,x] = sum_{i,j} K[c][s,i,j] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)]
+ * Channel c has the bits of sdirt_render_psf_volume at channels = 1 on img[:, c] and volume[c].  The arguments,
+ * limits and statuses of sdirt_render_psf_volume; in addition the whole volume holds at most 2^31 - 1 floats
+ * (SDIRT_ERR_UNSUPPORTED otherwise).  batch == 0: SDIRT_OK, nothing to write. */
+int sdirt_render_psf_volume_chroma(const float* img /*dev [B,C,H,W]*/, const float* volume /*dev [C,Dz,Gy,Gx,2,ks,ks]*/,
+                                   const int32_t* ix /*dev*/, const float* fx /*dev*/, const int32_t* iy /*dev*/,
+                                   const float* fy /*dev*/, const int32_t* iz /*dev*/, const float* fz /*dev*/,
+                                   int32_t batch, int32_t channels, int32_t height, int32_t width, int32_t ks,
+                                   int32_t depth_nodes, int32_t y_nodes, int32_t x_nodes,
+                                   float* out_l /*dev [B,C,H,W]*/, float* out_r /*dev [B,C,H,W]*/, void* stream);
+
+/* Backward pass of sdirt_render_psf_volume_chroma with respect to the volume (autograd of
+ * deeplens/render_psf.py:157-188 per channel on the kernels of deeplens/optics.py:999-1015's wavelengths):
+ *   grad_volume[c,dz,gy,gx,s,i,j] = sum_{b,y,x} w(b,y,x; node) * grad_s[b,c,y,x] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)]
+ * -- no sum over the channels.  grad_volume[c] has the bits of sdirt_render_psf_volume_grad at channels = 1 on that
+ * channel's slices.  EVERY element is written once (a node no pixel touches: exactly 0), fixed order, no atomics, no
+ * workspace.  batch == 0: SDIRT_OK, and grad_volume is still written, all 0. */
+int sdirt_render_psf_volume_chroma_grad(const float* img /*dev [B,C,H,W]*/, const float* grad_l /*dev [B,C,H,W]*/,
+                                        const float* grad_r /*dev [B,C,H,W]*/, const int32_t* ix /*dev*/,
+                                        const float* fx /*dev*/, const int32_t* iy /*dev*/, const float* fy /*dev*/,
+                                        const int32_t* iz /*dev*/, const float* fz /*dev*/, int32_t batch,
+                                        int32_t channels, int32_t height, int32_t width, int32_t ks,
+                                        int32_t depth_nodes, int32_t y_nodes, int32_t x_nodes,
+                                        float* grad_volume /*dev [C,Dz,Gy,Gx,2,ks,ks]*/, void* stream);
+
+/* Backward pass of sdirt_render_psf_volume_chroma with respect to the scene (autograd of
+ * deeplens/render_psf.py:157-188 per channel on the kernels of deeplens/optics.py:999-1015's wavelengths): the
+ * formulas of sdirt_render_psf_volume_grad_scene with K_s and dK_s/dfz of channel c taken from volume[c],
+ *   grad_fz[b,y,x] = sum_s sum_c grad_s[b,c,y,x] * sum_{i,j} (dK_s[c]/dfz)[i,j] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)].
+ * grad_img[:, c] has the bits of sdirt_render_psf_volume_grad_scene at channels = 1 on that channel's slices; grad_fz
+ * is the sum over the channels, exactly 0 where the two depth planes are the same node.  Either output may be NULL;
+ * both NULL is SDIRT_ERR_INVALID_ARGUMENT.  batch == 0: SDIRT_OK, nothing to write. */
+int sdirt_render_psf_volume_chroma_grad_scene(const float* img /*dev [B,C,H,W]*/,
+                                              const float* volume /*dev [C,Dz,Gy,Gx,2,ks,ks]*/,
+                                              const float* grad_l /*dev [B,C,H,W]*/,
+                                              const float* grad_r /*dev [B,C,H,W]*/, const int32_t* ix /*dev*/,
+                                              const float* fx /*dev*/, const int32_t* iy /*dev*/,
+                                              const float* fy /*dev*/, const int32_t* iz /*dev*/,
+                                              const float* fz /*dev*/, int32_t batch, int32_t channels, int32_t height,
+                                              int32_t width, int32_t ks, int32_t depth_nodes, int32_t y_nodes,
+                                              int32_t x_nodes, float* grad_img /*dev [B,C,H,W] or NULL*/,
+                                              float* grad_fz /*dev [B,H,W] or NULL*/, void* stream);
+
 /* ---- the PSF network itself ------------------------------------------------ */
 
 /* The network is described by its layer widths: widths[0..n_layers] = in, hidden..., out.  The

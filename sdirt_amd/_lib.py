@@ -150,6 +150,9 @@ SIGNATURES = {
     "sdirt_render_psf_volume": (C.c_int, [_P] * 8 + [_I32] * 8 + [_P, _P, _P]),
     "sdirt_render_psf_volume_grad": (C.c_int, [_P] * 9 + [_I32] * 8 + [_P, _P]),
     "sdirt_render_psf_volume_grad_scene": (C.c_int, [_P] * 10 + [_I32] * 8 + [_P, _P, _P]),
+    "sdirt_render_psf_volume_chroma": (C.c_int, [_P] * 8 + [_I32] * 8 + [_P, _P, _P]),
+    "sdirt_render_psf_volume_chroma_grad": (C.c_int, [_P] * 9 + [_I32] * 8 + [_P, _P]),
+    "sdirt_render_psf_volume_chroma_grad_scene": (C.c_int, [_P] * 10 + [_I32] * 8 + [_P, _P, _P]),
     "sdirt_mlp_packed_bytes": (_I64, [C.POINTER(_I32), _I32]),
     "sdirt_mlp_pack": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.POINTER(_I32), _I32, _P, _P]),
     "sdirt_psfnet_mlp": (C.c_int, [_P, C.POINTER(_I32), _I32, _P, _I64, _I32, _P, _P]),

@@ -11,6 +11,12 @@
 // The per-pixel kernels exist in registers only.  fp32 operands and sums, no atomics: every sum is taken by one
 // thread (or one wave's butterfly) in a fixed order.  The tables are operands: an index outside [0, n-2] is clamped,
 // the upper node of a segment is min(i + 1, n - 1), so no table value can make a kernel read outside V.
+//
+// A CHROMATIC volume [C,Dz,Gy,Gx,2,ks,ks] holds one such V per image channel (the three wavelengths of psf_rgb,
+// deeplens/optics.py:999-1015): channel c is rendered with V[c], which lies c * Dz*Gy*Gx*2*ks*ks floats after V[0].
+// The k_*_chroma kernels are siblings of the four achromatic ones: same geometry, same helpers in the same order, so
+// one channel of a chromatic call has the bits of the achromatic call at C = 1 on that channel's slices.  Forward and
+// depth gradient form a pixel's corners once for all channels; the other two take the channel as a grid dimension.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -89,6 +95,44 @@ __device__ __forceinline__ void kernel_tap(const Corners& cn, int t, int kk, flo
     for (int k = 0; k < 8; ++k) {
         kl += cn.w[k] * cn.v[k][t];
         kr += cn.w[k] * cn.v[k][kk + t];
+    }
+}
+
+// Tap t of channel c of a chromatic volume, whose channels lie ch floats apart, as the tap index kernel_tap takes.
+// The sum is made opaque and kept in a VGPR: left to the compiler, the wave-uniform c * ch is folded into the corner
+// pointers, C sets of eight -- in the forward they no longer fit the SGPRs (73 v_writelane spills and a wait after
+// every load at C = 3).
+__device__ __forceinline__ int channel_tap(int c, int ch, int t)
+{
+    int tc = c * ch + t;
+    asm("" : "+v"(tc));
+    return tc;
+}
+
+// Tap t of the interpolated L and R kernels of all C channels, the 16 C corner values read before the first of them is
+// used: per channel kernel_tap's sums in kernel_tap's order.
+template <int C>
+__device__ __forceinline__ void kernel_taps(const Corners& cn, int ch, int t, int kk, float (&kl)[C], float (&kr)[C])
+{
+    float vl[C][8], vr[C][8];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int tc = channel_tap(c, ch, t);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            vl[c][k] = cn.v[k][tc];
+            vr[c][k] = cn.v[k][kk + tc];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        kl[c] = 0.0f;
+        kr[c] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            kl[c] += cn.w[k] * vl[c][k];
+            kr[c] += cn.w[k] * vr[c][k];
+        }
     }
 }
 
@@ -398,6 +442,252 @@ k_render_psf_volume_grad_img(const float* __restrict__ vol, const float* __restr
 }
 
 // ---------------------------------------------------------------------------
+// chromatic volumes: one V per channel
+// ---------------------------------------------------------------------------
+// The forward of a chromatic volume: k_render_psf_volume with K_l[c], K_r[c] per channel -- 16 C corner values per tap,
+// the corners of a channel added in kernel_tap's order, one pixel value per channel.
+template <int C>
+__global__ void __launch_bounds__(kBlock)
+k_render_psf_volume_chroma(const float* __restrict__ img, const float* __restrict__ vol, const SegmentTables tb, int H,
+                           int W, int ks, int Dz, int Gy, int Gx, float* __restrict__ outl, float* __restrict__ outr)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int y = blockIdx.y, b = blockIdx.z, pad = (ks - 1) / 2, kk = ks * ks;
+    const int64_t HW = (int64_t)H * W;
+    const int ch = Dz * Gy * Gx * 2 * kk;                              // floats of one channel's V (the entry checks C * ch)
+    const float* __restrict__ img_b = img + (int64_t)b * C * HW;
+    const TapWalker tap0(lane, 64, ks);
+    const Segment sy(tb.iy[y], tb.fy[y], Gy);
+    const int x_end = min(W, ((int)blockIdx.x + 1) * kPixChunk);
+    for (int x = blockIdx.x * kPixChunk + wave; x < x_end; x += kBlock / 64) {
+        const int64_t pixel = (int64_t)b * HW + (int64_t)y * W + x;
+        const Corners cn(vol, Gy, Gx, kk, Segment(tb.iz[pixel], tb.fz[pixel], Dz), sy, Segment(tb.ix[x], tb.fx[x], Gx));
+        float accl[C], accr[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) { accl[c] = 0.0f; accr[c] = 0.0f; }
+        TapWalker tap = tap0;
+        for (int t = lane; t < kk; t += 64) {
+            const float* px = clamped_pixel(img_b, y + pad - tap.i, x + pad - tap.j, H, W);
+            float kl[C], kr[C];
+            kernel_taps<C>(cn, ch, t, kk, kl, kr);
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float p = px[c * HW];
+                accl[c] += kl[c] * p;
+                accr[c] += kr[c] * p;
+            }
+            tap.next();
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            float a = accl[c], r = accr[c];
+            shuffle_sum(a, r);
+            if (lane == 0) {
+                const int64_t o = ((int64_t)(b * C + c) * H + y) * W + x;
+                outl[o] = a;
+                outr[o] = r;
+            }
+        }
+    }
+}
+
+// dV[c,dz,gy,gx,s,i,j] = sum_{b,y,x} w(y,x; node) * G_s[b,c,y,x] * img[b,c,clamp(y+pad-i),clamp(x+pad-j)]: no sum over
+// the channels.  k_render_psf_volume_grad<1> on channel c of C, the channel a grid dimension: one workgroup per
+// ((x, y) node, (channel, side), chunk of depth planes), blockIdx.y = 2 c + side; the LDS budget and the chunks are
+// those of one channel.  Every element of dV is written once, by the workgroup of its channel.
+__global__ void __launch_bounds__(kBlock)
+k_render_psf_volume_chroma_grad(const float* __restrict__ img, const float* __restrict__ gl,
+                                const float* __restrict__ gr, const SegmentTables tb, int B, int C, int H, int W, int ks,
+                                int Dz, int Gy, int Gx, int planes, float* __restrict__ dvol)
+{
+    extern __shared__ __attribute__((aligned(16))) float acc[];          // [planes][ks*ks]
+    __shared__ float s_w0[kBlock], s_w1[kBlock], s_g[kBlock];
+    __shared__ int s_l0[kBlock], s_l1[kBlock], s_y[kBlock], s_x[kBlock];
+    __shared__ int s_range[4][kBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int gx = blockIdx.x % Gx, gy = blockIdx.x / Gx, side = blockIdx.y & 1, c = blockIdx.y >> 1;
+    const int z_first = blockIdx.z * planes, nz = min(planes, Dz - z_first);
+    const int pad = (ks - 1) / 2, kk = ks * ks;
+    const int64_t HW = (int64_t)H * W;
+    const float* __restrict__ gs = (side ? gr : gl) + c * HW;
+    const TapWalker tap0(tid, kBlock, ks);
+
+    for (int l = 0; l < nz; ++l)
+        for (int t = tid; t < kk; t += kBlock) acc[l * kk + t] = 0.0f;
+
+    // the columns [x_lo, x_hi) and rows [y_lo, y_hi) that hold every pixel touching this node
+    int x_lo = W, x_hi = 0, y_lo = H, y_hi = 0;
+    for (int x = tid; x < W; x += kBlock)
+        if (Segment(tb.ix[x], 0.0f, Gx).touches(gx)) { x_lo = min(x_lo, x); x_hi = max(x_hi, x + 1); }
+    for (int y = tid; y < H; y += kBlock)
+        if (Segment(tb.iy[y], 0.0f, Gy).touches(gy)) { y_lo = min(y_lo, y); y_hi = max(y_hi, y + 1); }
+    for (int off = 32; off > 0; off >>= 1) {
+        x_lo = min(x_lo, __shfl_xor(x_lo, off));
+        x_hi = max(x_hi, __shfl_xor(x_hi, off));
+        y_lo = min(y_lo, __shfl_xor(y_lo, off));
+        y_hi = max(y_hi, __shfl_xor(y_hi, off));
+    }
+    if (lane == 0) { s_range[0][wave] = x_lo; s_range[1][wave] = x_hi; s_range[2][wave] = y_lo; s_range[3][wave] = y_hi; }
+    __syncthreads();
+    for (int k = 0; k < kBlock / 64; ++k) {
+        x_lo = min(x_lo, s_range[0][k]);
+        x_hi = max(x_hi, s_range[1][k]);
+        y_lo = min(y_lo, s_range[2][k]);
+        y_hi = max(y_hi, s_range[3][k]);
+    }
+    const int nx = max(x_hi - x_lo, 0), ny = max(y_hi - y_lo, 0);
+    const int64_t npix = (int64_t)nx * ny;
+
+    for (int b = 0; b < B; ++b) {
+        const float* __restrict__ img_c = img + ((int64_t)b * C + c) * HW;
+        for (int64_t first = 0; first < npix; first += kBlock) {
+            __syncthreads();                                             // the previous batch has been consumed
+            const int64_t p = first + tid;
+            int l0 = -1, l1 = -1;
+            if (p < npix) {
+                const int y = y_lo + (int)(p / nx), x = x_lo + (int)(p - (p / nx) * nx);
+                const Segment sy(tb.iy[y], tb.fy[y], Gy), sx(tb.ix[x], tb.fx[x], Gx);
+                const bool touches = sy.touches(gy) && sx.touches(gx);
+                const float wy = node_weight(sy, gy), wx = node_weight(sx, gx);
+                const int64_t pixel = (int64_t)b * HW + (int64_t)y * W + x;
+                const Segment sz(tb.iz[pixel], tb.fz[pixel], Dz);
+                const float w0 = (sz.w_lo * wy) * wx, w1 = (sz.w_hi * wy) * wx;
+                if (touches && w0 != 0.0f && sz.lo >= z_first && sz.lo < z_first + nz) l0 = sz.lo - z_first;
+                if (touches && w1 != 0.0f && sz.hi >= z_first && sz.hi < z_first + nz) l1 = sz.hi - z_first;
+                s_w0[tid] = w0;
+                s_w1[tid] = w1;
+                s_y[tid] = y + pad;
+                s_x[tid] = x + pad;
+                s_g[tid] = gs[(int64_t)b * C * HW + (int64_t)y * W + x];
+            }
+            s_l0[tid] = l0;
+            s_l1[tid] = l1;
+            __syncthreads();
+            const int n = (int)min((int64_t)kBlock, npix - first);
+            for (int q = 0; q < n; ++q) {
+                const int q0 = __builtin_amdgcn_readfirstlane(s_l0[q]), q1 = __builtin_amdgcn_readfirstlane(s_l1[q]);
+                if (q0 < 0 && q1 < 0) continue;
+                const float w0 = s_w0[q], w1 = s_w1[q], u = s_g[q];
+                const int yb = s_y[q], xb = s_x[q];
+                TapWalker tap = tap0;
+                for (int t = tid; t < kk; t += kBlock) {
+                    const float d = u * *clamped_pixel(img_c, yb - tap.i, xb - tap.j, H, W);
+                    if (q0 >= 0) acc[q0 * kk + t] += w0 * d;
+                    if (q1 >= 0) acc[q1 * kk + t] += w1 * d;
+                    tap.next();
+                }
+            }
+        }
+    }
+    for (int l = 0; l < nz; ++l) {
+        float* __restrict__ out = dvol + (((((int64_t)c * Dz + z_first + l) * Gy + gy) * Gx + gx) * 2 + side) * kk;
+        for (int t = tid; t < kk; t += kBlock) out[t] = acc[l * kk + t];
+    }
+}
+
+// dfz of a chromatic volume: dK_s/dfz depends on the channel, so the upstream values cannot be folded before the
+// kernel is applied as k_render_psf_volume_grad_depth does; per tap and channel
+//   acc += G_l[c] * ((dK_l[c]/dfz) * img[c, .]) + G_r[c] * ((dK_r[c]/dfz) * img[c, .]).
+// A pixel whose two depth planes are the same node gets exactly 0.
+template <int C>
+__global__ void __launch_bounds__(kBlock)
+k_render_psf_volume_chroma_grad_depth(const float* __restrict__ img, const float* __restrict__ vol,
+                                      const float* __restrict__ gl, const float* __restrict__ gr,
+                                      const SegmentTables tb, int H, int W, int ks, int Dz, int Gy, int Gx,
+                                      float* __restrict__ dfz)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int y = blockIdx.y, b = blockIdx.z, pad = (ks - 1) / 2, kk = ks * ks;
+    const int64_t HW = (int64_t)H * W;
+    const int ch = Dz * Gy * Gx * 2 * kk;                              // floats of one channel's V (the entry checks C * ch)
+    const float* __restrict__ img_b = img + (int64_t)b * C * HW;
+    const TapWalker tap0(lane, 64, ks);
+    const Segment sy(tb.iy[y], tb.fy[y], Gy);
+    const int x_end = min(W, ((int)blockIdx.x + 1) * kPixChunk);
+    for (int x = blockIdx.x * kPixChunk + wave; x < x_end; x += kBlock / 64) {
+        const int64_t pixel = (int64_t)b * HW + (int64_t)y * W + x;
+        const Segment sz(tb.iz[pixel], 0.0f, Dz);                        // K is linear in fz: its value is no operand
+        float acc = 0.0f;
+        if (sz.lo != sz.hi) {
+            const Corners cn(vol, Gy, Gx, kk, sz, sy, Segment(tb.ix[x], tb.fx[x], Gx), true);
+            float ul[C], ur[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const int64_t o = (int64_t)b * C * HW + c * HW + (int64_t)y * W + x;
+                ul[c] = gl[o];
+                ur[c] = gr[o];
+            }
+            TapWalker tap = tap0;
+            for (int t = lane; t < kk; t += 64) {
+                const float* px = clamped_pixel(img_b, y + pad - tap.i, x + pad - tap.j, H, W);
+                float kl[C], kr[C];
+                kernel_taps<C>(cn, ch, t, kk, kl, kr);
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const float p = px[c * HW];
+                    acc += ul[c] * (kl[c] * p) + ur[c] * (kr[c] * p);
+                }
+                tap.next();
+            }
+            acc = shuffle_sum(acc);
+        }
+        if (lane == 0) dfz[pixel] = acc;
+    }
+}
+
+// dImg of a chromatic volume: k_render_psf_volume_grad_img<1> on channel c of C, the channel a grid dimension --
+// blockIdx.x = c * chunks + (16 positions of a row), so that the workgroups in flight together work on one channel's
+// volume, as three achromatic calls would.  (With the channels inside the wave, S_l[c], S_r[c] on shared per-lane
+// corners, the scattered reads of the three volumes at once ran 1.7 times as long as those three calls.)
+__global__ void __launch_bounds__(kBlock)
+k_render_psf_volume_chroma_grad_img(const float* __restrict__ vol, const float* __restrict__ gl,
+                                    const float* __restrict__ gr, const SegmentTables tb, int C, int H, int W, int ks,
+                                    int Dz, int Gy, int Gx, int chunks, float* __restrict__ dimg)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = blockIdx.x / chunks, chunk = blockIdx.x - c * chunks;
+    const int v = blockIdx.y, b = blockIdx.z;
+    const int pad = (ks - 1) / 2, kk = ks * ks;
+    const int64_t HW = (int64_t)H * W;
+    const float* __restrict__ vol_c = vol + (int64_t)c * Dz * Gy * Gx * 2 * kk;
+    const float* __restrict__ gl_c = gl + ((int64_t)b * C + c) * HW;
+    const float* __restrict__ gr_c = gr + ((int64_t)b * C + c) * HW;
+    const TapWalker rel0(lane, 64, ks);                                 // (yr, xr) = (rel.i, rel.j)
+    const int u_end = min(W, (chunk + 1) * kPixChunk);
+    for (int u = chunk * kPixChunk + wave; u < u_end; u += kBlock / 64) {
+        float acc = 0.0f;
+        TapWalker rel = rel0;
+        for (int p = lane; p < kk; p += 64) {
+            const int y = v - pad + rel.i, x = u - pad + rel.j;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                // the taps of pixel (y, x) that read a padded position clamping onto (v, u)
+                const int i_lo = v == H - 1 ? 0 : rel.i, i_hi = v == 0 ? ks - 1 : rel.i;
+                const int j_lo = u == W - 1 ? 0 : rel.j, j_hi = u == 0 ? ks - 1 : rel.j;
+                const int64_t pixel = (int64_t)y * W + x;
+                const Corners cn(vol_c, Gy, Gx, kk,
+                                 Segment(tb.iz[(int64_t)b * HW + pixel], tb.fz[(int64_t)b * HW + pixel], Dz),
+                                 Segment(tb.iy[y], tb.fy[y], Gy), Segment(tb.ix[x], tb.fx[x], Gx));
+                float sl = 0.0f, sr = 0.0f;
+                for (int i = i_lo; i <= i_hi; ++i)
+                    for (int j = j_lo; j <= j_hi; ++j) {
+                        float kl, kr;
+                        kernel_tap(cn, i * ks + j, kk, kl, kr);
+                        sl += kl;
+                        sr += kr;
+                    }
+                acc += gl_c[pixel] * sl + gr_c[pixel] * sr;
+            }
+            rel.next();
+        }
+        acc = shuffle_sum(acc);
+        if (lane == 0) dimg[(((int64_t)b * C + c) * H + v) * W + u] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
 namespace {
@@ -435,6 +725,109 @@ int launch_volume_grad(dim3 grid, size_t lds, hipStream_t st, const float* img, 
     return SDIRT_OK;
 }
 
+// a chromatic volume's own rule: its kernels reach channel c by an int offset of the tap index
+int check_chroma_volume(int C, int ks, int Dz, int Gy, int Gx)
+{
+    if ((int64_t)Dz * Gy * Gx > INT32_MAX / ((int64_t)2 * ks * ks * C))
+        return fail(SDIRT_ERR_UNSUPPORTED, "a chromatic volume of %d x %d x %d x %d nodes at ks=%d (more than 2^31 - 1 floats)",
+                    C, Dz, Gy, Gx, ks);
+    return SDIRT_OK;
+}
+
+// The three entries, each for both kinds of volume: chroma = one V per channel, [C,Dz,Gy,Gx,2,ks,ks].
+
+int render_volume(bool chroma, const float* img, const float* volume, const SegmentTables& tb, int B, int C, int H,
+                  int W, int ks, int Dz, int Gy, int Gx, float* out_l, float* out_r, void* stream)
+{
+    if (int rc = check_volume_render(img, volume, out_l, out_r, tb, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
+    if (chroma)
+        if (int rc = check_chroma_volume(C, ks, Dz, Gy, Gx)) return rc;
+    if (B == 0) return SDIRT_OK;
+    const dim3 grid = pixel_grid(B, H, W);
+    hipStream_t st = as_stream(stream);
+    with_channels(C, [&](auto c) {
+        constexpr int Cc = decltype(c)::value;
+        if (chroma)
+            k_render_psf_volume_chroma<Cc><<<grid, kBlock, 0, st>>>(img, volume, tb, H, W, ks, Dz, Gy, Gx, out_l, out_r);
+        else
+            k_render_psf_volume<Cc><<<grid, kBlock, 0, st>>>(img, volume, tb, H, W, ks, Dz, Gy, Gx, out_l, out_r);
+        return SDIRT_OK;
+    });
+    LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+
+int render_volume_grad(bool chroma, const float* img, const float* grad_l, const float* grad_r, const SegmentTables& tb,
+                       int B, int C, int H, int W, int ks, int Dz, int Gy, int Gx, float* grad_volume, void* stream)
+{
+    if (int rc = check_volume_render(img, grad_l, grad_r, grad_volume, tb, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
+    if (chroma)
+        if (int rc = check_chroma_volume(C, ks, Dz, Gy, Gx)) return rc;
+    // (an empty batch is launched like any other: every element of grad_volume is written, all 0)
+    const int planes = planes_per_chunk(Dz, ks), chunks = (Dz + planes - 1) / planes;
+    if (chunks > 65535) return fail(SDIRT_ERR_UNSUPPORTED, "%d depth planes at ks=%d", Dz, ks);
+    const size_t lds = sizeof(float) * (size_t)planes * ks * ks;
+    hipStream_t st = as_stream(stream);
+    if (chroma) {
+        // the channel is a grid dimension: blockIdx.y = 2 c + side
+        const dim3 grid((unsigned)(Gy * Gx), 2u * (unsigned)C, (unsigned)chunks);
+        if (lds > 32 * 1024)
+            if (int rc = allow_large_lds<&k_render_psf_volume_chroma_grad>(kGradLds)) return rc;
+        k_render_psf_volume_chroma_grad<<<grid, kBlock, lds, st>>>(img, grad_l, grad_r, tb, B, C, H, W, ks, Dz, Gy, Gx,
+                                                                  planes, grad_volume);
+    } else {
+        const dim3 grid((unsigned)(Gy * Gx), 2u, (unsigned)chunks);
+        if (int rc = with_channels(C, [&](auto c) {
+                return launch_volume_grad<decltype(c)::value>(grid, lds, st, img, grad_l, grad_r, tb, B, H, W, ks, Dz,
+                                                              Gy, Gx, planes, grad_volume);
+            }))
+            return rc;
+    }
+    LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+
+int render_volume_grad_scene(bool chroma, const float* img, const float* volume, const float* grad_l,
+                             const float* grad_r, const SegmentTables& tb, int B, int C, int H, int W, int ks, int Dz,
+                             int Gy, int Gx, float* grad_img, float* grad_fz, void* stream)
+{
+    if (!grad_img && !grad_fz) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer (neither gradient is asked for)");
+    if (int rc = check_volume_render(img, volume, grad_l, grad_r, tb, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
+    if (chroma)
+        if (int rc = check_chroma_volume(C, ks, Dz, Gy, Gx)) return rc;
+    if (B == 0) return SDIRT_OK;
+    const dim3 grid = pixel_grid(B, H, W);
+    hipStream_t st = as_stream(stream);
+    if (grad_fz) {
+        with_channels(C, [&](auto c) {
+            constexpr int Cc = decltype(c)::value;
+            if (chroma)
+                k_render_psf_volume_chroma_grad_depth<Cc><<<grid, kBlock, 0, st>>>(img, volume, grad_l, grad_r, tb, H, W,
+                                                                                 ks, Dz, Gy, Gx, grad_fz);
+            else
+                k_render_psf_volume_grad_depth<Cc><<<grid, kBlock, 0, st>>>(img, volume, grad_l, grad_r, tb, H, W, ks,
+                                                                          Dz, Gy, Gx, grad_fz);
+            return SDIRT_OK;
+        });
+        LAUNCH_CHECK();
+    }
+    if (grad_img) {
+        if (chroma) {
+            // the channel is a grid dimension: blockIdx.x = c * (16-position chunks of a row) + chunk
+            k_render_psf_volume_chroma_grad_img<<<dim3(grid.x * (unsigned)C, grid.y, grid.z), kBlock, 0, st>>>(
+                volume, grad_l, grad_r, tb, C, H, W, ks, Dz, Gy, Gx, (int)grid.x, grad_img);
+        } else {
+            with_channels(C, [&](auto c) {
+                k_render_psf_volume_grad_img<decltype(c)::value><<<grid, kBlock, 0, st>>>(volume, grad_l, grad_r, tb, H, W,
+                                                                                        ks, Dz, Gy, Gx, grad_img);
+                return SDIRT_OK;
+            });
+        }
+        LAUNCH_CHECK();
+    }
+    return SDIRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -444,18 +837,15 @@ int sdirt_render_psf_volume(const float* img, const float* volume, const int32_t
                             int32_t C, int32_t H, int32_t W, int32_t ks, int32_t Dz, int32_t Gy, int32_t Gx,
                             float* out_l, float* out_r, void* stream)
 {
-    const SegmentTables tb{ix, fx, iy, fy, iz, fz};
-    if (int rc = check_volume_render(img, volume, out_l, out_r, tb, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
-    if (B == 0) return SDIRT_OK;
-    const dim3 grid = pixel_grid(B, H, W);
-    hipStream_t st = as_stream(stream);
-    with_channels(C, [&](auto c) {
-        k_render_psf_volume<decltype(c)::value><<<grid, kBlock, 0, st>>>(img, volume, tb, H, W, ks, Dz, Gy, Gx, out_l,
-                                                                       out_r);
-        return SDIRT_OK;
-    });
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    return render_volume(false, img, volume, {ix, fx, iy, fy, iz, fz}, B, C, H, W, ks, Dz, Gy, Gx, out_l, out_r, stream);
+}
+
+int sdirt_render_psf_volume_chroma(const float* img, const float* volume, const int32_t* ix, const float* fx,
+                                   const int32_t* iy, const float* fy, const int32_t* iz, const float* fz, int32_t B,
+                                   int32_t C, int32_t H, int32_t W, int32_t ks, int32_t Dz, int32_t Gy, int32_t Gx,
+                                   float* out_l, float* out_r, void* stream)
+{
+    return render_volume(true, img, volume, {ix, fx, iy, fy, iz, fz}, B, C, H, W, ks, Dz, Gy, Gx, out_l, out_r, stream);
 }
 
 int sdirt_render_psf_volume_grad(const float* img, const float* grad_l, const float* grad_r, const int32_t* ix,
@@ -463,21 +853,17 @@ int sdirt_render_psf_volume_grad(const float* img, const float* grad_l, const fl
                                  const float* fz, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ks, int32_t Dz,
                                  int32_t Gy, int32_t Gx, float* grad_volume, void* stream)
 {
-    const SegmentTables tb{ix, fx, iy, fy, iz, fz};
-    if (int rc = check_volume_render(img, grad_l, grad_r, grad_volume, tb, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
-    // (an empty batch is launched like any other: every element of grad_volume is written, all 0)
-    const int planes = planes_per_chunk(Dz, ks), chunks = (Dz + planes - 1) / planes;
-    if (chunks > 65535) return fail(SDIRT_ERR_UNSUPPORTED, "%d depth planes at ks=%d", Dz, ks);
-    const dim3 grid((unsigned)(Gy * Gx), 2u, (unsigned)chunks);
-    const size_t lds = sizeof(float) * (size_t)planes * ks * ks;
-    hipStream_t st = as_stream(stream);
-    if (int rc = with_channels(C, [&](auto c) {
-            return launch_volume_grad<decltype(c)::value>(grid, lds, st, img, grad_l, grad_r, tb, B, H, W, ks, Dz, Gy,
-                                                          Gx, planes, grad_volume);
-        }))
-        return rc;
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    return render_volume_grad(false, img, grad_l, grad_r, {ix, fx, iy, fy, iz, fz}, B, C, H, W, ks, Dz, Gy, Gx,
+                              grad_volume, stream);
+}
+
+int sdirt_render_psf_volume_chroma_grad(const float* img, const float* grad_l, const float* grad_r, const int32_t* ix,
+                                        const float* fx, const int32_t* iy, const float* fy, const int32_t* iz,
+                                        const float* fz, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ks,
+                                        int32_t Dz, int32_t Gy, int32_t Gx, float* grad_volume, void* stream)
+{
+    return render_volume_grad(true, img, grad_l, grad_r, {ix, fx, iy, fy, iz, fz}, B, C, H, W, ks, Dz, Gy, Gx,
+                              grad_volume, stream);
 }
 
 int sdirt_render_psf_volume_grad_scene(const float* img, const float* volume, const float* grad_l,
@@ -486,29 +872,18 @@ int sdirt_render_psf_volume_grad_scene(const float* img, const float* volume, co
                                        int32_t H, int32_t W, int32_t ks, int32_t Dz, int32_t Gy, int32_t Gx,
                                        float* grad_img, float* grad_fz, void* stream)
 {
-    const SegmentTables tb{ix, fx, iy, fy, iz, fz};
-    if (!grad_img && !grad_fz) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null pointer (neither gradient is asked for)");
-    if (int rc = check_volume_render(img, volume, grad_l, grad_r, tb, B, C, H, W, ks, Dz, Gy, Gx)) return rc;
-    if (B == 0) return SDIRT_OK;
-    const dim3 grid = pixel_grid(B, H, W);
-    hipStream_t st = as_stream(stream);
-    if (grad_fz) {
-        with_channels(C, [&](auto c) {
-            k_render_psf_volume_grad_depth<decltype(c)::value><<<grid, kBlock, 0, st>>>(
-                img, volume, grad_l, grad_r, tb, H, W, ks, Dz, Gy, Gx, grad_fz);
-            return SDIRT_OK;
-        });
-        LAUNCH_CHECK();
-    }
-    if (grad_img) {
-        with_channels(C, [&](auto c) {
-            k_render_psf_volume_grad_img<decltype(c)::value><<<grid, kBlock, 0, st>>>(
-                volume, grad_l, grad_r, tb, H, W, ks, Dz, Gy, Gx, grad_img);
-            return SDIRT_OK;
-        });
-        LAUNCH_CHECK();
-    }
-    return SDIRT_OK;
+    return render_volume_grad_scene(false, img, volume, grad_l, grad_r, {ix, fx, iy, fy, iz, fz}, B, C, H, W, ks, Dz, Gy,
+                                    Gx, grad_img, grad_fz, stream);
+}
+
+int sdirt_render_psf_volume_chroma_grad_scene(const float* img, const float* volume, const float* grad_l,
+                                              const float* grad_r, const int32_t* ix, const float* fx,
+                                              const int32_t* iy, const float* fy, const int32_t* iz, const float* fz,
+                                              int32_t B, int32_t C, int32_t H, int32_t W, int32_t ks, int32_t Dz,
+                                              int32_t Gy, int32_t Gx, float* grad_img, float* grad_fz, void* stream)
+{
+    return render_volume_grad_scene(true, img, volume, grad_l, grad_r, {ix, fx, iy, fy, iz, fz}, B, C, H, W, ks, Dz, Gy,
+                                    Gx, grad_img, grad_fz, stream);
 }
 
 }  // extern "C"

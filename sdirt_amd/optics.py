@@ -1429,19 +1429,44 @@ class Lensgroup:
         Lensgroup, psfnet.py:15-16).
 
         ONE psf_lr call on the Dz*Gy*Gx points, so it is differentiable exactly where psf_lr is (h, f, w of dp,
-        surface_params, the call's sensor position d_sensor); L and R are stacked and each divided by its own sum with torch ops, which keeps the graph."""
+        surface_params, the call's sensor position d_sensor); L and R are stacked and each divided by its own sum with torch ops, which keeps the graph.
+
+        wvln: a number -> psf [Dz,Gy,Gx,2,ks,ks].  A sequence of wavelengths (WAVE_RGB: the three of psf_rgb,
+        optics.py:999-1015) -> a CHROMATIC volume, psf [Cw,Dz,Gy,Gx,2,ks,ks]: one psf_lr call per wavelength on the same
+        points, each centred through the green lens as every psf_lr call is, with the same dp, surface_params and
+        d_sensor (the gradient of a shared parameter is the sum over the wavelengths), stacked on a new leading axis;
+        psf[c] is the volume of wvln[c], rendered into image channel c.  pupil_xy / center_pupil_xy are then either
+        (x[spp], y[spp]), shared by the wavelengths, or per wavelength, [2, Cw, spp] / [2, Cw, 2048] (psf_rgb's
+        convention); without them every wavelength draws fresh samples, in the order given."""
         from .render_psf import PSFVolume
         gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
         z_nodes = (z.detach().to(torch.float32).reshape(-1).cpu() if torch.is_tensor(z)
                    else torch.linspace(0, 1, int(z)) if int(z) > 1 else torch.zeros(1))
         d_min, d_max = float(getattr(self, "d_min", -200.0)), float(getattr(self, "d_max", -20000.0))
+        chromatic = not (np.isscalar(wvln) or (torch.is_tensor(wvln) and wvln.dim() == 0))
+        waves = tuple(float(w) for w in wvln) if chromatic else (float(wvln),)
+        if not waves:
+            raise ValueError("psf_volume needs at least one wavelength")
         vol = PSFVolume(None, torch.linspace(-1 + 1 / (2 * gx), 1 - 1 / (2 * gx), gx),
-                        torch.linspace(1 - 1 / (2 * gy), -1 + 1 / (2 * gy), gy), z_nodes, d_min, d_max)
-        L, R = self.psf_lr(vol.points(), ks=ks, wvln=wvln, spp=spp, dp=dp, pupil_xy=pupil_xy,
-                           center_pupil_xy=center_pupil_xy, surface_params=surface_params, d_sensor=d_sensor)
-        psf = torch.stack((L, R), -3)                                              # [N, 2, ks, ks]
-        psf = psf / psf.sum((-1, -2), keepdim=True).clamp_min(1e-30)               # (a node no ray reaches stays 0)
-        vol.psf = psf.reshape(len(z_nodes), gy, gx, 2, ks, ks)
+                        torch.linspace(1 - 1 / (2 * gy), -1 + 1 / (2 * gy), gy), z_nodes, d_min, d_max, waves)
+
+        def samples_of(xy, i):
+            # (x[n], y[n]) for every wavelength, or [2, Cw, n]: wavelength i's pair
+            if xy is None or not chromatic or xy[0].dim() == 1:
+                return xy
+            if len(xy[0]) != len(waves):
+                raise ValueError(f"pupil points per wavelength must be [2, {len(waves)}, n], got {len(xy[0])} sets")
+            return xy[0][i], xy[1][i]
+
+        points, psfs = vol.points(), []
+        for i, w in enumerate(waves):
+            L, R = self.psf_lr(points, ks=ks, wvln=w, spp=spp, dp=dp, pupil_xy=samples_of(pupil_xy, i),
+                               center_pupil_xy=samples_of(center_pupil_xy, i), surface_params=surface_params,
+                               d_sensor=d_sensor)
+            psf = torch.stack((L, R), -3)                                          # [N, 2, ks, ks]
+            psf = psf / psf.sum((-1, -2), keepdim=True).clamp_min(1e-30)           # (a node no ray reaches stays 0)
+            psfs.append(psf.reshape(len(z_nodes), gy, gx, 2, ks, ks))
+        vol.psf = torch.stack(psfs) if chromatic else psfs[0]
         dev = vol.psf.device
         vol.x_nodes, vol.y_nodes, vol.z_nodes = vol.x_nodes.to(dev), vol.y_nodes.to(dev), vol.z_nodes.to(dev)
         return vol

@@ -441,7 +441,9 @@ class PSFNet(Lensgroup):
         negative) -> [N,2C,H,W].  Not under no_grad: a volume that requires a gradient gets one (torch ops for the
         tone curve); the same call without gradients is the ground truth a fitted network is judged against.
         scene_grad=True: an `img` or a `depth` that requires a gradient gets one as well (depth2z and degamma are torch
-        ops; local_dp_psf_render_volume's scene_grad)."""
+        ops; local_dp_psf_render_volume's scene_grad).  A chromatic volume (psf_volume(wvln=WAVE_RGB), psf
+        [C,Dz,Gy,Gx,2,ks,ks]) renders channel c with its own PSFs, nothing else changes: the tone curves are per
+        element."""
         if img.dim() != 4:
             raise ValueError("render_volume expects img [N,C,H,W] and depth [N,1,H,W]")
         z = self.depth2z(depth + self.d_sensor).squeeze(1)

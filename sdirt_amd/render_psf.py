@@ -10,7 +10,7 @@ import dataclasses
 import torch
 
 from . import _lib
-from .basics import dptr, stream_ptr
+from .basics import DEFAULT_WAVE, dptr, stream_ptr
 
 
 def _render(input, psf, kernel_size, half):
@@ -133,9 +133,13 @@ def volume_segment_tables(x_nodes, y_nodes, z_nodes, z, height, width):
 
 def _volume_shape(img, volume, tables, ks):
     b, c, h, w = img.shape
-    dz, gy, gx = volume.shape[:3]
-    if tuple(volume.shape) != (dz, gy, gx, 2, ks, ks):
-        raise ValueError(f"volume must be [Dz, Gy, Gx, 2, {ks}, {ks}], got {tuple(volume.shape)}")
+    dz, gy, gx = volume.shape[-6:-3] if volume.dim() in (6, 7) else (0, 0, 0)
+    if volume.dim() not in (6, 7) or tuple(volume.shape[-6:]) != (dz, gy, gx, 2, ks, ks):
+        raise ValueError(f"volume must be [Dz, Gy, Gx, 2, {ks}, {ks}] or, chromatic, [C, Dz, Gy, Gx, 2, {ks}, {ks}], "
+                         f"got {tuple(volume.shape)}")
+    if volume.dim() == 7 and volume.shape[0] != c:
+        raise ValueError(f"a chromatic volume holds one PSF volume per image channel: {volume.shape[0]} for an image of "
+                         f"{c} channels")
     want = ((w,), (w,), (h,), (h,), (b, h, w), (b, h, w))
     for t, shape, dtype in zip(tables, want, (torch.int32, torch.float32) * 3):
         if tuple(t.shape) != shape or t.dtype != dtype or t.device != img.device or not t.is_contiguous():
@@ -143,21 +147,29 @@ def _volume_shape(img, volume, tables, ks):
     return b, c, h, w, dz, gy, gx
 
 
+def _volume_entry(volume_shape, suffix=""):
+    """The C entry for a volume of this shape: sdirt_render_psf_volume<suffix>, or its _chroma sibling for a chromatic
+    volume [C,Dz,Gy,Gx,2,ks,ks]."""
+    return getattr(_lib.lib(), "sdirt_render_psf_volume" + ("_chroma" if len(volume_shape) == 7 else "") + suffix)
+
+
 def _render_volume(img, volume, tables, ks):
-    """img [B,C,H,W] and volume [Dz,Gy,Gx,2,ks,ks], fp32 contiguous on the GPU -> (left, right) [B,C,H,W]."""
+    """img [B,C,H,W] and volume [Dz,Gy,Gx,2,ks,ks] or [C,Dz,Gy,Gx,2,ks,ks], fp32 contiguous on the GPU -> (left, right)
+    [B,C,H,W]."""
     if img.device.type != "cuda":
         raise _lib.SdirtError("sdirt_amd renders on the GPU only (no CPU fallback)")
     b, c, h, w, dz, gy, gx = _volume_shape(img, volume, tables, ks)
     rl = torch.empty((b, c, h, w), dtype=torch.float32, device=img.device)
     rr = torch.empty_like(rl)
-    _lib.check(_lib.lib().sdirt_render_psf_volume(dptr(img), dptr(volume), *(dptr(t) for t in tables), b, c, h, w, ks,
-                                                  dz, gy, gx, dptr(rl), dptr(rr), stream_ptr(img.device)))
+    _lib.check(_volume_entry(volume.shape)(dptr(img), dptr(volume), *(dptr(t) for t in tables), b, c, h, w, ks,
+                                           dz, gy, gx, dptr(rl), dptr(rr), stream_ptr(img.device)))
     return rl, rr
 
 
 class _RenderPsfVolume(torch.autograd.Function):
     """local_dp_psf_render_volume under autograd: the forward is _render_volume's kernel call on the same operands
-    (bit-equal to the no-grad call), the backward sdirt_render_psf_volume_grad."""
+    (bit-equal to the no-grad call), the backward sdirt_render_psf_volume_grad.  A chromatic
+    volume [C,Dz,Gy,Gx,2,ks,ks] goes through the _chroma entries, forward and backward (_volume_entry)."""
 
     @staticmethod
     def forward(ctx, volume, img, ks, *tables):
@@ -172,12 +184,12 @@ class _RenderPsfVolume(torch.autograd.Function):
     def backward(ctx, grad):
         img, *tables = ctx.saved_tensors
         b, c, h, w = img.shape
-        dz, gy, gx = ctx.volume_shape[:3]
+        dz, gy, gx = ctx.volume_shape[-6:-3]
         gl, gr = _grad_halves(grad, c)
         dvol = torch.empty(ctx.volume_shape, dtype=torch.float32, device=img.device)
-        _lib.check(_lib.lib().sdirt_render_psf_volume_grad(dptr(img), dptr(gl), dptr(gr), *(dptr(t) for t in tables),
-                                                           b, c, h, w, ctx.kernel_size, dz, gy, gx, dptr(dvol),
-                                                           stream_ptr(img.device)))
+        _lib.check(_volume_entry(ctx.volume_shape, "_grad")(dptr(img), dptr(gl), dptr(gr), *(dptr(t) for t in tables),
+                                                            b, c, h, w, ctx.kernel_size, dz, gy, gx, dptr(dvol),
+                                                            stream_ptr(img.device)))
         return (dvol.to(ctx.volume_dtype), None, None) + (None,) * len(tables)
 
 
@@ -186,7 +198,7 @@ class _RenderPsfVolumeScene(torch.autograd.Function):
     the same operands (bit-equal to the plain call); the backward calls only what ctx.needs_input_grad asks for --
     sdirt_render_psf_volume_grad for the volume, sdirt_render_psf_volume_grad_scene for the image, the depth table
     value fz or both, with NULL for the one that is not wanted.  The step from fz to z is
-    axis_segments' torch ops, outside this Function."""
+    axis_segments' torch ops, outside this Function.  A chromatic volume goes through the _chroma entries."""
 
     @staticmethod
     def forward(ctx, volume, img, fz, ks, ix, fx, iy, fy, iz):
@@ -202,24 +214,24 @@ class _RenderPsfVolumeScene(torch.autograd.Function):
         vol, img, fz, ix, fx, iy, fy, iz = ctx.saved_tensors
         tables = (ix, fx, iy, fy, iz, fz)
         b, c, h, w = img.shape
-        dz, gy, gx = vol.shape[:3]
+        dz, gy, gx = vol.shape[-6:-3]
         shape = (b, c, h, w, ctx.kernel_size, dz, gy, gx)
-        lib, stream = _lib.lib(), stream_ptr(img.device)
+        stream = stream_ptr(img.device)
         gl, gr = _grad_halves(grad, c)
         dvol = dimg = dfz = None
         if ctx.needs_input_grad[0]:
             dvol = torch.empty(vol.shape, dtype=torch.float32, device=img.device)
-            _lib.check(lib.sdirt_render_psf_volume_grad(dptr(img), dptr(gl), dptr(gr), *(dptr(t) for t in tables),
-                                                        *shape, dptr(dvol), stream))
+            _lib.check(_volume_entry(vol.shape, "_grad")(dptr(img), dptr(gl), dptr(gr), *(dptr(t) for t in tables),
+                                                         *shape, dptr(dvol), stream))
             dvol = dvol.to(ctx.volume_dtype)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             if ctx.needs_input_grad[1]:
                 dimg = torch.empty(img.shape, dtype=torch.float32, device=img.device)
             if ctx.needs_input_grad[2]:
                 dfz = torch.empty(fz.shape, dtype=torch.float32, device=img.device)
-            _lib.check(lib.sdirt_render_psf_volume_grad_scene(dptr(img), dptr(vol), dptr(gl), dptr(gr),
-                                                              *(dptr(t) for t in tables), *shape, dptr(dimg),
-                                                              dptr(dfz), stream))
+            _lib.check(_volume_entry(vol.shape, "_grad_scene")(dptr(img), dptr(vol), dptr(gl), dptr(gr),
+                                                               *(dptr(t) for t in tables), *shape, dptr(dimg),
+                                                               dptr(dfz), stream))
         return dvol, dimg, dfz, None, None, None, None, None, None
 
 
@@ -234,6 +246,10 @@ def local_dp_psf_render_volume(input, volume, x_nodes, y_nodes, z_nodes, z, kern
     Pixel x = linspace(-1, 1, W), pixel y = linspace(1, -1, H).  Outside the nodes the end PSF is used.  The kernel
     does no normalisation: sum-normalised node PSFs give sum-normalised per-pixel kernels.
 
+    A CHROMATIC volume [C,Dz,Gy,Gx,2,ks,ks] (Lensgroup.psf_volume with a sequence of wavelengths) renders channel c of
+    the image with volume[c], in the same single kernel call; its leading extent must be the image's C (ValueError
+    otherwise).  Everything below holds for it unchanged, the gradients included.
+
     Differentiable in `volume` (a call in grad mode on a volume that requires a gradient goes through _RenderPsfVolume:
     same forward kernel, same values).  By default gradients in the image and in the depth are not taken: asking for
     them raises.
@@ -246,6 +262,9 @@ def local_dp_psf_render_volume(input, volume, x_nodes, y_nodes, z_nodes, z, kern
     gradient, scene_grad=True is the plain call."""
     if input.dim() < 4:
         input = input.unsqueeze(0)
+    if volume.dim() == 7 and volume.shape[0] != input.shape[1]:
+        raise ValueError(f"local_dp_psf_render_volume: a chromatic volume holds one PSF volume per image channel, got "
+                         f"{volume.shape[0]} for an image of {input.shape[1]} channels")
     grad_mode = torch.is_grad_enabled()
     if scene_grad and grad_mode and (input.requires_grad or z.requires_grad or volume.requires_grad):
         b, _, h, w = input.shape
@@ -278,13 +297,16 @@ class PSFVolume:
     """A ray-traced PSF grid as local_dp_psf_render_volume consumes it (Lensgroup.psf_volume makes one).
     psf [Dz,Gy,Gx,2,ks,ks]: left and right PSF of every node, each sum-normalised; x_nodes [Gx], y_nodes [Gy]:
     normalised sensor coordinates (y decreases, as the image's rows do); z_nodes [Dz]: normalised depth
-    z = (depth - d_min) / (d_max - d_min) (PSFNet.depth2z), depth in mm."""
+    z = (depth - d_min) / (d_max - d_min) (PSFNet.depth2z), depth in mm.  wvln: the wavelengths (um) the PSFs were
+    traced at -- one: psf is the 6-D volume above; several: psf is chromatic, [len(wvln),Dz,Gy,Gx,2,ks,ks], psf[c] the
+    volume of wvln[c], rendered into channel c."""
     psf: torch.Tensor
     x_nodes: torch.Tensor
     y_nodes: torch.Tensor
     z_nodes: torch.Tensor
     d_min: float
     d_max: float
+    wvln: tuple = (DEFAULT_WAVE,)
 
     def points(self):
         """[Dz*Gy*Gx, 3] points (x, y normalised, depth in mm) in the volume's order: what psf_lr is given."""
