@@ -34,7 +34,8 @@ constexpr float kNewtonStepBound = 5.0f;   // deeplens/surfaces.py:29
 // ---------------------------------------------------------------------------
 struct alignas(64) SurfHot {
     uint32_t flags;      // bits 0-1 kind (0 plane, 1 sphere, 2 asphere) | 2 do_refract (plane: eta != 1,
-                         // surfaces.py:450) | 3 k > -1 (:727,738) | 4 c > 0 | 5 1 + k == 1 | 8-11 ai_degree
+                         // surfaces.py:450) | 3 k > -1 (:727,738) | 4 c > 0 | 5 1 + k == 1 | 8-11 ai_degree |
+                         // 12-19 the visit word (visit_bits below)
     float d, c;
     float c2;            // c*c (fp32)
     float onepk;         // 1 + k
@@ -63,6 +64,32 @@ static_assert(sizeof(SurfHot) == 64 && sizeof(SurfPoly) == 64 && sizeof(DevSurfa
 
 constexpr uint32_t kFlagRefract = 4u, kFlagKgtM1 = 8u, kFlagCpos = 16u;
 constexpr uint32_t kFlagUnitK = 32u;      // 1 + k == 1.0f exactly (every sphere): (1 + k) * r2 is r2
+// Bits 12-21, the visit word: which path each half of a visit takes (surface_reaction), one bit per path, written by
+// the host (visit_bits) from the fields above.  Exactly one of the four "hit" bits is set, and at most one of the four
+// "bend" bits (a stop has none).  A kernel tests a bit with one scalar instruction and a branch, and tests of
+// different bits say nothing about one another to the compiler: no kind is decoded with and / add / compare, and
+// nothing has to keep the tests apart.
+constexpr uint32_t kHitPlane = 1u << 12;     // kind 0
+constexpr uint32_t kHitSphere = 1u << 13;    // kind 1 with 1 + k == 1: the Newton copy without the product, a sphere's own validity
+constexpr uint32_t kHitConic = 1u << 14;     // any other surface without polynomial terms
+constexpr uint32_t kHitTerms = 1u << 15;     // an asphere with terms (kind 2, degree > 0)
+constexpr uint32_t kBendTerms = 1u << 16;    // the refraction of the same four ...
+constexpr uint32_t kBendSphere = 1u << 17;   // ... but this one is every kind 1: the normal is o - centre whatever k is
+constexpr uint32_t kBendConic = 1u << 18;    // kind 2 without terms
+constexpr uint32_t kBendPlane = 1u << 19;    // kind 0 between two different media
+// ... and one bit per half that says "not the sphere's path": the three rarer paths of a half stand inside ONE test,
+// so a sphere walks past one skipped test per half and not three.  (A bit of its own and not the sphere's bit
+// negated: of `if (A) ... if (!A) ...` the compiler makes an if / else, whose merge is what brought the copies at
+// the back edge -- see apart().)
+constexpr uint32_t kHitOther = 1u << 20, kBendOther = 1u << 21;
+__host__ __device__ constexpr uint32_t visit_bits(uint32_t f)
+{
+    const uint32_t kind = f & 3u, terms = (f & 0xf00u) != 0u;
+    if (kind == 0u) return kHitPlane | kHitOther | ((f & kFlagRefract) ? kBendPlane | kBendOther : 0u);
+    if (terms) return kHitTerms | kHitOther | kBendTerms | kBendOther;
+    if (kind == 1u) return ((f & kFlagUnitK) ? kHitSphere : kHitConic | kHitOther) | kBendSphere;
+    return kHitConic | kHitOther | kBendConic | kBendOther;
+}
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
@@ -559,26 +586,37 @@ __device__ __forceinline__ NewtonEnd newton_k(const S& s, const P& pol, const Ra
     };
     // the periodicity test costs four vector and five scalar instructions per trip: it is run
     // where it can pay, on tables longer than kPeriodicFrom trips (a wave-uniform choice of loop)
+    // (the skipped trips are written down inside the periodic copy's own branch: behind the merge of the two copies
+    // the plain loop would arrive with `skipped` and three lane masks set to zero -- seven scalar instructions -- only
+    // to find that it skipped nothing)
     if (cap > kPeriodicFrom) {
         while (left > 0) trip(std::true_type{});
-    } else
-    {
-        while (left > 0) trip(std::false_type{});
+        if (skipped > 0) {
+            // the open flags of the skipped trips alternate A, B, A, ...: B = the last flag (the state
+            // t[n]); A belongs to the state t[n+1], which a fixed-point ray shares with t[n] and a
+            // period-two ray with t[n-1]
+            const bool a_open = ((open_cur & fixed) | (open_prev & ~fixed)) != 0ull;
+            const uint32_t pat = (a_open ? 0xAAAAu : 0u) | ((rmask & 1u) ? 0x5555u : 0u);
+            rmask = (rmask << skipped) | (pat >> (16 - skipped));
+            t = (skipped & 1) ? t_odd : t;
+        }
     }
-    if (skipped > 0) {
-        // the open flags of the skipped trips alternate A, B, A, ...: B = the last flag (the state
-        // t[n]); A belongs to the state t[n+1], which a fixed-point ray shares with t[n] and a
-        // period-two ray with t[n-1]
-        const bool a_open = ((open_cur & fixed) | (open_prev & ~fixed)) != 0ull;
-        const uint32_t pat = (a_open ? 0xAAAAu : 0u) | ((rmask & 1u) ? 0x5555u : 0u);
-        rmask = (rmask << skipped) | (pat >> (16 - skipped));
-        t = (skipped & 1) ? t_odd : t;
+    // ... and the plain copy stands behind it without an `else`: the periodic copy leaves with no trip left (run out,
+    // or cleared by its exit), so this loop then runs none.  Of the if / else the compiler made two `Flow` blocks: a
+    // 64-bit "came from there" flag set, cleared and branched on around the copy that does not run
+    while (left > 0) trip(std::false_type{});
+    // trip j (0-based) -> bit j + 1.  n trips ran: cap, or in adaptive mode up to and including the first closed one,
+    // which is the number of bits rmask holds: every trip before a wave's last one was open, so the oldest bit is set
+    // (one trip: rmask | 1 counts it), and an all-open run of cap trips holds cap ones -- 32 - clz(rmask | 1) is n
+    // whenever the table is adaptive, with the skipped trips of a periodic wave written down (they fill up to cap, and
+    // the wave only skips behind an open trip).  The shift 31 - n is what is kept; a fixed table takes it from cap and
+    // walks past the three instructions of the count (the empty statement keeps that a branch, not a select).
+    uint32_t sh = 31u - (uint32_t)cap;
+    if (adaptive) {
+        asm volatile("");
+        sh = (uint32_t)__builtin_clz(rmask | 1u) - 1u;
     }
-    // trip j (0-based) -> bit j + 1.  n trips ran: cap, or in adaptive mode up to and including
-    // the first closed one (rmask = 1..10 then; an all-open run ends in a 1)
-    uint32_t n = (uint32_t)cap;
-    if (adaptive && !(rmask & 1u)) n = 32u - (uint32_t)__builtin_clz(rmask | 1u);
-    const uint32_t mask = __builtin_bitreverse32(rmask) >> (31u - n);
+    const uint32_t mask = __builtin_bitreverse32(rmask) >> sh;
     mask_out = mask;
     const float t1 = t - t0;   // :563
     t = t0 + t1;               // :567
@@ -599,7 +637,8 @@ __device__ __forceinline__ NewtonEnd newton_k(const S& s, const P& pol, const Ra
     return NewtonEnd{t, ft, rr, tight};
 }
 
-// The kinds' paths are `if (A) {...} if (B) {...}` with B the complement of A behind an empty statement, not
+// The visit's paths are `if (A) {...} if (B) {...}` on conditions the compiler cannot relate -- different bits of the
+// visit word, and behind `between` the word read "once more" through an empty statement -- not
 // `if (A) {...} else {...}`: each path then updates the ray in place and merges with "the ray as it was" only.  Of an
 // if / else the compiler makes one merge of two fresh sets of registers, which start undefined on the other path
 // while the old ray is still live there -- that overlap is what kept old and new ray in separate registers.
@@ -636,7 +675,9 @@ __device__ __forceinline__ uint32_t apart(uint32_t flags)        // the surface'
 // Where a ROUNDS to 1 (k > -1, rr one or two floats under lim_loose: the host's fp32(1 - 1e-9) is 1.0f) the radicand
 // is 0 and both forms give a NaN normal -- the general one through (a / 2) / 0, whose Lean::div is NaN, this one
 // through 0 * rsq(0): the ray fails c2i > 0.1, keeps its direction and dies either way.  Ieee: the literal sqrt.
-template <bool FWD, class M, bool UNIT_W = false, bool PLANE = false, class P, class S>
+// BEND (Lean, no terms): the caller has the surface's bend bit -- kBendSphere or kBendConic -- and the kind is not
+// looked at again; 0: it is decoded here (strict IEEE, whose two kinds share one Snell block).
+template <bool FWD, class M, bool UNIT_W = false, bool PLANE = false, uint32_t BEND = 0u, class P, class S>
 __device__ __forceinline__ void refract(const S& s, const P& pol, Ray& r, const bool live)
 {
     // Snell's law on the normal sgn * normalize(nx, ny, nz), sgn = neg ? -1 : +1 (Lean) or the normal as it stands (Ieee).
@@ -669,13 +710,14 @@ __device__ __forceinline__ void refract(const S& s, const P& pol, Ray& r, const 
         float g, ds;
         sag_g_dgd<M, true, ConicS, false, P, false>(conic_s(s), pol, s.ai_degree(), xv * xv + yv * yv, g, ds);
         nx = (ds * 2.0f) * xv; ny = (ds * 2.0f) * yv; nz = -1.0f;
-    } else if (PLANE) {
+    } else if constexpr (PLANE) {
         nx = 0.0f; ny = 0.0f; nz = -1.0f;
-    } else if (M::kFused) {
+    } else if constexpr (M::kFused) {
         // the sphere has its own copy of what follows: its normal is read where the position lies (no moves into
         // registers shared with the other kinds), and its sign is the only one that is not a constant
-        if (s.kind() == 1) snell(r.ox, r.oy, r.oz - s.d_plus_R(), s.c_pos() == FWD);
-        if ((apart(s.a[0]) & 3u) != 1u) {                         // conic without polynomial terms
+        static_assert(BEND == kBendSphere || BEND == kBendConic, "the caller dispatches on the visit word");
+        if constexpr (BEND == kBendSphere) snell(r.ox, r.oy, r.oz - s.d_plus_R(), s.c_pos() == FWD);
+        else {                                                    // conic without polynomial terms
             const float vf = live ? 1.0f : 0.0f;
             const float xv = r.ox * vf, yv = r.oy * vf;
             float g, ds;
@@ -701,15 +743,18 @@ __device__ __forceinline__ void refract(const S& s, const P& pol, Ray& r, const 
 // r.ra > 0 is compared ONCE per visit: `alive` serves the Newton solve and the sphere's validity test, and the
 // validity v -- which implies it, and is all that is left of it once ra = keep_if(ra, v) -- serves the refraction.
 // Newton's own validity is asked for on the non-sphere branch only (NewtonEnd::valid): a sphere's is its own test.
-template <class M, bool UNIT_W = false, class P, class S>
+// SPHERE: the surface's hit bit is kHitSphere -- kind 1 with 1 + k == 1 (every sphere the reference can describe): the
+// Newton copy without the product by 1 + k and the sphere's own validity, nothing decoded.  Otherwise the copy is chosen
+// by the side of k = -1 (a pure conic with 1 + k == 1 takes the k > -1 copy: its product by 1.0f changes no bit), and
+// only a surface without terms can be of kind 1 (a kind-1 surface with k != 0, which the reference has no class for).
+template <class M, bool UNIT_W = false, bool SPHERE = false, class P, class S>
 __device__ __forceinline__ bool curved_hit(const S& s, const P& pol, Ray& r, int trips, uint32_t& mask)
 {
     const bool alive = r.ra > 0.0f;
     // k > -1 (every sphere, ellipsoid, mild asphere) and k <= -1 differ only in the domain test
     // (surfaces.py:727-743); the branch is wave-uniform and taken once, outside the loop
-    // (and, for pure conics, a copy for 1 + k == 1: every sphere)
     NewtonEnd e;
-    if (std::is_same<P, NoPoly>::value && s.unit_k())
+    if constexpr (SPHERE)
         e = newton_k<M, true, P, true>(s, pol, r, alive, trips, mask);
     else
         e = s.k_gt_m1() ? newton_k<M, true>(s, pol, r, alive, trips, mask)
@@ -717,7 +762,11 @@ __device__ __forceinline__ bool curved_hit(const S& s, const P& pol, Ray& r, int
     const float t = e.t;
     const float nx = r.ox + t * r.dx, ny = r.oy + t * r.dy, nz = r.oz + t * r.dz;
     bool v;
-    if (s.kind() == 1) {                                                                  // :464
+    if constexpr (SPHERE) {
+        v = nx * nx + ny * ny <= s.r2_lim() && t >= 0.0f && alive;                        // :464
+    } else if constexpr (!std::is_same<P, NoPoly>::value) {
+        v = e.valid();                                                                    // :495 (false on a dead ray)
+    } else if (s.kind() == 1) {                                                           // :464
         // (the empty statement keeps the two kinds' lane masks a branch merged on the scalar unit: with no compare
         // of ra left in here the compiler otherwise picks between them per lane, five vector instructions)
         asm volatile("");
@@ -732,11 +781,11 @@ __device__ __forceinline__ bool curved_hit(const S& s, const P& pol, Ray& r, int
 
 // Aspheric.ray_reaction, surfaces.py:391-520, on surface `blk` whose constants `s` are already in
 // registers.  Returns the Newton convergence mask of this wave on this surface (0 for planes).
-// `between` runs ONCE, after the intersection and before the refraction (the trace loop's prefetch of the next
-// surface): the three kinds -- plane, curved without polynomial terms, asphere with terms -- are three `if`s in a row
-// before it (intersection, validity, position) and three after it (refraction), each updating the ray in place (see
-// apart() for why they are no if / else chain).  The asphere's halves stand next to `between`, so that its polynomial
-// block is live across nothing else.
+// `between(mask)` runs ONCE, after the intersection and before the refraction (the trace loop's hand-over of the mask
+// and its prefetch of the next surface).  Each half is the sphere's path and, inside one test of their own, the three
+// rarer ones -- plane, curved without polynomial terms, asphere with terms -- as `if`s in a row, each updating the ray
+// in place (see apart() for why they are no if / else chain): a sphere's visit is two taken and two skipped tests.
+// The asphere's halves stand next to `between`, so that its polynomial block is live across nothing else.
 //
 // The plane's aperture test (surfaces.py:421), sqrt(x^2 + y^2) <= r.  A correctly rounded square root is monotone, so
 // the test holds exactly when x^2 + y^2 <= X, X the largest fp32 whose rounded root is <= r; the host finds X once
@@ -748,36 +797,45 @@ __device__ __forceinline__ uint32_t surface_reaction(const S& s, const DevSurfac
 {
     uint32_t mask = 0;
     bool v = false;
-    const uint32_t f0 = s.a[0], f1 = apart(f0), f2 = apart(f0);
-    // wave-uniform, all three, and ONE scalar compare each (a conjunction of two comes out as two 64-bit masks, an
-    // s_and_b64 and a branch on vcc: ten scalar instructions per test, six tests per visit).  Only an asphere has
-    // a degree (make_dev_surface), so "has terms" is the degree field alone.
-    const bool plane = (f0 & 3u) == 0u;
-    const bool conic = (f1 & 0xf03u) - 1u < 2u;                    // kind 1 or 2, degree 0: sphere, or conic without terms
-    const bool terms = (f2 & 0xf00u) != 0u;
-    if (plane) {
-        const float t = M::div(s.d() - r.oz, r.dz);
-        const float nx = r.ox + t * r.dx, ny = r.oy + t * r.dy, nz = r.oz + t * r.dz;
-        const float rr = nx * nx + ny * ny;
-        const bool inside = M::kFused ? rr <= s.r2_lim() : M::sqrt(rr) <= s.r_lim();
-        v = inside && r.ra > 0.0f;
-        r.ox = v ? nx : r.ox; r.oy = v ? ny : r.oy; r.oz = v ? nz : r.oz;
-        r.ra = M::keep_if(r.ra, v);
-    }
-    if (conic) v = curved_hit<M, UNIT_W>(s, NoPoly{}, r, trips, mask);
+    // wave-uniform, every one, and ONE scalar test each: a bit of the visit word the host wrote (visit_bits)
+    const uint32_t f = s.a[0];
+    if (f & kHitSphere) v = curved_hit<M, UNIT_W, true>(s, NoPoly{}, r, trips, mask);
     Poly pol;
-    if (terms) {
-        pol = s.poly(blk);                        // the polynomial block is fetched (one more round trip) on aspheres only
-        v = curved_hit<M, UNIT_W>(s, pol, r, trips, mask);
+    if (f & kHitOther) {
+        if (f & kHitPlane) {
+            const float t = M::div(s.d() - r.oz, r.dz);
+            const float nx = r.ox + t * r.dx, ny = r.oy + t * r.dy, nz = r.oz + t * r.dz;
+            const float rr = nx * nx + ny * ny;
+            const bool inside = M::kFused ? rr <= s.r2_lim() : M::sqrt(rr) <= s.r_lim();
+            v = inside && r.ra > 0.0f;
+            r.ox = v ? nx : r.ox; r.oy = v ? ny : r.oy; r.oz = v ? nz : r.oz;
+            r.ra = M::keep_if(r.ra, v);
+        }
+        if (f & kHitConic) v = curved_hit<M, UNIT_W>(s, NoPoly{}, r, trips, mask);
+        if (f & kHitTerms) {
+            pol = s.poly(blk);                    // the polynomial block is fetched (one more round trip) on aspheres only
+            v = curved_hit<M, UNIT_W>(s, pol, r, trips, mask);
+        }
     }
-    between();
-    // (the kinds are decoded again: a condition carried across `between` comes back as a lane mask, a v_cndmask and a
-    // v_cmp per visit)
-    const uint32_t g1 = apart(f0), g2 = apart(f0);
-    if ((g2 & 0xf00u) != 0u) refract<FWD, M, UNIT_W>(s, pol, r, v);
-    if ((g1 & 0xf03u) - 1u < 2u) refract<FWD, M, UNIT_W>(s, NoPoly{}, r, v);
-    if ((f0 & (3u | kFlagRefract)) == kFlagRefract)
-        refract<FWD, M, false, true>(s, NoPoly{}, r, v);            // a refracting plane (rare: it keeps both weight updates)
+    between(mask);
+    // (the visit word is read once more: a condition carried across `between` comes back as a lane mask, a v_cndmask
+    // and a v_cmp per visit)
+    const uint32_t g = apart(f);
+    if (g & kBendOther) {
+        if (g & kBendTerms) refract<FWD, M, UNIT_W>(s, pol, r, v);
+        if constexpr (M::kFused) {
+            if (g & kBendConic) refract<FWD, M, UNIT_W, false, kBendConic>(s, NoPoly{}, r, v);
+        } else {
+            if (g & kBendConic) refract<FWD, M, UNIT_W>(s, NoPoly{}, r, v);
+        }
+        if (g & kBendPlane)
+            refract<FWD, M, false, true>(s, NoPoly{}, r, v);        // a refracting plane (rare: it keeps both weight updates)
+    }
+    if constexpr (M::kFused) {
+        if (g & kBendSphere) refract<FWD, M, UNIT_W, false, kBendSphere>(s, NoPoly{}, r, v);
+    } else {
+        if (g & kBendSphere) refract<FWD, M, UNIT_W>(s, NoPoly{}, r, v);
+    }
     return mask;
 }
 

@@ -510,7 +510,7 @@ k_chief_center(TripTable trips /* kernarg offset 0 */, const DevSurface* __restr
     for (int s = threadIdx.x; s < sc_end; s += kFused, xcp += kFused, ycp += kFused, --left) {
         if (left > 0) prio_by_work_left(left);
         Ray r = make_ray<HotMath>(px, py, pzo, *xcp, *ycp, pzv);
-        trace_ray<true, HotMath, true, true>(lens, 0, K, kernarg_at(0), r, lds_mask);
+        trace_ray<true, HotMath, true, true, true>(lens, 0, K, kernarg_at(0), r, lds_mask);
         propagate_to<HotMath>(r, zsv);
         sx += (double)(r.ox * r.ra);
         sy += (double)(r.oy * r.ra);
@@ -563,7 +563,7 @@ k_chief_center_slope(TripTable trips /* kernarg offset 0 */, const DevSurface* _
     int any = 0;
     for (int s = threadIdx.x; s < sc_end; s += kFused, xcp += kFused, ycp += kFused) {
         Ray r = make_ray<HotMath>(px, py, pzo, *xcp, *ycp, pzv);
-        trace_ray<true, HotMath, true, true>(lens, 0, K, kernarg_at(0), r, lds_mask);
+        trace_ray<true, HotMath, true, true, true>(lens, 0, K, kernarg_at(0), r, lds_mask);
         propagate_to<HotMath>(r, zsv);
         sx += (double)(r.ox * r.ra);
         sy += (double)(r.oy * r.ra);
@@ -652,7 +652,7 @@ k_chief_slices(TripTable trips /* kernarg offset 0 */, SplitArgs sa, const DevSu
     GlobalF ycp = in_vgpr((GlobalF)yc + s0);
     for (int s = s0; s < s_end; s += kFused, xcp += kFused, ycp += kFused) {
         Ray r = make_ray<HotMath>(px, py, pzo, *xcp, *ycp, pzv);
-        trace_ray<true, HotMath, true, true>(lens, 0, K, trip_words, r, lds_mask);
+        trace_ray<true, HotMath, true, true, true>(lens, 0, K, trip_words, r, lds_mask);
         propagate_to<HotMath>(r, zsv);
         sx += (double)(r.ox * r.ra);
         sy += (double)(r.oy * r.ra);
@@ -914,7 +914,7 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, LoopBlock lb /* 64 */, PrimarySet
             Ray r = make_ray<HotMath>(px, py, pzo, kPin ? *xcp : ca.xc[s], kPin ? *ycp : ca.yc[s], pz);
             if constexpr (kPin) { xcp += THREADS; ycp += THREADS; }
             // (the masks of a call that asks for none are gathered all the same and dropped below: one flag less to keep)
-            trace_ray<true, HotMath, true, true>(ca.lens_c, 0, K, kernarg_at(kTripsCAt + 64 * w), r, lds_mask);
+            trace_ray<true, HotMath, true, true, true>(ca.lens_c, 0, K, kernarg_at(kTripsCAt + 64 * w), r, lds_mask);
             propagate_to<HotMath>(r, zs);
             sx += (double)(r.ox * r.ra);
             sy += (double)(r.oy * r.ra);
@@ -1032,7 +1032,7 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, LoopBlock lb /* 64 */, PrimarySet
             if (left > 0) prio_by_work_left(left);
             Ray r = make_ray<HotMath>(px, py, pzo, kPin ? *x2p : x2[s], kPin ? *y2p : y2[s], pz);
             if constexpr (kPin) { x2p += THREADS; y2p += THREADS; }
-            trace_ray<true, HotMath, true, true>(lens, 0, K, primary_trips, r, lds_mask);
+            trace_ray<true, HotMath, true, true, true>(lens, 0, K, primary_trips, r, lds_mask);
             propagate_to<HotMath>(r, zs);
             splat(r.ox, r.oy, r.dx, r.dz, r.ra);
         }

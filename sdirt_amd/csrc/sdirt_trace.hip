@@ -63,6 +63,7 @@ static DevSurface make_dev_surface(const sdirt_surface_desc& in)
     const bool do_refract = in.kind == SDIRT_PLANE ? (eta_f != 1.0) : true;
     h.flags = (uint32_t)in.kind | (do_refract ? kFlagRefract : 0u) | (in.k > -1.0f ? kFlagKgtM1 : 0u) |
               (in.c > 0.0f ? kFlagCpos : 0u) | (h.onepk == 1.0f ? kFlagUnitK : 0u) | ((uint32_t)deg << 8);
+    h.flags |= visit_bits(h.flags);               // the path each half of a visit takes, decoded here once per surface
     for (int i = 0; i < kMaxAi; ++i) {
         s.p.ai[i] = i < deg ? in.ai[i] : 0.0f;
         s.p.kai[i] = (float)(i + 1) * s.p.ai[i];

@@ -46,7 +46,8 @@ __device__ __forceinline__ void lds_or_first_lane(uint32_t* p, uint32_t m)
 // reference form the load-time selftest compares the prefetching loop against).
 // UNIT_W: every ray's weight is exactly 0 or 1 (the fused kernels: make_ray's 1, then 0/1 flags only) -- one weight
 // update per visit (refract()).
-template <bool FWD, class M = Ieee, bool PREFETCH = true, bool UNIT_W = false>
+// MASKS: lds_mask is never null (the fused kernels gather the masks whether the call asks for them or not).
+template <bool FWD, class M = Ieee, bool PREFETCH = true, bool UNIT_W = false, bool MASKS = false>
 __device__ __forceinline__ void trace_ray(const DevSurface* __restrict__ lens, int first, int last,
                                           const void* trip_words, Ray& r, uint32_t* lds_mask)
 {
@@ -57,19 +58,29 @@ __device__ __forceinline__ void trace_ray(const DevSurface* __restrict__ lens, i
     surf_issue<FWD>(cur, lens + k, trip_words, k);
     surf_wait(cur);
     for (int step = 0; step < n; ++step) {
-        // the constants of the next surface (of this one again after the last: a harmless load)
-        const int kn = step + 1 < n ? (FWD ? k + 1 : k - 1) : k;
         SurfRaw nxt;
         Surf s;
         s.a = cur.a; s.b = cur.b;
-        const uint32_t m = surface_reaction<FWD, M, UNIT_W>(s, lens + k, surf_trips(cur, k), r, [&] {
-            if (PREFETCH) surf_issue<FWD>(nxt, lens + kn, trip_words, kn);
+        // the constants of the next surface (of this one again after the last: a harmless load)
+        // (k +- the compare's carry, written out and in place, and an unsigned byte offset: two and three scalar
+        // instructions, where the select and the 64-bit index of `lens + kn` took five and four)
+        auto issue_next = [&] {
+            if (FWD) asm("s_cmp_lt_u32 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(k) : "s"(step + 1), "s"(n) : "scc");
+            else asm("s_cmp_lt_u32 %1, %2\n\ts_subb_u32 %0, %0, 0" : "+s"(k) : "s"(step + 1), "s"(n) : "scc");
+            static_assert(sizeof(DevSurface) == 128, "the shift below");
+            surf_issue<FWD>(nxt, (const DevSurface*)((const char*)lens + ((uint32_t)k << 7)), trip_words, k);
+        };
+        // The visit's mask goes to LDS between its halves, ahead of the prefetch: nothing reads k behind that point, so
+        // the next index is formed in k's own register and nothing is copied for it at the back edge.
+        // (MASKS: `lds_mask && m != 0u` with an lds_mask that is never null still came out as two 64-bit masks, an
+        // s_or_b64 and a branch on vcc -- six scalar instructions per visit for a compare and a branch)
+        surface_reaction<FWD, M, UNIT_W>(s, lens + k, surf_trips(cur, k), r, [&](uint32_t m) {
+            if (MASKS ? m != 0u : lds_mask && m != 0u) lds_or_first_lane(&lds_mask[k], m);
+            if (PREFETCH) issue_next();
         });
-        if (lds_mask && m != 0u) lds_or_first_lane(&lds_mask[k], m);
-        if (!PREFETCH) surf_issue<FWD>(nxt, lens + kn, trip_words, kn);
+        if (!PREFETCH) issue_next();
         surf_wait(nxt);
         cur = nxt;
-        k = kn;
     }
 }
 

@@ -58,7 +58,7 @@ k_trace_record(TripTable trips /* kernarg offset 0 */, const DevSurface* __restr
             surf_wait(raw);
             Surf s;
             s.a = raw.a; s.b = raw.b;
-            const uint32_t m = surface_reaction<true, MP>(s, lens + k, surf_trips(raw, k), r, [] {});
+            const uint32_t m = surface_reaction<true, MP>(s, lens + k, surf_trips(raw, k), r, [](uint32_t) {});
             if (conv_mask && m != 0u) lds_or_first_lane(&lds_mask[k], m);
         }
         store_ckpt(ws, M, K, i, r);
