@@ -340,6 +340,21 @@ int sdirt_trace2sensor_grad(const sdirt_lens* lens, const int32_t* trips /*host 
                             const float* ray_grad /*dev [4,n_rays]*/, int64_t n_rays,
                             double* partial /*dev [n_workgroups,K,3+SDIRT_MAX_AI]*/, int32_t n_workgroups, void* stream);
 
+/* sdirt_trace2sensor_grad with ONE MORE column: partial is [n_workgroups, K, 3 + SDIRT_MAX_AI + 1], its last column
+ * dLoss/d eta_k of the recorded trace, eta_k = n1 / n2 of surface k taken as a parameter of the refraction
+ * d' = sr n + eta (d - cosi n), sr = sqrt(1 - eta^2 (1 - cosi^2)) (deeplens/surfaces.py:44-53, 401-405, 633-669 with
+ * eta in the graph; the caller's chain rule through eta_k = n_k(lambda) / n_k+1(lambda) gives the gradient in n and V
+ * of every medium, basics.py:316-362).  Per ray the term is g . (d - cosi n) - eta (1 - cosi^2) / sr (g . n), g the
+ * adjoint of d' on arrival; the validity tests of the refraction are the forward's decisions without a gradient.  The
+ * column is owned by every surface that refracts (every curved surface, and a plane between different media) and is
+ * exactly 0 elsewhere (the stop).  The first 3 + SDIRT_MAX_AI columns are what sdirt_trace2sensor_grad returns.  Same
+ * arguments, same checks (n_workgroups = sdirt_trace2sensor_grad_workgroups, trips >= 0), no atomics. */
+int sdirt_trace2sensor_grad_eta(const sdirt_lens* lens, const int32_t* trips /*host [K]*/, uint32_t flags, double d_sensor,
+                                const void* workspace /*dev*/, const float* ra /*dev [n_rays]*/,
+                                const float* ray_grad /*dev [4,n_rays]*/, int64_t n_rays,
+                                double* partial /*dev [n_workgroups,K,3+SDIRT_MAX_AI+1]*/, int32_t n_workgroups,
+                                void* stream);
+
 /* deeplens/optics.py:983-987: psf / (max + 1e-6), per point, in place. */
 int sdirt_psf_normalize(float* psf /*dev [N,ks,ks]*/, int64_t n_points, int32_t ks, void* stream);
 

@@ -2,7 +2,7 @@
 // surfaces.py:391-679 under autograd): the gradients of a loss with respect to the lens prescription -- every surface's
 // d, c, k and ai -- given its gradients with respect to the sensor-plane rays (sdirt_forward_integral_grad_rays).
 //
-// Two kernels.
+// Three kernels.
 //  k_trace_record: sdirt_trace2sensor's trace (the same device functions, surface by surface, the constants loaded
 //      and waited for on the spot) that also stores every ray's (o, d) on ENTRY to each surface and before the final
 //      propagation: the checkpoints, [K + 1][6][M] fp32.
@@ -17,6 +17,9 @@
 //  Reduction: the terms of the surface being walked are summed across the wave with shuffles and added, by lane 0, to
 //      the wave's own float64 row in LDS; after the walk the rows of the workgroup's waves are added in a fixed order
 //      and ONE [K, 3 + SDIRT_MAX_AI] float64 block is stored per workgroup.  No atomics: the same bits every run.
+//  k_trace_grad_eta: the same walk with one more column per surface, dLoss/d eta of its refraction (eta = n1 / n2 as a
+//      leaf: deeplens/surfaces.py:44-53, 401-405, 633-669; Python's chain rule takes it to n and V of every medium,
+//      basics.py:316-362).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -189,6 +192,17 @@ __device__ __forceinline__ void refract_adjoint(double eta, double vx, double vy
     gx = eta * gx + cb * nx; gy = eta * gy + cb * ny; gz = eta * gz + cb * nz;
 }
 
+// The same refraction's derivative in eta (surfaces.py:663-669 with eta a leaf): d d'/d eta = (d - cosi n) - eta (1 - cosi^2) / sr n,
+// taken with the adjoint g of d' AS IT ARRIVES, i.e. before refract_adjoint overwrites it.
+__device__ __forceinline__ double refract_eta_bar(double eta, double vx, double vy, double vz, double nx, double ny, double nz,
+                                                  double gx, double gy, double gz)
+{
+    const double cosi = vx * nx + vy * ny + vz * nz;
+    const double sr = sqrt(1.0 - eta * eta * (1.0 - cosi * cosi));
+    const double gn = gx * nx + gy * ny + gz * nz;
+    return gx * (vx - cosi * nx) + gy * (vy - cosi * ny) + gz * (vz - cosi * nz) - eta * (1.0 - cosi * cosi) / sr * gn;
+}
+
 // o' = o + t d with t = (z - o.z) / d.z: the adjoint of (o, d) from the adjoint of o' (in A.o*) and of d (in A.d*);
 // returns the adjoint of z
 __device__ __forceinline__ double plane_adjoint(double t, double vx, double vy, double vz, Adj& A)
@@ -218,6 +232,8 @@ __device__ __forceinline__ Ray load_ckpt(const float* __restrict__ ws, int64_t M
 
 // The adjoint of one curved surface for a live ray: r = the ray on entry, P = its position on the surface (the next
 // checkpoint's o), A = in: the adjoint of the ray that leaves, out: of the ray that enters; par += the parameter terms.
+// ETA (k_trace_grad_eta): par[kParams] = the term of eta as well.
+template <bool ETA>
 __device__ __forceinline__ void curved_adjoint(const SurfHot& h, const double* a, int deg, const Ray& r, const Regain& rg,
                                                double Px, double Py, double Pz, Adj& A, double* par)
 {
@@ -237,6 +253,7 @@ __device__ __forceinline__ void curved_adjoint(const SurfHot& h, const double* a
     const double nrm = sqrt(Nx * Nx + Ny * Ny + Nz * Nz);
     const double nx = -Nx / nrm, ny = -Ny / nrm, nz = -Nz / nrm;       // forward: the normal is negated (surfaces.py:656)
     double nbx, nby, nbz;
+    if constexpr (ETA) par[kParams] = refract_eta_bar(eta, vx, vy, vz, nx, ny, nz, A.dx, A.dy, A.dz);
     refract_adjoint(eta, vx, vy, vz, nx, ny, nz, A.dx, A.dy, A.dz, nbx, nby, nbz);
     const double nn = nbx * nx + nby * ny + nbz * nz;
     const double Nbx = -(nbx - nn * nx) / nrm, Nby = -(nby - nn * ny) / nrm, Nbz = -(nbz - nn * nz) / nrm;
@@ -339,7 +356,7 @@ k_trace_grad(TripTable trips, const DevSurface* __restrict__ lens, int K, const 
                     rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, NoPoly{}, r, trip)
                                                 : newton_regain<MP, false>(h, NoPoly{}, r, trip);
                 }
-                curved_adjoint(h, a, deg, r, rg, Px, Py, Pz, A, par);
+                curved_adjoint<false>(h, a, deg, r, rg, Px, Py, Pz, A, par);
             }
             Px = r.ox; Py = r.oy; Pz = r.oz;
             // the columns this surface owns (Aspheric.activate_grad, surfaces.py:837-860): d; c unless a plane; k of an
@@ -360,6 +377,92 @@ k_trace_grad(TripTable trips, const DevSurface* __restrict__ lens, int K, const 
         double v = 0.0;
         for (int w = 0; w < kAdjWaves; ++w) v += acc[w][k][c];
         partial[(int64_t)blockIdx.x * K * kParams + e] = v;
+    }
+}
+
+// k_trace_grad with one more column per surface: dLoss/d eta of its refraction, for every surface that refracts (every
+// curved one, and a plane between different media; the stop's stays exactly 0).  The term is taken from the adjoint of
+// d' before refract_adjoint overwrites it, in curved_adjoint and in the plane branch.  A kernel of its own: a walk
+// shared with k_trace_grad moved that kernel's register allocation (tools/isa_compare.py).
+constexpr int kParamsEta = kParams + 1;
+
+template <class MP>
+__global__ void __launch_bounds__(kBlock)
+k_trace_grad_eta(TripTable trips, const DevSurface* __restrict__ lens, int K, const float* __restrict__ ws,
+                 const float* __restrict__ ra, const float* __restrict__ ray_grad, int64_t M, float z_sensor,
+                 double* __restrict__ partial)
+{
+    __shared__ double acc[kAdjWaves][SDIRT_MAX_SURFACES][kParamsEta];
+    for (int e = threadIdx.x; e < kAdjWaves * SDIRT_MAX_SURFACES * kParamsEta; e += kBlock) (&acc[0][0][0])[e] = 0.0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t base = (int64_t)blockIdx.x * kBlock; base < M; base += (int64_t)gridDim.x * kBlock) {
+        const int64_t i = base + threadIdx.x;
+        Adj A{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        bool live = false;
+        if (i < M && ra[i] != 0.0f) {
+            A.ox = ray_grad[i]; A.oy = ray_grad[M + i]; A.dx = ray_grad[2 * M + i]; A.dz = ray_grad[3 * M + i];
+            live = A.ox != 0.0 || A.oy != 0.0 || A.dx != 0.0 || A.dz != 0.0;
+        }
+        if (__ballot(live) == 0ull) continue;
+        const int64_t ii = i < M ? i : M - 1;                 // idle lanes read a ray that exists and contribute nothing
+        {   // the final propagation to the sensor plane: in the ray only
+            const Ray r = load_ckpt(ws, M, K, ii);
+            const double t = ((double)z_sensor - (double)r.oz) / (double)r.dz;
+            (void)plane_adjoint(t, r.dx, r.dy, r.dz, A);
+        }
+        float Px = ws[ckpt_at(M, K, 0, ii)], Py = ws[ckpt_at(M, K, 1, ii)], Pz = ws[ckpt_at(M, K, 2, ii)];
+        for (int k = K - 1; k >= 0; --k) {
+            const SurfHot& h = lens[k].h;
+            const Ray r = load_ckpt(ws, M, k, ii);
+            const int kind = (int)(h.flags & 3u), deg = (int)((h.flags >> 8) & 15u);
+            double par[kParamsEta];
+#pragma unroll
+            for (int c = 0; c < kParamsEta; ++c) par[c] = 0.0;
+            if (kind == 0) {
+                if (h.flags & kFlagRefract) {
+                    double nbx, nby, nbz;
+                    par[kParams] = refract_eta_bar((double)h.eta_f, r.dx, r.dy, r.dz, 0.0, 0.0, 1.0, A.dx, A.dy, A.dz);
+                    refract_adjoint((double)h.eta_f, r.dx, r.dy, r.dz, 0.0, 0.0, 1.0, A.dx, A.dy, A.dz, nbx, nby, nbz);
+                }
+                const double t = ((double)h.d - (double)r.oz) / (double)r.dz;
+                par[0] = plane_adjoint(t, r.dx, r.dy, r.dz, A);
+            } else {
+                const int trip = (int)(int8_t)(trips.w[k >> 2] >> ((k & 3) * 8));
+                double a[kMaxAi];
+                Regain rg;
+                if (deg > 0) {
+                    PolyF pol;
+#pragma unroll
+                    for (int c = 0; c < kMaxAi; ++c) { pol.a[c] = lens[k].p.ai[c]; pol.ka[c] = lens[k].p.kai[c]; a[c] = pol.a[c]; }
+                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, pol, r, trip) : newton_regain<MP, false>(h, pol, r, trip);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < kMaxAi; ++c) a[c] = 0.0;
+                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, NoPoly{}, r, trip)
+                                                : newton_regain<MP, false>(h, NoPoly{}, r, trip);
+                }
+                curved_adjoint<true>(h, a, deg, r, rg, Px, Py, Pz, A, par);
+            }
+            Px = r.ox; Py = r.oy; Pz = r.oz;
+            // the columns of k_trace_grad, and eta for every surface that refracts; every other column stays exactly 0
+            const bool own_k = kind == 2 && h.k != 0.0f, own_eta = (h.flags & kFlagRefract) != 0u;
+#pragma unroll
+            for (int c = 0; c < kParamsEta; ++c) {
+                const bool own = c == 0 || (c == 1 && kind != 0) || (c == 2 && own_k) || (c >= 3 && c < kParams && c - 3 < deg) ||
+                                 (c == kParams && own_eta);
+                if (!own) continue;                                          // wave-uniform
+                const double v = wave_sum(live ? par[c] : 0.0);
+                if (lane == 0) acc[wave][k][c] += v;
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < K * kParamsEta; e += kBlock) {
+        const int k = e / kParamsEta, c = e - k * kParamsEta;
+        double v = 0.0;
+        for (int w = 0; w < kAdjWaves; ++w) v += acc[w][k][c];
+        partial[(int64_t)blockIdx.x * K * kParamsEta + e] = v;
     }
 }
 
@@ -405,9 +508,10 @@ int sdirt_trace2sensor_record(const sdirt_lens* lens, const int32_t* trips, uint
     return SDIRT_OK;
 }
 
-int sdirt_trace2sensor_grad(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, double d_sensor,
-                            const void* workspace, const float* ra, const float* ray_grad, int64_t M, double* partial,
-                            int32_t n_workgroups, void* stream)
+// sdirt_trace2sensor_grad (eta = false) and sdirt_trace2sensor_grad_eta (true): one argument check, one launch
+static int launch_trace_grad(bool eta, const sdirt_lens* lens, const int32_t* trips, uint32_t flags, double d_sensor,
+                             const void* workspace, const float* ra, const float* ray_grad, int64_t M, double* partial,
+                             int32_t n_workgroups, void* stream)
 {
     if (!lens || !workspace || !ra || !ray_grad || !partial) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
     TripTable tt;
@@ -423,12 +527,27 @@ int sdirt_trace2sensor_grad(const sdirt_lens* lens, const int32_t* trips, uint32
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_workgroups=%d, the launch has %d (sdirt_trace2sensor_grad_workgroups)",
                     n_workgroups, grid);
     with_math(flags, [&](auto m) {
-        k_trace_grad<decltype(m)><<<grid, kBlock, 0, as_stream(stream)>>>(
+        auto* kernel = eta ? k_trace_grad_eta<decltype(m)> : k_trace_grad<decltype(m)>;
+        kernel<<<grid, kBlock, 0, as_stream(stream)>>>(
             tt, lens->dev, lens->n_surfaces, (const float*)workspace, ra, ray_grad, M, (float)d_sensor, partial);
         return 0;
     });
     LAUNCH_CHECK();
     return SDIRT_OK;
+}
+
+int sdirt_trace2sensor_grad(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, double d_sensor,
+                            const void* workspace, const float* ra, const float* ray_grad, int64_t M, double* partial,
+                            int32_t n_workgroups, void* stream)
+{
+    return launch_trace_grad(false, lens, trips, flags, d_sensor, workspace, ra, ray_grad, M, partial, n_workgroups, stream);
+}
+
+int sdirt_trace2sensor_grad_eta(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, double d_sensor,
+                                const void* workspace, const float* ra, const float* ray_grad, int64_t M, double* partial,
+                                int32_t n_workgroups, void* stream)
+{
+    return launch_trace_grad(true, lens, trips, flags, d_sensor, workspace, ra, ray_grad, M, partial, n_workgroups, stream);
 }
 
 }  // extern "C"

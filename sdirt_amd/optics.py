@@ -15,6 +15,7 @@ libsdirt_dp.so is not built or no MI355X is visible.
 import contextlib
 import ctypes as C
 import json
+import math
 import types
 import weakref
 
@@ -22,11 +23,11 @@ import numpy as np
 import torch
 
 from . import _hostrng, _lib, basics
-from .basics import DEFAULT_WAVE, DEPTH, GEO_SPP, WAVE_RGB, Ray, dptr, stream_ptr
+from .basics import DEFAULT_WAVE, DEPTH, GEO_SPP, WAVE_RGB, Material, Ray, dptr, stream_ptr
 from .monte_carlo import _requires_grad, splat_autograd
 from .newton import NEWTON_MAXITER, TripPlanner
 from .surfaces import Aspheric
-from .trace_grad import N_COLUMNS, SurfaceGradFunction, TraceRecord
+from .trace_grad import N_COLUMNS, SurfaceGradFunction, TraceRecord, glass_eta
 
 
 def _as_device(device):
@@ -329,6 +330,98 @@ class Lensgroup:
             self._dev, self._pupil_cache, self.trips = saved[:3]
             if saved[3] is not None:
                 self.__dict__["_curved_cache"] = saved[3]
+
+    # ------------------------------------------------------- glass parameters
+    def _media(self):
+        """The K + 1 media as lists of the Material objects that hold them: medium j is surfaces[j].mat1 and
+        surfaces[j-1].mat2, medium K is surfaces[K-1].mat2.  ValueError when the two objects of one medium disagree."""
+        K = len(self.surfaces)
+        media = [[self.surfaces[0].mat1]] + [[self.surfaces[j - 1].mat2, self.surfaces[j].mat1] for j in range(1, K)] \
+            + [[self.surfaces[K - 1].mat2]]
+        for j, objs in enumerate(media):
+            a, b = objs[0], objs[-1]
+            if (a.n, a.V, a.dispersion) != (b.n, b.V, b.dispersion):
+                raise ValueError(f"medium {j}: surface {j - 1} leaves into {a.name!r} and surface {j} starts in {b.name!r}")
+        return media
+
+    def glass_owned(self):
+        """bool [K + 1]: the media that are parameters with a gradient -- the Cauchy glasses written as 'n/V' strings
+        (Material.dispersion == 'naive').  Air-like media and register_material() glasses are constants."""
+        return torch.tensor([objs[0].dispersion == "naive" for objs in self._media()])
+
+    def glass_parameters(self):
+        """The glass as ONE tensor: a fresh float64 CPU tensor [K + 1, 2], columns n, V, row j = medium j (medium j lies
+        in front of surface j; medium K behind the last surface).  What `glass_params=` of psf_lr / psf_diff / psf_rgb /
+        psf_volume takes; the rows that are parameters are glass_owned().  Every other row holds (Material.n, V or 0
+        for an infinite V) and must stay as it is."""
+        return torch.tensor([[objs[0].n, 0.0 if math.isinf(objs[0].V) else objs[0].V] for objs in self._media()],
+                            dtype=torch.float64).reshape(-1, 2)
+
+    def _glass_values(self, glass):
+        """glass_parameters()-shaped values checked against the lens: -> (float64 numpy [K + 1, 2], the media)."""
+        media = self._media()
+        v = torch.as_tensor(glass).detach().to("cpu", torch.float64).numpy()
+        if v.shape != (len(media), 2):
+            raise ValueError(f"glass parameters must have shape [{len(media)}, 2]")
+        now = self.glass_parameters().numpy()
+        for j, objs in enumerate(media):
+            if objs[0].dispersion == "naive":
+                if not (np.isfinite(v[j]).all() and v[j, 0] > 1.0 and v[j, 1] > 0.0):
+                    raise ValueError(f"medium {j}: a glass needs finite n > 1 and V > 0, got {v[j].tolist()}")
+            elif not np.array_equal(v[j], now[j]):
+                raise ValueError(f"medium {j} ({objs[0].name!r}) is a constant, not a parameter of this lens")
+        return v, media
+
+    @staticmethod
+    def _write_glass(mat, n, V):
+        mat.n, mat.V = n, V
+        mat.A, mat.B = Material.nV_to_AB(n, V)
+        mat.name = f"{n!r}/{V!r}"
+
+    def set_glass_parameters(self, glass):
+        """Write glass_parameters()-shaped values back: n, V, the Cauchy A and B and the 'n/V' name of both Material objects
+        of every owned medium (write_lens_json -> read_lens_json then gives the lens back bit for bit).  ValueError,
+        and no object changed, on a wrong shape, a non-finite value, n <= 1 or V <= 0 in an owned row, or a constant's row
+        that differs from glass_parameters().  Device tables, pupils and planner are dropped, as by
+        set_surface_parameters."""
+        values, media = self._glass_values(glass)
+        for row, objs in zip(values, media):
+            if objs[0].dispersion == "naive":
+                for m in objs:
+                    self._write_glass(m, float(row[0]), float(row[1]))
+        self._invalidate()
+        self.trips = TripPlanner()
+        return self
+
+    @contextlib.contextmanager
+    def _glass_borrowed(self, glass):
+        """The lens as set_glass_parameters(glass) would make it, for the duration of one call: afterwards (also on an
+        exception) every Material field is the old value and the device tables, pupils and planner are the old OBJECTS.
+        Nothing is touched when the values are already the lens's."""
+        values, media = self._glass_values(glass)
+        if np.array_equal(values, self.glass_parameters().numpy()):
+            yield
+            return
+        old = [[(m, m.n, m.V, m.A, m.B, m.name) for m in objs] for objs in media]
+        saved = (self._dev, self._pupil_cache, self.trips, self.__dict__.get("_curved_cache"))
+        try:
+            self._dev, self._pupil_cache = {}, {}
+            self.set_glass_parameters(values)
+            yield
+        finally:
+            for objs in old:
+                for m, n, V, A, B, name in objs:
+                    m.n, m.V, m.A, m.B, m.name = n, V, A, B, name
+            self._dev, self._pupil_cache, self.trips = saved[:3]
+            if saved[3] is not None:
+                self.__dict__["_curved_cache"] = saved[3]
+
+    def _glass_eta(self, glass, wvln):
+        """trace_grad.glass_eta of this lens: eta [K] at `wvln` as a float64 torch function of `glass`."""
+        wv = wvln if wvln < 10 else wvln * 1e-3
+        media = self._media()
+        return glass_eta(glass.cpu(), [objs[0].dispersion == "naive" for objs in media],
+                         [float(objs[0].ior(wv)) for objs in media], wv)
 
     @contextlib.contextmanager
     def _sensor_borrowed(self, d_sensor):
@@ -886,14 +979,14 @@ class Lensgroup:
         return self.psf_diff(points=points, wvln=wvln, ks=ks, spp=spp, center=center)
 
     def psf_diff(self, points, wvln=DEFAULT_WAVE, ks=31, spp=GEO_SPP, center=True,
-                 param_list=None, _defer=False, surface_params=None, d_sensor=None):
+                 param_list=None, _defer=False, surface_params=None, d_sensor=None, glass_params=None):
         """optics.py:934-996: normalised points [N,3] (or [3]) -> max-normalised
         PSF [N,ks,ks] (or [ks,ks]) of the left sub-pixel (right if param_list[4] != 'l').
-        d_sensor: the sensor position of this call (psf_lr)."""
+        d_sensor: the sensor position of this call; glass_params: its glass (psf_lr)."""
         dp, right = _parse_param_list(param_list)
         res = self.psf_lr(points, ks=ks, wvln=wvln, spp=spp, center=center, dp=dp, want_r=right,
                           _default_r_zero=(param_list is None), defer=_defer, surface_params=surface_params,
-                          d_sensor=d_sensor)
+                          d_sensor=d_sensor, glass_params=glass_params)
         pick = (lambda lr: lr[1]) if right else (lambda lr: lr[0])
         if _defer:
             return PendingPSF(lambda: pick(res.wait()))
@@ -970,7 +1063,7 @@ class Lensgroup:
     def psf_lr(self, points, ks=31, wvln=DEFAULT_WAVE, spp=GEO_SPP, center=True,
                dp=(0.78, 1.44, 0.3, 0.5), normalize=True, want_r=True, _default_r_zero=False,
                pupil_xy=None, center_pupil_xy=None, out=None, defer=False, center_out=None, surface_params=None,
-               d_sensor=None, _focus=None):
+               d_sensor=None, _focus=None, glass_params=None):
         """Left AND right dual-pixel PSFs of one ray-traced batch: (L, R), each
         [N,ks,ks] (or [ks,ks] for a single point), max-normalised separately as
         optics.py:983-987 would normalise each of them.  dp = (h, f, w, r) of
@@ -1015,14 +1108,23 @@ class Lensgroup:
         a ray meets the sensor plane at o' + d (s - o'.z) / d.z, so the splat shifts by d.xy / d.z per unit of s, and
         with center=True the chief-ray centre moves with the sensor as well, which is part of the derivative (the
         reference keeps that centre out of its graph).  The points' z are positions in the lens frame
-        and do not move with the sensor; hfov, r_last and the pinhole scale stay constants."""
+        and do not move with the sensor; hfov, r_last and the pinhole scale stay constants.
+
+        glass_params: a glass_parameters()-shaped tensor [K + 1, 2] (n, V of every medium), next to surface_params.
+        When it requires a gradient the PSFs are those of the lens set_glass_parameters(glass.detach()) would make -- the
+        Material objects are put back afterwards -- and loss.backward() fills its .grad with the gradient the
+        reference's graph gives n and V of every owned medium (glass_owned(); the other rows get exactly 0) at this
+        call's wavelength: eta = n1(lambda) / n2(lambda) of every refraction carries it; the pupil, the
+        chief-ray centres and every validity test stay constants.  Otherwise the call is set_glass_parameters(glass)
+        followed by the ordinary call.  defer, out=, center_out= and trip_policy='adaptive' are refused with a gradient
+        as they are for surface_params; all of surface_params, glass_params and d_sensor may require one in one call."""
         if d_sensor is not None:
             focus = d_sensor if _requires_grad(d_sensor) else None
             if focus is not None and focus.numel() != 1:
                 raise ValueError("d_sensor must be a 0-d (one-element) tensor to get a gradient")
             with self._sensor_borrowed(d_sensor):
                 res = self.psf_lr(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
-                                  center_pupil_xy, out, defer, center_out, surface_params, None, focus)
+                                  center_pupil_xy, out, defer, center_out, surface_params, None, focus, glass_params)
             if isinstance(res, PendingPSF):
                 # the trip check of a deferred call may launch again: with this call's sensor position
                 def finish(pending=res):
@@ -1031,13 +1133,21 @@ class Lensgroup:
                 return PendingPSF(finish)
             return res
         focus_kw = {} if _focus is None else {"focus": _focus}
-        if surface_params is not None:
+        if glass_params is not None and not _requires_grad(glass_params):
+            self.set_glass_parameters(glass_params)
+            glass_params = None
+        if surface_params is not None and not _requires_grad(surface_params):
+            self.set_surface_parameters(surface_params)
+            surface_params = None
+        if surface_params is not None or glass_params is not None:
             args = (points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy, center_pupil_xy,
                     out, defer, center_out)
-            if _requires_grad(surface_params):
-                with self._surfaces_borrowed(surface_params):
-                    return self._psf_lr_grad(*args, surface_params=surface_params, **focus_kw)
-            self.set_surface_parameters(surface_params)
+            with contextlib.ExitStack() as borrowed:
+                if surface_params is not None:
+                    borrowed.enter_context(self._surfaces_borrowed(surface_params))
+                if glass_params is not None:
+                    borrowed.enter_context(self._glass_borrowed(glass_params))
+                return self._psf_lr_grad(*args, surface_params=surface_params, glass_params=glass_params, **focus_kw)
         if _psf_needs_grad(dp if not _default_r_zero else None, points, center, _focus):
             return self._psf_lr_grad(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero,
                                      pupil_xy, center_pupil_xy, out, defer, center_out, **focus_kw)
@@ -1374,7 +1484,7 @@ class Lensgroup:
         return TraceRecord(dev_lens, trips, self.precision, self.d_sensor, ws, ray, K)
 
     def _psf_lr_grad(self, points, ks, wvln, spp, center, dp, normalize, want_r, default_r_zero, pupil_xy,
-                     center_pupil_xy, out, defer, center_out, surface_params=None, focus=None):
+                     center_pupil_xy, out, defer, center_out, surface_params=None, focus=None, glass_params=None):
         """psf_lr under autograd: the staged chain's rays and centres (no gradient: optics.py:459, :888 are no_grad),
         then the RAW grids through monte_carlo.SplatFunction -- differentiable in h, f, w and, with center=False, in
         the pinhole centres points[:, :2] * sensor_size / 2 (optics.py:973-976) -- and the max-normalisation of
@@ -1397,8 +1507,9 @@ class Lensgroup:
             cen = torch.empty((N, 2), dtype=torch.float32, device=self.device)
             cen_slope = (torch.empty((N, 2), dtype=torch.float64, device=self.device)
                          if focus is not None and center else None)
+            record = surface_params is not None or glass_params is not None
             staged = self._staged_rays(points.detach(), po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen,
-                                       record=surface_params is not None, cen_slope=cen_slope)
+                                       record=record, cen_slope=cen_slope)
             ray, spp = staged[:2]
         if not center:
             # the pinhole centres of _pinhole_centres as torch ops on the caller's points: the same fp32 products
@@ -1406,12 +1517,14 @@ class Lensgroup:
             cen = torch.stack((pts[:, 0] * (self.sensor_size[1] / 2), pts[:, 1] * (self.sensor_size[0] / 2)), -1)
         param_list = None if (dp is None or default_r_zero) else (*dp[:4], "l")
         L, R = splat_autograd(ray, self.pixel_size, ks, cen, param_list, self.precision, focus, cen_slope)
-        if surface_params is not None:
+        if record:
             # the rays' share of the graph: dLoss/d(raw grids) -> the sensor-plane rays -> the recorded trace -> theta
+            # and eta(glass) (the lens is the borrowed one: its constants' indices are those the device table holds)
             dpp = None if param_list is None else _lib.DpParams(*[float(v) for v in param_list[:4]])
             cen_c = cen.detach().to(self.device, torch.float32).reshape(N, 2).contiguous()
             staged[2].center = cen_c
-            L, R = SurfaceGradFunction.apply(surface_params, L, R, staged[2], cen_c, self.pixel_size, ks, dpp)
+            eta = None if glass_params is None else self._glass_eta(glass_params, wvln)
+            L, R = SurfaceGradFunction.apply(surface_params, eta, L, R, staged[2], cen_c, self.pixel_size, ks, dpp)
         if normalize:
             L = L / (L.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
             R = R / (R.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
@@ -1420,7 +1533,7 @@ class Lensgroup:
         return _epilogue(L, R, want_r, single_point)
 
     def psf_volume(self, grid=(32, 32), z=16, ks=21, spp=GEO_SPP, dp=(0.78, 1.44, 0.3, 0.5), wvln=DEFAULT_WAVE,
-                   surface_params=None, pupil_xy=None, center_pupil_xy=None, d_sensor=None):
+                   surface_params=None, pupil_xy=None, center_pupil_xy=None, d_sensor=None, glass_params=None):
         """The ray-traced PSF grid of the whole field and depth range as a render_psf.PSFVolume, for
         local_dp_psf_render_volume / PSFNet.render_volume: grid = (rows, columns) of cell-centred sensor nodes
         (psfnet.py:220-226: x from -1 + 1/(2 gx) to 1 - 1/(2 gx), y from 1 - 1/(2 gy) down), z = a number of depth
@@ -1429,12 +1542,12 @@ class Lensgroup:
         Lensgroup, psfnet.py:15-16).
 
         ONE psf_lr call on the Dz*Gy*Gx points, so it is differentiable exactly where psf_lr is (h, f, w of dp,
-        surface_params, the call's sensor position d_sensor); L and R are stacked and each divided by its own sum with torch ops, which keeps the graph.
+        surface_params, glass_params, the call's sensor position d_sensor); L and R are stacked and each divided by its own sum with torch ops, which keeps the graph.
 
         wvln: a number -> psf [Dz,Gy,Gx,2,ks,ks].  A sequence of wavelengths (WAVE_RGB: the three of psf_rgb,
         optics.py:999-1015) -> a CHROMATIC volume, psf [Cw,Dz,Gy,Gx,2,ks,ks]: one psf_lr call per wavelength on the same
-        points, each centred through the green lens as every psf_lr call is, with the same dp, surface_params and
-        d_sensor (the gradient of a shared parameter is the sum over the wavelengths), stacked on a new leading axis;
+        points, each centred through the green lens as every psf_lr call is, with the same dp, surface_params,
+        glass_params and d_sensor (the gradient of a shared parameter is the sum over the wavelengths), stacked on a new leading axis;
         psf[c] is the volume of wvln[c], rendered into image channel c.  pupil_xy / center_pupil_xy are then either
         (x[spp], y[spp]), shared by the wavelengths, or per wavelength, [2, Cw, spp] / [2, Cw, 2048] (psf_rgb's
         convention); without them every wavelength draws fresh samples, in the order given."""
@@ -1462,7 +1575,7 @@ class Lensgroup:
         for i, w in enumerate(waves):
             L, R = self.psf_lr(points, ks=ks, wvln=w, spp=spp, dp=dp, pupil_xy=samples_of(pupil_xy, i),
                                center_pupil_xy=samples_of(center_pupil_xy, i), surface_params=surface_params,
-                               d_sensor=d_sensor)
+                               d_sensor=d_sensor, glass_params=glass_params)
             psf = torch.stack((L, R), -3)                                          # [N, 2, ks, ks]
             psf = psf / psf.sum((-1, -2), keepdim=True).clamp_min(1e-30)           # (a node no ray reaches stays 0)
             psfs.append(psf.reshape(len(z_nodes), gy, gx, 2, ks, ks))
@@ -1472,7 +1585,7 @@ class Lensgroup:
         return vol
 
     def psf_rgb(self, points, ks=31, spp=GEO_SPP, center=True, param_list=None, pupil_xy=None,
-                center_pupil_xy=None, surface_params=None, d_sensor=None):
+                center_pupil_xy=None, surface_params=None, d_sensor=None, glass_params=None):
         """optics.py:999-1015: [N,3,ks,ks] (or [3,ks,ks]) -- the three wavelengths of WAVE_RGB, each an
         independent psf_diff (fresh pupil draws, in the reference's order; every chief-ray centre
         through the green lens).  The three calls are ONE kernel launch whatever the number of points
@@ -1481,7 +1594,8 @@ class Lensgroup:
         pupil_xy [2, 3, spp] / center_pupil_xy [2, 3, 2048]: explicit pupil sample points per
         wavelength instead of random draws (ray-level parity hand-off).
         d_sensor: the sensor position of this call (psf_lr).  When it requires a gradient the three wavelengths are
-        three differentiable psf_lr calls, each centred through the green lens, and its gradient is their sum."""
+        three differentiable psf_lr calls, each centred through the green lens, and its gradient is their sum.
+        glass_params: the glass of this call (psf_lr); with a gradient likewise, glass.grad the sum over the wavelengths."""
         if not torch.is_tensor(points):
             points = torch.tensor(points)
         if center_pupil_xy is not None and not center:
@@ -1489,14 +1603,18 @@ class Lensgroup:
         focus_grad = d_sensor is not None and _requires_grad(d_sensor)
         if d_sensor is not None and not focus_grad:
             with self._sensor_borrowed(d_sensor):
-                return self.psf_rgb(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy, surface_params)
+                return self.psf_rgb(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy, surface_params,
+                                    None, glass_params)
         n_points = points.shape[0] if points.dim() == 2 else 1
         dp, right = _parse_param_list(param_list)
         surface_grad = surface_params is not None and _requires_grad(surface_params)
         if surface_params is not None and not surface_grad:
             self.set_surface_parameters(surface_params)
+        glass_grad = glass_params is not None and _requires_grad(glass_params)
+        if glass_params is not None and not glass_grad:
+            self.set_glass_parameters(glass_params)
         if (n_points > 0 and self.device.type == "cuda" and self.mask_reduce is None and ks <= _lib.MAX_KS
-                and not surface_grad and not focus_grad and not _psf_needs_grad(dp, points, center)):
+                and not surface_grad and not glass_grad and not focus_grad and not _psf_needs_grad(dp, points, center)):
             return self._psf_rgb_fused(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy)
         # not one launch (grids above SDIRT_MAX_KS, a rank of a sharded run, or a call that records gradients: one
         # differentiable psf_diff per wavelength, stacked, as optics.py:1010-1014 does): wavelength by wavelength
@@ -1508,7 +1626,8 @@ class Lensgroup:
                              pupil_xy=None if pupil_xy is None else (pupil_xy[0][i], pupil_xy[1][i]),
                              center_pupil_xy=None if center_pupil_xy is None else (center_pupil_xy[0][i], center_pupil_xy[1][i]),
                              surface_params=surface_params if surface_grad else None,
-                             d_sensor=d_sensor if focus_grad else None)
+                             d_sensor=d_sensor if focus_grad else None,
+                             glass_params=glass_params if glass_grad else None)
             psfs.append(lr[1] if right else lr[0])
         return torch.stack(psfs, dim=-3)
 

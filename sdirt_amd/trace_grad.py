@@ -1,22 +1,40 @@
 """The backward pass of the staged trace as an autograd op: surface parameters theta [K, 3 + MAX_AI] (columns d, c, k,
-ai2, ai4, ...) get the gradient the reference's graph gives them (deeplens/surfaces.py:523-679 under autograd).
+ai2, ai4, ...) get the gradient the reference's graph gives them (deeplens/surfaces.py:523-679 under autograd), and the
+glass [K + 1, 2] (columns n, V of every medium) gets its own through eta_k = n_k(lambda) / n_k+1(lambda).
 
-The forward of a psf call with `surface_params=` is the staged chain with a RECORDING trace (sdirt_trace2sensor_record:
-every ray's (o, d) on entry to each surface); the raw grids come from monte_carlo.SplatFunction as in every other
-differentiable call.  SurfaceGradFunction sits behind those grids as an identity: its backward receives dLoss/d(raw
-grids), turns it into dLoss/d(sensor-plane rays) (sdirt_forward_integral_grad_rays) and walks the recorded trace
-backwards (sdirt_trace2sensor_grad); the grids' gradients pass through unchanged to SplatFunction, so h, f, w and the
-pinhole centres get theirs in the same backward.
+The forward of a psf call with `surface_params=` or `glass_params=` is the staged chain with a RECORDING trace
+(sdirt_trace2sensor_record: every ray's (o, d) on entry to each surface); the raw grids come from
+monte_carlo.SplatFunction as in every other differentiable call.  SurfaceGradFunction sits behind those grids as an
+identity: its backward receives dLoss/d(raw grids), turns it into dLoss/d(sensor-plane rays)
+(sdirt_forward_integral_grad_rays) and walks the recorded trace backwards ONCE (sdirt_trace2sensor_grad; with a glass,
+sdirt_trace2sensor_grad_eta, whose extra column is dLoss/d eta); the grids' gradients pass through unchanged to
+SplatFunction, so h, f, w and the pinhole centres get theirs in the same backward.  eta is a float64 torch function of the
+glass (glass_eta), so torch's own autograd takes dLoss/d eta on to (n, V).
 """
 import ctypes as C
 
 import torch
 
 from . import _lib
-from .basics import dptr, stream_ptr
+from .basics import Material, dptr, stream_ptr
 from .monte_carlo import _flags
 
 N_COLUMNS = 3 + _lib.MAX_AI
+
+
+def glass_eta(glass, owned, constants, wvln):
+    """eta [K] = n_k(wvln) / n_k+1(wvln), float64, as a torch function of glass [K + 1, 2] (columns n, V).  An owned
+    medium j (owned[j]) is the Cauchy glass of its row, n(lambda) = A + B / lambda_nm^2 with Material.nV_to_AB's A and B
+    in Material.ior's order of operations (basics.py:336-338, 355-362): the values are the n1 / n2 the device table is
+    built from.  Every other medium is the constant constants[j] (its Material.ior(wvln)) without a gradient."""
+    wv = wvln if wvln < 10 else wvln * 1e-3
+    g = glass.to(torch.float64)
+    n, V = g[:, 0], g[:, 1]
+    own = torch.as_tensor(owned, dtype=torch.bool)
+    V = torch.where(own, V, torch.ones_like(V))                       # (a constant's V may be 0: never divided by)
+    A, B = Material.nV_to_AB(n, V)
+    ior = torch.where(own, A + B / (wv * 1e3) ** 2, torch.as_tensor(constants, dtype=torch.float64))
+    return ior[:-1] / ior[1:]
 
 
 class TraceRecord:
@@ -30,10 +48,12 @@ class TraceRecord:
 
 
 class SurfaceGradFunction(torch.autograd.Function):
+    """theta: surface parameters or None; eta: glass_eta(...) [K] or None (then the backward is the old entry's)."""
+
     @staticmethod
-    def forward(ctx, theta, lg, rg, rec, center, ps, ks, dp):
+    def forward(ctx, theta, eta, lg, rg, rec, center, ps, ks, dp):
         ctx.rec, ctx.geom, ctx.dp = rec, (float(ps), int(ks)), dp
-        ctx.meta = (theta.dtype, theta.device, tuple(theta.shape))
+        ctx.meta = [None if t is None else (t.dtype, t.device, tuple(t.shape)) for t in (theta, eta)]
         ctx.save_for_backward(center)
         return lg.clone(), rg.clone()
 
@@ -54,10 +74,19 @@ class SurfaceGradFunction(torch.autograd.Function):
             ray.c_rays(), S, N, ps, ks, dptr(center), C.byref(dp) if dp is not None else None, _flags(rec.precision),
             dptr(gl), dptr(gr), None, ns, dptr(ray_grad), st))
         nwg = int(h.sdirt_trace2sensor_grad_workgroups(M, ncu))
-        partial = torch.empty((nwg, K, N_COLUMNS), dtype=torch.float64, device=dev)
-        _lib.check(h.sdirt_trace2sensor_grad(
+        theta_meta, eta_meta = ctx.meta
+        with_eta = eta_meta is not None and ctx.needs_input_grad[1]
+        entry = h.sdirt_trace2sensor_grad_eta if with_eta else h.sdirt_trace2sensor_grad
+        partial = torch.empty((nwg, K, N_COLUMNS + (1 if with_eta else 0)), dtype=torch.float64, device=dev)
+        _lib.check(entry(
             rec.dev_lens.handle, (C.c_int32 * K)(*rec.trips), _flags(rec.precision), rec.d_sensor, dptr(rec.workspace),
             ray.c_rays().ra, dptr(ray_grad), M, dptr(partial), nwg, st))
-        dtype, device, shape = ctx.meta
-        g = partial.sum(0).to(device=device, dtype=dtype).reshape(shape)     # the workgroups in a fixed order
-        return g, gl, gr, None, None, None, None, None
+        total = partial.sum(0)                                               # the workgroups in a fixed order
+        g_theta = g_eta = None
+        if theta_meta is not None and ctx.needs_input_grad[0]:
+            dtype, device, shape = theta_meta
+            g_theta = total[:, :N_COLUMNS].to(device=device, dtype=dtype).reshape(shape)
+        if with_eta:
+            dtype, device, shape = eta_meta
+            g_eta = total[:, N_COLUMNS].to(device=device, dtype=dtype).reshape(shape)
+        return g_theta, g_eta, gl, gr, None, None, None, None, None

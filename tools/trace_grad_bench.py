@@ -6,8 +6,9 @@
         python3 tools/trace_grad_bench.py --shape 4096x4096 --steps 5 --warmup 2
 
 One batch of N points x S samples through rf50mm (K = 12): sdirt_trace2sensor (k_trace, the yardstick),
-sdirt_trace2sensor_record (k_trace_record) and sdirt_trace2sensor_grad (k_trace_grad) with the same trip table, every
-ray given an upstream gradient.  The kernel times are rocprofv3's (*_kernel_stats.csv); the device-event times printed
+sdirt_trace2sensor_record (k_trace_record), sdirt_trace2sensor_grad (k_trace_grad) and sdirt_trace2sensor_grad_eta
+(k_trace_grad_eta: the eta column as well; skipped where the library has no such entry, so that the
+script also times a build from before it) with the same trip table, every ray given an upstream gradient.  The kernel times are rocprofv3's (*_kernel_stats.csv); the device-event times printed
 here include the launches and are a cross-check only.  One JSON line: event times, the bytes each call has to move
 (bundle in and out: 28 + 28 per ray; checkpoints: 24 (K + 1) per ray written by the recording trace and read by the
 backward, which also reads 4 + 16 per ray), and what that is of 8 TB/s."""
@@ -54,11 +55,11 @@ def main():
     h, st = _lib.lib(), stream_ptr(dev)
     handle = lens.dev_lens(src.wvln)
     trips = (C.c_int32 * K)(*lens._fixed_trips_for("max").tolist())
-    out = Ray.empty(src.shape, src.wvln, dev)
+    out = Ray.empty(src.shape, src.wvln, dev, obliq=src.has_obliq)
     ws = torch.empty(h.sdirt_trace2sensor_grad_workspace_bytes(M, K) // 4, dtype=torch.float32, device=dev)
     ray_grad = torch.ones((4, M), dtype=torch.float32, device=dev)
     nwg = h.sdirt_trace2sensor_grad_workgroups(M, torch.cuda.get_device_properties(dev).multi_processor_count)
-    partial = torch.empty((nwg, K, 3 + _lib.MAX_AI), dtype=torch.float64, device=dev)
+    partial = torch.empty((nwg, K, 3 + _lib.MAX_AI + 1), dtype=torch.float64, device=dev)       # room for the eta column
     calls = {
         "trace2sensor": lambda: _lib.check(h.sdirt_trace2sensor(handle, trips, 0, float(lens.d_sensor), src.c_rays(), out.c_rays(),
                                                                 M, None, st)),
@@ -68,6 +69,10 @@ def main():
                                                              dptr(ray_grad), M, dptr(partial), nwg, st)),
     }
     nbytes = {"trace2sensor": 56 * M, "record": (56 + 24 * (K + 1)) * M, "grad": (24 * (K + 1) + 20) * M}
+    if hasattr(h, "sdirt_trace2sensor_grad_eta"):
+        calls["grad_eta"] = lambda: _lib.check(h.sdirt_trace2sensor_grad_eta(handle, trips, 0, float(lens.d_sensor), dptr(ws),
+                                                                             out.c_rays().ra, dptr(ray_grad), M, dptr(partial), nwg, st))
+        nbytes["grad_eta"] = nbytes["grad"]
     res = {"shape": [N, S], "surfaces": K, "live": None}
     for name, fn in calls.items():
         t = timed(fn, a.steps, a.warmup)
