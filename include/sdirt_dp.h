@@ -314,6 +314,37 @@ int sdirt_forward_integral_grad_rays(sdirt_rays rays, int64_t spp, int64_t n_poi
                                      const float* grad_r /*dev or NULL*/, double* partial /*dev [N,n_slices,5] or NULL*/,
                                      int32_t n_slices, float* ray_grad /*dev [4,n_rays]*/, void* stream);
 
+/* ---- photometric dual-pixel PSFs: the energy of every point ----
+ * partial (dev float64 [N, n_slices, 3], fully overwritten; the caller sums over the slices) = per point and slice of the
+ * spp axis (sum ra s_l(x_tan), sum ra s_r(x_tan), sum ra) over ALL the point's rays of the sensor-plane bundle, inside
+ * the splat's window or not: s_l, s_r are the closed-form sub-pixel areas d_l, d_r of assign_points_to_pixels_small_r /
+ * _big_r (deeplens/monte_carlo.py:135-240, 242-372) at x_tan = -d.x / d.z (:48), the fp32 values sdirt_forward_integral
+ * splats under the same `flags`.  It is what the reference's forward_integral -- "including PSF and vignetting",
+ * monte_carlo.py:10 -- loses twice: the rays outside the ks window are zeroed (:37-38), and psf_diff computes
+ * lum = psf.sum / light_nums and drops it (the `* lum` line is commented out, optics.py:979-991).  Divided by spp the
+ * three sums are the left and right energy and the share of the sampled rays that reach the sensor.
+ * dp must not be NULL.  n_slices = sdirt_forward_integral_grad_slices(N, spp, n_cus) of the current device.  Products and
+ * sums are float64 in a fixed order, no atomics and no pre-zeroed output: the same bits every run.  12 bytes per ray
+ * (d.x, d.z, ra).  N = 0: SDIRT_OK, nothing launched. */
+int sdirt_dp_energy(sdirt_rays rays, int64_t spp, int64_t n_points, const sdirt_dp_params* dp /*host, not NULL*/,
+                    uint32_t flags /*SDIRT_PSF_STRICT_IEEE or 0*/, double* partial /*dev [N,n_slices,3]*/,
+                    int32_t n_slices, void* stream);
+
+/* The backward pass of sdirt_dp_energy: given grad_e (dev float64 [N, 3] = dLoss/d(the three sums); column 2 is not
+ * read, ra is a forward decision and carries no gradient),
+ *   partial  (dev float64 [N, n_slices, 3], fully overwritten, or NULL) = (dh, df, dw) per point and slice, with the
+ *            derivatives of s_l, s_r and the clamp rule of sdirt_forward_integral_grad;
+ *   ray_grad (dev fp32 [4, n_rays], the layout of sdirt_forward_integral_grad_rays, or NULL): rows 2 and 3 =
+ *            dLoss/d(d.x, d.z) through x_tan = -d.x / d.z.  accumulate = 0: all four rows are written, rows 0 and 1
+ *            (o.x, o.y: a position carries no energy) exactly 0, a ray with ra = 0 exactly 0.  accumulate != 0: each
+ *            term is rounded to fp32 and added in fp32 to what rows 2 and 3 hold (the splat's terms, for ONE walk of
+ *            sdirt_trace2sensor_grad); rows 0 and 1 are left alone.
+ * At least one of partial and ray_grad; dp, flags and n_slices as in the forward call.  No atomics. */
+int sdirt_dp_energy_grad(sdirt_rays rays, int64_t spp, int64_t n_points, const sdirt_dp_params* dp /*host, not NULL*/,
+                         uint32_t flags /*SDIRT_PSF_STRICT_IEEE or 0*/, const double* grad_e /*dev [N,3]*/,
+                         double* partial /*dev [N,n_slices,3] or NULL*/, int32_t n_slices,
+                         float* ray_grad /*dev [4,n_rays] or NULL*/, int32_t accumulate, void* stream);
+
 /* ---- the backward pass of the staged trace: gradients in the prescription (d, c, k, ai of every surface) ----
  * sdirt_trace2sensor_record is sdirt_trace2sensor (the same sensor-plane bundle, bit for bit, under the same trip
  * table and math flag) that also stores each ray's (o, d) on entry to every surface and before the final propagation

@@ -110,6 +110,8 @@ SIGNATURES = {
     "sdirt_forward_integral_grad_slices": (_I32, [_I64, _I64, _I32]),
     "sdirt_forward_integral_grad_rays": (C.c_int, [Rays, _I64, _I64, _D, _I32, _P, C.POINTER(DpParams), _U32,
                                                    _P, _P, _P, _I32, _P, _P]),
+    "sdirt_dp_energy": (C.c_int, [Rays, _I64, _I64, C.POINTER(DpParams), _U32, _P, _I32, _P]),
+    "sdirt_dp_energy_grad": (C.c_int, [Rays, _I64, _I64, C.POINTER(DpParams), _U32, _P, _P, _I32, _P, _I32, _P]),
     "sdirt_trace2sensor_grad_workspace_bytes": (_I64, [_I64, _I32]),
     "sdirt_trace2sensor_record": (C.c_int, [_P, C.POINTER(_I32), _U32, _D, Rays, Rays, _I64, _P, _P, _P]),
     "sdirt_trace2sensor_grad_workgroups": (_I32, [_I64, _I32]),

@@ -14,6 +14,9 @@
 // Reduction: one workgroup per (point, slice of the spp axis); the ray terms are summed in float64 registers, across
 // the wave with shuffles, across the workgroup through LDS, and ONE float64 partial of 5 values is stored per
 // (point, slice).  No atomics: the gradients are the same bits from run to run.
+//
+// The same launch shape carries the energy of a point (k_dp_energy: the sums of ra s_l, ra s_r and ra over ALL its rays) and
+// its backward pass (k_dp_energy_grad), further down.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -424,6 +427,120 @@ k_forward_integral_grad_rays(sdirt_rays R, int64_t S, int64_t Mtot, SplatGeom gm
     }
 }
 
+// The energy of a point: E[n] = (sum ra s_l(x_tan), sum ra s_r(x_tan), sum ra) over ALL its spp rays, in the window or
+// not -- what the raw grids would sum to if forward_integral did not zero the rays outside its window
+// (monte_carlo.py:37-38; the four bilinear taps of a ray sum to 1), and what psf_diff computes as lum and drops
+// (optics.py:979-991).  s_l, s_r are the splat's own fp32 weights (dp_weights_small<M> / dp_weights_big on
+// x_tan = (-d.x) / d.z); the products and sums are float64, a thread's rays in order, the wave by shuffles, the
+// workgroup through LDS: one partial of 3 values per (point, slice), no atomics.  12 bytes per ray.
+constexpr int kEnergyComps = 3;
+
+template <bool BIG, class M>
+__global__ void __launch_bounds__(kGradThreads)
+k_dp_energy(sdirt_rays R, int64_t S, DevDpParams dp, GradLaunch gl_, double* __restrict__ partial)
+{
+    __shared__ double red[kGradThreads / 64][kEnergyComps];
+    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
+    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
+    const auto div_fmh = UDiv<M>::make(dp.fmh);
+    double acc[kEnergyComps] = {0.0, 0.0, 0.0};
+    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
+    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
+        const int64_t i = n * S + s;
+        const float dx = R.dx[i], dz = R.dz[i], ra = R.ra[i];
+        if (!(ra != 0.0f)) continue;
+        const float x_tan = (-dx) / dz;                   // monte_carlo.py:48
+        float sl, sr;
+        if (BIG) dp_weights_big(dp, x_tan, sl, sr);
+        else dp_weights_small<M>(dp, div_fmh, x_tan, sl, sr);
+        const double w = ra;
+        acc[0] += w * (double)sl;
+        acc[1] += w * (double)sr;
+        acc[2] += w;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < kEnergyComps; ++c) {
+        const double v = wave_sum(acc[c]);
+        if (lane == 0) red[wave][c] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kEnergyComps) {
+        double v = 0.0;
+        for (int k = 0; k < kGradThreads / 64; ++k) v += red[k][threadIdx.x];
+        partial[(n * gl_.nslices + j) * kEnergyComps + threadIdx.x] = v;
+    }
+}
+
+// The backward pass of k_dp_energy: given grad_e [N, 3] = dLoss/dE (column 2 is not read: ra is a forward decision),
+//   partial  [N, nslices, 3] = sum over the slice's rays of ra (g_l ds_l/dtheta + g_r ds_r/dtheta), theta = h, f, w
+//            (dz_boundaries: the derivatives and clamp rule of k_forward_integral_grad), and / or
+//   ray_grad [4, M]: rows 2 and 3 = dLoss/d(d.x, d.z) through x_tan = -d.x / d.z (dz_dt, as
+//            k_forward_integral_grad_rays); a position carries no energy: rows 0 and 1 are written as 0 (ACCUM: left
+//            alone, and rows 2 and 3 get buffer + fp32(term), added in fp32).
+// PARTIAL and RAYS pick the outputs; a ray with ra = 0 contributes exactly 0.
+template <bool BIG, class M, bool PARTIAL, bool RAYS, bool ACCUM>
+__global__ void __launch_bounds__(kGradThreads)
+k_dp_energy_grad(sdirt_rays R, int64_t S, int64_t Mtot, DevDpParams dp, DpGrad q, GradLaunch gl_,
+                 const double* __restrict__ grad_e, double* __restrict__ partial, float* __restrict__ ray_grad)
+{
+    __shared__ double red[kGradThreads / 64][kEnergyComps];
+    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
+    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
+    const auto div_fmh = UDiv<M>::make(dp.fmh);
+    const double g_l = grad_e[kEnergyComps * n], g_r = grad_e[kEnergyComps * n + 1];
+    double acc[kEnergyComps] = {0.0, 0.0, 0.0};
+    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
+    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
+        const int64_t i = n * S + s;
+        const float dx = R.dx[i], dz = R.dz[i], ra = R.ra[i];
+        float g_dx = 0.0f, g_dz = 0.0f;
+        if (ra != 0.0f) {
+            const float x_tan = (-dx) / dz;
+            const double w = ra;
+            if (PARTIAL) {
+                double dZ[3][3];
+                dz_boundaries<BIG, M>(dp, div_fmh, q, x_tan, dZ);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const double dsr = dZ[1][c] - dZ[0][c], dsl = dZ[2][c] - dZ[1][c];
+                    acc[c] += w * (g_l * dsl + g_r * dsr);
+                }
+            }
+            if (RAYS) {
+                double dT[3];
+                dz_dt<BIG, M>(dp, div_fmh, q, x_tan, dT);
+                const double dt = w * (g_l * (dT[2] - dT[1]) + g_r * (dT[1] - dT[0]));          // dLoss/d(x_tan)
+                const double z = (double)dz;
+                g_dx = (float)(-dt / z);
+                g_dz = (float)(dt * (double)dx / (z * z));
+            }
+        }
+        if (RAYS) {
+            if (ACCUM) {
+                ray_grad[2 * Mtot + i] = ray_grad[2 * Mtot + i] + g_dx;
+                ray_grad[3 * Mtot + i] = ray_grad[3 * Mtot + i] + g_dz;
+            } else {
+                ray_grad[i] = 0.0f; ray_grad[Mtot + i] = 0.0f; ray_grad[2 * Mtot + i] = g_dx; ray_grad[3 * Mtot + i] = g_dz;
+            }
+        }
+    }
+    if (PARTIAL) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (int c = 0; c < kEnergyComps; ++c) {
+            const double v = wave_sum(acc[c]);
+            if (lane == 0) red[wave][c] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < kEnergyComps) {
+            double v = 0.0;
+            for (int k = 0; k < kGradThreads / 64; ++k) v += red[k][threadIdx.x];
+            partial[(n * gl_.nslices + j) * kEnergyComps + threadIdx.x] = v;
+        }
+    }
+}
+
 GradLaunch plan_grad(int64_t N, int64_t S, int ncu)
 {
     GradLaunch g{};
@@ -512,6 +629,72 @@ int sdirt_forward_integral_grad_rays(sdirt_rays rays, int64_t S, int64_t N, doub
 {
     if (!ray_grad) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null ray_grad");      // partial may be NULL: the rays' terms only
     return launch_integral_grad(rays, S, N, ps, ks, center, dp, flags, grad_l, grad_r, partial, n_slices, ray_grad, false, stream);
+}
+
+// The argument checks and the launch plan the two energy entries share: SDIRT_OK with gl.nslices = 0 when N = 0.
+static int plan_energy(const sdirt_rays& rays, int64_t S, int64_t N, const sdirt_dp_params* dp, int32_t n_slices,
+                       GradLaunch& gl)
+{
+    gl = GradLaunch{};
+    if (int rc = check_rays(rays)) return rc;
+    if (!dp) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null dp: the energy needs the dual-pixel parameters");
+    if (S < 0 || N < 0 || N > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (!(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
+    if (!(dp->f != dp->h)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->f must differ from dp->h");
+    if (N == 0) return SDIRT_OK;
+    int ncu = 0;
+    if (int rc = device_cus(&ncu)) return rc;
+    gl = plan_grad(N, S, ncu);
+    if (n_slices != gl.nslices)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_slices=%d, the launch has %d (sdirt_forward_integral_grad_slices)",
+                    n_slices, gl.nslices);
+    return SDIRT_OK;
+}
+
+int sdirt_dp_energy(sdirt_rays rays, int64_t S, int64_t N, const sdirt_dp_params* dp, uint32_t flags, double* partial,
+                    int32_t n_slices, void* stream)
+{
+    if (!partial) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null partial");
+    GradLaunch gl;
+    if (int rc = plan_energy(rays, S, N, dp, n_slices, gl)) return rc;
+    if (N == 0) return SDIRT_OK;
+    const DevDpParams dpp = make_dp(dp);
+    const unsigned grid = (unsigned)(N * gl.nslices);
+    hipStream_t st = as_stream(stream);
+    with_bool(dpp.big, [&](auto bg) { return with_math(flags, [&](auto m) {
+        k_dp_energy<decltype(bg)::value, decltype(m)><<<grid, kGradThreads, 0, st>>>(rays, S, dpp, gl, partial);
+        return 0;
+    }); });
+    LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+
+int sdirt_dp_energy_grad(sdirt_rays rays, int64_t S, int64_t N, const sdirt_dp_params* dp, uint32_t flags,
+                         const double* grad_e, double* partial, int32_t n_slices, float* ray_grad, int32_t accumulate,
+                         void* stream)
+{
+    if (!grad_e) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null grad_e");
+    if (!partial && !ray_grad) return fail(SDIRT_ERR_INVALID_ARGUMENT, "partial and ray_grad are both null");
+    GradLaunch gl;
+    if (int rc = plan_energy(rays, S, N, dp, n_slices, gl)) return rc;
+    if (N == 0) return SDIRT_OK;
+    const DevDpParams dpp = make_dp(dp);
+    const DpGrad q{dp->h, dp->f, dp->w, dp->r, dp->f - dp->h};
+    const unsigned grid = (unsigned)(N * gl.nslices);
+    hipStream_t st = as_stream(stream);
+    with_bool(dpp.big, [&](auto bg) { return with_math(flags, [&](auto m) {
+        constexpr bool BG = decltype(bg)::value;
+        using Mm = decltype(m);
+        if (partial)
+            k_dp_energy_grad<BG, Mm, true, false, false><<<grid, kGradThreads, 0, st>>>(rays, S, S * N, dpp, q, gl, grad_e, partial, nullptr);
+        if (ray_grad && accumulate)
+            k_dp_energy_grad<BG, Mm, false, true, true><<<grid, kGradThreads, 0, st>>>(rays, S, S * N, dpp, q, gl, grad_e, nullptr, ray_grad);
+        else if (ray_grad)
+            k_dp_energy_grad<BG, Mm, false, true, false><<<grid, kGradThreads, 0, st>>>(rays, S, S * N, dpp, q, gl, grad_e, nullptr, ray_grad);
+        return 0;
+    }); });
+    LAUNCH_CHECK();
+    return SDIRT_OK;
 }
 
 }  // extern "C"

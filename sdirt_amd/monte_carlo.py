@@ -3,7 +3,9 @@
 Same call signatures as deeplens/monte_carlo.py (forward_integral :9,
 assign_points_to_pixels_small_r :135, _big_r :242); the work is one HIP kernel
 (sdirt_forward_integral): window test, closed-form left/right sub-pixel areas
-and the 4-tap bilinear scatter-add.
+and the 4-tap bilinear scatter-add.  dp_energy (sdirt_dp_energy) sums the same
+sub-pixel areas over ALL rays of a point: the energy the window and the
+normalisations of the PSF path discard.
 """
 import ctypes as C
 
@@ -103,6 +105,72 @@ def splat_autograd(ray, ps, ks, center, param_list, precision="lean", d_sensor=N
     if d_sensor is not None:
         d_sensor = d_sensor.reshape(())
     return SplatFunction.apply(h, f, w, center, ray, ps, ks, float(r), have_dp, precision, d_sensor, center_slope)
+
+
+def _energy_slices(ray):
+    S, N = ray.shape
+    ncu = int(torch.cuda.get_device_properties(ray.device).multi_processor_count)
+    return int(_lib.lib().sdirt_forward_integral_grad_slices(N, S, ncu))
+
+
+class EnergyFunction(torch.autograd.Function):
+    """The energy of every point as an autograd op: (h, f, w) -> [N, 3] float64 sums over ALL spp rays of the
+    sensor-plane bundle (sum ra s_l, sum ra s_r, sum ra), s_l / s_r the splat's own sub-pixel areas at
+    x_tan = -d.x / d.z (sdirt_dp_energy).  Differentiable in h, f, w exactly as SplatFunction is (0-d tensors; Python
+    numbers get no gradient); the rays, r and the precision are constants, and column 2 has no gradient to give.
+    d_sensor (a 0-d tensor or None) gets a gradient of exactly 0: the propagation to the sensor plane changes neither a
+    ray's direction nor its weight."""
+
+    @staticmethod
+    def forward(ctx, h, f, w, ray, r, precision, d_sensor=None):
+        S, N = ray.shape
+        dev = ray.device
+        dp = _lib.DpParams(float(h), float(f), float(w), float(r))
+        ctx.ray, ctx.dp, ctx.precision = ray, dp, precision
+        ctx.meta = [(v.dtype, v.device) if torch.is_tensor(v) else None for v in (h, f, w, d_sensor)]
+        if N == 0:
+            return torch.zeros((0, 3), dtype=torch.float64, device=dev)
+        ns = _energy_slices(ray)
+        partial = torch.empty((N, ns, 3), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().sdirt_dp_energy(ray.c_rays(), S, N, C.byref(dp), _flags(precision), dptr(partial), ns,
+                                              stream_ptr(dev)))
+        return partial.sum(1)                                  # the slices in a fixed order
+
+    @staticmethod
+    def backward(ctx, ge):
+        ray = ctx.ray
+        S, N = ray.shape
+        dev = ray.device
+        theta = torch.zeros(3, dtype=torch.float64, device=dev)
+        if N > 0 and any(ctx.needs_input_grad[:3]):
+            ns = _energy_slices(ray)
+            ge = ge.to(dev, torch.float64).contiguous()
+            partial = torch.empty((N, ns, 3), dtype=torch.float64, device=dev)
+            _lib.check(_lib.lib().sdirt_dp_energy_grad(ray.c_rays(), S, N, C.byref(ctx.dp), _flags(ctx.precision), dptr(ge),
+                                                       dptr(partial), ns, None, 0, stream_ptr(dev)))
+            theta = partial.sum(1).sum(0)
+        grads = [theta[i].to(device=ctx.meta[i][1], dtype=ctx.meta[i][0]) if ctx.needs_input_grad[i] else None
+                 for i in range(3)]
+        gs = torch.zeros((), dtype=ctx.meta[3][0], device=ctx.meta[3][1]) if ctx.needs_input_grad[6] else None
+        return (*grads, None, None, None, gs)
+
+
+def dp_energy(ray, param_list, precision="lean", d_sensor=None):
+    """[N, 3] float64: per point of the [spp, N] sensor-plane bundle `ray` the sums over ALL its rays, inside the PSF
+    window or not, of (ra d_l(x_tan), ra d_r(x_tan), ra) -- d_l, d_r the closed-form sub-pixel areas of
+    assign_points_to_pixels_small_r / _big_r (monte_carlo.py:135-240, 242-372) the splat weighs a ray with, in the
+    fp32 the splat computes them in.  Divided by spp: the left and right energy of the point and the share of its rays
+    that arrive -- the vignetting and the dual-pixel shading forward_integral's window and the PSF normalisations
+    discard.  param_list = (h, f, w, r[, direct]); differentiable in tensor h, f, w (EnergyFunction), r and the rays
+    are constants.  d_sensor: a 0-d tensor that gets a gradient of exactly 0."""
+    if len(ray.shape) != 2:
+        raise ValueError("ray must have shape [spp, N]")
+    if param_list is None:
+        raise ValueError("dp_energy needs the dual-pixel parameters (h, f, w, r)")
+    h, f, w = (_as_scalar(v) for v in param_list[:3])
+    if d_sensor is not None:
+        d_sensor = d_sensor.reshape(())
+    return EnergyFunction.apply(h, f, w, ray, float(param_list[3]), precision, d_sensor)
 
 
 def _flags(precision):

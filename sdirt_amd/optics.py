@@ -24,7 +24,7 @@ import torch
 
 from . import _hostrng, _lib, basics
 from .basics import DEFAULT_WAVE, DEPTH, GEO_SPP, WAVE_RGB, Material, Ray, dptr, stream_ptr
-from .monte_carlo import _requires_grad, splat_autograd
+from .monte_carlo import _requires_grad, dp_energy, splat_autograd
 from .newton import NEWTON_MAXITER, TripPlanner
 from .surfaces import Aspheric
 from .trace_grad import N_COLUMNS, SurfaceGradFunction, TraceRecord, glass_eta
@@ -1063,7 +1063,7 @@ class Lensgroup:
     def psf_lr(self, points, ks=31, wvln=DEFAULT_WAVE, spp=GEO_SPP, center=True,
                dp=(0.78, 1.44, 0.3, 0.5), normalize=True, want_r=True, _default_r_zero=False,
                pupil_xy=None, center_pupil_xy=None, out=None, defer=False, center_out=None, surface_params=None,
-               d_sensor=None, _focus=None, glass_params=None):
+               d_sensor=None, _focus=None, glass_params=None, energy=False):
         """Left AND right dual-pixel PSFs of one ray-traced batch: (L, R), each
         [N,ks,ks] (or [ks,ks] for a single point), max-normalised separately as
         optics.py:983-987 would normalise each of them.  dp = (h, f, w, r) of
@@ -1117,14 +1117,25 @@ class Lensgroup:
         call's wavelength: eta = n1(lambda) / n2(lambda) of every refraction carries it; the pupil, the
         chief-ray centres and every validity test stay constants.  Otherwise the call is set_glass_parameters(glass)
         followed by the ordinary call.  defer, out=, center_out= and trip_policy='adaptive' are refused with a gradient
-        as they are for surface_params; all of surface_params, glass_params and d_sensor may require one in one call."""
+        as they are for surface_params; all of surface_params, glass_params and d_sensor may require one in one call.
+
+        energy=True: -> (L, R, E), E [N, 3] float64 ([3] for a single point) = (E_L, E_R, T): the sums over ALL spp
+        rays of the point, inside the ks window or not, of ra d_l(x_tan), ra d_r(x_tan) and ra, divided by spp
+        (monte_carlo.dp_energy): the left and right energy -- lens vignetting times the dual-pixel shading the
+        normalisations above discard -- and the share T of the sampled rays that reach the sensor.  Such a call takes
+        the staged chain at every ks (L and R are that chain's); dp is required, defer=True and _default_r_zero are
+        refused.  In grad mode E has gradients in h, f, w, and with surface_params / glass_params its rays' terms join
+        the splat's for the one walk of the recorded trace; d_sensor gets exactly 0 from E."""
+        if energy and (defer or _default_r_zero or dp is None):
+            raise ValueError("energy=True needs dp and the staged chain: defer=True and _default_r_zero are not supported")
         if d_sensor is not None:
             focus = d_sensor if _requires_grad(d_sensor) else None
             if focus is not None and focus.numel() != 1:
                 raise ValueError("d_sensor must be a 0-d (one-element) tensor to get a gradient")
             with self._sensor_borrowed(d_sensor):
                 res = self.psf_lr(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
-                                  center_pupil_xy, out, defer, center_out, surface_params, None, focus, glass_params)
+                                  center_pupil_xy, out, defer, center_out, surface_params, None, focus, glass_params,
+                                  energy)
             if isinstance(res, PendingPSF):
                 # the trip check of a deferred call may launch again: with this call's sensor position
                 def finish(pending=res):
@@ -1133,6 +1144,8 @@ class Lensgroup:
                 return PendingPSF(finish)
             return res
         focus_kw = {} if _focus is None else {"focus": _focus}
+        if energy:
+            focus_kw["energy"] = True
         if glass_params is not None and not _requires_grad(glass_params):
             self.set_glass_parameters(glass_params)
             glass_params = None
@@ -1152,12 +1165,13 @@ class Lensgroup:
             return self._psf_lr_grad(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero,
                                      pupil_xy, center_pupil_xy, out, defer, center_out, **focus_kw)
         return self._psf_lr(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
-                            center_pupil_xy, out, defer, center_out)
+                            center_pupil_xy, out, defer, center_out, energy)
 
     @torch.no_grad()
     def _psf_lr(self, points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
-                center_pupil_xy, out, defer, center_out):
-        """psf_lr without autograd: the fused kernels (ks <= SDIRT_MAX_KS) or the staged chain."""
+                center_pupil_xy, out, defer, center_out, energy=False):
+        """psf_lr without autograd: the fused kernels (ks <= SDIRT_MAX_KS) or the staged chain (larger grids, and every
+        call that asks for the energy: it is a sum over the sensor-plane bundle, which only that chain holds)."""
         self._require_gpu()
         if not torch.is_tensor(points):
             points = torch.tensor(points)
@@ -1168,6 +1182,9 @@ class Lensgroup:
         if torch.is_tensor(out) and (dp is None or _default_r_zero or not want_r):
             raise ValueError("out=[N, 2, ks, ks] holds a left AND a right grid per point: needs dp and want_r")
         reference = self.trip_policy == "reference"
+        if N == 0 and energy:
+            e = torch.empty((0, ks, ks), dtype=torch.float32, device=self.device)
+            return e, (e.clone() if want_r else None), torch.zeros((0, 3), dtype=torch.float64, device=self.device)
         if N == 0 and not (self.mask_reduce is not None and center and reference):
             # empty batch: nothing to trace, no random numbers drawn
             e = torch.empty((0, ks, ks), dtype=torch.float32, device=self.device)
@@ -1176,12 +1193,12 @@ class Lensgroup:
         # (an empty SHARD of a multi-rank call goes on: its rank must enter the same mask
         # reductions and take the same re-launch decisions as its peers, with nothing to launch)
         po = self._points_to_object(points) if N else torch.empty((0, 3), device=self.device)
-        if ks > _lib.MAX_KS:
+        if ks > _lib.MAX_KS or energy:
             # a point's two grids no longer fit in LDS (draw_mtf: ks 256): the staged chain
             if defer or torch.is_tensor(out):
-                raise ValueError(f"defer=True / out=[N, 2, ks, ks] need ks <= {_lib.MAX_KS}")
+                raise ValueError(f"defer=True / out=[N, 2, ks, ks] need ks <= {_lib.MAX_KS} and no energy")
             return self._psf_lr_staged(points, po, N, ks, wvln, spp, center, dp, normalize, want_r,
-                                       _default_r_zero, pupil_xy, center_pupil_xy, out, center_out, single_point)
+                                       _default_r_zero, pupil_xy, center_pupil_xy, out, center_out, single_point, energy)
         if defer and not center:
             raise ValueError("defer=True needs center=True")
         call = self._psf_request(po, ks, wvln, center, dp, normalize, want_r, _default_r_zero, out, center_out,
@@ -1411,8 +1428,9 @@ class Lensgroup:
         return hbuf
 
     def _psf_lr_staged(self, points, po, N, ks, wvln, spp, center, dp, normalize, want_r, default_r_zero,
-                       pupil_xy, center_pupil_xy, out, center_out, single_point):
-        """psf_lr for SDIRT_MAX_KS < ks <= SDIRT_MAX_KS_STAGED: the reference's own sequence of optics.py:962-987
+                       pupil_xy, center_pupil_xy, out, center_out, single_point, energy=False):
+        """psf_lr for SDIRT_MAX_KS < ks <= SDIRT_MAX_KS_STAGED (and, with energy=True, for every ks; then a sixth call,
+        sdirt_dp_energy on the same bundle, gives E): the reference's own sequence of optics.py:962-987
         as five library calls -- sample_from_points, psf_center, trace2sensor, forward_integral (adds into the
         grids in HBM instead of LDS), normalise -- on [spp, N] rays held in HBM (28 bytes per ray).  Same rays,
         centres and trip tables as the fused kernel; the plots that ask for such grids (draw_mtf) trace a
@@ -1430,6 +1448,10 @@ class Lensgroup:
                                                 C.byref(dpp) if dpp is not None else None,
                                                 self._math_flags() | (_lib.PSF_NORMALIZE if normalize else 0),
                                                 dptr(L), dptr(R), st))
+        if energy:
+            with self._timed("dp_energy"):
+                E = dp_energy(ray, dp, self.precision) / spp
+            return (*_epilogue(L, R, want_r, single_point), E[0] if single_point else E)
         return _epilogue(L, R, want_r, single_point)
 
     def _staged_rays(self, points, po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen, record=False,
@@ -1484,7 +1506,8 @@ class Lensgroup:
         return TraceRecord(dev_lens, trips, self.precision, self.d_sensor, ws, ray, K)
 
     def _psf_lr_grad(self, points, ks, wvln, spp, center, dp, normalize, want_r, default_r_zero, pupil_xy,
-                     center_pupil_xy, out, defer, center_out, surface_params=None, focus=None, glass_params=None):
+                     center_pupil_xy, out, defer, center_out, surface_params=None, focus=None, glass_params=None,
+                     energy=False):
         """psf_lr under autograd: the staged chain's rays and centres (no gradient: optics.py:459, :888 are no_grad),
         then the RAW grids through monte_carlo.SplatFunction -- differentiable in h, f, w and, with center=False, in
         the pinhole centres points[:, :2] * sensor_size / 2 (optics.py:973-976) -- and the max-normalisation of
@@ -1517,6 +1540,8 @@ class Lensgroup:
             cen = torch.stack((pts[:, 0] * (self.sensor_size[1] / 2), pts[:, 1] * (self.sensor_size[0] / 2)), -1)
         param_list = None if (dp is None or default_r_zero) else (*dp[:4], "l")
         L, R = splat_autograd(ray, self.pixel_size, ks, cen, param_list, self.precision, focus, cen_slope)
+        # the sums over the whole bundle (EnergyFunction: h, f, w; exactly 0 to the sensor position)
+        Es = dp_energy(ray, param_list, self.precision, focus) if energy else None
         if record:
             # the rays' share of the graph: dLoss/d(raw grids) -> the sensor-plane rays -> the recorded trace -> theta
             # and eta(glass) (the lens is the borrowed one: its constants' indices are those the device table holds)
@@ -1524,16 +1549,23 @@ class Lensgroup:
             cen_c = cen.detach().to(self.device, torch.float32).reshape(N, 2).contiguous()
             staged[2].center = cen_c
             eta = None if glass_params is None else self._glass_eta(glass_params, wvln)
-            L, R = SurfaceGradFunction.apply(surface_params, eta, L, R, staged[2], cen_c, self.pixel_size, ks, dpp)
+            if energy:
+                L, R, Es = SurfaceGradFunction.apply(surface_params, eta, L, R, staged[2], cen_c, self.pixel_size, ks, dpp, Es)
+            else:
+                L, R = SurfaceGradFunction.apply(surface_params, eta, L, R, staged[2], cen_c, self.pixel_size, ks, dpp)
         if normalize:
             L = L / (L.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
             R = R / (R.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
         if not want_r:
             R = None
+        if energy:
+            E = Es / spp
+            return (*_epilogue(L, R, want_r, single_point), E[0] if single_point else E)
         return _epilogue(L, R, want_r, single_point)
 
     def psf_volume(self, grid=(32, 32), z=16, ks=21, spp=GEO_SPP, dp=(0.78, 1.44, 0.3, 0.5), wvln=DEFAULT_WAVE,
-                   surface_params=None, pupil_xy=None, center_pupil_xy=None, d_sensor=None, glass_params=None):
+                   surface_params=None, pupil_xy=None, center_pupil_xy=None, d_sensor=None, glass_params=None,
+                   photometric=False):
         """The ray-traced PSF grid of the whole field and depth range as a render_psf.PSFVolume, for
         local_dp_psf_render_volume / PSFNet.render_volume: grid = (rows, columns) of cell-centred sensor nodes
         (psfnet.py:220-226: x from -1 + 1/(2 gx) to 1 - 1/(2 gx), y from 1 - 1/(2 gy) down), z = a number of depth
@@ -1550,8 +1582,15 @@ class Lensgroup:
         glass_params and d_sensor (the gradient of a shared parameter is the sum over the wavelengths), stacked on a new leading axis;
         psf[c] is the volume of wvln[c], rendered into image channel c.  pupil_xy / center_pupil_xy are then either
         (x[spp], y[spp]), shared by the wavelengths, or per wavelength, [2, Cw, spp] / [2, Cw, 2048] (psf_rgb's
-        convention); without them every wavelength draws fresh samples, in the order given."""
-        from .render_psf import PSFVolume
+        convention); without them every wavelength draws fresh samples, in the order given.
+
+        photometric=True: the PSFs carry their energy.  Every wavelength's call is psf_lr(energy=True); the volume's
+        `energy` holds the nodes' (E_L, E_R, T) [Dz,Gy,Gx,3] ([Cw,Dz,Gy,Gx,3]) and every node's sum-normalised L and R are
+        multiplied by E[node, side] / mean(E[:, :2]), the mean over all nodes and both sides of that wavelength
+        (render_psf.photometric_scale; torch ops, in the graph).  The render kernels normalise nothing, so the volume
+        renders lens vignetting and dual-pixel shading as it stands, and an image loss reaches h, f, w and the lens
+        through the energy as well as through the blur shape."""
+        from .render_psf import PSFVolume, photometric_scale
         gy, gx = (int(grid), int(grid)) if np.isscalar(grid) else (int(grid[0]), int(grid[1]))
         z_nodes = (z.detach().to(torch.float32).reshape(-1).cpu() if torch.is_tensor(z)
                    else torch.linspace(0, 1, int(z)) if int(z) > 1 else torch.zeros(1))
@@ -1571,15 +1610,20 @@ class Lensgroup:
                 raise ValueError(f"pupil points per wavelength must be [2, {len(waves)}, n], got {len(xy[0])} sets")
             return xy[0][i], xy[1][i]
 
-        points, psfs = vol.points(), []
+        points, psfs, energies = vol.points(), [], []
         for i, w in enumerate(waves):
-            L, R = self.psf_lr(points, ks=ks, wvln=w, spp=spp, dp=dp, pupil_xy=samples_of(pupil_xy, i),
-                               center_pupil_xy=samples_of(center_pupil_xy, i), surface_params=surface_params,
-                               d_sensor=d_sensor, glass_params=glass_params)
+            L, R, *E = self.psf_lr(points, ks=ks, wvln=w, spp=spp, dp=dp, pupil_xy=samples_of(pupil_xy, i),
+                                   center_pupil_xy=samples_of(center_pupil_xy, i), surface_params=surface_params,
+                                   d_sensor=d_sensor, glass_params=glass_params, energy=bool(photometric))
+            if photometric:
+                energies.append(E[0].reshape(len(z_nodes), gy, gx, 3))
             psf = torch.stack((L, R), -3)                                          # [N, 2, ks, ks]
             psf = psf / psf.sum((-1, -2), keepdim=True).clamp_min(1e-30)           # (a node no ray reaches stays 0)
             psfs.append(psf.reshape(len(z_nodes), gy, gx, 2, ks, ks))
         vol.psf = torch.stack(psfs) if chromatic else psfs[0]
+        if photometric:
+            vol.energy = torch.stack(energies) if chromatic else energies[0]
+            vol.psf = photometric_scale(vol.psf, vol.energy)
         dev = vol.psf.device
         vol.x_nodes, vol.y_nodes, vol.z_nodes = vol.x_nodes.to(dev), vol.y_nodes.to(dev), vol.z_nodes.to(dev)
         return vol

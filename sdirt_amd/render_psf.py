@@ -292,6 +292,24 @@ def local_dp_psf_render_volume(input, volume, x_nodes, y_nodes, z_nodes, z, kern
     return torch.cat([rl, rr], dim=1).to(input.dtype)
 
 
+def photometric_scale(psf, energy):
+    """Sum-normalised node PSFs -> PSFs that carry their energy: psf [..., 2, ks, ks] (a PSFVolume's psf, or any batch
+    of (left, right) pairs) times energy[..., side] / mean(energy[..., :2]), energy [..., 3] = (E_L, E_R, T) of
+    Lensgroup.psf_lr(energy=True) with the same leading shape.  The mean runs over all nodes and both sides, so the
+    kernel sums of a scaled volume average 1: the definition is free of a gain (exposure is a scalar of any fit) and
+    keeps what the data can show -- vignetting across the field and the left / right shading.  A chromatic volume
+    [C, Dz, Gy, Gx, 2, ks, ks] with energy [C, Dz, Gy, Gx, 3] is scaled wavelength by wavelength, each by its own mean.
+    torch ops throughout: differentiable in psf and in energy.  The render kernels normalise nothing, so a scaled
+    volume renders shading as it stands."""
+    if energy.shape[-1] != 3 or tuple(energy.shape[:-1]) != tuple(psf.shape[:-3]) or psf.shape[-3] != 2:
+        raise ValueError(f"photometric_scale: psf [..., 2, ks, ks] and energy [..., 3] must share their leading shape, "
+                         f"got {tuple(psf.shape)} and {tuple(energy.shape)}")
+    e = energy[..., :2].to(device=psf.device, dtype=torch.float64)
+    waves = e.shape[0] if psf.dim() == 7 else 1
+    mean = e.reshape(waves, -1).mean(1).reshape((waves,) + (1,) * (e.dim() - 1) if psf.dim() == 7 else ())
+    return psf * (e / mean).to(psf.dtype).unsqueeze(-1).unsqueeze(-1)
+
+
 @dataclasses.dataclass
 class PSFVolume:
     """A ray-traced PSF grid as local_dp_psf_render_volume consumes it (Lensgroup.psf_volume makes one).
@@ -299,7 +317,11 @@ class PSFVolume:
     normalised sensor coordinates (y decreases, as the image's rows do); z_nodes [Dz]: normalised depth
     z = (depth - d_min) / (d_max - d_min) (PSFNet.depth2z), depth in mm.  wvln: the wavelengths (um) the PSFs were
     traced at -- one: psf is the 6-D volume above; several: psf is chromatic, [len(wvln),Dz,Gy,Gx,2,ks,ks], psf[c] the
-    volume of wvln[c], rendered into channel c."""
+    volume of wvln[c], rendered into channel c.  energy: None, or -- psf_volume(photometric=True) -- the nodes'
+    (E_L, E_R, T) [Dz,Gy,Gx,3] ([len(wvln),Dz,Gy,Gx,3]) the PSFs were scaled with (photometric_scale): their sums are
+    then energy / mean(energy) instead of 1.  It is the trailing argument of the constructor and an attribute of the
+    volume (dataclasses.replace carries it over), declared init-only so that dataclasses.fields() -- the tensors a
+    volume is made of, ending with wvln -- stays what it was."""
     psf: torch.Tensor
     x_nodes: torch.Tensor
     y_nodes: torch.Tensor
@@ -307,6 +329,10 @@ class PSFVolume:
     d_min: float
     d_max: float
     wvln: tuple = (DEFAULT_WAVE,)
+    energy: dataclasses.InitVar[torch.Tensor] = None
+
+    def __post_init__(self, energy):
+        self.energy = energy
 
     def points(self):
         """[Dz*Gy*Gx, 3] points (x, y normalised, depth in mm) in the volume's order: what psf_lr is given."""

@@ -48,17 +48,25 @@ class TraceRecord:
 
 
 class SurfaceGradFunction(torch.autograd.Function):
-    """theta: surface parameters or None; eta: glass_eta(...) [K] or None (then the backward is the old entry's)."""
+    """theta: surface parameters or None; eta: glass_eta(...) [K] or None (then the backward is the old entry's).
+    energy: the [N, 3] sums of monte_carlo.dp_energy on the recorded bundle, or None.  With it the op has a third output,
+    the sums, and dLoss/d(sums) reaches the rays as well: sdirt_dp_energy_grad adds its terms in d.x, d.z to the splat's
+    ray_grad (accumulate = 1) before the ONE walk -- or writes the buffer (accumulate = 0) when no gradient arrives from
+    the grids."""
 
     @staticmethod
-    def forward(ctx, theta, eta, lg, rg, rec, center, ps, ks, dp):
+    def forward(ctx, theta, eta, lg, rg, rec, center, ps, ks, dp, energy=None):
         ctx.rec, ctx.geom, ctx.dp = rec, (float(ps), int(ks)), dp
         ctx.meta = [None if t is None else (t.dtype, t.device, tuple(t.shape)) for t in (theta, eta)]
         ctx.save_for_backward(center)
-        return lg.clone(), rg.clone()
+        ctx.has_energy = energy is not None
+        if energy is None:
+            return lg.clone(), rg.clone()
+        ctx.set_materialize_grads(False)        # an output the loss does not use arrives as None, not as zeros
+        return lg.clone(), rg.clone(), energy.clone()
 
     @staticmethod
-    def backward(ctx, gl, gr):
+    def backward(ctx, gl, gr, *ge):
         (center,) = ctx.saved_tensors
         rec, (ps, ks), dp = ctx.rec, ctx.geom, ctx.dp
         ray = rec.ray
@@ -68,11 +76,17 @@ class SurfaceGradFunction(torch.autograd.Function):
         ncu = int(torch.cuda.get_device_properties(dev).multi_processor_count)
         gl = gl.to(torch.float32).contiguous() if gl is not None else None
         gr = gr.to(torch.float32).contiguous() if gr is not None else None
+        ge = ge[0].to(dev, torch.float64).contiguous() if ge and ge[0] is not None else None
         ray_grad = torch.empty((4, M), dtype=torch.float32, device=dev)
         ns = int(h.sdirt_forward_integral_grad_slices(N, S, ncu))
-        _lib.check(h.sdirt_forward_integral_grad_rays(
-            ray.c_rays(), S, N, ps, ks, dptr(center), C.byref(dp) if dp is not None else None, _flags(rec.precision),
-            dptr(gl), dptr(gr), None, ns, dptr(ray_grad), st))
+        from_grids = gl is not None or gr is not None or ge is None
+        if from_grids:
+            _lib.check(h.sdirt_forward_integral_grad_rays(
+                ray.c_rays(), S, N, ps, ks, dptr(center), C.byref(dp) if dp is not None else None, _flags(rec.precision),
+                dptr(gl), dptr(gr), None, ns, dptr(ray_grad), st))
+        if ge is not None:
+            _lib.check(h.sdirt_dp_energy_grad(ray.c_rays(), S, N, C.byref(dp), _flags(rec.precision), dptr(ge), None, ns,
+                                              dptr(ray_grad), 1 if from_grids else 0, st))
         nwg = int(h.sdirt_trace2sensor_grad_workgroups(M, ncu))
         theta_meta, eta_meta = ctx.meta
         with_eta = eta_meta is not None and ctx.needs_input_grad[1]
@@ -89,4 +103,5 @@ class SurfaceGradFunction(torch.autograd.Function):
         if with_eta:
             dtype, device, shape = eta_meta
             g_eta = total[:, N_COLUMNS].to(device=device, dtype=dtype).reshape(shape)
-        return g_theta, g_eta, gl, gr, None, None, None, None, None
+        # (the sums' own gradient goes on to EnergyFunction, which gives h, f, w theirs)
+        return (g_theta, g_eta, gl, gr, None, None, None, None, None) + ((ge,) if ctx.has_energy else ())
