@@ -386,6 +386,29 @@ int sdirt_trace2sensor_grad_eta(const sdirt_lens* lens, const int32_t* trips /*h
                                 double* partial /*dev [n_workgroups,K,3+SDIRT_MAX_AI+1]*/, int32_t n_workgroups,
                                 void* stream);
 
+/* The recorded trace walked back for the OBJECT POINTS (deeplens/optics.py:460-494, 889-904, 956-960 with the two
+ * @torch.no_grad() decorators of sample_from_points and psf_center taken off and the pupil draws held fixed).  The bundle
+ * is the point-major [spp, n_points] bundle of sdirt_sample_rays(point_obj, x2, y2, pupil_z) recorded by
+ * sdirt_trace2sensor_record (n_rays = spp * n_points); ray_grad, ra, trips, flags and d_sensor as for
+ * sdirt_trace2sensor_grad, whose walk this is -- the same fp32 decisions, the same float64 derivatives, a ray without an
+ * upstream gradient skipped -- without its parameter columns.  After surface 0 the adjoint A of the sampled ray
+ * o0 = p, d0 = v / |v|, v = q_s - p, q_s = (x2[s], y2[s], pupil_z) (basics.py:245; its 1e-12 clamp is never active)
+ * goes on to the point:  p_bar += A.o - (A.d - d0 (d0 . A.d)) / |v|,  float64 from the fp32 p (checkpoint 0's o), x2,
+ * y2 and (float)pupil_z.
+ * partial (dev float64 [N, n_slices, 3], fully overwritten) = per point and slice of the spp axis the sum of its rays'
+ * terms of dLoss/d(point_obj[n]); the caller sums over the slices and applies the pinhole scale of optics.py:956-960
+ * (s = -z tan(hfov) / r_last: dx = p_bar.x s W/2, dy = p_bar.y s H/2,
+ * dz = p_bar.z - (x W/2 p_bar.x + y H/2 p_bar.y) tan(hfov) / r_last).  A point whose rays are all dead or outside the
+ * window gets exactly 0.  n_slices must be sdirt_forward_integral_grad_slices(N, spp, n_cus) of the current device; trip
+ * counts must be >= 0 (SDIRT_ERR_UNSUPPORTED).  No atomics and no pre-zeroed output: the same bits every run.  N = 0:
+ * SDIRT_OK, nothing launched.  The chief-ray centre c = -sum(o ra) / (sum ra + 1e-9) (optics.py:903-904) takes the same
+ * entry: its rays' ray_grad is rows 0, 1 = -g_c ra / (sum ra + 1e-9), rows 2, 3 = 0. */
+int sdirt_trace2sensor_grad_points(const sdirt_lens* lens, const int32_t* trips /*host [K]*/, uint32_t flags, double d_sensor,
+                                   const void* workspace /*dev*/, const float* ra /*dev [n_rays]*/,
+                                   const float* ray_grad /*dev [4,n_rays]*/, int64_t spp, int64_t n_points,
+                                   const float* x2 /*dev [spp]*/, const float* y2 /*dev [spp]*/, double pupil_z,
+                                   double* partial /*dev [N,n_slices,3]*/, int32_t n_slices, void* stream);
+
 /* deeplens/optics.py:983-987: psf / (max + 1e-6), per point, in place. */
 int sdirt_psf_normalize(float* psf /*dev [N,ks,ks]*/, int64_t n_points, int32_t ks, void* stream);
 

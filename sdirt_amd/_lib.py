@@ -117,6 +117,8 @@ SIGNATURES = {
     "sdirt_trace2sensor_grad_workgroups": (_I32, [_I64, _I32]),
     "sdirt_trace2sensor_grad": (C.c_int, [_P, C.POINTER(_I32), _U32, _D, _P, _P, _P, _I64, _P, _I32, _P]),
     "sdirt_trace2sensor_grad_eta": (C.c_int, [_P, C.POINTER(_I32), _U32, _D, _P, _P, _P, _I64, _P, _I32, _P]),
+    "sdirt_trace2sensor_grad_points": (C.c_int, [_P, C.POINTER(_I32), _U32, _D, _P, _P, _P, _I64, _I64, _P, _P, _D, _P,
+                                                 _I32, _P]),
     "sdirt_psf_normalize": (C.c_int, [_P, _I64, _I32, _P]),
     "sdirt_chief_center": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _D, _D, C.POINTER(_I32), _U32,
                                      _P, _P, _P, _P]),

@@ -20,6 +20,9 @@
 //  k_trace_grad_eta: the same walk with one more column per surface, dLoss/d eta of its refraction (eta = n1 / n2 as a
 //      leaf: deeplens/surfaces.py:44-53, 401-405, 633-669; Python's chain rule takes it to n and V of every medium,
 //      basics.py:316-362).
+//  k_trace_grad_points: the same walk without parameter columns, one workgroup per (point, spp slice); the adjoint of
+//      the ray that enters surface 0 goes on through d = normalize(q - p) to the object point (optics.py:460-494;
+//      DESIGN.md 7k).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -466,6 +469,99 @@ k_trace_grad_eta(TripTable trips, const DevSurface* __restrict__ lens, int K, co
     }
 }
 
+// The walk once more, for the OBJECT POINTS: no parameter columns, no LDS rows.  One workgroup per (point, slice of the
+// spp axis) of a point-major bundle (ray (s, n) = n S + s).  After surface 0 the adjoint A is that of the sampled ray
+// (o0, d0) = (p, normalize(q_s - p)), q_s = (x2[s], y2[s], pupil_z) (deeplens/optics.py:490-494, basics.py:245), so the
+// ray's term of the point's adjoint is A.o - (A.d - d0 (d0 . A.d)) / |q_s - p|, float64 from the fp32 p (checkpoint 0's
+// o), x2, y2 and pupil_z.  A thread adds its rays' terms in order, the wave sums by shuffles, the four waves meet in
+// LDS: ONE float64 triple per (point, slice), no atomics, nothing pre-zeroed.  A kernel of its own: a walk shared with
+// k_trace_grad would move that kernel's register allocation (tools/isa_compare.py).
+template <class MP>
+__global__ void __launch_bounds__(kBlock)
+k_trace_grad_points(TripTable trips, const DevSurface* __restrict__ lens, int K, const float* __restrict__ ws,
+                    const float* __restrict__ ra, const float* __restrict__ ray_grad, int64_t M, int64_t S, int nslices,
+                    int64_t chunk, float z_sensor, const float* __restrict__ x2, const float* __restrict__ y2, float pupil_z,
+                    double* __restrict__ partial)
+{
+    __shared__ double red[kAdjWaves][3];
+    const int64_t n = blockIdx.x / (uint32_t)nslices;
+    const int j = (int)(blockIdx.x - (uint32_t)n * nslices);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double acc[3] = {0.0, 0.0, 0.0};
+    const int64_t s_begin = (int64_t)j * chunk, s_end = min(S, s_begin + chunk);
+    for (int64_t base = s_begin; base < s_end; base += kBlock) {
+        const int64_t s = base + threadIdx.x;
+        const int64_t ss = s < s_end ? s : s_end - 1;         // idle lanes read a ray that exists and contribute nothing
+        const int64_t ii = n * S + ss;
+        Adj A{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        bool live = false;
+        if (s < s_end && ra[ii] != 0.0f) {
+            A.ox = ray_grad[ii]; A.oy = ray_grad[M + ii]; A.dx = ray_grad[2 * M + ii]; A.dz = ray_grad[3 * M + ii];
+            live = A.ox != 0.0 || A.oy != 0.0 || A.dx != 0.0 || A.dz != 0.0;
+        }
+        if (__ballot(live) == 0ull) continue;
+        {   // the final propagation to the sensor plane
+            const Ray r = load_ckpt(ws, M, K, ii);
+            const double t = ((double)z_sensor - (double)r.oz) / (double)r.dz;
+            (void)plane_adjoint(t, r.dx, r.dy, r.dz, A);
+        }
+        float Px = ws[ckpt_at(M, K, 0, ii)], Py = ws[ckpt_at(M, K, 1, ii)], Pz = ws[ckpt_at(M, K, 2, ii)];
+        for (int k = K - 1; k >= 0; --k) {
+            const SurfHot& h = lens[k].h;
+            const Ray r = load_ckpt(ws, M, k, ii);
+            const int kind = (int)(h.flags & 3u), deg = (int)((h.flags >> 8) & 15u);
+            if (kind == 0) {
+                if (h.flags & kFlagRefract) {
+                    double nbx, nby, nbz;
+                    refract_adjoint((double)h.eta_f, r.dx, r.dy, r.dz, 0.0, 0.0, 1.0, A.dx, A.dy, A.dz, nbx, nby, nbz);
+                }
+                const double t = ((double)h.d - (double)r.oz) / (double)r.dz;
+                (void)plane_adjoint(t, r.dx, r.dy, r.dz, A);
+            } else {
+                const int trip = (int)(int8_t)(trips.w[k >> 2] >> ((k & 3) * 8));
+                double a[kMaxAi], par[kParams];          // (the parameter terms are dead: nothing reads par)
+                Regain rg;
+                if (deg > 0) {
+                    PolyF pol;
+#pragma unroll
+                    for (int c = 0; c < kMaxAi; ++c) { pol.a[c] = lens[k].p.ai[c]; pol.ka[c] = lens[k].p.kai[c]; a[c] = pol.a[c]; }
+                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, pol, r, trip) : newton_regain<MP, false>(h, pol, r, trip);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < kMaxAi; ++c) a[c] = 0.0;
+                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, NoPoly{}, r, trip)
+                                                : newton_regain<MP, false>(h, NoPoly{}, r, trip);
+                }
+#pragma unroll
+                for (int c = 0; c < kParams; ++c) par[c] = 0.0;
+                curved_adjoint<false>(h, a, deg, r, rg, Px, Py, Pz, A, par);
+            }
+            Px = r.ox; Py = r.oy; Pz = r.oz;
+        }
+        if (live) {
+            // (Px, Py, Pz) is checkpoint 0's o: the point itself
+            const double vx = (double)x2[ss] - (double)Px, vy = (double)y2[ss] - (double)Py, vz = (double)pupil_z - (double)Pz;
+            const double len = sqrt(vx * vx + vy * vy + vz * vz);
+            const double ux = vx / len, uy = vy / len, uz = vz / len;
+            const double ud = ux * A.dx + uy * A.dy + uz * A.dz;
+            acc[0] += A.ox - (A.dx - ux * ud) / len;
+            acc[1] += A.oy - (A.dy - uy * ud) / len;
+            acc[2] += A.oz - (A.dz - uz * ud) / len;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double v = wave_sum(acc[c]);
+        if (lane == 0) red[wave][c] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double v = 0.0;
+        for (int w = 0; w < kAdjWaves; ++w) v += red[w][threadIdx.x];
+        partial[(n * nslices + j) * 3 + threadIdx.x] = v;
+    }
+}
+
 int grad_workgroups(int64_t M, int ncu)
 {
     return (int)std::max<int64_t>(1, std::min<int64_t>((M + kBlock - 1) / kBlock, 8 * (int64_t)ncu));
@@ -548,6 +644,37 @@ int sdirt_trace2sensor_grad_eta(const sdirt_lens* lens, const int32_t* trips, ui
                                 int32_t n_workgroups, void* stream)
 {
     return launch_trace_grad(true, lens, trips, flags, d_sensor, workspace, ra, ray_grad, M, partial, n_workgroups, stream);
+}
+
+int sdirt_trace2sensor_grad_points(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, double d_sensor,
+                                   const void* workspace, const float* ra, const float* ray_grad, int64_t S, int64_t N,
+                                   const float* x2, const float* y2, double pupil_z, double* partial, int32_t n_slices,
+                                   void* stream)
+{
+    if (!lens || !workspace || !ra || !ray_grad || !x2 || !y2 || !partial) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
+    TripTable tt;
+    if (int rc = make_trips(lens, trips, tt)) return rc;
+    for (int k = 0; k < lens->n_surfaces; ++k)
+        if (trips && trips[k] < 0)
+            return fail(SDIRT_ERR_UNSUPPORTED, "trips[%d] < 0: the per-wave trip count of the speed mode is not recorded", k);
+    if (S < 0 || N < 0 || N > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "spp < 0 or n_points out of range");
+    if (N == 0) return SDIRT_OK;
+    int ncu = 0;
+    if (int rc = device_cus(&ncu)) return rc;
+    const int32_t ns = sdirt_forward_integral_grad_slices(N, S, ncu);
+    if (n_slices != ns)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_slices=%d, the launch has %d (sdirt_forward_integral_grad_slices)", n_slices, ns);
+    if (N * (int64_t)ns > 0x7fffffffll) return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_points * n_slices exceeds the grid");
+    // the slices cover the spp axis in runs of `chunk` samples (a trailing slice may be empty: it stores zeros)
+    const int64_t chunk = std::max<int64_t>(1, (S + ns - 1) / ns);
+    with_math(flags, [&](auto m) {
+        k_trace_grad_points<decltype(m)><<<(unsigned)(N * ns), kBlock, 0, as_stream(stream)>>>(
+            tt, lens->dev, lens->n_surfaces, (const float*)workspace, ra, ray_grad, S * N, S, ns, chunk, (float)d_sensor, x2, y2,
+            (float)pupil_z, partial);
+        return 0;
+    });
+    LAUNCH_CHECK();
+    return SDIRT_OK;
 }
 
 }  // extern "C"

@@ -27,7 +27,8 @@ from .basics import DEFAULT_WAVE, DEPTH, GEO_SPP, WAVE_RGB, Material, Ray, dptr,
 from .monte_carlo import _requires_grad, dp_energy, splat_autograd
 from .newton import NEWTON_MAXITER, TripPlanner
 from .surfaces import Aspheric
-from .trace_grad import N_COLUMNS, SurfaceGradFunction, TraceRecord, glass_eta
+from .trace_grad import (N_COLUMNS, ChiefCentreFunction, PointGradFunction, PointSamples, SurfaceGradFunction, TraceRecord,
+                         glass_eta)
 
 
 def _as_device(device):
@@ -979,14 +980,16 @@ class Lensgroup:
         return self.psf_diff(points=points, wvln=wvln, ks=ks, spp=spp, center=center)
 
     def psf_diff(self, points, wvln=DEFAULT_WAVE, ks=31, spp=GEO_SPP, center=True,
-                 param_list=None, _defer=False, surface_params=None, d_sensor=None, glass_params=None):
+                 param_list=None, _defer=False, surface_params=None, d_sensor=None, glass_params=None,
+                 point_grad=False):
         """optics.py:934-996: normalised points [N,3] (or [3]) -> max-normalised
         PSF [N,ks,ks] (or [ks,ks]) of the left sub-pixel (right if param_list[4] != 'l').
-        d_sensor: the sensor position of this call; glass_params: its glass (psf_lr)."""
+        d_sensor: the sensor position of this call; glass_params: its glass; point_grad: the gradient in the points
+        through the rays (psf_lr)."""
         dp, right = _parse_param_list(param_list)
         res = self.psf_lr(points, ks=ks, wvln=wvln, spp=spp, center=center, dp=dp, want_r=right,
                           _default_r_zero=(param_list is None), defer=_defer, surface_params=surface_params,
-                          d_sensor=d_sensor, glass_params=glass_params)
+                          d_sensor=d_sensor, glass_params=glass_params, point_grad=point_grad)
         pick = (lambda lr: lr[1]) if right else (lambda lr: lr[0])
         if _defer:
             return PendingPSF(lambda: pick(res.wait()))
@@ -1063,7 +1066,7 @@ class Lensgroup:
     def psf_lr(self, points, ks=31, wvln=DEFAULT_WAVE, spp=GEO_SPP, center=True,
                dp=(0.78, 1.44, 0.3, 0.5), normalize=True, want_r=True, _default_r_zero=False,
                pupil_xy=None, center_pupil_xy=None, out=None, defer=False, center_out=None, surface_params=None,
-               d_sensor=None, _focus=None, glass_params=None, energy=False):
+               d_sensor=None, _focus=None, glass_params=None, energy=False, point_grad=False):
         """Left AND right dual-pixel PSFs of one ray-traced batch: (L, R), each
         [N,ks,ks] (or [ks,ks] for a single point), max-normalised separately as
         optics.py:983-987 would normalise each of them.  dp = (h, f, w, r) of
@@ -1125,7 +1128,20 @@ class Lensgroup:
         normalisations above discard -- and the share T of the sampled rays that reach the sensor.  Such a call takes
         the staged chain at every ks (L and R are that chain's); dp is required, defer=True and _default_r_zero are
         refused.  In grad mode E has gradients in h, f, w, and with surface_params / glass_params its rays' terms join
-        the splat's for the one walk of the recorded trace; d_sensor gets exactly 0 from E."""
+        the splat's for the one walk of the recorded trace; d_sensor gets exactly 0 from E.
+
+        point_grad=True: `points` gets its whole gradient -- how the rays, and so the blur shape, the L/R disparity and
+        the energy, change with x, y and the depth -- in both centre modes: the derivative of optics.py:934-996 with the
+        two @torch.no_grad() of sample_from_points and psf_center taken off and the four pupil draws held fixed; the
+        depth's way into point_obj.xy through the pinhole scale is part of it.  With grad mode on and points.requires_grad the call is a grad call: the staged chain with a
+        recorded trace, trace_grad.PointGradFunction behind the raw grids (and behind E), and with center=True the
+        chief-ray centre in the graph through a staged, recorded chief bundle (the fused pass's centres, bit for bit).
+        With center=False the pinhole-centre term of the default call is kept and the rays' term is added to it.  The
+        default, False, leaves every call and gradient as it was.  It composes with surface_params, glass_params and
+        d_sensor; each keeps its own walk over the one record.  defer, out=, center_out= and trip_policy='adaptive' are
+        refused as for surface_params; with points that require no gradient it is the ordinary call.  Workspace:
+        24 (K + 1) bytes per ray for the primary record and again for the 2048 N chief rays of center=True (rf50mm:
+        0.64 MB per point), held until the graph is freed."""
         if energy and (defer or _default_r_zero or dp is None):
             raise ValueError("energy=True needs dp and the staged chain: defer=True and _default_r_zero are not supported")
         if d_sensor is not None:
@@ -1135,7 +1151,7 @@ class Lensgroup:
             with self._sensor_borrowed(d_sensor):
                 res = self.psf_lr(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
                                   center_pupil_xy, out, defer, center_out, surface_params, None, focus, glass_params,
-                                  energy)
+                                  energy, point_grad)
             if isinstance(res, PendingPSF):
                 # the trip check of a deferred call may launch again: with this call's sensor position
                 def finish(pending=res):
@@ -1146,6 +1162,11 @@ class Lensgroup:
         focus_kw = {} if _focus is None else {"focus": _focus}
         if energy:
             focus_kw["energy"] = True
+        if point_grad and _requires_grad(points):
+            if self.trip_policy == "adaptive":
+                raise ValueError("point_grad=True needs trip_policy 'reference' or 'max': the per-wave trip counts of "
+                                 "'adaptive' are not recorded")
+            focus_kw["point_grad"] = True
         if glass_params is not None and not _requires_grad(glass_params):
             self.set_glass_parameters(glass_params)
             glass_params = None
@@ -1161,7 +1182,7 @@ class Lensgroup:
                 if glass_params is not None:
                     borrowed.enter_context(self._glass_borrowed(glass_params))
                 return self._psf_lr_grad(*args, surface_params=surface_params, glass_params=glass_params, **focus_kw)
-        if _psf_needs_grad(dp if not _default_r_zero else None, points, center, _focus):
+        if "point_grad" in focus_kw or _psf_needs_grad(dp if not _default_r_zero else None, points, center, _focus):
             return self._psf_lr_grad(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero,
                                      pupil_xy, center_pupil_xy, out, defer, center_out, **focus_kw)
         return self._psf_lr(points, ks, wvln, spp, center, dp, normalize, want_r, _default_r_zero, pupil_xy,
@@ -1454,12 +1475,29 @@ class Lensgroup:
             return (*_epilogue(L, R, want_r, single_point), E[0] if single_point else E)
         return _epilogue(L, R, want_r, single_point)
 
+    def _chief_center_recorded(self, po, xc, yc, pupilz, center):
+        """The chief-ray centres of `po` into `center` by the STAGED chain -- sdirt_sample_rays on the green lens,
+        the recording trace, sdirt_center_from_rays -- the centres of the fused sdirt_chief_center, bit for bit.
+        -> the TraceRecord of the chief bundle (24 (K + 1) bytes per ray, 2048 rays per point)."""
+        N, S = po.shape[0], xc.shape[0]
+        ray = Ray.empty((S, N), DEFAULT_WAVE, self.device)                         # optics.py:900: always green
+        _lib.check(_lib.lib().sdirt_sample_rays(dptr(po), N, dptr(xc), dptr(yc), S, float(pupilz), ray.c_rays(),
+                                                stream_ptr(self.device)))
+        rec = self._trace2sensor_recorded(ray)
+        anyv = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().sdirt_center_from_rays(ray.c_rays(), S, N, dptr(center), dptr(anyv),
+                                                     stream_ptr(self.device)))
+        if self.trip_policy == "reference":
+            assert int(anyv.item()) == 1, "No sampled rays is valid."   # optics.py:902
+        return rec
+
     def _staged_rays(self, points, po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen, record=False,
-                     cen_slope=None):
+                     cen_slope=None, chief_record=None):
         """The first stages of the staged chain: sample_from_points, psf_center (or the pinhole centres of
         center=False) into `cen`, trace2sensor.  -> (the [spp, N] sensor-plane rays, spp); record=True: the trace
         keeps its checkpoints, -> (rays, spp, trace_grad.TraceRecord).  cen_slope (float64 [N, 2], center=True):
-        the chief-ray pass also writes d(centre)/d(d_sensor) there."""
+        the chief-ray pass also writes d(centre)/d(d_sensor) there.  chief_record (a list, center=True): the centres come
+        from the staged, recorded chief bundle (_chief_center_recorded), whose TraceRecord is appended to it."""
         pupilz, pupilr = self.entrance_pupil()
         # optics.py:963 (first two draws)
         x2, y2 = self._pupil_samples(spp, pupilr) if pupil_xy is None else map(self._on_device, pupil_xy)
@@ -1473,7 +1511,13 @@ class Lensgroup:
             # optics.py:969 (draws three and four)
             xc, yc = (self._pupil_samples(GEO_SPP, pupilr_c) if center_pupil_xy is None
                       else map(self._on_device, center_pupil_xy))
-            self._chief_center(po, xc, yc, pupilz_c, cen, cen_slope)
+            if chief_record is not None:
+                chief_record.append(self._chief_center_recorded(po, xc, yc, pupilz_c, cen))
+                if cen_slope is not None:
+                    # the slope comes from the fused pass alone: one more chief-ray pass, the same centres
+                    self._chief_center(po, xc, yc, pupilz_c, torch.empty_like(cen), cen_slope)
+            else:
+                self._chief_center(po, xc, yc, pupilz_c, cen, cen_slope)
         else:
             self._pinhole_centres(points, cen)
         self.last_pupil_points = (x2, y2, xc, yc)
@@ -1507,13 +1551,17 @@ class Lensgroup:
 
     def _psf_lr_grad(self, points, ks, wvln, spp, center, dp, normalize, want_r, default_r_zero, pupil_xy,
                      center_pupil_xy, out, defer, center_out, surface_params=None, focus=None, glass_params=None,
-                     energy=False):
+                     energy=False, point_grad=False):
         """psf_lr under autograd: the staged chain's rays and centres (no gradient: optics.py:459, :888 are no_grad),
         then the RAW grids through monte_carlo.SplatFunction -- differentiable in h, f, w and, with center=False, in
         the pinhole centres points[:, :2] * sensor_size / 2 (optics.py:973-976) -- and the max-normalisation of
         optics.py:983-987 as torch ops, so that its gradient goes to the arg-max pixel as in the reference.
         focus: the call's sensor position as a 0-d tensor that requires a gradient (the lens is already set to its
-        value): the chief-ray pass also returns the centres' slope in it, and SplatFunction takes both."""
+        value): the chief-ray pass also returns the centres' slope in it, and SplatFunction takes both.
+        point_grad: the points get the gradient through the rays as well (the two no_grad decorators taken off, the
+        pupil draws held fixed): the trace is recorded, trace_grad.PointGradFunction sits behind the raw
+        grids (and the energy sums), and with center=True the centres are those of a staged, recorded chief bundle
+        behind trace_grad.ChiefCentreFunction."""
         if defer or out is not None or center_out is not None:
             raise ValueError("defer=True, out= and center_out= are not supported when psf_lr records gradients")
         self._require_gpu()
@@ -1530,10 +1578,21 @@ class Lensgroup:
             cen = torch.empty((N, 2), dtype=torch.float32, device=self.device)
             cen_slope = (torch.empty((N, 2), dtype=torch.float64, device=self.device)
                          if focus is not None and center else None)
-            record = surface_params is not None or glass_params is not None
+            lens_grad = surface_params is not None or glass_params is not None
+            record = lens_grad or point_grad
+            chief = [] if point_grad and center else None
             staged = self._staged_rays(points.detach(), po, N, wvln, spp, center, pupil_xy, center_pupil_xy, cen,
-                                       record=record, cen_slope=cen_slope)
+                                       record=record, cen_slope=cen_slope, chief_record=chief)
             ray, spp = staged[:2]
+        if point_grad:
+            x2, y2, xc, yc = self.last_pupil_points
+
+            def samples(x, y, pupil_z):
+                return PointSamples(x, y, pupil_z, np.tan(self.hfov), self.r_last, self.sensor_size[1], self.sensor_size[0])
+            if center:
+                # the chief-ray centre in the graph: dLoss/d(centre), which SplatFunction returns, walks the chief bundle
+                cen = ChiefCentreFunction.apply(points, cen, chief[0],
+                                                samples(xc, yc, self.entrance_pupil(shrink_pupil=True)[0]))
         if not center:
             # the pinhole centres of _pinhole_centres as torch ops on the caller's points: the same fp32 products
             pts = points.to(self.device, torch.float32)
@@ -1548,11 +1607,19 @@ class Lensgroup:
             dpp = None if param_list is None else _lib.DpParams(*[float(v) for v in param_list[:4]])
             cen_c = cen.detach().to(self.device, torch.float32).reshape(N, 2).contiguous()
             staged[2].center = cen_c
+        if lens_grad:
             eta = None if glass_params is None else self._glass_eta(glass_params, wvln)
             if energy:
                 L, R, Es = SurfaceGradFunction.apply(surface_params, eta, L, R, staged[2], cen_c, self.pixel_size, ks, dpp, Es)
             else:
                 L, R = SurfaceGradFunction.apply(surface_params, eta, L, R, staged[2], cen_c, self.pixel_size, ks, dpp)
+        if point_grad:
+            # the points' share through the rays: a walk of its own over the same record
+            args = (points, L, R, staged[2], cen_c, self.pixel_size, ks, dpp, samples(x2, y2, self.entrance_pupil()[0]))
+            if energy:
+                L, R, Es = PointGradFunction.apply(*args, Es)
+            else:
+                L, R = PointGradFunction.apply(*args)
         if normalize:
             L = L / (L.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
             R = R / (R.reshape(N, -1).max(dim=-1).values.reshape(N, 1, 1) + 1e-6)
@@ -1629,7 +1696,7 @@ class Lensgroup:
         return vol
 
     def psf_rgb(self, points, ks=31, spp=GEO_SPP, center=True, param_list=None, pupil_xy=None,
-                center_pupil_xy=None, surface_params=None, d_sensor=None, glass_params=None):
+                center_pupil_xy=None, surface_params=None, d_sensor=None, glass_params=None, point_grad=False):
         """optics.py:999-1015: [N,3,ks,ks] (or [3,ks,ks]) -- the three wavelengths of WAVE_RGB, each an
         independent psf_diff (fresh pupil draws, in the reference's order; every chief-ray centre
         through the green lens).  The three calls are ONE kernel launch whatever the number of points
@@ -1639,7 +1706,8 @@ class Lensgroup:
         wavelength instead of random draws (ray-level parity hand-off).
         d_sensor: the sensor position of this call (psf_lr).  When it requires a gradient the three wavelengths are
         three differentiable psf_lr calls, each centred through the green lens, and its gradient is their sum.
-        glass_params: the glass of this call (psf_lr); with a gradient likewise, glass.grad the sum over the wavelengths."""
+        glass_params: the glass of this call (psf_lr); with a gradient likewise, glass.grad the sum over the wavelengths.
+        point_grad: the points' gradient through the rays (psf_lr); likewise, points.grad the sum over the wavelengths."""
         if not torch.is_tensor(points):
             points = torch.tensor(points)
         if center_pupil_xy is not None and not center:
@@ -1648,7 +1716,7 @@ class Lensgroup:
         if d_sensor is not None and not focus_grad:
             with self._sensor_borrowed(d_sensor):
                 return self.psf_rgb(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy, surface_params,
-                                    None, glass_params)
+                                    None, glass_params, point_grad)
         n_points = points.shape[0] if points.dim() == 2 else 1
         dp, right = _parse_param_list(param_list)
         surface_grad = surface_params is not None and _requires_grad(surface_params)
@@ -1658,7 +1726,8 @@ class Lensgroup:
         if glass_params is not None and not glass_grad:
             self.set_glass_parameters(glass_params)
         if (n_points > 0 and self.device.type == "cuda" and self.mask_reduce is None and ks <= _lib.MAX_KS
-                and not surface_grad and not glass_grad and not focus_grad and not _psf_needs_grad(dp, points, center)):
+                and not surface_grad and not glass_grad and not focus_grad and not _psf_needs_grad(dp, points, center)
+                and not (point_grad and _requires_grad(points))):
             return self._psf_rgb_fused(points, ks, spp, center, param_list, pupil_xy, center_pupil_xy)
         # not one launch (grids above SDIRT_MAX_KS, a rank of a sharded run, or a call that records gradients: one
         # differentiable psf_diff per wavelength, stacked, as optics.py:1010-1014 does): wavelength by wavelength
@@ -1671,7 +1740,7 @@ class Lensgroup:
                              center_pupil_xy=None if center_pupil_xy is None else (center_pupil_xy[0][i], center_pupil_xy[1][i]),
                              surface_params=surface_params if surface_grad else None,
                              d_sensor=d_sensor if focus_grad else None,
-                             glass_params=glass_params if glass_grad else None)
+                             glass_params=glass_params if glass_grad else None, point_grad=point_grad)
             psfs.append(lr[1] if right else lr[0])
         return torch.stack(psfs, dim=-3)
 

@@ -47,6 +47,122 @@ class TraceRecord:
         self.center = None          # the [N, 2] centres the splat used (set by the psf call)
 
 
+class PointSamples:
+    """What takes a recorded bundle's adjoint on to the caller's points: the pupil sample points the bundle was sampled
+    with (x2, y2 [spp] fp32 on the device, pupil_z) and the constants of the pinhole scale (optics.py:956-960)."""
+
+    def __init__(self, x2, y2, pupil_z, tan_hfov, r_last, sensor_w, sensor_h):
+        self.x2, self.y2, self.pupil_z = x2, y2, float(pupil_z)
+        self.tan_hfov, self.r_last, self.sensor_w, self.sensor_h = float(tan_hfov), float(r_last), float(sensor_w), float(sensor_h)
+
+
+def points_bar(rec, ray_grad, smp):
+    """p_bar [N, 3] float64 = dLoss/d(point_obj): sdirt_trace2sensor_grad_points on the record `rec` with the rays'
+    upstream gradient ray_grad [4, M] fp32, summed over the slices in a fixed order."""
+    ray = rec.ray
+    S, N = ray.shape
+    K, dev = rec.n_surfaces, ray.device
+    if N == 0:
+        return torch.zeros((0, 3), dtype=torch.float64, device=dev)
+    h = _lib.lib()
+    ncu = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+    ns = int(h.sdirt_forward_integral_grad_slices(N, S, ncu))
+    partial = torch.empty((N, ns, 3), dtype=torch.float64, device=dev)
+    _lib.check(h.sdirt_trace2sensor_grad_points(
+        rec.dev_lens.handle, (C.c_int32 * K)(*rec.trips), _flags(rec.precision), rec.d_sensor, dptr(rec.workspace),
+        ray.c_rays().ra, dptr(ray_grad), S, N, dptr(smp.x2), dptr(smp.y2), smp.pupil_z, dptr(partial), ns, stream_ptr(dev)))
+    return partial.sum(1)
+
+
+def points_chain(points, p_bar, smp):
+    """dLoss/d(points) [N, 3] float64 from p_bar = dLoss/d(point_obj) through point_obj = (x s W/2, y s H/2, z),
+    s = -z tan(hfov) / r_last (optics.py:956-960, calc_scale_pinhole :1302-1306)."""
+    p = points.detach().to(p_bar.device, torch.float64).reshape(-1, 3)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    hw, hh, q = smp.sensor_w / 2, smp.sensor_h / 2, smp.tan_hfov / smp.r_last
+    s = -z * q
+    return torch.stack((p_bar[:, 0] * s * hw, p_bar[:, 1] * s * hh,
+                        p_bar[:, 2] - (x * hw * p_bar[:, 0] + y * hh * p_bar[:, 1]) * q), -1)
+
+
+class PointGradFunction(torch.autograd.Function):
+    """An identity behind the raw grids (and the energy sums) of a psf call with point_grad=True.  Its backward turns
+    dLoss/d(raw grids) into dLoss/d(sensor-plane rays) (sdirt_forward_integral_grad_rays; with an energy gradient
+    sdirt_dp_energy_grad adds its terms, or writes the buffer alone when the loss uses only the sums, as
+    SurfaceGradFunction does), walks the recorded trace back to the object points (sdirt_trace2sensor_grad_points)
+    and applies the pinhole scale: the rays' share of dLoss/d(points).  The grids' gradients pass through unchanged."""
+
+    @staticmethod
+    def forward(ctx, points, lg, rg, rec, center, ps, ks, dp, smp, energy=None):
+        ctx.rec, ctx.geom, ctx.dp, ctx.smp = rec, (float(ps), int(ks)), dp, smp
+        ctx.meta = (points.dtype, points.device, tuple(points.shape))
+        ctx.save_for_backward(center, points.detach())
+        ctx.has_energy = energy is not None
+        if energy is None:
+            return lg.clone(), rg.clone()
+        ctx.set_materialize_grads(False)        # an output the loss does not use arrives as None, not as zeros
+        return lg.clone(), rg.clone(), energy.clone()
+
+    @staticmethod
+    def backward(ctx, gl, gr, *ge):
+        center, points = ctx.saved_tensors
+        rec, (ps, ks), dp = ctx.rec, ctx.geom, ctx.dp
+        ray = rec.ray
+        S, N = ray.shape
+        dev = ray.device
+        h, st = _lib.lib(), stream_ptr(dev)
+        ncu = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+        gl = gl.to(torch.float32).contiguous() if gl is not None else None
+        gr = gr.to(torch.float32).contiguous() if gr is not None else None
+        ge = ge[0].to(dev, torch.float64).contiguous() if ge and ge[0] is not None else None
+        g_points = None
+        if ctx.needs_input_grad[0] and N > 0:
+            ray_grad = torch.empty((4, S * N), dtype=torch.float32, device=dev)
+            ns = int(h.sdirt_forward_integral_grad_slices(N, S, ncu))
+            from_grids = gl is not None or gr is not None or ge is None
+            if from_grids:
+                _lib.check(h.sdirt_forward_integral_grad_rays(
+                    ray.c_rays(), S, N, ps, ks, dptr(center), C.byref(dp) if dp is not None else None, _flags(rec.precision),
+                    dptr(gl), dptr(gr), None, ns, dptr(ray_grad), st))
+            if ge is not None:
+                _lib.check(h.sdirt_dp_energy_grad(ray.c_rays(), S, N, C.byref(dp), _flags(rec.precision), dptr(ge), None, ns,
+                                                  dptr(ray_grad), 1 if from_grids else 0, st))
+            dtype, device, shape = ctx.meta
+            g_points = points_chain(points, points_bar(rec, ray_grad, ctx.smp), ctx.smp).to(device=device, dtype=dtype).reshape(shape)
+        return (g_points, gl, gr, None, None, None, None, None, None) + ((ge,) if ctx.has_energy else ())
+
+
+class ChiefCentreFunction(torch.autograd.Function):
+    """points -> the chief-ray centres [N, 2] of a staged, recorded chief bundle (optics.py:889-904 without its
+    no_grad): the values are `center` (sdirt_center_from_rays on the record's bundle).  The centre is
+    c = -sum(o ra) / (sum ra + 1e-9), so with g_c = dLoss/dc the chief rays' sensor-plane adjoint is
+    A.o.xy = -g_c ra / (sum ra + 1e-9), A.d = 0; it walks back like the primary bundle's."""
+
+    @staticmethod
+    def forward(ctx, points, center, rec, smp):
+        ctx.rec, ctx.smp = rec, smp
+        ctx.meta = (points.dtype, points.device, tuple(points.shape))
+        ctx.save_for_backward(points.detach())
+        return center.clone()
+
+    @staticmethod
+    def backward(ctx, gc):
+        (points,) = ctx.saved_tensors
+        rec = ctx.rec
+        S, N = rec.ray.shape
+        dev = rec.ray.device
+        if gc is None or N == 0:
+            return None, None, None, None
+        ra = rec.ray.soa[6, :S * N].view(N, S).to(torch.float64)                   # point-major
+        scale = -gc.to(dev, torch.float64).reshape(N, 2) / (ra.sum(1, keepdim=True) + 1e-9)
+        ray_grad = torch.zeros((4, N, S), dtype=torch.float32, device=dev)
+        ray_grad[0] = (scale[:, 0:1] * ra).to(torch.float32)
+        ray_grad[1] = (scale[:, 1:2] * ra).to(torch.float32)
+        dtype, device, shape = ctx.meta
+        g = points_chain(points, points_bar(rec, ray_grad.view(4, N * S), ctx.smp), ctx.smp)
+        return g.to(device=device, dtype=dtype).reshape(shape), None, None, None
+
+
 class SurfaceGradFunction(torch.autograd.Function):
     """theta: surface parameters or None; eta: glass_eta(...) [K] or None (then the backward is the old entry's).
     energy: the [N, 3] sums of monte_carlo.dp_energy on the recorded bundle, or None.  With it the op has a third output,
