@@ -2,7 +2,8 @@
 // surfaces.py:391-679 under autograd): the gradients of a loss with respect to the lens prescription -- every surface's
 // d, c, k and ai -- given its gradients with respect to the sensor-plane rays (sdirt_forward_integral_grad_rays).
 //
-// Three kernels.
+// Three kernels: the recording trace and two backward kernels, k_trace_grad<MP, ETA> and k_trace_grad_points<MP>, which
+// walk the record with the same head and the same surface step (load_ray_grad, sensor_adjoint, surface_adjoint: DESIGN.md 7l).
 //  k_trace_record: sdirt_trace2sensor's trace (the same device functions, surface by surface, the constants loaded
 //      and waited for on the spot) that also stores every ray's (o, d) on ENTRY to each surface and before the final
 //      propagation: the checkpoints, [K + 1][6][M] fp32.
@@ -17,9 +18,9 @@
 //  Reduction: the terms of the surface being walked are summed across the wave with shuffles and added, by lane 0, to
 //      the wave's own float64 row in LDS; after the walk the rows of the workgroup's waves are added in a fixed order
 //      and ONE [K, 3 + SDIRT_MAX_AI] float64 block is stored per workgroup.  No atomics: the same bits every run.
-//  k_trace_grad_eta: the same walk with one more column per surface, dLoss/d eta of its refraction (eta = n1 / n2 as a
-//      leaf: deeplens/surfaces.py:44-53, 401-405, 633-669; Python's chain rule takes it to n and V of every medium,
-//      basics.py:316-362).
+//  k_trace_grad<.., ETA = true>: the same kernel with one more column per surface, dLoss/d eta of its refraction
+//      (eta = n1 / n2 as a leaf: deeplens/surfaces.py:44-53, 401-405, 633-669; Python's chain rule takes it to n and V of
+//      every medium, basics.py:316-362).
 //  k_trace_grad_points: the same walk without parameter columns, one workgroup per (point, spp slice); the adjoint of
 //      the ray that enters surface 0 goes on through d = normalize(q - p) to the object point (optics.py:460-494;
 //      DESIGN.md 7k).
@@ -235,7 +236,7 @@ __device__ __forceinline__ Ray load_ckpt(const float* __restrict__ ws, int64_t M
 
 // The adjoint of one curved surface for a live ray: r = the ray on entry, P = its position on the surface (the next
 // checkpoint's o), A = in: the adjoint of the ray that leaves, out: of the ray that enters; par += the parameter terms.
-// ETA (k_trace_grad_eta): par[kParams] = the term of eta as well.
+// ETA: par[kParams] = the term of eta as well, taken from the adjoint of d' before refract_adjoint overwrites it.
 template <bool ETA>
 __device__ __forceinline__ void curved_adjoint(const SurfHot& h, const double* a, int deg, const Ray& r, const Regain& rg,
                                                double Px, double Py, double Pz, Adj& A, double* par)
@@ -304,154 +305,101 @@ __device__ __forceinline__ void curved_adjoint(const SurfHot& h, const double* a
     A.dz -= tb * t0 / vz;
 }
 
-template <class MP>
+// ---------------------------------------------------------------------------------------------------------------
+// the walk: one head, one surface step, shared by the kernels below
+// ---------------------------------------------------------------------------------------------------------------
+// The upstream gradient of ray i (o.x, o.y, d.x, d.z of the sensor-plane ray) into A; returns whether the ray has one.
+// `in_range`: the lane has a ray at all.
+__device__ __forceinline__ bool load_ray_grad(bool in_range, const float* __restrict__ ra, const float* __restrict__ ray_grad,
+                                              int64_t M, int64_t i, Adj& A)
+{
+    if (!(in_range && ra[i] != 0.0f)) return false;
+    A.ox = ray_grad[i]; A.oy = ray_grad[M + i]; A.dx = ray_grad[2 * M + i]; A.dz = ray_grad[3 * M + i];
+    return A.ox != 0.0 || A.oy != 0.0 || A.dx != 0.0 || A.dz != 0.0;
+}
+
+// The final propagation to the sensor plane (in the ray only), and P = checkpoint K's o: where the ray left surface K - 1.
+__device__ __forceinline__ void sensor_adjoint(const float* __restrict__ ws, int64_t M, int K, int64_t ii, float z_sensor,
+                                               Adj& A, float& Px, float& Py, float& Pz)
+{
+    const Ray r = load_ckpt(ws, M, K, ii);
+    const double t = ((double)z_sensor - (double)r.oz) / (double)r.dz;
+    (void)plane_adjoint(t, r.dx, r.dy, r.dz, A);
+    Px = ws[ckpt_at(M, K, 0, ii)]; Py = ws[ckpt_at(M, K, 1, ii)]; Pz = ws[ckpt_at(M, K, 2, ii)];
+}
+
+// One step of the walk, surface k of ray ii: A = in: the adjoint of the ray that leaves the surface, out: of the ray
+// that enters it; par[NP] = the surface's parameter terms of this ray (zeroed here; with ETA, par[kParams] = eta's);
+// P = in: the ray's position on the surface, out: on the surface before it (checkpoint k's o).
+template <class MP, bool ETA, int NP>
+__device__ __forceinline__ void surface_adjoint(const TripTable& trips, const DevSurface* __restrict__ lens, int k,
+                                                const float* __restrict__ ws, int64_t M, int64_t ii, float& Px, float& Py,
+                                                float& Pz, Adj& A, double* par)
+{
+    const SurfHot& h = lens[k].h;
+    const Ray r = load_ckpt(ws, M, k, ii);
+    const int kind = (int)(h.flags & 3u), deg = (int)((h.flags >> 8) & 15u);
+#pragma unroll
+    for (int c = 0; c < NP; ++c) par[c] = 0.0;
+    if (kind == 0) {
+        if (h.flags & kFlagRefract) {
+            double nbx, nby, nbz;
+            if constexpr (ETA) par[kParams] = refract_eta_bar((double)h.eta_f, r.dx, r.dy, r.dz, 0.0, 0.0, 1.0, A.dx, A.dy, A.dz);
+            refract_adjoint((double)h.eta_f, r.dx, r.dy, r.dz, 0.0, 0.0, 1.0, A.dx, A.dy, A.dz, nbx, nby, nbz);
+        }
+        const double t = ((double)h.d - (double)r.oz) / (double)r.dz;
+        par[0] = plane_adjoint(t, r.dx, r.dy, r.dz, A);
+    } else {
+        const int trip = (int)(int8_t)(trips.w[k >> 2] >> ((k & 3) * 8));
+        double a[kMaxAi];
+        Regain rg;
+        if (deg > 0) {
+            PolyF pol;
+#pragma unroll
+            for (int c = 0; c < kMaxAi; ++c) { pol.a[c] = lens[k].p.ai[c]; pol.ka[c] = lens[k].p.kai[c]; a[c] = pol.a[c]; }
+            rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, pol, r, trip) : newton_regain<MP, false>(h, pol, r, trip);
+        } else {
+#pragma unroll
+            for (int c = 0; c < kMaxAi; ++c) a[c] = 0.0;
+            rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, NoPoly{}, r, trip)
+                                        : newton_regain<MP, false>(h, NoPoly{}, r, trip);
+        }
+        curved_adjoint<ETA>(h, a, deg, r, rg, Px, Py, Pz, A, par);
+    }
+    Px = r.ox; Py = r.oy; Pz = r.oz;
+}
+
+// The surface parameters' kernel.  ETA: one more column per surface, dLoss/d eta of its refraction, for every surface
+// that refracts (every curved one, and a plane between different media; the stop's stays exactly 0).
+template <class MP, bool ETA>
 __global__ void __launch_bounds__(kBlock)
 k_trace_grad(TripTable trips, const DevSurface* __restrict__ lens, int K, const float* __restrict__ ws,
              const float* __restrict__ ra, const float* __restrict__ ray_grad, int64_t M, float z_sensor,
              double* __restrict__ partial)
 {
-    __shared__ double acc[kAdjWaves][SDIRT_MAX_SURFACES][kParams];
-    for (int e = threadIdx.x; e < kAdjWaves * SDIRT_MAX_SURFACES * kParams; e += kBlock) (&acc[0][0][0])[e] = 0.0;
+    constexpr int NP = kParams + (ETA ? 1 : 0);
+    __shared__ double acc[kAdjWaves][SDIRT_MAX_SURFACES][NP];
+    for (int e = threadIdx.x; e < kAdjWaves * SDIRT_MAX_SURFACES * NP; e += kBlock) (&acc[0][0][0])[e] = 0.0;
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t base = (int64_t)blockIdx.x * kBlock; base < M; base += (int64_t)gridDim.x * kBlock) {
         const int64_t i = base + threadIdx.x;
         Adj A{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        bool live = false;
-        if (i < M && ra[i] != 0.0f) {
-            A.ox = ray_grad[i]; A.oy = ray_grad[M + i]; A.dx = ray_grad[2 * M + i]; A.dz = ray_grad[3 * M + i];
-            live = A.ox != 0.0 || A.oy != 0.0 || A.dx != 0.0 || A.dz != 0.0;
-        }
+        const bool live = load_ray_grad(i < M, ra, ray_grad, M, i, A);
         if (__ballot(live) == 0ull) continue;
         const int64_t ii = i < M ? i : M - 1;                 // idle lanes read a ray that exists and contribute nothing
-        {   // the final propagation to the sensor plane: in the ray only
-            const Ray r = load_ckpt(ws, M, K, ii);
-            const double t = ((double)z_sensor - (double)r.oz) / (double)r.dz;
-            (void)plane_adjoint(t, r.dx, r.dy, r.dz, A);
-        }
-        float Px = ws[ckpt_at(M, K, 0, ii)], Py = ws[ckpt_at(M, K, 1, ii)], Pz = ws[ckpt_at(M, K, 2, ii)];
+        float Px, Py, Pz;
+        sensor_adjoint(ws, M, K, ii, z_sensor, A, Px, Py, Pz);
         for (int k = K - 1; k >= 0; --k) {
-            const SurfHot& h = lens[k].h;
-            const Ray r = load_ckpt(ws, M, k, ii);
+            const SurfHot& h = lens[k].h;       // (read before the step, which decodes the same two: one decode)
             const int kind = (int)(h.flags & 3u), deg = (int)((h.flags >> 8) & 15u);
-            double par[kParams];
-#pragma unroll
-            for (int c = 0; c < kParams; ++c) par[c] = 0.0;
-            if (kind == 0) {
-                if (h.flags & kFlagRefract) {
-                    double nbx, nby, nbz;
-                    refract_adjoint((double)h.eta_f, r.dx, r.dy, r.dz, 0.0, 0.0, 1.0, A.dx, A.dy, A.dz, nbx, nby, nbz);
-                }
-                const double t = ((double)h.d - (double)r.oz) / (double)r.dz;
-                par[0] = plane_adjoint(t, r.dx, r.dy, r.dz, A);
-            } else {
-                const int trip = (int)(int8_t)(trips.w[k >> 2] >> ((k & 3) * 8));
-                double a[kMaxAi];
-                Regain rg;
-                if (deg > 0) {
-                    PolyF pol;
-#pragma unroll
-                    for (int c = 0; c < kMaxAi; ++c) { pol.a[c] = lens[k].p.ai[c]; pol.ka[c] = lens[k].p.kai[c]; a[c] = pol.a[c]; }
-                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, pol, r, trip) : newton_regain<MP, false>(h, pol, r, trip);
-                } else {
-#pragma unroll
-                    for (int c = 0; c < kMaxAi; ++c) a[c] = 0.0;
-                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, NoPoly{}, r, trip)
-                                                : newton_regain<MP, false>(h, NoPoly{}, r, trip);
-                }
-                curved_adjoint<false>(h, a, deg, r, rg, Px, Py, Pz, A, par);
-            }
-            Px = r.ox; Py = r.oy; Pz = r.oz;
+            double par[NP];
+            surface_adjoint<MP, ETA, NP>(trips, lens, k, ws, M, ii, Px, Py, Pz, A, par);
             // the columns this surface owns (Aspheric.activate_grad, surfaces.py:837-860): d; c unless a plane; k of an
-            // asphere with k != 0; its ai.  Every other column stays exactly 0.
-            const bool own_k = kind == 2 && h.k != 0.0f;
+            // asphere with k != 0; its ai; with ETA, eta if it refracts.  Every other column stays exactly 0.
+            const bool own_k = kind == 2 && h.k != 0.0f, own_eta = ETA && (h.flags & kFlagRefract) != 0u;
 #pragma unroll
-            for (int c = 0; c < kParams; ++c) {
-                const bool own = c == 0 || (c == 1 && kind != 0) || (c == 2 && own_k) || (c >= 3 && c - 3 < deg);
-                if (!own) continue;                                          // wave-uniform
-                const double v = wave_sum(live ? par[c] : 0.0);
-                if (lane == 0) acc[wave][k][c] += v;
-            }
-        }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < K * kParams; e += kBlock) {
-        const int k = e / kParams, c = e - k * kParams;
-        double v = 0.0;
-        for (int w = 0; w < kAdjWaves; ++w) v += acc[w][k][c];
-        partial[(int64_t)blockIdx.x * K * kParams + e] = v;
-    }
-}
-
-// k_trace_grad with one more column per surface: dLoss/d eta of its refraction, for every surface that refracts (every
-// curved one, and a plane between different media; the stop's stays exactly 0).  The term is taken from the adjoint of
-// d' before refract_adjoint overwrites it, in curved_adjoint and in the plane branch.  A kernel of its own: a walk
-// shared with k_trace_grad moved that kernel's register allocation (tools/isa_compare.py).
-constexpr int kParamsEta = kParams + 1;
-
-template <class MP>
-__global__ void __launch_bounds__(kBlock)
-k_trace_grad_eta(TripTable trips, const DevSurface* __restrict__ lens, int K, const float* __restrict__ ws,
-                 const float* __restrict__ ra, const float* __restrict__ ray_grad, int64_t M, float z_sensor,
-                 double* __restrict__ partial)
-{
-    __shared__ double acc[kAdjWaves][SDIRT_MAX_SURFACES][kParamsEta];
-    for (int e = threadIdx.x; e < kAdjWaves * SDIRT_MAX_SURFACES * kParamsEta; e += kBlock) (&acc[0][0][0])[e] = 0.0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t base = (int64_t)blockIdx.x * kBlock; base < M; base += (int64_t)gridDim.x * kBlock) {
-        const int64_t i = base + threadIdx.x;
-        Adj A{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        bool live = false;
-        if (i < M && ra[i] != 0.0f) {
-            A.ox = ray_grad[i]; A.oy = ray_grad[M + i]; A.dx = ray_grad[2 * M + i]; A.dz = ray_grad[3 * M + i];
-            live = A.ox != 0.0 || A.oy != 0.0 || A.dx != 0.0 || A.dz != 0.0;
-        }
-        if (__ballot(live) == 0ull) continue;
-        const int64_t ii = i < M ? i : M - 1;                 // idle lanes read a ray that exists and contribute nothing
-        {   // the final propagation to the sensor plane: in the ray only
-            const Ray r = load_ckpt(ws, M, K, ii);
-            const double t = ((double)z_sensor - (double)r.oz) / (double)r.dz;
-            (void)plane_adjoint(t, r.dx, r.dy, r.dz, A);
-        }
-        float Px = ws[ckpt_at(M, K, 0, ii)], Py = ws[ckpt_at(M, K, 1, ii)], Pz = ws[ckpt_at(M, K, 2, ii)];
-        for (int k = K - 1; k >= 0; --k) {
-            const SurfHot& h = lens[k].h;
-            const Ray r = load_ckpt(ws, M, k, ii);
-            const int kind = (int)(h.flags & 3u), deg = (int)((h.flags >> 8) & 15u);
-            double par[kParamsEta];
-#pragma unroll
-            for (int c = 0; c < kParamsEta; ++c) par[c] = 0.0;
-            if (kind == 0) {
-                if (h.flags & kFlagRefract) {
-                    double nbx, nby, nbz;
-                    par[kParams] = refract_eta_bar((double)h.eta_f, r.dx, r.dy, r.dz, 0.0, 0.0, 1.0, A.dx, A.dy, A.dz);
-                    refract_adjoint((double)h.eta_f, r.dx, r.dy, r.dz, 0.0, 0.0, 1.0, A.dx, A.dy, A.dz, nbx, nby, nbz);
-                }
-                const double t = ((double)h.d - (double)r.oz) / (double)r.dz;
-                par[0] = plane_adjoint(t, r.dx, r.dy, r.dz, A);
-            } else {
-                const int trip = (int)(int8_t)(trips.w[k >> 2] >> ((k & 3) * 8));
-                double a[kMaxAi];
-                Regain rg;
-                if (deg > 0) {
-                    PolyF pol;
-#pragma unroll
-                    for (int c = 0; c < kMaxAi; ++c) { pol.a[c] = lens[k].p.ai[c]; pol.ka[c] = lens[k].p.kai[c]; a[c] = pol.a[c]; }
-                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, pol, r, trip) : newton_regain<MP, false>(h, pol, r, trip);
-                } else {
-#pragma unroll
-                    for (int c = 0; c < kMaxAi; ++c) a[c] = 0.0;
-                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, NoPoly{}, r, trip)
-                                                : newton_regain<MP, false>(h, NoPoly{}, r, trip);
-                }
-                curved_adjoint<true>(h, a, deg, r, rg, Px, Py, Pz, A, par);
-            }
-            Px = r.ox; Py = r.oy; Pz = r.oz;
-            // the columns of k_trace_grad, and eta for every surface that refracts; every other column stays exactly 0
-            const bool own_k = kind == 2 && h.k != 0.0f, own_eta = (h.flags & kFlagRefract) != 0u;
-#pragma unroll
-            for (int c = 0; c < kParamsEta; ++c) {
+            for (int c = 0; c < NP; ++c) {
                 const bool own = c == 0 || (c == 1 && kind != 0) || (c == 2 && own_k) || (c >= 3 && c < kParams && c - 3 < deg) ||
                                  (c == kParams && own_eta);
                 if (!own) continue;                                          // wave-uniform
@@ -461,11 +409,11 @@ k_trace_grad_eta(TripTable trips, const DevSurface* __restrict__ lens, int K, co
         }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < K * kParamsEta; e += kBlock) {
-        const int k = e / kParamsEta, c = e - k * kParamsEta;
+    for (int e = threadIdx.x; e < K * NP; e += kBlock) {
+        const int k = e / NP, c = e - k * NP;
         double v = 0.0;
         for (int w = 0; w < kAdjWaves; ++w) v += acc[w][k][c];
-        partial[(int64_t)blockIdx.x * K * kParamsEta + e] = v;
+        partial[(int64_t)blockIdx.x * K * NP + e] = v;
     }
 }
 
@@ -474,8 +422,8 @@ k_trace_grad_eta(TripTable trips, const DevSurface* __restrict__ lens, int K, co
 // (o0, d0) = (p, normalize(q_s - p)), q_s = (x2[s], y2[s], pupil_z) (deeplens/optics.py:490-494, basics.py:245), so the
 // ray's term of the point's adjoint is A.o - (A.d - d0 (d0 . A.d)) / |q_s - p|, float64 from the fp32 p (checkpoint 0's
 // o), x2, y2 and pupil_z.  A thread adds its rays' terms in order, the wave sums by shuffles, the four waves meet in
-// LDS: ONE float64 triple per (point, slice), no atomics, nothing pre-zeroed.  A kernel of its own: a walk shared with
-// k_trace_grad would move that kernel's register allocation (tools/isa_compare.py).
+// LDS: ONE float64 triple per (point, slice), no atomics, nothing pre-zeroed.  A kernel of its own for its grid,
+// reduction and tail; the head and the surface step are k_trace_grad's.
 template <class MP>
 __global__ void __launch_bounds__(kBlock)
 k_trace_grad_points(TripTable trips, const DevSurface* __restrict__ lens, int K, const float* __restrict__ ws,
@@ -494,49 +442,13 @@ k_trace_grad_points(TripTable trips, const DevSurface* __restrict__ lens, int K,
         const int64_t ss = s < s_end ? s : s_end - 1;         // idle lanes read a ray that exists and contribute nothing
         const int64_t ii = n * S + ss;
         Adj A{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        bool live = false;
-        if (s < s_end && ra[ii] != 0.0f) {
-            A.ox = ray_grad[ii]; A.oy = ray_grad[M + ii]; A.dx = ray_grad[2 * M + ii]; A.dz = ray_grad[3 * M + ii];
-            live = A.ox != 0.0 || A.oy != 0.0 || A.dx != 0.0 || A.dz != 0.0;
-        }
+        const bool live = load_ray_grad(s < s_end, ra, ray_grad, M, ii, A);
         if (__ballot(live) == 0ull) continue;
-        {   // the final propagation to the sensor plane
-            const Ray r = load_ckpt(ws, M, K, ii);
-            const double t = ((double)z_sensor - (double)r.oz) / (double)r.dz;
-            (void)plane_adjoint(t, r.dx, r.dy, r.dz, A);
-        }
-        float Px = ws[ckpt_at(M, K, 0, ii)], Py = ws[ckpt_at(M, K, 1, ii)], Pz = ws[ckpt_at(M, K, 2, ii)];
+        float Px, Py, Pz;
+        sensor_adjoint(ws, M, K, ii, z_sensor, A, Px, Py, Pz);
         for (int k = K - 1; k >= 0; --k) {
-            const SurfHot& h = lens[k].h;
-            const Ray r = load_ckpt(ws, M, k, ii);
-            const int kind = (int)(h.flags & 3u), deg = (int)((h.flags >> 8) & 15u);
-            if (kind == 0) {
-                if (h.flags & kFlagRefract) {
-                    double nbx, nby, nbz;
-                    refract_adjoint((double)h.eta_f, r.dx, r.dy, r.dz, 0.0, 0.0, 1.0, A.dx, A.dy, A.dz, nbx, nby, nbz);
-                }
-                const double t = ((double)h.d - (double)r.oz) / (double)r.dz;
-                (void)plane_adjoint(t, r.dx, r.dy, r.dz, A);
-            } else {
-                const int trip = (int)(int8_t)(trips.w[k >> 2] >> ((k & 3) * 8));
-                double a[kMaxAi], par[kParams];          // (the parameter terms are dead: nothing reads par)
-                Regain rg;
-                if (deg > 0) {
-                    PolyF pol;
-#pragma unroll
-                    for (int c = 0; c < kMaxAi; ++c) { pol.a[c] = lens[k].p.ai[c]; pol.ka[c] = lens[k].p.kai[c]; a[c] = pol.a[c]; }
-                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, pol, r, trip) : newton_regain<MP, false>(h, pol, r, trip);
-                } else {
-#pragma unroll
-                    for (int c = 0; c < kMaxAi; ++c) a[c] = 0.0;
-                    rg = (h.flags & kFlagKgtM1) ? newton_regain<MP, true>(h, NoPoly{}, r, trip)
-                                                : newton_regain<MP, false>(h, NoPoly{}, r, trip);
-                }
-#pragma unroll
-                for (int c = 0; c < kParams; ++c) par[c] = 0.0;
-                curved_adjoint<false>(h, a, deg, r, rg, Px, Py, Pz, A, par);
-            }
-            Px = r.ox; Py = r.oy; Pz = r.oz;
+            double par[kParams];                         // (the parameter terms are dead: nothing reads par)
+            surface_adjoint<MP, false, kParams>(trips, lens, k, ws, M, ii, Px, Py, Pz, A, par);
         }
         if (live) {
             // (Px, Py, Pz) is checkpoint 0's o: the point itself
@@ -604,17 +516,24 @@ int sdirt_trace2sensor_record(const sdirt_lens* lens, const int32_t* trips, uint
     return SDIRT_OK;
 }
 
+// What every backward walk checks first.  `pointers`: all of the entry's pointer arguments are there.
+static int walk_arguments(bool pointers, const sdirt_lens* lens, const int32_t* trips, TripTable& tt)
+{
+    if (!pointers) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = make_trips(lens, trips, tt)) return rc;
+    for (int k = 0; k < lens->n_surfaces; ++k)
+        if (trips && trips[k] < 0)
+            return fail(SDIRT_ERR_UNSUPPORTED, "trips[%d] < 0: the per-wave trip count of the speed mode is not recorded", k);
+    return SDIRT_OK;
+}
+
 // sdirt_trace2sensor_grad (eta = false) and sdirt_trace2sensor_grad_eta (true): one argument check, one launch
 static int launch_trace_grad(bool eta, const sdirt_lens* lens, const int32_t* trips, uint32_t flags, double d_sensor,
                              const void* workspace, const float* ra, const float* ray_grad, int64_t M, double* partial,
                              int32_t n_workgroups, void* stream)
 {
-    if (!lens || !workspace || !ra || !ray_grad || !partial) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
     TripTable tt;
-    if (int rc = make_trips(lens, trips, tt)) return rc;
-    for (int k = 0; k < lens->n_surfaces; ++k)
-        if (trips && trips[k] < 0)
-            return fail(SDIRT_ERR_UNSUPPORTED, "trips[%d] < 0: the per-wave trip count of the speed mode is not recorded", k);
+    if (int rc = walk_arguments(lens && workspace && ra && ray_grad && partial, lens, trips, tt)) return rc;
     if (M < 0) return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_rays < 0");
     int ncu = 0;
     if (int rc = device_cus(&ncu)) return rc;
@@ -623,7 +542,7 @@ static int launch_trace_grad(bool eta, const sdirt_lens* lens, const int32_t* tr
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_workgroups=%d, the launch has %d (sdirt_trace2sensor_grad_workgroups)",
                     n_workgroups, grid);
     with_math(flags, [&](auto m) {
-        auto* kernel = eta ? k_trace_grad_eta<decltype(m)> : k_trace_grad<decltype(m)>;
+        auto* kernel = eta ? k_trace_grad<decltype(m), true> : k_trace_grad<decltype(m), false>;
         kernel<<<grid, kBlock, 0, as_stream(stream)>>>(
             tt, lens->dev, lens->n_surfaces, (const float*)workspace, ra, ray_grad, M, (float)d_sensor, partial);
         return 0;
@@ -651,12 +570,8 @@ int sdirt_trace2sensor_grad_points(const sdirt_lens* lens, const int32_t* trips,
                                    const float* x2, const float* y2, double pupil_z, double* partial, int32_t n_slices,
                                    void* stream)
 {
-    if (!lens || !workspace || !ra || !ray_grad || !x2 || !y2 || !partial) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
     TripTable tt;
-    if (int rc = make_trips(lens, trips, tt)) return rc;
-    for (int k = 0; k < lens->n_surfaces; ++k)
-        if (trips && trips[k] < 0)
-            return fail(SDIRT_ERR_UNSUPPORTED, "trips[%d] < 0: the per-wave trip count of the speed mode is not recorded", k);
+    if (int rc = walk_arguments(lens && workspace && ra && ray_grad && x2 && y2 && partial, lens, trips, tt)) return rc;
     if (S < 0 || N < 0 || N > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "spp < 0 or n_points out of range");
     if (N == 0) return SDIRT_OK;
     int ncu = 0;

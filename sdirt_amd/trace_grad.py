@@ -56,6 +56,47 @@ class PointSamples:
         self.tan_hfov, self.r_last, self.sensor_w, self.sensor_h = float(tan_hfov), float(r_last), float(sensor_w), float(sensor_h)
 
 
+def _n_cus(dev):
+    return int(torch.cuda.get_device_properties(dev).multi_processor_count)
+
+
+def _identity_outputs(ctx, lg, rg, energy):
+    """The forward of an identity behind the raw grids (and, with `energy`, the sums)."""
+    ctx.has_energy = energy is not None
+    if energy is None:
+        return lg.clone(), rg.clone()
+    ctx.set_materialize_grads(False)        # an output the loss does not use arrives as None, not as zeros
+    return lg.clone(), rg.clone(), energy.clone()
+
+
+def ray_adjoint(rec, center, geom, dp, gl, gr, ge, wanted=True):
+    """dLoss/d(sensor-plane rays) of the record `rec` from dLoss/d(raw grids) gl, gr and dLoss/d(sums) ge (`ge` as
+    backward's *args; each may be None): sdirt_forward_integral_grad_rays writes ray_grad [4, M] fp32 unless only the
+    sums bring a gradient, and sdirt_dp_energy_grad adds the sums' terms to it (accumulate = 1) or writes it alone
+    (accumulate = 0).  -> (ray_grad, gl, gr, ge), the three in the types the library takes; ray_grad is None, and
+    nothing is launched, when it is not `wanted`."""
+    ray, (ps, ks) = rec.ray, geom
+    S, N = ray.shape
+    dev = ray.device
+    h, st = _lib.lib(), stream_ptr(dev)
+    gl = gl.to(torch.float32).contiguous() if gl is not None else None
+    gr = gr.to(torch.float32).contiguous() if gr is not None else None
+    ge = ge[0].to(dev, torch.float64).contiguous() if ge and ge[0] is not None else None
+    if not wanted:
+        return None, gl, gr, ge
+    ray_grad = torch.empty((4, S * N), dtype=torch.float32, device=dev)
+    ns = int(h.sdirt_forward_integral_grad_slices(N, S, _n_cus(dev)))
+    from_grids = gl is not None or gr is not None or ge is None
+    if from_grids:
+        _lib.check(h.sdirt_forward_integral_grad_rays(
+            ray.c_rays(), S, N, ps, ks, dptr(center), C.byref(dp) if dp is not None else None, _flags(rec.precision),
+            dptr(gl), dptr(gr), None, ns, dptr(ray_grad), st))
+    if ge is not None:
+        _lib.check(h.sdirt_dp_energy_grad(ray.c_rays(), S, N, C.byref(dp), _flags(rec.precision), dptr(ge), None, ns,
+                                          dptr(ray_grad), 1 if from_grids else 0, st))
+    return ray_grad, gl, gr, ge
+
+
 def points_bar(rec, ray_grad, smp):
     """p_bar [N, 3] float64 = dLoss/d(point_obj): sdirt_trace2sensor_grad_points on the record `rec` with the rays'
     upstream gradient ray_grad [4, M] fp32, summed over the slices in a fixed order."""
@@ -65,8 +106,7 @@ def points_bar(rec, ray_grad, smp):
     if N == 0:
         return torch.zeros((0, 3), dtype=torch.float64, device=dev)
     h = _lib.lib()
-    ncu = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-    ns = int(h.sdirt_forward_integral_grad_slices(N, S, ncu))
+    ns = int(h.sdirt_forward_integral_grad_slices(N, S, _n_cus(dev)))
     partial = torch.empty((N, ns, 3), dtype=torch.float64, device=dev)
     _lib.check(h.sdirt_trace2sensor_grad_points(
         rec.dev_lens.handle, (C.c_int32 * K)(*rec.trips), _flags(rec.precision), rec.d_sensor, dptr(rec.workspace),
@@ -86,47 +126,26 @@ def points_chain(points, p_bar, smp):
 
 
 class PointGradFunction(torch.autograd.Function):
-    """An identity behind the raw grids (and the energy sums) of a psf call with point_grad=True.  Its backward turns
-    dLoss/d(raw grids) into dLoss/d(sensor-plane rays) (sdirt_forward_integral_grad_rays; with an energy gradient
-    sdirt_dp_energy_grad adds its terms, or writes the buffer alone when the loss uses only the sums, as
-    SurfaceGradFunction does), walks the recorded trace back to the object points (sdirt_trace2sensor_grad_points)
-    and applies the pinhole scale: the rays' share of dLoss/d(points).  The grids' gradients pass through unchanged."""
+    """An identity behind the raw grids (and the energy sums) of a psf call with point_grad=True.  Its backward takes
+    ray_adjoint's dLoss/d(sensor-plane rays), walks the recorded trace back to the object points
+    (sdirt_trace2sensor_grad_points) and applies the pinhole scale: the rays' share of dLoss/d(points).  The grids'
+    gradients pass through unchanged."""
 
     @staticmethod
     def forward(ctx, points, lg, rg, rec, center, ps, ks, dp, smp, energy=None):
         ctx.rec, ctx.geom, ctx.dp, ctx.smp = rec, (float(ps), int(ks)), dp, smp
         ctx.meta = (points.dtype, points.device, tuple(points.shape))
         ctx.save_for_backward(center, points.detach())
-        ctx.has_energy = energy is not None
-        if energy is None:
-            return lg.clone(), rg.clone()
-        ctx.set_materialize_grads(False)        # an output the loss does not use arrives as None, not as zeros
-        return lg.clone(), rg.clone(), energy.clone()
+        return _identity_outputs(ctx, lg, rg, energy)
 
     @staticmethod
     def backward(ctx, gl, gr, *ge):
         center, points = ctx.saved_tensors
-        rec, (ps, ks), dp = ctx.rec, ctx.geom, ctx.dp
-        ray = rec.ray
-        S, N = ray.shape
-        dev = ray.device
-        h, st = _lib.lib(), stream_ptr(dev)
-        ncu = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-        gl = gl.to(torch.float32).contiguous() if gl is not None else None
-        gr = gr.to(torch.float32).contiguous() if gr is not None else None
-        ge = ge[0].to(dev, torch.float64).contiguous() if ge and ge[0] is not None else None
+        rec = ctx.rec
+        wanted = ctx.needs_input_grad[0] and rec.ray.shape[1] > 0
+        ray_grad, gl, gr, ge = ray_adjoint(rec, center, ctx.geom, ctx.dp, gl, gr, ge, wanted)
         g_points = None
-        if ctx.needs_input_grad[0] and N > 0:
-            ray_grad = torch.empty((4, S * N), dtype=torch.float32, device=dev)
-            ns = int(h.sdirt_forward_integral_grad_slices(N, S, ncu))
-            from_grids = gl is not None or gr is not None or ge is None
-            if from_grids:
-                _lib.check(h.sdirt_forward_integral_grad_rays(
-                    ray.c_rays(), S, N, ps, ks, dptr(center), C.byref(dp) if dp is not None else None, _flags(rec.precision),
-                    dptr(gl), dptr(gr), None, ns, dptr(ray_grad), st))
-            if ge is not None:
-                _lib.check(h.sdirt_dp_energy_grad(ray.c_rays(), S, N, C.byref(dp), _flags(rec.precision), dptr(ge), None, ns,
-                                                  dptr(ray_grad), 1 if from_grids else 0, st))
+        if wanted:
             dtype, device, shape = ctx.meta
             g_points = points_chain(points, points_bar(rec, ray_grad, ctx.smp), ctx.smp).to(device=device, dtype=dtype).reshape(shape)
         return (g_points, gl, gr, None, None, None, None, None, None) + ((ge,) if ctx.has_energy else ())
@@ -166,44 +185,24 @@ class ChiefCentreFunction(torch.autograd.Function):
 class SurfaceGradFunction(torch.autograd.Function):
     """theta: surface parameters or None; eta: glass_eta(...) [K] or None (then the backward is the old entry's).
     energy: the [N, 3] sums of monte_carlo.dp_energy on the recorded bundle, or None.  With it the op has a third output,
-    the sums, and dLoss/d(sums) reaches the rays as well: sdirt_dp_energy_grad adds its terms in d.x, d.z to the splat's
-    ray_grad (accumulate = 1) before the ONE walk -- or writes the buffer (accumulate = 0) when no gradient arrives from
-    the grids."""
+    the sums, and dLoss/d(sums) reaches the rays as well (ray_adjoint: its terms in d.x, d.z) before the ONE walk."""
 
     @staticmethod
     def forward(ctx, theta, eta, lg, rg, rec, center, ps, ks, dp, energy=None):
         ctx.rec, ctx.geom, ctx.dp = rec, (float(ps), int(ks)), dp
         ctx.meta = [None if t is None else (t.dtype, t.device, tuple(t.shape)) for t in (theta, eta)]
         ctx.save_for_backward(center)
-        ctx.has_energy = energy is not None
-        if energy is None:
-            return lg.clone(), rg.clone()
-        ctx.set_materialize_grads(False)        # an output the loss does not use arrives as None, not as zeros
-        return lg.clone(), rg.clone(), energy.clone()
+        return _identity_outputs(ctx, lg, rg, energy)
 
     @staticmethod
     def backward(ctx, gl, gr, *ge):
         (center,) = ctx.saved_tensors
-        rec, (ps, ks), dp = ctx.rec, ctx.geom, ctx.dp
+        rec = ctx.rec
         ray = rec.ray
-        S, N = ray.shape
-        M, K, dev = S * N, rec.n_surfaces, ray.device
+        M, K, dev = ray.shape[0] * ray.shape[1], rec.n_surfaces, ray.device
         h, st = _lib.lib(), stream_ptr(dev)
-        ncu = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-        gl = gl.to(torch.float32).contiguous() if gl is not None else None
-        gr = gr.to(torch.float32).contiguous() if gr is not None else None
-        ge = ge[0].to(dev, torch.float64).contiguous() if ge and ge[0] is not None else None
-        ray_grad = torch.empty((4, M), dtype=torch.float32, device=dev)
-        ns = int(h.sdirt_forward_integral_grad_slices(N, S, ncu))
-        from_grids = gl is not None or gr is not None or ge is None
-        if from_grids:
-            _lib.check(h.sdirt_forward_integral_grad_rays(
-                ray.c_rays(), S, N, ps, ks, dptr(center), C.byref(dp) if dp is not None else None, _flags(rec.precision),
-                dptr(gl), dptr(gr), None, ns, dptr(ray_grad), st))
-        if ge is not None:
-            _lib.check(h.sdirt_dp_energy_grad(ray.c_rays(), S, N, C.byref(dp), _flags(rec.precision), dptr(ge), None, ns,
-                                              dptr(ray_grad), 1 if from_grids else 0, st))
-        nwg = int(h.sdirt_trace2sensor_grad_workgroups(M, ncu))
+        ray_grad, gl, gr, ge = ray_adjoint(rec, center, ctx.geom, ctx.dp, gl, gr, ge)
+        nwg = int(h.sdirt_trace2sensor_grad_workgroups(M, _n_cus(dev)))
         theta_meta, eta_meta = ctx.meta
         with_eta = eta_meta is not None and ctx.needs_input_grad[1]
         entry = h.sdirt_trace2sensor_grad_eta if with_eta else h.sdirt_trace2sensor_grad

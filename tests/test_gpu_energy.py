@@ -21,6 +21,7 @@ from conftest import load_state, make_lens
 from energy_f64 import energy_f64, energy_grad_f64, energy_scale_f64, x_tan_f64
 from splat_f64 import fragile_x
 from test_gpu_dp_grad import FRAGILE_CAP, FUZZ_TABLE, fuzz_case, make_case
+from test_gpu_trace_grad import _abi
 
 from sdirt_amd import _lib
 from sdirt_amd.basics import DEFAULT_WAVE, dptr, stream_ptr
@@ -402,18 +403,6 @@ def test_mirrored_points_swap_left_and_right_energy(lens, pupil):
     assert abs(float(E[1, 0] / E[1, 1]) - 1.0) > 1e-3                             # and off axis there is shading to swap
 
 
-def _abi_trace_grad(rec, ray_grad, entry):
-    h = _lib.lib()
-    K, M = rec.n_surfaces, rec.ray.numel
-    nwg = int(h.sdirt_trace2sensor_grad_workgroups(M, _ncu()))
-    cols = N_COLUMNS + (1 if entry.endswith("_eta") else 0)
-    partial = torch.full((nwg, K, cols), float("nan"), dtype=torch.float64, device=DEV)
-    _lib.check(getattr(h, entry)(rec.dev_lens.handle, (C.c_int32 * K)(*rec.trips), _flags(rec.precision), rec.d_sensor,
-                                 dptr(rec.workspace), rec.ray.c_rays().ra, dptr(ray_grad), M, dptr(partial), nwg,
-                                 stream_ptr(torch.device(DEV))))
-    return partial.sum(0)
-
-
 def _energy_ray_grad(rec, ge):
     ray = rec.ray
     S, N = ray.shape
@@ -434,7 +423,7 @@ def test_energy_only_loss_reaches_the_surfaces_through_the_recorded_trace(lens, 
     (G * E).sum().backward()
     (rec,) = cap.records
     rg = _energy_ray_grad(rec, (G / SPP).contiguous())
-    want = _abi_trace_grad(rec, rg, "sdirt_trace2sensor_grad")[:, :N_COLUMNS].to(torch.float32).cpu()
+    want = _abi(rec, rg, "sdirt_trace2sensor_grad").sum(0)[:, :N_COLUMNS].to(torch.float32).cpu()
     assert float(theta.grad.abs().max()) > 0 and torch.equal(theta.grad, want)
 
 
@@ -448,7 +437,7 @@ def test_energy_only_loss_reaches_the_glass_through_the_eta_entry(lens, pupil):
     (G * E).sum().backward()
     (rec,) = cap.records
     rg = _energy_ray_grad(rec, (G / SPP).contiguous())
-    g_eta = _abi_trace_grad(rec, rg, "sdirt_trace2sensor_grad_eta")[:, N_COLUMNS]
+    g_eta = _abi(rec, rg, "sdirt_trace2sensor_grad_eta").sum(0)[:, N_COLUMNS]
     again = lens.glass_parameters().requires_grad_()
     eta = lens._glass_eta(again, DEFAULT_WAVE)
     eta.backward(g_eta.to(device=eta.device, dtype=eta.dtype))

@@ -23,14 +23,13 @@ import torch
 
 import glass_f64 as G
 from conftest import ROOT, load_state, make_lens
-from test_gpu_trace_grad import _Capture, _points, _pupil, _ray_grad
+from test_gpu_trace_grad import _abi, _Capture, _points, _pupil, _ray_grad
 from test_gpu_trace_grad import _restated as _restated_theta
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from sdirt_amd import _lib
 from sdirt_amd.basics import WAVE_RGB, dptr, stream_ptr
-from sdirt_amd.monte_carlo import _flags
 from sdirt_amd.trace_grad import N_COLUMNS
 
 pytestmark = pytest.mark.gpu
@@ -162,20 +161,6 @@ def _upstream(lens, rec, ks, seed=3):
     return _ray_grad(rec, rec.center, lens.pixel_size, ks, GL, GR)
 
 
-def _abi(rec, ray_grad, entry):
-    """One call of `entry` on a captured record: partial [n_workgroups, K, columns] float64."""
-    h = _lib.lib()
-    K, M = rec.n_surfaces, rec.ray.numel
-    ncu = int(torch.cuda.get_device_properties(DEV).multi_processor_count)
-    nwg = int(h.sdirt_trace2sensor_grad_workgroups(M, ncu))
-    cols = N_COLUMNS + (1 if entry.endswith("_eta") else 0)
-    partial = torch.full((nwg, K, cols), float("nan"), dtype=torch.float64, device=DEV)
-    _lib.check(getattr(h, entry)(rec.dev_lens.handle, (C.c_int32 * K)(*rec.trips), _flags(rec.precision), rec.d_sensor,
-                                 dptr(rec.workspace), rec.ray.c_rays().ra, dptr(ray_grad), M, dptr(partial), nwg,
-                                 stream_ptr(torch.device(DEV))))
-    return partial
-
-
 def test_abi_eta_entry_returns_the_old_columns_and_an_exact_zero_on_the_stop():
     lens = _lens("rf50mm")
     pts, ks = _points(6), 21
@@ -194,6 +179,9 @@ def test_abi_eta_entry_returns_the_old_columns_and_an_exact_zero_on_the_stop():
     diff = (new[..., :N_COLUMNS].sum(0) - old.sum(0)).abs().cpu()
     print(f"columns 0-10, eta entry against the old one: max |diff| / sum|terms| = {float((diff / mag.clamp_min(1e-300)).max()):.3e}")
     assert bool((diff <= 1e-12 * mag).all())
+    # ... and bit for bit, workgroup by workgroup: the two entries are one kernel body, the same float64
+    # operations in the same order
+    assert torch.equal(new[..., :N_COLUMNS], old)
     eta_col = new[..., N_COLUMNS]
     assert bool((eta_col[:, lens.aper_idx] == 0).all())
     others = [k for k in range(len(lens.surfaces)) if k != lens.aper_idx]

@@ -21,6 +21,7 @@ import point_f64 as P
 import trace_f64 as T
 from conftest import load_state, make_lens
 from splat_f64 import max_normalise
+from test_gpu_trace_grad import _points
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 
@@ -40,13 +41,6 @@ CORNERS = {"rf50mm": 0.98, "rf35mm": 1.08}
 
 def _lens(name):
     return make_lens(name, DEV, load_state(name))
-
-
-def _points(n, depth_lo=-3000.0, depth_hi=-800.0, field=0.7, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    xy = (torch.rand(n, 2, generator=g) * 2 - 1) * field
-    z = depth_lo + (depth_hi - depth_lo) * torch.rand(n, 1, generator=g)
-    return torch.cat((xy, z), 1)
 
 
 def _corner_points(name):

@@ -97,6 +97,21 @@ def _ray_grad(rec, cen, ps, ks, GL, GR, dp=DP):
     return out
 
 
+def _abi(rec, ray_grad, entry):
+    """One call of `entry` (sdirt_trace2sensor_grad or .._grad_eta) on a captured record: partial [n_workgroups, K, columns]
+    float64."""
+    h = _lib.lib()
+    K, M = rec.n_surfaces, rec.ray.numel
+    ncu = int(torch.cuda.get_device_properties(DEV).multi_processor_count)
+    nwg = int(h.sdirt_trace2sensor_grad_workgroups(M, ncu))
+    cols = 3 + _lib.MAX_AI + (1 if entry.endswith("_eta") else 0)
+    partial = torch.full((nwg, K, cols), float("nan"), dtype=torch.float64, device=DEV)
+    _lib.check(getattr(h, entry)(rec.dev_lens.handle, (C.c_int32 * K)(*rec.trips), _flags(rec.precision), rec.d_sensor,
+                                 dptr(rec.workspace), rec.ray.c_rays().ra, dptr(ray_grad), M, dptr(partial), nwg,
+                                 stream_ptr(torch.device(DEV))))
+    return partial
+
+
 def _restated(lens, rec, ray_grad, wvln=0.589, chunk=1 << 16):
     """(gradient, sum of |per-ray terms|) [K, C] float64 of sum_rays ray_grad . (o.x, o.y, d.x, d.z) at the sensor by the
     float64 restatement on the kernel's checkpoints, per-ray parameter leaves, on the GPU in chunks of rays."""

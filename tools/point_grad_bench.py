@@ -41,7 +41,9 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--ks", type=int, default=21)
+    ap.add_argument("--precision", default="lean", choices=("lean", "ieee"), help="the math policy of the three entries")
     a = ap.parse_args()
+    fl = _lib.PSF_STRICT_IEEE if a.precision == "ieee" else 0
     N, S = (int(v) for v in a.shape.split("x"))
     dev = torch.device("cuda:0")
     lens = Lensgroup(os.path.join(os.path.dirname(_lib.HERE), "sdirt_amd", "data", "rf50mm.json"), sensor_res=(512, 768), device=dev)
@@ -58,7 +60,7 @@ def main():
     trips = (C.c_int32 * K)(*lens._fixed_trips_for("max").tolist())
     out = Ray.empty(src.shape, src.wvln, dev, obliq=src.has_obliq)
     ws = torch.empty(h.sdirt_trace2sensor_grad_workspace_bytes(M, K) // 4, dtype=torch.float32, device=dev)
-    _lib.check(h.sdirt_trace2sensor_record(handle, trips, 0, float(lens.d_sensor), src.c_rays(), out.c_rays(), M, None, dptr(ws), st))
+    _lib.check(h.sdirt_trace2sensor_record(handle, trips, fl, float(lens.d_sensor), src.c_rays(), out.c_rays(), M, None, dptr(ws), st))
     ray_grad = torch.ones((4, M), dtype=torch.float32, device=dev)
     ncu = torch.cuda.get_device_properties(dev).multi_processor_count
     nwg = h.sdirt_trace2sensor_grad_workgroups(M, ncu)
@@ -66,13 +68,13 @@ def main():
     partial = torch.empty((nwg, K, 3 + _lib.MAX_AI), dtype=torch.float64, device=dev)
     p_partial = torch.empty((N, ns, 3), dtype=torch.float64, device=dev)
     calls = {
-        "grad": lambda: _lib.check(h.sdirt_trace2sensor_grad(handle, trips, 0, float(lens.d_sensor), dptr(ws), out.c_rays().ra,
+        "grad": lambda: _lib.check(h.sdirt_trace2sensor_grad(handle, trips, fl, float(lens.d_sensor), dptr(ws), out.c_rays().ra,
                                                              dptr(ray_grad), M, dptr(partial), nwg, st)),
         "grad_points": lambda: _lib.check(h.sdirt_trace2sensor_grad_points(
-            handle, trips, 0, float(lens.d_sensor), dptr(ws), out.c_rays().ra, dptr(ray_grad), S, N, dptr(x2), dptr(y2),
+            handle, trips, fl, float(lens.d_sensor), dptr(ws), out.c_rays().ra, dptr(ray_grad), S, N, dptr(x2), dptr(y2),
             float(pupil_z), dptr(p_partial), ns, st)),
     }
-    res = {"shape": [N, S], "surfaces": K, "workgroups": {"grad": int(nwg), "grad_points": int(N * ns)},
+    res = {"shape": [N, S], "precision": a.precision, "surfaces": K, "workgroups": {"grad": int(nwg), "grad_points": int(N * ns)},
            "live": float((out.ra != 0).float().mean())}
     for name, fn in calls.items():
         res[name + "_event_s"] = timed(fn, a.steps, a.warmup)

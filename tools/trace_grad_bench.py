@@ -6,9 +6,10 @@
         python3 tools/trace_grad_bench.py --shape 4096x4096 --steps 5 --warmup 2
 
 One batch of N points x S samples through rf50mm (K = 12): sdirt_trace2sensor (k_trace, the yardstick),
-sdirt_trace2sensor_record (k_trace_record), sdirt_trace2sensor_grad (k_trace_grad) and sdirt_trace2sensor_grad_eta
-(k_trace_grad_eta: the eta column as well; skipped where the library has no such entry, so that the
-script also times a build from before it) with the same trip table, every ray given an upstream gradient.  The kernel times are rocprofv3's (*_kernel_stats.csv); the device-event times printed
+sdirt_trace2sensor_record (k_trace_record), sdirt_trace2sensor_grad (k_trace_grad<.., false>) and
+sdirt_trace2sensor_grad_eta (k_trace_grad<.., true>: the eta column as well, DESIGN.md sections 7i and 7l; skipped where
+the library has no such entry, so that the script also times a build from before it) with the same trip table and
+--precision, every ray given an upstream gradient.  The kernel times are rocprofv3's (*_kernel_stats.csv); the device-event times printed
 here include the launches and are a cross-check only.  One JSON line: event times, the bytes each call has to move
 (bundle in and out: 28 + 28 per ray; checkpoints: 24 (K + 1) per ray written by the recording trace and read by the
 backward, which also reads 4 + 16 per ray), and what that is of 8 TB/s."""
@@ -44,7 +45,9 @@ def main():
     ap.add_argument("--shape", default="4096x4096", help="points x samples (also: 64x65536)")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--precision", default="lean", choices=("lean", "ieee"), help="the math policy of every call")
     a = ap.parse_args()
+    fl = _lib.PSF_STRICT_IEEE if a.precision == "ieee" else 0
     N, S = (int(v) for v in a.shape.split("x"))
     dev = torch.device("cuda:0")
     lens = Lensgroup(os.path.join(os.path.dirname(_lib.HERE), "sdirt_amd", "data", "rf50mm.json"), sensor_res=(512, 768), device=dev)
@@ -61,19 +64,19 @@ def main():
     nwg = h.sdirt_trace2sensor_grad_workgroups(M, torch.cuda.get_device_properties(dev).multi_processor_count)
     partial = torch.empty((nwg, K, 3 + _lib.MAX_AI + 1), dtype=torch.float64, device=dev)       # room for the eta column
     calls = {
-        "trace2sensor": lambda: _lib.check(h.sdirt_trace2sensor(handle, trips, 0, float(lens.d_sensor), src.c_rays(), out.c_rays(),
+        "trace2sensor": lambda: _lib.check(h.sdirt_trace2sensor(handle, trips, fl, float(lens.d_sensor), src.c_rays(), out.c_rays(),
                                                                 M, None, st)),
-        "record": lambda: _lib.check(h.sdirt_trace2sensor_record(handle, trips, 0, float(lens.d_sensor), src.c_rays(),
+        "record": lambda: _lib.check(h.sdirt_trace2sensor_record(handle, trips, fl, float(lens.d_sensor), src.c_rays(),
                                                                  out.c_rays(), M, None, dptr(ws), st)),
-        "grad": lambda: _lib.check(h.sdirt_trace2sensor_grad(handle, trips, 0, float(lens.d_sensor), dptr(ws), out.c_rays().ra,
+        "grad": lambda: _lib.check(h.sdirt_trace2sensor_grad(handle, trips, fl, float(lens.d_sensor), dptr(ws), out.c_rays().ra,
                                                              dptr(ray_grad), M, dptr(partial), nwg, st)),
     }
     nbytes = {"trace2sensor": 56 * M, "record": (56 + 24 * (K + 1)) * M, "grad": (24 * (K + 1) + 20) * M}
     if hasattr(h, "sdirt_trace2sensor_grad_eta"):
-        calls["grad_eta"] = lambda: _lib.check(h.sdirt_trace2sensor_grad_eta(handle, trips, 0, float(lens.d_sensor), dptr(ws),
+        calls["grad_eta"] = lambda: _lib.check(h.sdirt_trace2sensor_grad_eta(handle, trips, fl, float(lens.d_sensor), dptr(ws),
                                                                              out.c_rays().ra, dptr(ray_grad), M, dptr(partial), nwg, st))
         nbytes["grad_eta"] = nbytes["grad"]
-    res = {"shape": [N, S], "surfaces": K, "live": None}
+    res = {"shape": [N, S], "precision": a.precision, "surfaces": K, "live": None}
     for name, fn in calls.items():
         t = timed(fn, a.steps, a.warmup)
         res[name] = {"event_s": t, "bytes": nbytes[name], "share_of_8TBps": nbytes[name] / t / PEAK}
