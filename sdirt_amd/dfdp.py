@@ -148,8 +148,12 @@ def _layout(x):
         return x.shape[0], spatial
     fmt = {4: torch.channels_last, 5: torch.channels_last_3d}.get(x.dim())
     vl = 8 if x.dtype == torch.float16 else 4
-    if fmt is not None and x.is_contiguous(memory_format=fmt) and (x.shape[1] <= 256 or (x.shape[1] % vl == 0 and x.shape[1] <= 256 * vl)):
-        return x.shape[0] * spatial, 1
+    if fmt is not None and x.is_contiguous(memory_format=fmt):
+        # up to 256 channels: one channel per thread at any address; more: 16-byte groups only, which a view that does not
+        # start on a 16-byte boundary cannot have (sdirt_bn_relu refuses it)
+        C = x.shape[1]
+        if C <= 256 or (C % vl == 0 and C <= 256 * vl and x.data_ptr() % 16 == 0):
+            return x.shape[0] * spatial, 1
     return None
 
 
