@@ -1,22 +1,25 @@
 // sdirt_grad.hip -- the backward pass of the splat stage (deeplens/monte_carlo.py:9-68, 135-240, 242-372): the
-// gradients of a loss with respect to the dual-pixel parameters (h, f, w) and the PSF centres, given its gradients
-// with respect to the RAW left and right grids.  The rays carry no gradient (the reference's sample_from_points and
-// psf_center run under no_grad), nor does the microlens radius r (it is re-wrapped by torch.tensor(r) at :167, :274).
+// gradients of a loss with respect to the dual-pixel parameters (h, f, w), the PSF centres, the sensor position and
+// the sensor-plane rays, given its gradients with respect to the RAW left and right grids; and the energy of a point
+// with its backward pass.  The microlens radius r carries no gradient (it is re-wrapped by torch.tensor(r) at :167, :274).
 //
-// Per ray: the window test, the four bilinear taps and the sub-pixel areas s_l, s_r are recomputed with the
-// forward's own fp32 operations (the same rays in and out of the window, the same clamp decisions), then
+// Per ray (splat_ray): the window test, the four bilinear taps and the sub-pixel areas s_l, s_r are recomputed with the
+// forward's own fp32 operations (the same rays in and out of the window, the same clamp decisions: clamp_gates), then
 //   d/d(h, f, w) : ra * (gl . taps * ds_l/dtheta + gr . taps * ds_r/dtheta)
 //   d/d(cx, cy)  : ra * (s_l * d(gl . taps)/dc + s_r * d(gr . taps)/dc)      (through the bilinear weights)
 // in float64.  A segment area A(x) = r^2 (u - sin(2u)/2), u = acos(x/r), is differentiated by its chord,
 // dA/dx = -2 sqrt(r^2 - x^2): no acos in the derivative, and 0 where |x| = r (the reference's autograd gives a
 // non-finite value there).  Every torch.clamp passes the gradient where lo <= x <= hi and stops it outside.
 //
-// Reduction: one workgroup per (point, slice of the spp axis); the ray terms are summed in float64 registers, across
-// the wave with shuffles, across the workgroup through LDS, and ONE float64 partial of 5 values is stored per
-// (point, slice).  No atomics: the gradients are the same bits from run to run.
+// Launch: one workgroup per (point, slice of the spp axis) (block_slice).  The kernels that sum keep the ray terms in
+// float64 registers and reduce them across the wave with shuffles, across the workgroup through LDS, to ONE float64
+// partial per (point, slice) (block_sum_store).  No atomics: the gradients are the same bits from run to run.
 //
-// The same launch shape carries the energy of a point (k_dp_energy: the sums of ra s_l, ra s_r and ra over ALL its rays) and
-// its backward pass (k_dp_energy_grad), further down.
+// Each piece is written once and the five kernels are made of them:
+//   k_forward_integral_grad<.., FOCUS>  splat_ray + dz_boundaries, summed: 5 components, 6 with the sensor position
+//   k_forward_integral_grad_rays        splat_ray + dz_dt, stored per ray
+//   k_dp_energy                         the sums of ra s_l, ra s_r and ra over ALL rays of a point
+//   k_dp_energy_grad<.., PARTIAL, RAYS> its backward pass: dz_boundaries summed, or dz_dt stored per ray
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,7 +34,8 @@ namespace {
 
 constexpr int kGradThreads = 256;
 constexpr int kGradComps = 5;                       // h, f, w, cx, cy
-constexpr int kFocusComps = 6;                      // ... and the sensor position (k_forward_integral_grad_focus)
+constexpr int kFocusComps = 6;                      // ... and the sensor position (k_forward_integral_grad<.., FOCUS>)
+constexpr int kEnergyComps = 3;                     // sum ra s_l, sum ra s_r, sum ra; backward: h, f, w
 constexpr int kGradLdsBytes = 48 * 1024;            // both grids staged in LDS up to ks 78
 
 // The float64 copies of the parameters the derivatives are evaluated at.
@@ -45,6 +49,50 @@ struct GradLaunch {
     double dwr_dcx;       // d(column fraction)/d(cx) = -ksm1 / dx_rng (times the ray's weight)
     double dwb_dcy;       // d(row fraction)/d(cy)    = -ksm1 / dy_rng
 };
+
+// One workgroup per (point n, slice j) of samples [s_begin, s_end): blockIdx.x = n * nslices + j, which is also the
+// row of the workgroup's partial.
+struct Slice {
+    int64_t n, s_begin, s_end;
+    int j;
+};
+
+__device__ __forceinline__ Slice block_slice(const GradLaunch& g, int64_t S)
+{
+    Slice b;
+    b.n = blockIdx.x / (uint32_t)g.nslices;
+    b.j = (int)(blockIdx.x - (uint32_t)b.n * g.nslices);
+    b.s_begin = (int64_t)b.j * g.chunk;
+    b.s_end = min(S, b.s_begin + g.chunk);
+    return b;
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The workgroup's sum of every thread's acc[COMPS], stored at out[0 .. COMPS): the wave by shuffles, the waves 0 to 3
+// through LDS.  Called by all threads of the workgroup.
+template <int COMPS>
+__device__ __forceinline__ void block_sum_store(const double (&acc)[COMPS], double* __restrict__ out)
+{
+    __shared__ double red[kGradThreads / 64][COMPS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < COMPS; ++c) {
+        const double v = wave_sum(acc[c]);
+        if (lane == 0) red[wave][c] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < COMPS) {
+        double v = 0.0;
+        for (int k = 0; k < kGradThreads / 64; ++k) v += red[k][threadIdx.x];
+        out[threadIdx.x] = v;
+    }
+}
 
 // Window test and bilinear taps of one ray: splat_taps' operations, one by one (the same rays in the window, the
 // same taps), keeping the row / column fractions and the weight the bilinear weights are made of.
@@ -95,235 +143,20 @@ __device__ __forceinline__ void d_lens(const DpGrad& q, double t, double a, doub
     d[2] = a * q.f / D;
 }
 
-// d/d(h, f, w) of Z_a, a = +1, 0, -1 (right, middle, left), where s_r = Z_m - Z_r and s_l = Z_l - Z_m.
+// The clamp rule of Z_a, a = +1, 0, -1 (right, middle, left; k = 0, 1, 2), where s_r = Z_m - Z_r and s_l = Z_l - Z_m:
+// any derivative of Z_a is c1 * dx1 + c2 * dx2, x1 = the lens-projected boundary and x2 = a*w - h*t the margin
+// boundary (:186-188).  use(k, a, c1, c2) is called for k = 0, 1, 2.
 //  small r (monte_carlo.py:169-206): Z = A(clamp(x1, -r, r)) - c2 - A(clamp(c2, -r, r)), c2 = clamp(x2, -0.5, 0.5)
 //  big r (:278-338): Z = T(x1) - c2 - T(x2), T(x) = A(c) - r^2 seg(clamp(u, tr, tl)) - r cos(clamp(u, tr, tl)),
 //       c = clamp(x, -0.5, 0.5), u = acos(c / r); with the u clamp open T's derivative is -dc (the area terms cancel),
 //       closed it is A'(c) dc
-// with x1 = the lens-projected boundary (d_lens) and x2 = a*w - h*t the margin boundary (:186-188).
-// The clamp decisions are taken on the forward's fp32 values (x1f, x2f, and for big r the fp32 acos of the forward).
-template <bool BIG, class M, class Div>
-__device__ __forceinline__ void dz_boundaries(const DevDpParams& p, const Div& div_fmh, const DpGrad& q, float x_tan,
-                                              double dZ[3][3])
-{
-    const float fx = p.f * x_tan, hx = p.h * x_tan;
-    float x1f[3], x2f[3];
-    if (BIG) {      // dp_weights_big divides with '/'
-        x1f[0] = p.w - ((fx - p.w) * p.h) / p.fmh;
-        x1f[1] = ((-fx) * p.h) / p.fmh;
-        x1f[2] = (-p.w) - ((fx + p.w) * p.h) / p.fmh;
-    } else {
-        x1f[0] = p.w - div_fmh((fx - p.w) * p.h);
-        x1f[1] = div_fmh((-fx) * p.h);
-        x1f[2] = (-p.w) - div_fmh((fx + p.w) * p.h);
-    }
-    x2f[0] = p.w - hx; x2f[1] = 0.0f - hx; x2f[2] = (-p.w) - hx;
-    const double t = (double)x_tan;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double a = 1.0 - (double)k;                 // +1, 0, -1
-        double d1[3];
-        d_lens(q, t, a, d1);
-        const double x1 = a * q.w - (q.f * t - a * q.w) * q.h / q.fmh;
-        const double x2 = a * q.w - q.h * t;
-        const double d2[3] = {-t, 0.0, a};
-        double c1, c2;                                     // dZ = c1 * dx1 + c2 * dx2
-        if (BIG) {
-            const bool g1 = in_range(x1f[k], -0.5f, 0.5f), g2 = in_range(x2f[k], -0.5f, 0.5f);
-            const float u1 = __ocml_acos_f32(clampf(x1f[k], -0.5f, 0.5f) / p.r);
-            const float u2 = __ocml_acos_f32(clampf(x2f[k], -0.5f, 0.5f) / p.r);
-            const bool gu1 = in_range(u1, p.tr, p.tl), gu2 = in_range(u2, p.tr, p.tl);
-            c1 = g1 ? (gu1 ? -1.0 : chord(q.r, x1)) : 0.0;
-            c2 = g2 ? -1.0 - (gu2 ? -1.0 : chord(q.r, x2)) : 0.0;
-        } else {
-            const bool g1 = in_range(x1f[k], -p.r, p.r), g2 = in_range(x2f[k], -0.5f, 0.5f);
-            const bool gi = in_range(clampf(x2f[k], -0.5f, 0.5f), -p.r, p.r);
-            c1 = g1 ? chord(q.r, x1) : 0.0;
-            c2 = g2 ? -1.0 - (gi ? chord(q.r, x2) : 0.0) : 0.0;
-        }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) dZ[k][j] = c1 * d1[j] + c2 * d2[j];
-    }
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// One workgroup per (point n, slice j): blockIdx.x = n * nslices + j.  LDS: the point's two upstream grids (when
-// they fit, else they are read through L2) and the per-wave sums.
-template <bool BIG, class M, bool STAGE>
-__global__ void __launch_bounds__(kGradThreads)
-k_forward_integral_grad(sdirt_rays R, int64_t S, SplatGeom gm, DevDpParams dp, DpGrad q, GradLaunch gl_,
-                        const float* __restrict__ center, const float* __restrict__ gl, const float* __restrict__ gr,
-                        double* __restrict__ partial)
-{
-    extern __shared__ __attribute__((aligned(16))) float g_lds[];
-    __shared__ double red[kGradThreads / 64][kGradComps];
-    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
-    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
-    const int tile = gm.ks * gm.ks;
-    const float* GL = gl ? gl + n * tile : nullptr;
-    const float* GR = gr ? gr + n * tile : nullptr;
-    if (STAGE) {
-        for (int e = threadIdx.x; e < tile; e += kGradThreads) {
-            g_lds[e] = GL ? GL[e] : 0.0f;
-            g_lds[tile + e] = GR ? GR[e] : 0.0f;
-        }
-        __syncthreads();
-    }
-    const float cx = center[2 * n], cy = center[2 * n + 1];
-    const auto div_dy = UDiv<M>::make(gm.dy_rng), div_dx = UDiv<M>::make(gm.dx_rng);
-    const auto div_fmh = UDiv<M>::make(dp.fmh);
-    double acc[kGradComps] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
-    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
-        const int64_t i = n * S + s;
-        const float ox = R.ox[i], oy = R.oy[i], dx = R.dx[i], dz = R.dz[i], ra = R.ra[i];
-        GradTaps tp;
-        if (!grad_taps(gm, div_dy, div_dx, ox, oy, cx, cy, ra, tp)) continue;
-        const float x_tan = (-dx) / dz;                   // monte_carlo.py:48
-        float sl, sr;
-        if (BIG) dp_weights_big(dp, x_tan, sl, sr);
-        else dp_weights_small<M>(dp, div_fmh, x_tan, sl, sr);
-        // upstream gradients at the four taps
-        double lt, lr_, lb, lbr, rt = 0.0, rr_ = 0.0, rb = 0.0, rbr = 0.0;
-        if (STAGE) {
-            lt = g_lds[tp.i_tl]; lr_ = g_lds[tp.i_tr]; lb = g_lds[tp.i_bl]; lbr = g_lds[tp.i_br];
-            rt = g_lds[tile + tp.i_tl]; rr_ = g_lds[tile + tp.i_tr]; rb = g_lds[tile + tp.i_bl];
-            rbr = g_lds[tile + tp.i_br];
-        } else {
-            lt = GL ? GL[tp.i_tl] : 0.0f; lr_ = GL ? GL[tp.i_tr] : 0.0f;
-            lb = GL ? GL[tp.i_bl] : 0.0f; lbr = GL ? GL[tp.i_br] : 0.0f;
-            if (GR) { rt = GR[tp.i_tl]; rr_ = GR[tp.i_tr]; rb = GR[tp.i_bl]; rbr = GR[tp.i_br]; }
-        }
-        const double wb = tp.wb, wr = tp.wr, w = tp.w;
-        // g . bilinear weights, and its derivatives by the column (wr) and row (wb) fractions
-        const double bl = (1.0 - wb) * ((1.0 - wr) * lt + wr * lr_) + wb * ((1.0 - wr) * lb + wr * lbr);
-        const double br = (1.0 - wb) * ((1.0 - wr) * rt + wr * rr_) + wb * ((1.0 - wr) * rb + wr * rbr);
-        const double bl_wr = (1.0 - wb) * (lr_ - lt) + wb * (lbr - lb), bl_wb = (1.0 - wr) * (lb - lt) + wr * (lbr - lr_);
-        const double br_wr = (1.0 - wb) * (rr_ - rt) + wb * (rbr - rb), br_wb = (1.0 - wr) * (rb - rt) + wr * (rbr - rr_);
-        double dZ[3][3];
-        dz_boundaries<BIG, M>(dp, div_fmh, q, x_tan, dZ);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double dsr = dZ[1][c] - dZ[0][c], dsl = dZ[2][c] - dZ[1][c];
-            acc[c] += w * (bl * dsl + br * dsr);
-        }
-        // the centre moves the shifted point (times the weight, :38) and so the bilinear fractions
-        const double cs = w * ((double)sl * bl_wr + (double)sr * br_wr), cr = w * ((double)sl * bl_wb + (double)sr * br_wb);
-        acc[3] += w * gl_.dwr_dcx * cs;
-        acc[4] += w * gl_.dwb_dcy * cr;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < kGradComps; ++c) {
-        const double v = wave_sum(acc[c]);
-        if (lane == 0) red[wave][c] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kGradComps) {
-        double v = 0.0;
-        for (int k = 0; k < kGradThreads / 64; ++k) v += red[k][threadIdx.x];
-        partial[(n * gl_.nslices + j) * kGradComps + threadIdx.x] = v;
-    }
-}
-
-// k_forward_integral_grad with a SIXTH component, the sensor position s (the focus setting): the sensor-plane point of a
-// ray is o = o' + d (s - o'.z) / d.z, so d(o.xy)/ds = d.xy / d.z, and o enters the splat as the centre does (the shift is
-// -o - c): component 5 = sum over the rays of g_x d.x / d.z + g_y d.y / d.z, g_x and g_y the ray's own terms of
-// components 3 and 4.  The slopes and the sum are float64, from the forward's fp32 d; the window, the taps and the clamp
-// decisions are the forward's and carry no gradient; x_tan = -d.x / d.z and ra do not depend on s.  24 bytes per ray (d.y
-// as well).  A kernel of its own, the body restated: k_forward_integral_grad keeps its registers and its ISA.  Components
-// 0 to 4 are the same operations in the same order: the same bits.
-template <bool BIG, class M, bool STAGE>
-__global__ void __launch_bounds__(kGradThreads)
-k_forward_integral_grad_focus(sdirt_rays R, int64_t S, SplatGeom gm, DevDpParams dp, DpGrad q, GradLaunch gl_,
-                              const float* __restrict__ center, const float* __restrict__ gl, const float* __restrict__ gr,
-                              double* __restrict__ partial)
-{
-    extern __shared__ __attribute__((aligned(16))) float g_lds[];
-    __shared__ double red[kGradThreads / 64][kFocusComps];
-    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
-    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
-    const int tile = gm.ks * gm.ks;
-    const float* GL = gl ? gl + n * tile : nullptr;
-    const float* GR = gr ? gr + n * tile : nullptr;
-    if (STAGE) {
-        for (int e = threadIdx.x; e < tile; e += kGradThreads) {
-            g_lds[e] = GL ? GL[e] : 0.0f;
-            g_lds[tile + e] = GR ? GR[e] : 0.0f;
-        }
-        __syncthreads();
-    }
-    const float cx = center[2 * n], cy = center[2 * n + 1];
-    const auto div_dy = UDiv<M>::make(gm.dy_rng), div_dx = UDiv<M>::make(gm.dx_rng);
-    const auto div_fmh = UDiv<M>::make(dp.fmh);
-    double acc[kFocusComps] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
-    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
-        const int64_t i = n * S + s;
-        const float ox = R.ox[i], oy = R.oy[i], dx = R.dx[i], dy = R.dy[i], dz = R.dz[i], ra = R.ra[i];
-        GradTaps tp;
-        if (!grad_taps(gm, div_dy, div_dx, ox, oy, cx, cy, ra, tp)) continue;
-        const float x_tan = (-dx) / dz;                   // monte_carlo.py:48
-        float sl, sr;
-        if (BIG) dp_weights_big(dp, x_tan, sl, sr);
-        else dp_weights_small<M>(dp, div_fmh, x_tan, sl, sr);
-        // upstream gradients at the four taps
-        double lt, lr_, lb, lbr, rt = 0.0, rr_ = 0.0, rb = 0.0, rbr = 0.0;
-        if (STAGE) {
-            lt = g_lds[tp.i_tl]; lr_ = g_lds[tp.i_tr]; lb = g_lds[tp.i_bl]; lbr = g_lds[tp.i_br];
-            rt = g_lds[tile + tp.i_tl]; rr_ = g_lds[tile + tp.i_tr]; rb = g_lds[tile + tp.i_bl];
-            rbr = g_lds[tile + tp.i_br];
-        } else {
-            lt = GL ? GL[tp.i_tl] : 0.0f; lr_ = GL ? GL[tp.i_tr] : 0.0f;
-            lb = GL ? GL[tp.i_bl] : 0.0f; lbr = GL ? GL[tp.i_br] : 0.0f;
-            if (GR) { rt = GR[tp.i_tl]; rr_ = GR[tp.i_tr]; rb = GR[tp.i_bl]; rbr = GR[tp.i_br]; }
-        }
-        const double wb = tp.wb, wr = tp.wr, w = tp.w;
-        // g . bilinear weights, and its derivatives by the column (wr) and row (wb) fractions
-        const double bl = (1.0 - wb) * ((1.0 - wr) * lt + wr * lr_) + wb * ((1.0 - wr) * lb + wr * lbr);
-        const double br = (1.0 - wb) * ((1.0 - wr) * rt + wr * rr_) + wb * ((1.0 - wr) * rb + wr * rbr);
-        const double bl_wr = (1.0 - wb) * (lr_ - lt) + wb * (lbr - lb), bl_wb = (1.0 - wr) * (lb - lt) + wr * (lbr - lr_);
-        const double br_wr = (1.0 - wb) * (rr_ - rt) + wb * (rbr - rb), br_wb = (1.0 - wr) * (rb - rt) + wr * (rbr - rr_);
-        double dZ[3][3];
-        dz_boundaries<BIG, M>(dp, div_fmh, q, x_tan, dZ);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double dsr = dZ[1][c] - dZ[0][c], dsl = dZ[2][c] - dZ[1][c];
-            acc[c] += w * (bl * dsl + br * dsr);
-        }
-        // the centre moves the shifted point (times the weight, :38) and so the bilinear fractions
-        const double cs = w * ((double)sl * bl_wr + (double)sr * br_wr), cr = w * ((double)sl * bl_wb + (double)sr * br_wb);
-        const double g_x = w * gl_.dwr_dcx * cs, g_y = w * gl_.dwb_dcy * cr;
-        acc[3] += g_x;
-        acc[4] += g_y;
-        // the sensor plane moves the ray's point along the ray: d(o.xy)/ds = d.xy / d.z
-        const double z = (double)dz;
-        acc[5] += g_x * ((double)dx / z) + g_y * ((double)dy / z);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < kFocusComps; ++c) {
-        const double v = wave_sum(acc[c]);
-        if (lane == 0) red[wave][c] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kFocusComps) {
-        double v = 0.0;
-        for (int k = 0; k < kGradThreads / 64; ++k) v += red[k][threadIdx.x];
-        partial[(n * gl_.nslices + j) * kFocusComps + threadIdx.x] = v;
-    }
-}
-
-// d/dt of Z_a, t = x_tan, a = +1, 0, -1: dz_boundaries' clamp decisions (the forward's fp32 values) with
-// dx1/dt = -f h / (f - h) and dx2/dt = -h -- what a ray's direction gets through x_tan = -d.x / d.z.
-template <bool BIG, class M, class Div>
-__device__ __forceinline__ void dz_dt(const DevDpParams& p, const Div& div_fmh, const DpGrad& q, float x_tan, double dT[3])
+// The clamp decisions are taken on the forward's fp32 values: x1f and x2f recomputed as dp_weights_big (which divides
+// with '/') and dp_weights_small (div_fmh) compute them, and for big r the fp32 acos of the forward.  The chords are
+// float64, at the float64 x1 and x2.  (A callable, not arrays c1[3], c2[3]: the user's terms stay in the iteration
+// that computes x1, whose product (f t - a w) h d_lens shares.)
+template <bool BIG, class M, class Div, class Use>
+__device__ __forceinline__ void clamp_gates(const DevDpParams& p, const Div& div_fmh, const DpGrad& q, float x_tan,
+                                            Use&& use)
 {
     const float fx = p.f * x_tan, hx = p.h * x_tan;
     float x1f[3], x2f[3];
@@ -337,10 +170,10 @@ __device__ __forceinline__ void dz_dt(const DevDpParams& p, const Div& div_fmh, 
         x1f[2] = (-p.w) - div_fmh((fx + p.w) * p.h);
     }
     x2f[0] = p.w - hx; x2f[1] = 0.0f - hx; x2f[2] = (-p.w) - hx;
-    const double t = (double)x_tan, d1 = -q.f * q.h / q.fmh, d2 = -q.h;
+    const double t = (double)x_tan;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const double a = 1.0 - (double)k;
+        const double a = 1.0 - (double)k;                 // +1, 0, -1
         const double x1 = a * q.w - (q.f * t - a * q.w) * q.h / q.fmh;
         const double x2 = a * q.w - q.h * t;
         double c1, c2;
@@ -357,8 +190,139 @@ __device__ __forceinline__ void dz_dt(const DevDpParams& p, const Div& div_fmh, 
             c1 = g1 ? chord(q.r, x1) : 0.0;
             c2 = g2 ? -1.0 - (gi ? chord(q.r, x2) : 0.0) : 0.0;
         }
-        dT[k] = c1 * d1 + c2 * d2;
+        use(k, a, c1, c2);
     }
+}
+
+// d/d(h, f, w) of Z_a: dx1 = d_lens, dx2 = (-t, 0, a)
+template <bool BIG, class M, class Div>
+__device__ __forceinline__ void dz_boundaries(const DevDpParams& p, const Div& div_fmh, const DpGrad& q, float x_tan,
+                                              double dZ[3][3])
+{
+    const double t = (double)x_tan;
+    clamp_gates<BIG, M>(p, div_fmh, q, x_tan, [&](int k, double a, double c1, double c2) {
+        double d1[3];
+        d_lens(q, t, a, d1);
+        const double d2[3] = {-t, 0.0, a};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) dZ[k][j] = c1 * d1[j] + c2 * d2[j];
+    });
+}
+
+// d/dt of Z_a, t = x_tan: dx1/dt = -f h / (f - h) and dx2/dt = -h -- what a ray's direction gets through
+// x_tan = -d.x / d.z.
+template <bool BIG, class M, class Div>
+__device__ __forceinline__ void dz_dt(const DevDpParams& p, const Div& div_fmh, const DpGrad& q, float x_tan, double dT[3])
+{
+    const double d1 = -q.f * q.h / q.fmh, d2 = -q.h;
+    clamp_gates<BIG, M>(p, div_fmh, q, x_tan, [&](int k, double, double c1, double c2) { dT[k] = c1 * d1 + c2 * d2; });
+}
+
+// The point's two upstream grids into LDS, [tile] left then [tile] right, a null grid as zeros.
+__device__ __forceinline__ void stage_grids(const float* GL, const float* GR, int tile, float* lds)
+{
+    for (int e = threadIdx.x; e < tile; e += kGradThreads) {
+        lds[e] = GL ? GL[e] : 0.0f;
+        lds[tile + e] = GR ? GR[e] : 0.0f;
+    }
+    __syncthreads();
+}
+
+// What one ray in the window, with weight, hands to the kernel's tail.
+struct RayTerms {
+    float x_tan;          // (-d.x) / d.z (monte_carlo.py:48)
+    double w;             // the ray's weight
+    double bl, br;        // g . bilinear weights, left and right grid
+    double g_x, g_y;      // the ray's terms of dLoss/d(cx, cy): the centre moves the shifted point (times the weight,
+};                        // :38) and so the bilinear fractions
+
+// The adjoint of the splat for one ray: the window test and taps, the forward's fp32 sub-pixel weights, the upstream
+// gradients at the four taps (STAGE: from LDS; else through L2, a null grid read as 0) and the bilinear terms; then
+// tail(RayTerms), in the same region.  A ray without weight or outside the window: no call.
+template <bool BIG, class M, bool STAGE, class Tail>
+__device__ __forceinline__ void splat_ray(const SplatGeom& gm, const DevDpParams& dp, const GradLaunch& gl_,
+                                          const UDiv<M>& div_dy, const UDiv<M>& div_dx, const UDiv<M>& div_fmh,
+                                          const float* GL, const float* GR, const float* g_lds, float cx, float cy,
+                                          float ox, float oy, float dx, float dz, float ra, Tail&& tail)
+{
+    // d.x and d.z are first used behind the window test.  Left alone, the compiler sinks their loads there in some
+    // instantiations (small r, lean, staged), and every ray in the window pays a second round trip to memory; this
+    // keeps a ray's loads together in front of the test.
+    asm volatile("" :: "v"(dx), "v"(dz));
+    GradTaps tp;
+    if (!grad_taps(gm, div_dy, div_dx, ox, oy, cx, cy, ra, tp)) return;
+    const float x_tan = (-dx) / dz;
+    float sl, sr;
+    if (BIG) dp_weights_big(dp, x_tan, sl, sr);
+    else dp_weights_small<M>(dp, div_fmh, x_tan, sl, sr);
+    double lt, lr_, lb, lbr, rt = 0.0, rr_ = 0.0, rb = 0.0, rbr = 0.0;
+    if (STAGE) {
+        const int tile = gm.ks * gm.ks;
+        lt = g_lds[tp.i_tl]; lr_ = g_lds[tp.i_tr]; lb = g_lds[tp.i_bl]; lbr = g_lds[tp.i_br];
+        rt = g_lds[tile + tp.i_tl]; rr_ = g_lds[tile + tp.i_tr]; rb = g_lds[tile + tp.i_bl];
+        rbr = g_lds[tile + tp.i_br];
+    } else {
+        lt = GL ? GL[tp.i_tl] : 0.0f; lr_ = GL ? GL[tp.i_tr] : 0.0f;
+        lb = GL ? GL[tp.i_bl] : 0.0f; lbr = GL ? GL[tp.i_br] : 0.0f;
+        if (GR) { rt = GR[tp.i_tl]; rr_ = GR[tp.i_tr]; rb = GR[tp.i_bl]; rbr = GR[tp.i_br]; }
+    }
+    const double wb = tp.wb, wr = tp.wr, w = tp.w;
+    // g . bilinear weights, and its derivatives by the column (wr) and row (wb) fractions
+    const double bl = (1.0 - wb) * ((1.0 - wr) * lt + wr * lr_) + wb * ((1.0 - wr) * lb + wr * lbr);
+    const double br = (1.0 - wb) * ((1.0 - wr) * rt + wr * rr_) + wb * ((1.0 - wr) * rb + wr * rbr);
+    const double bl_wr = (1.0 - wb) * (lr_ - lt) + wb * (lbr - lb), bl_wb = (1.0 - wr) * (lb - lt) + wr * (lbr - lr_);
+    const double br_wr = (1.0 - wb) * (rr_ - rt) + wb * (rbr - rb), br_wb = (1.0 - wr) * (rb - rt) + wr * (rbr - rr_);
+    const double cs = w * ((double)sl * bl_wr + (double)sr * br_wr), cr = w * ((double)sl * bl_wb + (double)sr * br_wb);
+    tail(RayTerms{x_tan, w, bl, br, w * gl_.dwr_dcx * cs, w * gl_.dwb_dcy * cr});
+}
+
+// The ray terms summed: partial [N, nslices, 5] = d/d(h, f, w, cx, cy).  LDS: the point's two upstream grids (STAGE:
+// they fit; else they are read through L2) and the per-wave sums.
+// FOCUS: a SIXTH component, the sensor position s (the focus setting): the sensor-plane point of a ray is
+// o = o' + d (s - o'.z) / d.z, so d(o.xy)/ds = d.xy / d.z, and o enters the splat as the centre does (the shift is
+// -o - c): component 5 = sum over the rays of g_x d.x / d.z + g_y d.y / d.z.  The slopes and the sum are float64, from
+// the forward's fp32 d; x_tan = -d.x / d.z and ra do not depend on s.  24 bytes per ray (d.y as well) instead of 20.
+// Components 0 to 4 are the same operations in the same order with and without FOCUS: the same bits.
+template <bool BIG, class M, bool STAGE, bool FOCUS>
+__global__ void __launch_bounds__(kGradThreads)
+k_forward_integral_grad(sdirt_rays R, int64_t S, SplatGeom gm, DevDpParams dp, DpGrad q, GradLaunch gl_,
+                        const float* __restrict__ center, const float* __restrict__ gl, const float* __restrict__ gr,
+                        double* __restrict__ partial)
+{
+    constexpr int COMPS = FOCUS ? kFocusComps : kGradComps;
+    extern __shared__ __attribute__((aligned(16))) float g_lds[];
+    const Slice b = block_slice(gl_, S);
+    const int tile = gm.ks * gm.ks;
+    const float* GL = gl ? gl + b.n * tile : nullptr;
+    const float* GR = gr ? gr + b.n * tile : nullptr;
+    if (STAGE) stage_grids(GL, GR, tile, g_lds);
+    const float cx = center[2 * b.n], cy = center[2 * b.n + 1];
+    const auto div_dy = UDiv<M>::make(gm.dy_rng), div_dx = UDiv<M>::make(gm.dx_rng);
+    const auto div_fmh = UDiv<M>::make(dp.fmh);
+    double acc[COMPS] = {};
+    for (int64_t s = b.s_begin + threadIdx.x; s < b.s_end; s += kGradThreads) {
+        const int64_t i = b.n * S + s;
+        const float ox = R.ox[i], oy = R.oy[i], dx = R.dx[i], dz = R.dz[i], ra = R.ra[i];
+        float dy = 0.0f;
+        if constexpr (FOCUS) dy = R.dy[i];
+        splat_ray<BIG, M, STAGE>(gm, dp, gl_, div_dy, div_dx, div_fmh, GL, GR, g_lds, cx, cy, ox, oy, dx, dz, ra,
+                                 [&](const RayTerms& t) {
+            double dZ[3][3];
+            dz_boundaries<BIG, M>(dp, div_fmh, q, t.x_tan, dZ);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double dsr = dZ[1][c] - dZ[0][c], dsl = dZ[2][c] - dZ[1][c];
+                acc[c] += t.w * (t.bl * dsl + t.br * dsr);
+            }
+            acc[3] += t.g_x;
+            acc[4] += t.g_y;
+            if constexpr (FOCUS) {      // the sensor plane moves the ray's point along the ray
+                const double z = (double)dz;
+                acc[5] += t.g_x * ((double)dx / z) + t.g_y * ((double)dy / z);
+            }
+        });
+    }
+    block_sum_store<COMPS>(acc, partial + (b.n * gl_.nslices + b.j) * COMPS);
 }
 
 // The per-ray terms k_forward_integral_grad sums, stored instead: ray_grad [4, M] = dLoss/d(o.x, o.y, d.x, d.z) of the
@@ -372,57 +336,29 @@ k_forward_integral_grad_rays(sdirt_rays R, int64_t S, int64_t Mtot, SplatGeom gm
                              float* __restrict__ ray_grad)
 {
     extern __shared__ __attribute__((aligned(16))) float g_lds[];
-    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
-    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
+    const Slice b = block_slice(gl_, S);
     const int tile = gm.ks * gm.ks;
-    const float* GL = gl ? gl + n * tile : nullptr;
-    const float* GR = gr ? gr + n * tile : nullptr;
-    if (STAGE) {
-        for (int e = threadIdx.x; e < tile; e += kGradThreads) {
-            g_lds[e] = GL ? GL[e] : 0.0f;
-            g_lds[tile + e] = GR ? GR[e] : 0.0f;
-        }
-        __syncthreads();
-    }
-    const float cx = center[2 * n], cy = center[2 * n + 1];
+    const float* GL = gl ? gl + b.n * tile : nullptr;
+    const float* GR = gr ? gr + b.n * tile : nullptr;
+    if (STAGE) stage_grids(GL, GR, tile, g_lds);
+    const float cx = center[2 * b.n], cy = center[2 * b.n + 1];
     const auto div_dy = UDiv<M>::make(gm.dy_rng), div_dx = UDiv<M>::make(gm.dx_rng);
     const auto div_fmh = UDiv<M>::make(dp.fmh);
-    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
-    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
-        const int64_t i = n * S + s;
+    for (int64_t s = b.s_begin + threadIdx.x; s < b.s_end; s += kGradThreads) {
+        const int64_t i = b.n * S + s;
         const float ox = R.ox[i], oy = R.oy[i], dx = R.dx[i], dz = R.dz[i], ra = R.ra[i];
         float g_ox = 0.0f, g_oy = 0.0f, g_dx = 0.0f, g_dz = 0.0f;
-        GradTaps tp;
-        if (grad_taps(gm, div_dy, div_dx, ox, oy, cx, cy, ra, tp)) {
-            const float x_tan = (-dx) / dz;
-            float sl, sr;
-            if (BIG) dp_weights_big(dp, x_tan, sl, sr);
-            else dp_weights_small<M>(dp, div_fmh, x_tan, sl, sr);
-            double lt, lr_, lb, lbr, rt = 0.0, rr_ = 0.0, rb = 0.0, rbr = 0.0;
-            if (STAGE) {
-                lt = g_lds[tp.i_tl]; lr_ = g_lds[tp.i_tr]; lb = g_lds[tp.i_bl]; lbr = g_lds[tp.i_br];
-                rt = g_lds[tile + tp.i_tl]; rr_ = g_lds[tile + tp.i_tr]; rb = g_lds[tile + tp.i_bl];
-                rbr = g_lds[tile + tp.i_br];
-            } else {
-                lt = GL ? GL[tp.i_tl] : 0.0f; lr_ = GL ? GL[tp.i_tr] : 0.0f;
-                lb = GL ? GL[tp.i_bl] : 0.0f; lbr = GL ? GL[tp.i_br] : 0.0f;
-                if (GR) { rt = GR[tp.i_tl]; rr_ = GR[tp.i_tr]; rb = GR[tp.i_bl]; rbr = GR[tp.i_br]; }
-            }
-            const double wb = tp.wb, wr = tp.wr, w = tp.w;
-            const double bl = (1.0 - wb) * ((1.0 - wr) * lt + wr * lr_) + wb * ((1.0 - wr) * lb + wr * lbr);
-            const double br = (1.0 - wb) * ((1.0 - wr) * rt + wr * rr_) + wb * ((1.0 - wr) * rb + wr * rbr);
-            const double bl_wr = (1.0 - wb) * (lr_ - lt) + wb * (lbr - lb), bl_wb = (1.0 - wr) * (lb - lt) + wr * (lbr - lr_);
-            const double br_wr = (1.0 - wb) * (rr_ - rt) + wb * (rbr - rb), br_wb = (1.0 - wr) * (rb - rt) + wr * (rbr - rr_);
-            const double cs = w * ((double)sl * bl_wr + (double)sr * br_wr), cr = w * ((double)sl * bl_wb + (double)sr * br_wb);
+        splat_ray<BIG, M, STAGE>(gm, dp, gl_, div_dy, div_dx, div_fmh, GL, GR, g_lds, cx, cy, ox, oy, dx, dz, ra,
+                                 [&](const RayTerms& t) {
             double dT[3];
-            dz_dt<BIG, M>(dp, div_fmh, q, x_tan, dT);
-            const double dt = w * (bl * (dT[2] - dT[1]) + br * (dT[1] - dT[0]));          // dLoss/d(x_tan)
+            dz_dt<BIG, M>(dp, div_fmh, q, t.x_tan, dT);
+            const double dt = t.w * (t.bl * (dT[2] - dT[1]) + t.br * (dT[1] - dT[0]));          // dLoss/d(x_tan)
             const double z = (double)dz;
-            g_ox = (float)(w * gl_.dwr_dcx * cs);
-            g_oy = (float)(w * gl_.dwb_dcy * cr);
+            g_ox = (float)t.g_x;
+            g_oy = (float)t.g_y;
             g_dx = (float)(-dt / z);
             g_dz = (float)(dt * (double)dx / (z * z));
-        }
+        });
         ray_grad[i] = g_ox; ray_grad[Mtot + i] = g_oy; ray_grad[2 * Mtot + i] = g_dx; ray_grad[3 * Mtot + i] = g_dz;
     }
 }
@@ -431,22 +367,17 @@ k_forward_integral_grad_rays(sdirt_rays R, int64_t S, int64_t Mtot, SplatGeom gm
 // not -- what the raw grids would sum to if forward_integral did not zero the rays outside its window
 // (monte_carlo.py:37-38; the four bilinear taps of a ray sum to 1), and what psf_diff computes as lum and drops
 // (optics.py:979-991).  s_l, s_r are the splat's own fp32 weights (dp_weights_small<M> / dp_weights_big on
-// x_tan = (-d.x) / d.z); the products and sums are float64, a thread's rays in order, the wave by shuffles, the
-// workgroup through LDS: one partial of 3 values per (point, slice), no atomics.  12 bytes per ray.
-constexpr int kEnergyComps = 3;
-
+// x_tan = (-d.x) / d.z); the products and sums are float64, a thread's rays in order: one partial of 3 values per
+// (point, slice).  12 bytes per ray.
 template <bool BIG, class M>
 __global__ void __launch_bounds__(kGradThreads)
 k_dp_energy(sdirt_rays R, int64_t S, DevDpParams dp, GradLaunch gl_, double* __restrict__ partial)
 {
-    __shared__ double red[kGradThreads / 64][kEnergyComps];
-    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
-    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
+    const Slice b = block_slice(gl_, S);
     const auto div_fmh = UDiv<M>::make(dp.fmh);
-    double acc[kEnergyComps] = {0.0, 0.0, 0.0};
-    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
-    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
-        const int64_t i = n * S + s;
+    double acc[kEnergyComps] = {};
+    for (int64_t s = b.s_begin + threadIdx.x; s < b.s_end; s += kGradThreads) {
+        const int64_t i = b.n * S + s;
         const float dx = R.dx[i], dz = R.dz[i], ra = R.ra[i];
         if (!(ra != 0.0f)) continue;
         const float x_tan = (-dx) / dz;                   // monte_carlo.py:48
@@ -458,18 +389,7 @@ k_dp_energy(sdirt_rays R, int64_t S, DevDpParams dp, GradLaunch gl_, double* __r
         acc[1] += w * (double)sr;
         acc[2] += w;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < kEnergyComps; ++c) {
-        const double v = wave_sum(acc[c]);
-        if (lane == 0) red[wave][c] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kEnergyComps) {
-        double v = 0.0;
-        for (int k = 0; k < kGradThreads / 64; ++k) v += red[k][threadIdx.x];
-        partial[(n * gl_.nslices + j) * kEnergyComps + threadIdx.x] = v;
-    }
+    block_sum_store<kEnergyComps>(acc, partial + (b.n * gl_.nslices + b.j) * kEnergyComps);
 }
 
 // The backward pass of k_dp_energy: given grad_e [N, 3] = dLoss/dE (column 2 is not read: ra is a forward decision),
@@ -484,15 +404,12 @@ __global__ void __launch_bounds__(kGradThreads)
 k_dp_energy_grad(sdirt_rays R, int64_t S, int64_t Mtot, DevDpParams dp, DpGrad q, GradLaunch gl_,
                  const double* __restrict__ grad_e, double* __restrict__ partial, float* __restrict__ ray_grad)
 {
-    __shared__ double red[kGradThreads / 64][kEnergyComps];
-    const int64_t n = blockIdx.x / (uint32_t)gl_.nslices;
-    const int j = (int)(blockIdx.x - (uint32_t)n * gl_.nslices);
+    const Slice b = block_slice(gl_, S);
     const auto div_fmh = UDiv<M>::make(dp.fmh);
-    const double g_l = grad_e[kEnergyComps * n], g_r = grad_e[kEnergyComps * n + 1];
-    double acc[kEnergyComps] = {0.0, 0.0, 0.0};
-    const int64_t s_begin = (int64_t)j * gl_.chunk, s_end = min(S, s_begin + gl_.chunk);
-    for (int64_t s = s_begin + threadIdx.x; s < s_end; s += kGradThreads) {
-        const int64_t i = n * S + s;
+    const double g_l = grad_e[kEnergyComps * b.n], g_r = grad_e[kEnergyComps * b.n + 1];
+    double acc[kEnergyComps] = {};
+    for (int64_t s = b.s_begin + threadIdx.x; s < b.s_end; s += kGradThreads) {
+        const int64_t i = b.n * S + s;
         const float dx = R.dx[i], dz = R.dz[i], ra = R.ra[i];
         float g_dx = 0.0f, g_dz = 0.0f;
         if (ra != 0.0f) {
@@ -525,20 +442,7 @@ k_dp_energy_grad(sdirt_rays R, int64_t S, int64_t Mtot, DevDpParams dp, DpGrad q
             }
         }
     }
-    if (PARTIAL) {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int c = 0; c < kEnergyComps; ++c) {
-            const double v = wave_sum(acc[c]);
-            if (lane == 0) red[wave][c] = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < kEnergyComps) {
-            double v = 0.0;
-            for (int k = 0; k < kGradThreads / 64; ++k) v += red[k][threadIdx.x];
-            partial[(n * gl_.nslices + j) * kEnergyComps + threadIdx.x] = v;
-        }
-    }
+    if (PARTIAL) block_sum_store<kEnergyComps>(acc, partial + (b.n * gl_.nslices + b.j) * kEnergyComps);
 }
 
 GradLaunch plan_grad(int64_t N, int64_t S, int ncu)
@@ -550,6 +454,34 @@ GradLaunch plan_grad(int64_t N, int64_t S, int ncu)
     g.chunk = std::max<int64_t>(1, (S + ns - 1) / ns);
     g.nslices = (int)std::max<int64_t>(1, (S + g.chunk - 1) / g.chunk);
     return g;
+}
+
+DpGrad make_dp_grad(const sdirt_dp_params* dp)      // NULL: the reference's defaults, as make_dp
+{
+    const double h = dp ? dp->h : 0.78, f = dp ? dp->f : 1.44;
+    return DpGrad{h, f, dp ? dp->w : 0.3, dp ? dp->r : 0.5, f - h};
+}
+
+// The argument checks and the launch plan the five entries share, in the order the statuses come out; `own` holds the
+// checks of the entry that belong between the rays and the sizes.  SDIRT_OK with gl.nslices = 0 when N = 0.
+template <class Own>
+int check_and_plan(const sdirt_rays& rays, int64_t S, int64_t N, const sdirt_dp_params* dp, int32_t n_slices, Own&& own,
+                   GradLaunch& gl)
+{
+    gl = GradLaunch{};
+    if (int rc = check_rays(rays)) return rc;
+    if (int rc = own()) return rc;
+    if (S < 0 || N < 0 || N > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
+    if (dp && !(dp->f != dp->h)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->f must differ from dp->h");
+    if (N == 0) return SDIRT_OK;
+    int ncu = 0;
+    if (int rc = device_cus(&ncu)) return rc;
+    gl = plan_grad(N, S, ncu);
+    if (n_slices != gl.nslices)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_slices=%d, the launch has %d (sdirt_forward_integral_grad_slices)",
+                    n_slices, gl.nslices);
+    return SDIRT_OK;
 }
 
 }  // namespace
@@ -566,23 +498,18 @@ static int launch_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps
                                 const sdirt_dp_params* dp, uint32_t flags, const float* grad_l, const float* grad_r,
                                 double* partial, int32_t n_slices, float* ray_grad, bool focus, void* stream)
 {
-    if (int rc = check_rays(rays)) return rc;
-    if (int rc = check_ks(ks, SDIRT_MAX_KS_STAGED)) return rc;
-    if (!center || (!partial && !ray_grad) || S < 0 || N < 0 || N > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (dp && !(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
-    if (dp && !(dp->f != dp->h)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->f must differ from dp->h");
+    GradLaunch gl;
+    const auto own = [&] {
+        if (int rc = check_ks(ks, SDIRT_MAX_KS_STAGED)) return rc;
+        if (!center || (!partial && !ray_grad)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+        return (int)SDIRT_OK;
+    };
+    if (int rc = check_and_plan(rays, S, N, dp, n_slices, own, gl)) return rc;
     if (N == 0) return SDIRT_OK;
-    int ncu = 0;
-    if (int rc = device_cus(&ncu)) return rc;
-    GradLaunch gl = plan_grad(N, S, ncu);
-    if (n_slices != gl.nslices)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_slices=%d, the launch has %d (sdirt_forward_integral_grad_slices)",
-                    n_slices, gl.nslices);
     hipStream_t st = as_stream(stream);
     const SplatGeom gm = make_geom(ps, ks);
     const DevDpParams dpp = make_dp(dp);
-    const DpGrad q{dp ? dp->h : 0.78, dp ? dp->f : 1.44, dp ? dp->w : 0.3, dp ? dp->r : 0.5,
-                   (dp ? dp->f : 1.44) - (dp ? dp->h : 0.78)};
+    const DpGrad q = make_dp_grad(dp);
     gl.dwr_dcx = -(double)gm.ksm1 / (double)gm.dx_rng;
     gl.dwb_dcy = -(double)gm.ksm1 / (double)gm.dy_rng;
     // param_list=None: the R grid is all zero, nothing flows back from it
@@ -591,16 +518,15 @@ static int launch_integral_grad(sdirt_rays rays, int64_t S, int64_t N, double ps
     const bool stage = lds <= (size_t)kGradLdsBytes;
     const unsigned grid = (unsigned)(N * gl.nslices);
     with_bool(dpp.big, [&](auto bg) { return with_bool(stage, [&](auto stg) { return with_math(flags, [&](auto m) {
-        constexpr bool STG = decltype(stg)::value;
+        constexpr bool BG = decltype(bg)::value, STG = decltype(stg)::value;
+        using Mm = decltype(m);
+        const size_t dyn = STG ? lds : 0;
         if (partial && focus)        // [N, n_slices, 6]
-            k_forward_integral_grad_focus<decltype(bg)::value, decltype(m), STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(
-                rays, S, gm, dpp, q, gl, center, grad_l, gr, partial);
-        else if (partial)
-            k_forward_integral_grad<decltype(bg)::value, decltype(m), STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(
-                rays, S, gm, dpp, q, gl, center, grad_l, gr, partial);
+            k_forward_integral_grad<BG, Mm, STG, true><<<grid, kGradThreads, dyn, st>>>(rays, S, gm, dpp, q, gl, center, grad_l, gr, partial);
+        else if (partial)            // [N, n_slices, 5]
+            k_forward_integral_grad<BG, Mm, STG, false><<<grid, kGradThreads, dyn, st>>>(rays, S, gm, dpp, q, gl, center, grad_l, gr, partial);
         if (ray_grad)
-            k_forward_integral_grad_rays<decltype(bg)::value, decltype(m), STG><<<grid, kGradThreads, STG ? lds : 0, st>>>(
-                rays, S, S * N, gm, dpp, q, gl, center, grad_l, gr, ray_grad);
+            k_forward_integral_grad_rays<BG, Mm, STG><<<grid, kGradThreads, dyn, st>>>(rays, S, S * N, gm, dpp, q, gl, center, grad_l, gr, ray_grad);
         return 0;
     }); }); });
     LAUNCH_CHECK();
@@ -631,24 +557,10 @@ int sdirt_forward_integral_grad_rays(sdirt_rays rays, int64_t S, int64_t N, doub
     return launch_integral_grad(rays, S, N, ps, ks, center, dp, flags, grad_l, grad_r, partial, n_slices, ray_grad, false, stream);
 }
 
-// The argument checks and the launch plan the two energy entries share: SDIRT_OK with gl.nslices = 0 when N = 0.
-static int plan_energy(const sdirt_rays& rays, int64_t S, int64_t N, const sdirt_dp_params* dp, int32_t n_slices,
-                       GradLaunch& gl)
+// The energy needs the dual-pixel parameters: the one check of its own both energy entries make after the rays'.
+static int need_dp(const sdirt_dp_params* dp)
 {
-    gl = GradLaunch{};
-    if (int rc = check_rays(rays)) return rc;
-    if (!dp) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null dp: the energy needs the dual-pixel parameters");
-    if (S < 0 || N < 0 || N > (1ll << 30)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (!(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
-    if (!(dp->f != dp->h)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->f must differ from dp->h");
-    if (N == 0) return SDIRT_OK;
-    int ncu = 0;
-    if (int rc = device_cus(&ncu)) return rc;
-    gl = plan_grad(N, S, ncu);
-    if (n_slices != gl.nslices)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_slices=%d, the launch has %d (sdirt_forward_integral_grad_slices)",
-                    n_slices, gl.nslices);
-    return SDIRT_OK;
+    return dp ? (int)SDIRT_OK : fail(SDIRT_ERR_INVALID_ARGUMENT, "null dp: the energy needs the dual-pixel parameters");
 }
 
 int sdirt_dp_energy(sdirt_rays rays, int64_t S, int64_t N, const sdirt_dp_params* dp, uint32_t flags, double* partial,
@@ -656,7 +568,7 @@ int sdirt_dp_energy(sdirt_rays rays, int64_t S, int64_t N, const sdirt_dp_params
 {
     if (!partial) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null partial");
     GradLaunch gl;
-    if (int rc = plan_energy(rays, S, N, dp, n_slices, gl)) return rc;
+    if (int rc = check_and_plan(rays, S, N, dp, n_slices, [&] { return need_dp(dp); }, gl)) return rc;
     if (N == 0) return SDIRT_OK;
     const DevDpParams dpp = make_dp(dp);
     const unsigned grid = (unsigned)(N * gl.nslices);
@@ -676,10 +588,10 @@ int sdirt_dp_energy_grad(sdirt_rays rays, int64_t S, int64_t N, const sdirt_dp_p
     if (!grad_e) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null grad_e");
     if (!partial && !ray_grad) return fail(SDIRT_ERR_INVALID_ARGUMENT, "partial and ray_grad are both null");
     GradLaunch gl;
-    if (int rc = plan_energy(rays, S, N, dp, n_slices, gl)) return rc;
+    if (int rc = check_and_plan(rays, S, N, dp, n_slices, [&] { return need_dp(dp); }, gl)) return rc;
     if (N == 0) return SDIRT_OK;
     const DevDpParams dpp = make_dp(dp);
-    const DpGrad q{dp->h, dp->f, dp->w, dp->r, dp->f - dp->h};
+    const DpGrad q = make_dp_grad(dp);
     const unsigned grid = (unsigned)(N * gl.nslices);
     hipStream_t st = as_stream(stream);
     with_bool(dpp.big, [&](auto bg) { return with_math(flags, [&](auto m) {

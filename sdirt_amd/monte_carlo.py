@@ -22,6 +22,17 @@ def _dp(param_list):
     return _lib.DpParams(float(h), float(f), float(w), float(r)), direct
 
 
+def n_cus(dev):
+    return int(torch.cuda.get_device_properties(dev).multi_processor_count)
+
+
+def grad_slices(ray):
+    """n_slices of every launch that cuts the spp axis of the bundle `ray` [S, N] as the splat's backward does
+    (sdirt_forward_integral_grad_slices on the bundle's device)."""
+    S, N = ray.shape
+    return int(_lib.lib().sdirt_forward_integral_grad_slices(N, S, n_cus(ray.device)))
+
+
 def _requires_grad(*vals):
     """Whether autograd is recording and one of `vals` (tensors, Python numbers, None) requires a gradient."""
     return torch.is_grad_enabled() and any(torch.is_tensor(v) and v.requires_grad for v in vals)
@@ -63,8 +74,7 @@ class SplatFunction(torch.autograd.Function):
         (center,) = ctx.saved_tensors
         S, N, ps, ks = ctx.geom
         dev = center.device
-        ncu = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-        ns = int(_lib.lib().sdirt_forward_integral_grad_slices(N, S, ncu))
+        ns = grad_slices(ctx.ray)
         focus = ctx.needs_input_grad[10]
         partial = torch.empty((N, ns, 6 if focus else 5), dtype=torch.float64, device=dev)
         gl = gl.to(torch.float32).contiguous() if gl is not None else None
@@ -107,12 +117,6 @@ def splat_autograd(ray, ps, ks, center, param_list, precision="lean", d_sensor=N
     return SplatFunction.apply(h, f, w, center, ray, ps, ks, float(r), have_dp, precision, d_sensor, center_slope)
 
 
-def _energy_slices(ray):
-    S, N = ray.shape
-    ncu = int(torch.cuda.get_device_properties(ray.device).multi_processor_count)
-    return int(_lib.lib().sdirt_forward_integral_grad_slices(N, S, ncu))
-
-
 class EnergyFunction(torch.autograd.Function):
     """The energy of every point as an autograd op: (h, f, w) -> [N, 3] float64 sums over ALL spp rays of the
     sensor-plane bundle (sum ra s_l, sum ra s_r, sum ra), s_l / s_r the splat's own sub-pixel areas at
@@ -130,7 +134,7 @@ class EnergyFunction(torch.autograd.Function):
         ctx.meta = [(v.dtype, v.device) if torch.is_tensor(v) else None for v in (h, f, w, d_sensor)]
         if N == 0:
             return torch.zeros((0, 3), dtype=torch.float64, device=dev)
-        ns = _energy_slices(ray)
+        ns = grad_slices(ray)
         partial = torch.empty((N, ns, 3), dtype=torch.float64, device=dev)
         _lib.check(_lib.lib().sdirt_dp_energy(ray.c_rays(), S, N, C.byref(dp), _flags(precision), dptr(partial), ns,
                                               stream_ptr(dev)))
@@ -143,7 +147,7 @@ class EnergyFunction(torch.autograd.Function):
         dev = ray.device
         theta = torch.zeros(3, dtype=torch.float64, device=dev)
         if N > 0 and any(ctx.needs_input_grad[:3]):
-            ns = _energy_slices(ray)
+            ns = grad_slices(ray)
             ge = ge.to(dev, torch.float64).contiguous()
             partial = torch.empty((N, ns, 3), dtype=torch.float64, device=dev)
             _lib.check(_lib.lib().sdirt_dp_energy_grad(ray.c_rays(), S, N, C.byref(ctx.dp), _flags(ctx.precision), dptr(ge),

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from .basics import Material, dptr, stream_ptr
-from .monte_carlo import _flags
+from .monte_carlo import _flags, grad_slices, n_cus
 
 N_COLUMNS = 3 + _lib.MAX_AI
 
@@ -56,10 +56,6 @@ class PointSamples:
         self.tan_hfov, self.r_last, self.sensor_w, self.sensor_h = float(tan_hfov), float(r_last), float(sensor_w), float(sensor_h)
 
 
-def _n_cus(dev):
-    return int(torch.cuda.get_device_properties(dev).multi_processor_count)
-
-
 def _identity_outputs(ctx, lg, rg, energy):
     """The forward of an identity behind the raw grids (and, with `energy`, the sums)."""
     ctx.has_energy = energy is not None
@@ -85,7 +81,7 @@ def ray_adjoint(rec, center, geom, dp, gl, gr, ge, wanted=True):
     if not wanted:
         return None, gl, gr, ge
     ray_grad = torch.empty((4, S * N), dtype=torch.float32, device=dev)
-    ns = int(h.sdirt_forward_integral_grad_slices(N, S, _n_cus(dev)))
+    ns = grad_slices(ray)
     from_grids = gl is not None or gr is not None or ge is None
     if from_grids:
         _lib.check(h.sdirt_forward_integral_grad_rays(
@@ -106,7 +102,7 @@ def points_bar(rec, ray_grad, smp):
     if N == 0:
         return torch.zeros((0, 3), dtype=torch.float64, device=dev)
     h = _lib.lib()
-    ns = int(h.sdirt_forward_integral_grad_slices(N, S, _n_cus(dev)))
+    ns = grad_slices(ray)
     partial = torch.empty((N, ns, 3), dtype=torch.float64, device=dev)
     _lib.check(h.sdirt_trace2sensor_grad_points(
         rec.dev_lens.handle, (C.c_int32 * K)(*rec.trips), _flags(rec.precision), rec.d_sensor, dptr(rec.workspace),
@@ -202,7 +198,7 @@ class SurfaceGradFunction(torch.autograd.Function):
         M, K, dev = ray.shape[0] * ray.shape[1], rec.n_surfaces, ray.device
         h, st = _lib.lib(), stream_ptr(dev)
         ray_grad, gl, gr, ge = ray_adjoint(rec, center, ctx.geom, ctx.dp, gl, gr, ge)
-        nwg = int(h.sdirt_trace2sensor_grad_workgroups(M, _n_cus(dev)))
+        nwg = int(h.sdirt_trace2sensor_grad_workgroups(M, n_cus(dev)))
         theta_meta, eta_meta = ctx.meta
         with_eta = eta_meta is not None and ctx.needs_input_grad[1]
         entry = h.sdirt_trace2sensor_grad_eta if with_eta else h.sdirt_trace2sensor_grad

@@ -6,12 +6,13 @@ Kernels: 4096 points x 4096 samples of synthetic sensor-plane rays (|x_tan| < 0.
 over a ks 65 window), the reference's default stack with r = 0.5 unless --big.  Device events around `iters`
 back-to-back calls (launches included).  Counted bytes: the three ray arrays the energy kernels read (d.x, d.z, ra:
 12 B per ray), the two rows the ray-gradient forms write (8 B per ray; accumulate = 1 reads them as well, accumulate = 0
-writes all four) and the float64 partials.  --only NAME runs one entry in a loop of its own, for a kernel trace.
+writes all four) and the float64 partials.  --only NAME[,NAME...] runs those entries alone, each in a loop of its own,
+for a kernel trace (each has a kernel name of its own).
 
 psf_lr: rf50mm, `--points` field points at `--spp` samples, ks 150 (above SDIRT_MAX_KS, so that the call without the
 energy is the staged chain as well), fixed pupil samples, the two calls alternating in one process.
 
-Usage:  python tools/energy_bench.py [--iters 50] [--big] [--ieee] [--only energy|grad_partial|grad_rays|grad_rays_acc]
+Usage:  python tools/energy_bench.py [--iters 50] [--big] [--ieee] [--only energy,grad_partial,grad_rays,grad_rays_acc]
 """
 import argparse
 import ctypes as C
@@ -79,7 +80,7 @@ def kernels(N, S, iters, r, flags, only=None):
     }
     out = []
     for name, (launch, nbytes) in entries.items():
-        if only is not None and name != only:
+        if only is not None and name not in only.split(","):
             continue
         ms = timed(launch, iters)
         if name == "energy":
@@ -119,7 +120,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--big", action="store_true", help="r = 0.65 (big-r model)")
     ap.add_argument("--ieee", action="store_true", help="SDIRT_PSF_STRICT_IEEE")
-    ap.add_argument("--only", default=None, help="one kernel entry only (for a kernel trace)")
+    ap.add_argument("--only", default=None, help="these kernel entries only, comma-separated (for a kernel trace)")
     ap.add_argument("--points", type=int, default=256)
     ap.add_argument("--spp", type=int, default=4096)
     args = ap.parse_args()
