@@ -12,6 +12,30 @@
 
 namespace {
 
+constexpr int kGridCap = 256 * 64;        // workgroups of the grid-stride kernels (grid_for's own default: 256 * 16)
+constexpr int kMaxGroups = 256;           // 16-byte groups of channels of a pixel-major tensor: a thread of ONE workgroup each
+constexpr int kMaxWindowWidth = 12288;    // the planar window average keeps a row of column sums in LDS: 48 KiB
+
+// grid-stride kernels: peel the fastest remaining extent off a flat index (what is left at the end is the slowest one)
+__device__ __forceinline__ int peel(int64_t& rest, int n)
+{
+    const int r = (int)(rest % n);
+    rest /= n;
+    return r;
+}
+
+// Shift plane i of D over a row of W columns: the signed shift, and the columns [lo, hi) that receive data (the others
+// are zero).  The left view is read at the column itself, the right view at column - gap.
+struct ShiftWindow {
+    int gap, lo, hi;
+    __device__ __forceinline__ bool holds(int w) const { return w >= lo && w < hi; }
+};
+__device__ __forceinline__ ShiftWindow shift_window(int i, int D, int W)
+{
+    const int gap = i - D / 2;
+    return {gap, gap > 0 ? gap : 0, gap < 0 ? W + gap : W};
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_dp_cost_volume(const T* __restrict__ x, const T* __restrict__ y, int B, int C, int D, int H, int W,
@@ -22,22 +46,17 @@ k_dp_cost_volume(const T* __restrict__ x, const T* __restrict__ y, int B, int C,
     const int64_t total = (int64_t)B * 2 * C * D * H * wq;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
          t += (int64_t)gridDim.x * blockDim.x) {
-        const int q = (int)(t % wq);
-        int64_t rest = t / wq;
-        const int h = (int)(rest % H); rest /= H;
-        const int i = (int)(rest % D); rest /= D;
-        const int c2 = (int)(rest % (2 * C));
-        const int b = (int)(rest / (2 * C));
-        const int gap = i - D / 2;
+        int64_t rest = t;
+        const int q = peel(rest, wq), h = peel(rest, H), i = peel(rest, D), c2 = peel(rest, 2 * C), b = (int)rest;
+        const ShiftWindow s = shift_window(i, D, W);
         const bool right = c2 >= C;
         const T* src = (right ? y : x) + (((int64_t)b * C + (right ? c2 - C : c2)) * H + h) * W;
         T* dst = cost + ((((int64_t)b * 2 * C + c2) * D + i) * H + h) * W;
-        const int lo = gap > 0 ? gap : 0, hi = gap < 0 ? W + gap : W;     // columns that receive data
-        const int shift = right ? gap : 0;                                // y is read at w - gap
+        const int shift = right ? s.gap : 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int w = 4 * q + j;
-            if (w < W) dst[w] = (w >= lo && w < hi) ? src[w - shift] : (T)0;
+            if (w < W) dst[w] = s.holds(w) ? src[w - shift] : (T)0;
         }
     }
 }
@@ -56,18 +75,13 @@ k_dp_cost_volume_nhwc(const T* __restrict__ x, const T* __restrict__ y, int B, i
     const int64_t total = (int64_t)B * D * H * W * groups;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
          t += (int64_t)gridDim.x * blockDim.x) {
-        const int g = (int)(t % groups);
-        int64_t rest = t / groups;
-        const int w = (int)(rest % W); rest /= W;
-        const int h = (int)(rest % H); rest /= H;
-        const int i = (int)(rest % D);
-        const int b = (int)(rest / D);
-        const int gap = i - D / 2;
+        int64_t rest = t;
+        const int g = peel(rest, groups), w = peel(rest, W), h = peel(rest, H), i = peel(rest, D), b = (int)rest;
+        const ShiftWindow s = shift_window(i, D, W);
         const bool right = g >= half;
-        const int lo = gap > 0 ? gap : 0, hi = gap < 0 ? W + gap : W;     // columns that receive data
-        const int ws = right ? w - gap : w;                               // y is read at w - gap
+        const int ws = right ? w - s.gap : w;
         vec v = {};
-        if (w >= lo && w < hi)
+        if (s.holds(w))
             v = *reinterpret_cast<const vec*>((right ? y : x) + (((int64_t)b * H + h) * W + ws) * C +
                                               (int64_t)(right ? g - half : g) * VL);
         *reinterpret_cast<vec*>(cost + t * VL) = v;
@@ -85,23 +99,28 @@ k_dp_cost_volume_bwd(const T* __restrict__ gcost, int B, int C, int D, int H, in
     const int64_t plane = (int64_t)H * W;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
          t += (int64_t)gridDim.x * blockDim.x) {
-        const int w = (int)(t % W);
-        int64_t rest = t / W;
-        const int h = (int)(rest % H); rest /= H;
-        const int c2 = (int)(rest % (2 * C));
-        const int b = (int)(rest / (2 * C));
+        int64_t rest = t;
+        const int w = peel(rest, W), h = peel(rest, H), c2 = peel(rest, 2 * C), b = (int)rest;
         const bool right = c2 >= C;
         const T* src = gcost + (((int64_t)b * 2 * C + c2) * D) * plane + (int64_t)h * W;
         float acc = 0.0f;
         for (int i = 0; i < D; ++i) {
-            const int gap = i - D / 2;
-            const int wv = right ? w + gap : w;                        // column of the volume it went to
-            const int lo = gap > 0 ? gap : 0, hi = gap < 0 ? W + gap : W;
-            if (wv >= lo && wv < hi) acc += (float)src[i * plane + wv];
+            const ShiftWindow s = shift_window(i, D, W);
+            const int wv = right ? w + s.gap : w;                      // column of the volume it went to
+            if (s.holds(wv)) acc += (float)src[i * plane + wv];
         }
         T* dst = right ? gy : gx;
         dst[(((int64_t)b * C + (right ? c2 - C : c2)) * H + h) * W + w] = (T)acc;
     }
+}
+
+// the arguments of the three entries below; forward: a shift may not leave the row altogether
+inline int check_cost_volume(bool null, int batch, int channels, int d_max, int height, int width, bool forward)
+{
+    if (null || batch < 0 || !all_positive(channels, d_max, height, width))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (forward && d_max / 2 >= width) return fail(SDIRT_ERR_INVALID_ARGUMENT, "d_max/2 must be < width");
+    return SDIRT_OK;
 }
 
 }  // namespace
@@ -110,66 +129,48 @@ extern "C" int sdirt_dp_cost_volume_backward(const void* grad_cost, int32_t batc
                                              int32_t d_max, int32_t height, int32_t width,
                                              int32_t half_precision, void* grad_x, void* grad_y, void* stream)
 {
-    if (!grad_cost || !grad_x || !grad_y || batch < 0 || channels < 1 || d_max < 1 || height < 1 || width < 1)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (int rc = check_cost_volume(any_null(grad_cost, grad_x, grad_y), batch, channels, d_max, height, width, false)) return rc;
     if (batch == 0) return SDIRT_OK;
-    const int64_t total = (int64_t)batch * 2 * channels * height * width;
-    const int grid = (int)std::min<int64_t>((total + 255) / 256, 256 * 64);
-    if (half_precision)
-        k_dp_cost_volume_bwd<_Float16><<<grid, 256, 0, as_stream(stream)>>>(
-            static_cast<const _Float16*>(grad_cost), batch, channels, d_max, height, width,
-            static_cast<_Float16*>(grad_x), static_cast<_Float16*>(grad_y));
-    else
-        k_dp_cost_volume_bwd<float><<<grid, 256, 0, as_stream(stream)>>>(
-            static_cast<const float*>(grad_cost), batch, channels, d_max, height, width,
-            static_cast<float*>(grad_x), static_cast<float*>(grad_y));
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    const int grid = grid_for((int64_t)batch * 2 * channels * height * width, 256, kGridCap);
+    return with_bool(half_precision, [&](auto half) {
+        using T = half_or_float<decltype(half)>;
+        k_dp_cost_volume_bwd<T><<<grid, 256, 0, as_stream(stream)>>>(
+            static_cast<const T*>(grad_cost), batch, channels, d_max, height, width, static_cast<T*>(grad_x), static_cast<T*>(grad_y));
+        return launched();
+    });
 }
 
 extern "C" int sdirt_dp_cost_volume(const void* x, const void* y, int32_t batch, int32_t channels,
                                     int32_t d_max, int32_t height, int32_t width, int32_t half_precision,
                                     void* cost, void* stream)
 {
-    if (!x || !y || !cost || batch < 0 || channels < 1 || d_max < 1 || height < 1 || width < 1)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (d_max / 2 >= width) return fail(SDIRT_ERR_INVALID_ARGUMENT, "d_max/2 must be < width");
+    if (int rc = check_cost_volume(any_null(x, y, cost), batch, channels, d_max, height, width, true)) return rc;
     if (batch == 0) return SDIRT_OK;
-    const int64_t total = (int64_t)batch * 2 * channels * d_max * height * ((width + 3) / 4);
-    const int grid = (int)std::min<int64_t>((total + 255) / 256, 256 * 64);
-    if (half_precision)
-        k_dp_cost_volume<_Float16><<<grid, 256, 0, as_stream(stream)>>>(
-            static_cast<const _Float16*>(x), static_cast<const _Float16*>(y), batch, channels, d_max, height,
-            width, static_cast<_Float16*>(cost));
-    else
-        k_dp_cost_volume<float><<<grid, 256, 0, as_stream(stream)>>>(
-            static_cast<const float*>(x), static_cast<const float*>(y), batch, channels, d_max, height, width,
-            static_cast<float*>(cost));
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    const int grid = grid_for((int64_t)batch * 2 * channels * d_max * height * ((width + 3) / 4), 256, kGridCap);
+    return with_bool(half_precision, [&](auto half) {
+        using T = half_or_float<decltype(half)>;
+        k_dp_cost_volume<T><<<grid, 256, 0, as_stream(stream)>>>(static_cast<const T*>(x), static_cast<const T*>(y), batch,
+                                                                 channels, d_max, height, width, static_cast<T*>(cost));
+        return launched();
+    });
 }
 
 extern "C" int sdirt_dp_cost_volume_nhwc(const void* x, const void* y, int32_t batch, int32_t channels,
                                          int32_t d_max, int32_t height, int32_t width, int32_t half_precision,
                                          void* cost, void* stream)
 {
-    if (!x || !y || !cost || batch < 0 || channels < 1 || d_max < 1 || height < 1 || width < 1)
-        return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (d_max / 2 >= width) return fail(SDIRT_ERR_INVALID_ARGUMENT, "d_max/2 must be < width");
+    if (int rc = check_cost_volume(any_null(x, y, cost), batch, channels, d_max, height, width, true)) return rc;
     if (batch == 0) return SDIRT_OK;
     // 16-byte groups where the channel count and the pointers allow it, single elements otherwise
-    const int vl = half_precision ? 8 : 4;
-    const bool wide = channels % vl == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)cost) & 15) == 0;
-    const int64_t total = (int64_t)batch * d_max * height * width * (2 * channels / (wide ? vl : 1));
-    const int grid = (int)std::min<int64_t>((total + 255) / 256, 256 * 64);
-    hipStream_t st = as_stream(stream);
-#define SDIRT_CV(T, VL) k_dp_cost_volume_nhwc<T, VL><<<grid, 256, 0, st>>>(static_cast<const T*>(x), static_cast<const T*>(y), \
-                            batch, channels, d_max, height, width, static_cast<T*>(cost))
-    if (half_precision) { if (wide) SDIRT_CV(_Float16, 8); else SDIRT_CV(_Float16, 1); }
-    else { if (wide) SDIRT_CV(float, 4); else SDIRT_CV(float, 1); }
-#undef SDIRT_CV
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    const bool wide = groups_of_16_bytes(channels, half_precision, (uintptr_t)x | (uintptr_t)y | (uintptr_t)cost);
+    return with_elem(half_precision, wide, [&](auto e) {
+        using T = typename decltype(e)::type;
+        constexpr int VL = decltype(e)::lanes;
+        const int grid = grid_for((int64_t)batch * d_max * height * width * (2 * channels / VL), 256, kGridCap);
+        k_dp_cost_volume_nhwc<T, VL><<<grid, 256, 0, as_stream(stream)>>>(
+            static_cast<const T*>(x), static_cast<const T*>(y), batch, channels, d_max, height, width, static_cast<T*>(cost));
+        return launched();
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -180,12 +181,28 @@ extern "C" int sdirt_dp_cost_volume_nhwc(const void* x, const void* y, int32_t b
 // output, in place (MIOpen's inference batch norm + torch's clamp are two).  The arithmetic is torch's batch_norm transform
 // term by term -- gamma * (x - mean) * invstd + beta in fp32, rounded once to the tensor's type.
 // The tensor is [outer][C][inner] (planar: inner = the spatial size) or pixel-major (channels_last: inner = 1, C fastest).
-template <typename T>
-__device__ __forceinline__ T bn_relu_one(T x, float mean, float invstd, float gamma, float beta, int relu)
+struct BnChannel { float mean, invstd, gamma, beta; };
+__device__ __forceinline__ BnChannel bn_channel(const float* mean, const float* invstd, const float* gamma, const float* beta, int c)
 {
-    float y = gamma * ((float)x - mean) * invstd + beta;
+    return {mean[c], invstd[c], gamma[c], beta[c]};
+}
+template <typename T>
+__device__ __forceinline__ T bn_relu_one(T x, const BnChannel& k, int relu)
+{
+    float y = k.gamma * ((float)x - k.mean) * k.invstd + k.beta;
     if (relu) y = y < 0.0f ? 0.0f : y;                  // (NaN passes, as clamp_min lets it)
     return (T)y;
+}
+// one 16-byte group (VL = 1: one element) at `at`, in place; channel(j): the constants of its lane j
+template <typename T, int VL, class K>
+__device__ __forceinline__ void bn_relu_group(T* at, int relu, K&& channel)
+{
+    typedef T vec __attribute__((ext_vector_type(VL)));
+    vec* q = reinterpret_cast<vec*>(at);
+    vec v = *q;
+#pragma unroll
+    for (int j = 0; j < VL; ++j) v[j] = bn_relu_one<T>(v[j], channel(j), relu);
+    *q = v;
 }
 
 // pixel-major tensors [pixels][C]: a thread keeps ONE group of VL channels (its 4 x VL constants in registers) and walks
@@ -196,21 +213,13 @@ __global__ void __launch_bounds__(256)
 k_bn_relu_pixel_major(T* __restrict__ x, int64_t n_pixels, int C, const float* __restrict__ mean,
                       const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, int relu)
 {
-    typedef T vec __attribute__((ext_vector_type(VL)));
     const int groups = C / VL;
     const int g = threadIdx.x % groups, ppb = blockDim.x / groups;
-    float m[VL], is[VL], ga[VL], be[VL];
+    BnChannel k[VL];
 #pragma unroll
-    for (int j = 0; j < VL; ++j) {
-        m[j] = mean[g * VL + j]; is[j] = invstd[g * VL + j]; ga[j] = gamma[g * VL + j]; be[j] = beta[g * VL + j];
-    }
-    for (int64_t p = (int64_t)blockIdx.x * ppb + threadIdx.x / groups; p < n_pixels; p += (int64_t)gridDim.x * ppb) {
-        vec* q = reinterpret_cast<vec*>(x + p * C + g * VL);
-        vec v = *q;
-#pragma unroll
-        for (int j = 0; j < VL; ++j) v[j] = bn_relu_one<T>(v[j], m[j], is[j], ga[j], be[j], relu);
-        *q = v;
-    }
+    for (int j = 0; j < VL; ++j) k[j] = bn_channel(mean, invstd, gamma, beta, g * VL + j);
+    for (int64_t p = (int64_t)blockIdx.x * ppb + threadIdx.x / groups; p < n_pixels; p += (int64_t)gridDim.x * ppb)
+        bn_relu_group<T, VL>(x + p * C + g * VL, relu, [&](int j) -> const BnChannel& { return k[j]; });
 }
 
 // planar tensors [planes = B x C][inner]: a workgroup stays inside one plane (its four constants are uniform: scalar loads)
@@ -219,58 +228,48 @@ __global__ void __launch_bounds__(256)
 k_bn_relu_planar(T* __restrict__ x, int C, int64_t inner, int chunks_per_plane, const float* __restrict__ mean,
                  const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta, int relu)
 {
-    typedef T vec __attribute__((ext_vector_type(VL)));
     const int64_t plane = blockIdx.x / chunks_per_plane;
     const int chunk = blockIdx.x % chunks_per_plane;
-    const int c = (int)(plane % C);
-    const float m = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
+    const BnChannel k = bn_channel(mean, invstd, gamma, beta, (int)(plane % C));
     T* base = x + plane * inner;
     const int64_t n_vec = inner / VL;                        // (the host sends inner % VL != 0 through VL = 1)
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const int64_t i = ((int64_t)chunk * 4 + it) * 256 + threadIdx.x;
-        if (i < n_vec) {
-            vec* q = reinterpret_cast<vec*>(base + i * VL);
-            vec v = *q;
-#pragma unroll
-            for (int j = 0; j < VL; ++j) v[j] = bn_relu_one<T>(v[j], m, is, ga, be, relu);
-            *q = v;
-        }
+        if (i < n_vec) bn_relu_group<T, VL>(base + i * VL, relu, [&](int) -> const BnChannel& { return k; });
     }
 }
 
 extern "C" int sdirt_bn_relu(void* x, int64_t outer, int32_t channels, int64_t inner, const float* mean, const float* invstd,
                              const float* gamma, const float* beta, int32_t relu, int32_t half_precision, void* stream)
 {
-    if (!x || !mean || !invstd || !gamma || !beta || outer < 0 || channels < 1 || inner < 1)
+    if (any_null(x, mean, invstd, gamma, beta) || outer < 0 || !all_positive(channels, inner))
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (outer * channels * inner == 0) return SDIRT_OK;
-    const int vl = half_precision ? 8 : 4;
-    const bool aligned = ((uintptr_t)x & 15) == 0;
     hipStream_t st = as_stream(stream);
     if (inner == 1) {
         // pixel-major: 16-byte groups of channels when the count allows it, one channel per thread otherwise
-        const bool wide = aligned && channels % vl == 0 && channels / vl <= 256;
-        if (!wide && channels > 256) return fail(SDIRT_ERR_UNSUPPORTED, "pixel-major tensors: channels <= 256 or a multiple of %d up to %d", vl, 256 * vl);
-        const int groups = wide ? channels / vl : channels;
-        const int bdim = groups * (256 / groups), ppb = bdim / groups;
-        const int grid = (int)std::min<int64_t>((outer + ppb - 1) / ppb, 256 * 16);
-#define SDIRT_BN(T, VL) k_bn_relu_pixel_major<T, VL><<<grid, bdim, 0, st>>>(static_cast<T*>(x), outer, channels, mean, invstd, gamma, beta, relu)
-        if (half_precision) { if (wide) SDIRT_BN(_Float16, 8); else SDIRT_BN(_Float16, 1); }
-        else { if (wide) SDIRT_BN(float, 4); else SDIRT_BN(float, 1); }
-#undef SDIRT_BN
-    } else {
-        const bool wide = aligned && inner % vl == 0;
-        const int64_t n_vec = wide ? inner / vl : inner;
-        const int64_t cpp = (n_vec + 1023) / 1024, blocks = outer * channels * cpp;
-        if (cpp > (1 << 30) || blocks > (1ll << 31) - 1) return fail(SDIRT_ERR_UNSUPPORTED, "tensor too large");
-#define SDIRT_BN(T, VL) k_bn_relu_planar<T, VL><<<(unsigned)blocks, 256, 0, st>>>(static_cast<T*>(x), channels, inner, (int)cpp, mean, invstd, gamma, beta, relu)
-        if (half_precision) { if (wide) SDIRT_BN(_Float16, 8); else SDIRT_BN(_Float16, 1); }
-        else { if (wide) SDIRT_BN(float, 4); else SDIRT_BN(float, 1); }
-#undef SDIRT_BN
+        const int vl = half_precision ? 8 : 4;
+        const bool wide = groups_of_16_bytes(channels, half_precision, (uintptr_t)x, kMaxGroups);
+        if (!wide && channels > kMaxGroups)
+            return fail(SDIRT_ERR_UNSUPPORTED, "pixel-major tensors: channels <= %d or a multiple of %d up to %d", kMaxGroups, vl, kMaxGroups * vl);
+        return with_elem(half_precision, wide, [&](auto e) {
+            using T = typename decltype(e)::type;
+            constexpr int VL = decltype(e)::lanes;
+            const int groups = channels / VL, bdim = groups * (256 / groups), ppb = bdim / groups;
+            k_bn_relu_pixel_major<T, VL><<<grid_for(outer, ppb), bdim, 0, st>>>(static_cast<T*>(x), outer, channels, mean, invstd, gamma,
+                                                                                beta, relu);
+            return launched();
+        });
     }
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    return with_elem(half_precision, groups_of_16_bytes(inner, half_precision, (uintptr_t)x), [&](auto e) {
+        using T = typename decltype(e)::type;
+        constexpr int VL = decltype(e)::lanes;
+        const int64_t cpp = (inner / VL + 1023) / 1024, blocks = outer * channels * cpp;
+        if (cpp > (1 << 30) || blocks > (1ll << 31) - 1) return fail(SDIRT_ERR_UNSUPPORTED, "tensor too large");
+        k_bn_relu_planar<T, VL><<<(unsigned)blocks, 256, 0, st>>>(static_cast<T*>(x), channels, inner, (int)cpp, mean, invstd, gamma, beta, relu);
+        return launched();
+    });
 }
 
 namespace {
@@ -292,6 +291,17 @@ __device__ __forceinline__ Lerp lerp_at(int dst, int in, float scale, bool align
 inline float lerp_scale(int in, int out, bool align)
 {
     return align ? (out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.0f) : (float)in / (float)out;
+}
+// the in-plane part of a trilinear interpolation from the four neighbours a (h0, w0), b (h0, w1), c (h1, w0), d (h1, w1):
+// term order as torch's kernels (UpSampleTrilinear3d.cu) -- without contraction the order IS the result.  The neighbours
+// are fp32 values or 16-byte groups of which lane j is meant (read and converted where the term stands: the ISA of before)
+__device__ __forceinline__ float lane(float v, int) { return v; }
+template <class V>
+__device__ __forceinline__ float lane(const V& v, int j) { return (float)v[j]; }
+template <class V>
+__device__ __forceinline__ float blend(Lerp lh, Lerp lw, const V& a, const V& b, const V& c, const V& d, int j = 0)
+{
+    return lh.l0 * (lw.l0 * lane(a, j) + lw.l1 * lane(b, j)) + lh.l1 * (lw.l0 * lane(c, j) + lw.l1 * lane(d, j));
 }
 
 constexpr int kMaxDispIn = 32, kMaxDispOut = 64;
@@ -322,9 +332,8 @@ k_disparity_regression(const T* __restrict__ cost, int B, int D0_, int H0, int W
         for (int k = 0; k < (FIXED ? SD0 : kMaxDispIn); ++k) {
             if (!FIXED && k >= D0) break;
             const T* p = base + (int64_t)k * H0 * W0;
-            const float a = (float)p[lh.i0 * W0 + lw.i0], bb = (float)p[lh.i0 * W0 + lw.i1];
-            const float c = (float)p[lh.i1 * W0 + lw.i0], d = (float)p[lh.i1 * W0 + lw.i1];
-            plane[k] = lh.l0 * (lw.l0 * a + lw.l1 * bb) + lh.l1 * (lw.l0 * c + lw.l1 * d);
+            plane[k] = blend(lh, lw, (float)p[lh.i0 * W0 + lw.i0], (float)p[lh.i0 * W0 + lw.i1],
+                             (float)p[lh.i1 * W0 + lw.i0], (float)p[lh.i1 * W0 + lw.i1]);
         }
         // softmin = softmax of the negated values: maximum first, as torch's softmax kernels
         float v[FIXED ? SD : kMaxDispOut];
@@ -368,12 +377,8 @@ k_upsample_trilinear_ndhwc(const T* __restrict__ x, int B, int C, int D0, int H0
     const int groups = C / VL;
     const int64_t total = (int64_t)B * D * H * W * groups;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int g = (int)(t % groups);
-        int64_t rest = t / groups;
-        const int w = (int)(rest % W); rest /= W;
-        const int h = (int)(rest % H); rest /= H;
-        const int d = (int)(rest % D);
-        const int b = (int)(rest / D);
+        int64_t rest = t;
+        const int g = peel(rest, groups), w = peel(rest, W), h = peel(rest, H), d = peel(rest, D), b = (int)rest;
         const Lerp ld = lerp_at(d, D0, sd, true), lh = lerp_at(h, H0, sh, true), lw = lerp_at(w, W0, sw, true);
         const T* base = x + (int64_t)b * D0 * H0 * W0 * C + (int64_t)g * VL;
         auto at = [&](int dd, int hh, int ww) {
@@ -385,10 +390,7 @@ k_upsample_trilinear_ndhwc(const T* __restrict__ x, int B, int C, int D0, int H0
         vec r;
 #pragma unroll
         for (int j = 0; j < VL; ++j) {
-            const float lo = lh.l0 * (lw.l0 * (float)v000[j] + lw.l1 * (float)v001[j]) +
-                             lh.l1 * (lw.l0 * (float)v010[j] + lw.l1 * (float)v011[j]);
-            const float hi = lh.l0 * (lw.l0 * (float)v100[j] + lw.l1 * (float)v101[j]) +
-                             lh.l1 * (lw.l0 * (float)v110[j] + lw.l1 * (float)v111[j]);
+            const float lo = blend(lh, lw, v000, v001, v010, v011, j), hi = blend(lh, lw, v100, v101, v110, v111, j);
             r[j] = (T)(ld.l0 * lo + ld.l1 * hi);
         }
         *reinterpret_cast<vec*>(out + t * VL) = r;
@@ -401,47 +403,43 @@ extern "C" int sdirt_disparity_regression(const void* cost, int32_t batch, int32
                                           int32_t d_out, int32_t h_out, int32_t w_out, int32_t half_precision, float* disp,
                                           void* stream)
 {
-    if (!cost || !disp || batch < 0 || d_in < 1 || h_in < 1 || w_in < 1 || d_out < 1 || h_out < 1 || w_out < 1)
+    if (any_null(cost, disp) || batch < 0 || !all_positive(d_in, h_in, w_in, d_out, h_out, w_out))
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (d_in > kMaxDispIn || d_out > kMaxDispOut)
         return fail(SDIRT_ERR_UNSUPPORTED, "d_in <= %d and d_out <= %d (got %d, %d)", kMaxDispIn, kMaxDispOut, d_in, d_out);
     const int64_t total = (int64_t)batch * h_out * w_out;
     if (total == 0) return SDIRT_OK;
-    const int grid = (int)std::min<int64_t>((total + 255) / 256, 256 * 64);
+    const int grid = grid_for(total, 256, kGridCap);
     const float sd = lerp_scale(d_in, d_out, false), sh = lerp_scale(h_in, h_out, false), sw = lerp_scale(w_in, w_out, false);
-    hipStream_t st = as_stream(stream);
-#define SDIRT_DR(T, A, B_) k_disparity_regression<T, A, B_><<<grid, 256, 0, st>>>(static_cast<const T*>(cost), batch, d_in, h_in, w_in, \
-                               d_out, h_out, w_out, sd, sh, sw, disp)
-    // dddnet.py:112, 409-446: maxdisp 20, and the hourglass ends at the cost volume's own 20 planes (20 -> 20: the depth
-    // weights fold to the identity, the interpolation is the in-plane x 4); 10 -> 20: the same network on a half-depth volume
-    const int shape = d_out == 20 ? (d_in == 20 ? 2 : d_in == 10 ? 1 : 0) : 0;
-    if (half_precision) { if (shape == 2) SDIRT_DR(_Float16, 20, 20); else if (shape == 1) SDIRT_DR(_Float16, 10, 20); else SDIRT_DR(_Float16, 0, 0); }
-    else { if (shape == 2) SDIRT_DR(float, 20, 20); else if (shape == 1) SDIRT_DR(float, 10, 20); else SDIRT_DR(float, 0, 0); }
-#undef SDIRT_DR
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    return with_bool(half_precision, [&](auto half) {
+        using T = half_or_float<decltype(half)>;
+        // dddnet.py:112, 409-446: maxdisp 20, and the hourglass ends at the cost volume's own 20 planes (20 -> 20: the depth
+        // weights fold to the identity, the interpolation is the in-plane x 4); 10 -> 20: the same network on a half-depth volume
+        const auto kernel = d_out == 20 && d_in == 20   ? k_disparity_regression<T, 20, 20>
+                            : d_out == 20 && d_in == 10 ? k_disparity_regression<T, 10, 20>
+                                                        : k_disparity_regression<T, 0, 0>;
+        kernel<<<grid, 256, 0, as_stream(stream)>>>(static_cast<const T*>(cost), batch, d_in, h_in, w_in, d_out, h_out, w_out, sd, sh, sw, disp);
+        return launched();
+    });
 }
 
 extern "C" int sdirt_upsample_trilinear_ndhwc(const void* x, int32_t batch, int32_t channels, int32_t d_in, int32_t h_in,
                                               int32_t w_in, int32_t d_out, int32_t h_out, int32_t w_out,
                                               int32_t half_precision, void* out, void* stream)
 {
-    if (!x || !out || batch < 0 || channels < 1 || d_in < 1 || h_in < 1 || w_in < 1 || d_out < 1 || h_out < 1 || w_out < 1)
+    if (any_null(x, out) || batch < 0 || !all_positive(channels, d_in, h_in, w_in, d_out, h_out, w_out))
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (batch == 0) return SDIRT_OK;
-    const int vl = half_precision ? 8 : 4;
-    const bool wide = channels % vl == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
-    const int64_t total = (int64_t)batch * d_out * h_out * w_out * (channels / (wide ? vl : 1));
-    const int grid = (int)std::min<int64_t>((total + 255) / 256, 256 * 64);
+    const bool wide = groups_of_16_bytes(channels, half_precision, (uintptr_t)x | (uintptr_t)out);
     const float sd = lerp_scale(d_in, d_out, true), sh = lerp_scale(h_in, h_out, true), sw = lerp_scale(w_in, w_out, true);
-    hipStream_t st = as_stream(stream);
-#define SDIRT_UP(T, VL) k_upsample_trilinear_ndhwc<T, VL><<<grid, 256, 0, st>>>(static_cast<const T*>(x), batch, channels, d_in, \
-                            h_in, w_in, d_out, h_out, w_out, sd, sh, sw, static_cast<T*>(out))
-    if (half_precision) { if (wide) SDIRT_UP(_Float16, 8); else SDIRT_UP(_Float16, 1); }
-    else { if (wide) SDIRT_UP(float, 4); else SDIRT_UP(float, 1); }
-#undef SDIRT_UP
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    return with_elem(half_precision, wide, [&](auto e) {
+        using T = typename decltype(e)::type;
+        constexpr int VL = decltype(e)::lanes;
+        const int grid = grid_for((int64_t)batch * d_out * h_out * w_out * (channels / VL), 256, kGridCap);
+        k_upsample_trilinear_ndhwc<T, VL><<<grid, 256, 0, as_stream(stream)>>>(
+            static_cast<const T*>(x), batch, channels, d_in, h_in, w_in, d_out, h_out, w_out, sd, sh, sw, static_cast<T*>(out));
+        return launched();
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -517,44 +515,40 @@ __global__ void __launch_bounds__(256) k_avg_pool_windows_nhwc(const T* __restri
 extern "C" int sdirt_avg_pool_windows_nhwc(const void* x, int32_t batch, int32_t height, int32_t width, int32_t channels, int32_t k,
                                            int32_t half_precision, void* out, void* stream)
 {
-    if (!x || !out || batch < 0 || height < 1 || width < 1 || channels < 1 || k < 1 || height % k || width % k)
+    if (any_null(x, out) || batch < 0 || !all_positive(height, width, channels, k) || height % k || width % k)
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument (the window must divide height and width)");
     const int vl = half_precision ? 8 : 4;
-    if (channels % vl != 0 || channels / vl > 256 || ((uintptr_t)x & 15))
-        return fail(SDIRT_ERR_UNSUPPORTED, "channels must be a multiple of %d (at most %d) and x 16-byte aligned", vl, 256 * vl);
+    if (!groups_of_16_bytes(channels, half_precision, (uintptr_t)x, kMaxGroups))
+        return fail(SDIRT_ERR_UNSUPPORTED, "channels must be a multiple of %d (at most %d) and x 16-byte aligned", vl, kMaxGroups * vl);
     const int64_t blocks = (int64_t)batch * (height / k) * (width / k);
     if (blocks == 0) return SDIRT_OK;
     if (blocks > (1ll << 31) - 1) return fail(SDIRT_ERR_INVALID_ARGUMENT, "too many windows");
     const int groups = channels / vl, lanes = std::max(1, std::min(256 / groups, k * k));
     const size_t lds = sizeof(float) * (size_t)lanes * channels;
-    if (half_precision)
-        k_avg_pool_windows_nhwc<_Float16, 8><<<(unsigned)blocks, groups * lanes, lds, as_stream(stream)>>>(
-            static_cast<const _Float16*>(x), height, width, channels, k, static_cast<_Float16*>(out));
-    else
-        k_avg_pool_windows_nhwc<float, 4><<<(unsigned)blocks, groups * lanes, lds, as_stream(stream)>>>(
-            static_cast<const float*>(x), height, width, channels, k, static_cast<float*>(out));
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    return with_bool(half_precision, [&](auto half) {
+        using T = half_or_float<decltype(half)>;
+        k_avg_pool_windows_nhwc<T, 16 / sizeof(T)><<<(unsigned)blocks, groups * lanes, lds, as_stream(stream)>>>(
+            static_cast<const T*>(x), height, width, channels, k, static_cast<T*>(out));
+        return launched();
+    });
 }
 
 extern "C" int sdirt_avg_pool_windows(const void* x, int64_t planes, int32_t height, int32_t width, int32_t k,
                                       int32_t half_precision, void* out, void* stream)
 {
-    if (!x || !out || planes < 0 || height < 1 || width < 1 || k < 1 || height % k || width % k)
+    if (any_null(x, out) || planes < 0 || !all_positive(height, width, k) || height % k || width % k)
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument (the window must divide height and width)");
-    if (width > 12288) return fail(SDIRT_ERR_UNSUPPORTED, "width > 12288");
+    if (width > kMaxWindowWidth) return fail(SDIRT_ERR_UNSUPPORTED, "width > %d", kMaxWindowWidth);
     const int64_t blocks = planes * (height / k);
     if (blocks == 0) return SDIRT_OK;
     if (blocks > (1ll << 31) - 1) return fail(SDIRT_ERR_INVALID_ARGUMENT, "too many planes");
     const size_t lds = sizeof(float) * (size_t)width;
-    if (half_precision)
-        k_avg_pool_windows<_Float16><<<(unsigned)blocks, 256, lds, as_stream(stream)>>>(
-            static_cast<const _Float16*>(x), height, width, k, static_cast<_Float16*>(out));
-    else
-        k_avg_pool_windows<float><<<(unsigned)blocks, 256, lds, as_stream(stream)>>>(
-            static_cast<const float*>(x), height, width, k, static_cast<float*>(out));
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    return with_bool(half_precision, [&](auto half) {
+        using T = half_or_float<decltype(half)>;
+        k_avg_pool_windows<T><<<(unsigned)blocks, 256, lds, as_stream(stream)>>>(static_cast<const T*>(x), height, width, k,
+                                                                               static_cast<T*>(out));
+        return launched();
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -604,7 +598,7 @@ extern "C" int sdirt_tone_curve(const float* in, int64_t n, int32_t mode, float*
 {
     if (!in || !out || n < 0 || mode < 0 || mode > 1) return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
     if (n == 0) return SDIRT_OK;
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, 256 * 16);
+    const int grid = grid_for(n, 256);
     if (mode == 0) k_tone<0><<<grid, 256, 0, as_stream(stream)>>>(in, n, out);
     else k_tone<1><<<grid, 256, 0, as_stream(stream)>>>(in, n, out);
     LAUNCH_CHECK();

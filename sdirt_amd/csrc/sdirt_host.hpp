@@ -211,6 +211,39 @@ inline int with_bool(bool b, F&& f)
 {
     return b ? f(std::true_type{}) : f(std::false_type{});
 }
+// ... and f(Elem<T, lanes>{}) for the kernels over fp16 / fp32 tensors that give a thread either one 16-byte group of
+// elements (wide) or a single one: _Float16 / 8, _Float16 / 1, float / 4, float / 1.
+template <class T, int VL>
+struct Elem {
+    using type = T;
+    static constexpr int lanes = VL;
+};
+template <class F>
+inline int with_elem(bool half, bool wide, F&& f)
+{
+    if (half) return wide ? f(Elem<_Float16, 8>{}) : f(Elem<_Float16, 1>{});
+    return wide ? f(Elem<float, 4>{}) : f(Elem<float, 1>{});
+}
+// ... and what the launchers around them share: the element type of a with_bool(half precision?) tag, the two kinds of
+// argument check (a null pointer among these; every extent at least 1), the status behind a launch.
+template <class Half>
+using half_or_float = std::conditional_t<Half::value, _Float16, float>;
+template <class... P>
+inline bool any_null(P... p) { return (... || !p); }
+template <class... N>
+inline bool all_positive(N... n) { return (... && (n >= 1)); }
+inline int launched()
+{
+    LAUNCH_CHECK();
+    return SDIRT_OK;
+}
+// May `count` fp16 / fp32 elements behind the pointers OR-ed into `ptrs` be walked in 16-byte groups -- a whole number
+// of them, at most `max_groups`, every pointer on a 16-byte boundary?
+inline bool groups_of_16_bytes(int64_t count, bool half, uintptr_t ptrs, int64_t max_groups = INT64_MAX)
+{
+    const int vl = half ? 8 : 4;
+    return count % vl == 0 && count / vl <= max_groups && (ptrs & 15) == 0;
+}
 
 inline int check_ks(int ks, int max_ks = SDIRT_MAX_KS)
 {

@@ -23,6 +23,30 @@ import torch.nn.functional as F
 from . import _lib
 from .basics import dptr, stream_ptr
 
+# What the kernels take, for the gates below that pick one before anything is launched: their dtypes with the half_precision
+# argument of each (any other: not a kernel dtype), and their limits, each the constexpr of the same value in csrc/sdirt_dfdp.hip.
+_HALF = {torch.float16: 1, torch.float32: 0}
+_MAX_GROUPS = 256                           # kMaxGroups: 16-byte groups of channels of a pixel-major tensor
+_MAX_WINDOW_WIDTH = 12288                   # kMaxWindowWidth: row length of the planar window average
+_MAX_DISP_IN, _MAX_DISP_OUT = 32, 64        # kMaxDispIn, kMaxDispOut: depth planes in and out of the regression
+
+
+def _pixel_major(x):
+    """x [B, C, *spatial] is stored channels_last / channels_last_3d and not also planar (as a [B, C, 1, 1] map is)."""
+    fmt = {4: torch.channels_last, 5: torch.channels_last_3d}.get(x.dim())
+    return fmt is not None and not x.is_contiguous() and x.is_contiguous(memory_format=fmt)
+
+
+def _groups_of_16_bytes(x, count, max_groups):
+    """sdirt_host.hpp's predicate of this name: `count` elements of x are at most `max_groups` whole, aligned 16-byte groups."""
+    vl = 8 if x.dtype == torch.float16 else 4
+    return count % vl == 0 and count // vl <= max_groups and x.data_ptr() % 16 == 0
+
+
+def _call(name, x, *args):
+    """Entry point `name` of the library on x's device and torch's current stream there; any status but OK raises."""
+    _lib.check(getattr(_lib.lib(), name)(*args, stream_ptr(x.device)))
+
 
 def _cost_volume_reference(x, y, d_max):
     """The signed-shift cost volume in stock torch ops (zero-fill, then 2 * d_max slice copies, as
@@ -47,19 +71,13 @@ class _CostVolume(torch.autograd.Function):
         B, C, H, W = x.shape
         y = y.to(x.dtype)
         ctx.shape, ctx.d_max = (B, C, H, W), d_max
-        half = 1 if x.dtype == torch.float16 else 0
-        cl = torch.channels_last
-        if not x.is_contiguous() and x.is_contiguous(memory_format=cl) and y.is_contiguous(memory_format=cl):
-            # pixel-major feature maps (the inference layout of DfDPNet) -> a channels_last_3d volume: what the
-            # hourglass's convolutions compute in, nothing transposed in between
-            cost = torch.empty((B, 2 * C, d_max, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last_3d)
-            _lib.check(_lib.lib().sdirt_dp_cost_volume_nhwc(dptr(x), dptr(y), B, C, d_max, H, W, half,
-                                                            dptr(cost), stream_ptr(x.device)))
-            return cost
-        x, y = x.contiguous(), y.contiguous()
-        cost = torch.empty((B, 2 * C, d_max, H, W), dtype=x.dtype, device=x.device)
-        _lib.check(_lib.lib().sdirt_dp_cost_volume(dptr(x), dptr(y), B, C, d_max, H, W, half,
-                                                   dptr(cost), stream_ptr(x.device)))
+        # pixel-major feature maps (the inference layout of DfDPNet) -> a channels_last_3d volume: what the hourglass's
+        # convolutions compute in, nothing transposed in between; anything else -> planar maps, a planar volume
+        nhwc = _pixel_major(x) and y.is_contiguous(memory_format=torch.channels_last)
+        x, y = (x, y) if nhwc else (x.contiguous(), y.contiguous())
+        name, fmt = ("sdirt_dp_cost_volume_nhwc", torch.channels_last_3d) if nhwc else ("sdirt_dp_cost_volume", torch.contiguous_format)
+        cost = torch.empty((B, 2 * C, d_max, H, W), dtype=x.dtype, device=x.device, memory_format=fmt)
+        _call(name, x, dptr(x), dptr(y), B, C, d_max, H, W, _HALF[x.dtype], dptr(cost))
         return cost
 
     @staticmethod
@@ -68,15 +86,13 @@ class _CostVolume(torch.autograd.Function):
         g = grad_cost.contiguous()
         gx = torch.empty((B, C, H, W), dtype=g.dtype, device=g.device)
         gy = torch.empty_like(gx)
-        _lib.check(_lib.lib().sdirt_dp_cost_volume_backward(dptr(g), B, C, ctx.d_max, H, W,
-                                                            1 if g.dtype == torch.float16 else 0,
-                                                            dptr(gx), dptr(gy), stream_ptr(g.device)))
+        _call("sdirt_dp_cost_volume_backward", g, dptr(g), B, C, ctx.d_max, H, W, _HALF[g.dtype], dptr(gx), dptr(gy))
         return gx, gy, None
 
 
 def dp_cost_volume(x, y, d_max=20):
     """dddnet.py:155-178 / 136-148: x, y [B,C,H,W] -> [B,2C,d_max,H,W] (differentiable)."""
-    if x.is_cuda and x.dtype in (torch.float16, torch.float32):
+    if x.is_cuda and x.dtype in _HALF:
         return _CostVolume.apply(x, y, d_max)
     # CPU tensors, and the dtypes the kernel is not built for (bf16 autocast, float64 gradcheck):
     # the reference's own formulation in stock torch ops -- a documented path chosen by dtype,
@@ -91,18 +107,12 @@ class _WindowAverage(torch.autograd.Function):
     def forward(ctx, x, k):
         B, C, H, W = x.shape
         ctx.k = k
-        vl = 8 if x.dtype == torch.float16 else 4
-        if (not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last) and C % vl == 0 and C // vl <= 256
-                and x.data_ptr() % 16 == 0):
-            # a pixel-major map (the inference layout of DfDPNet): averaged as it lies (no re-laying copy of the map in front)
-            out = torch.empty((B, C, H // k, W // k), dtype=x.dtype, device=x.device)
-            _lib.check(_lib.lib().sdirt_avg_pool_windows_nhwc(dptr(x), B, H, W, C, k, 1 if x.dtype == torch.float16 else 0,
-                                                              dptr(out), stream_ptr(x.device)))
-            return out
-        x = x.contiguous()
+        # a pixel-major map (the inference layout of DfDPNet) of whole 16-byte groups of channels: averaged as it lies, not re-laid
+        nhwc = _pixel_major(x) and _groups_of_16_bytes(x, C, _MAX_GROUPS)
+        x = x if nhwc else x.contiguous()
         out = torch.empty((B, C, H // k, W // k), dtype=x.dtype, device=x.device)
-        _lib.check(_lib.lib().sdirt_avg_pool_windows(dptr(x), B * C, H, W, k, 1 if x.dtype == torch.float16 else 0,
-                                                     dptr(out), stream_ptr(x.device)))
+        name, dims = ("sdirt_avg_pool_windows_nhwc", (B, H, W, C)) if nhwc else ("sdirt_avg_pool_windows", (B * C, H, W))
+        _call(name, x, dptr(x), *dims, k, _HALF[x.dtype], dptr(out))
         return out
 
     @staticmethod
@@ -120,8 +130,8 @@ class WindowAverage(nn.AvgPool2d):
     def forward(self, x):
         k = self.kernel_size if isinstance(self.kernel_size, int) else self.kernel_size[0]
         square = (self.kernel_size, self.stride) in ((k, k), ((k, k), (k, k)), ((k, k), k), (k, (k, k)))
-        if (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float16, torch.float32) and square and self.padding in (0, (0, 0))
-                and x.shape[-2] % k == 0 and x.shape[-1] % k == 0 and x.shape[-1] <= 12288):
+        if (x.is_cuda and x.dim() == 4 and x.dtype in _HALF and square and self.padding in (0, (0, 0))
+                and x.shape[-2] % k == 0 and x.shape[-1] % k == 0 and x.shape[-1] <= _MAX_WINDOW_WIDTH):
             return _WindowAverage.apply(x, k)
         return super().forward(x)
 
@@ -141,19 +151,13 @@ def _hooked(m):
 
 def _layout(x):
     """(outer, inner) of a [B, C, *spatial] tensor as sdirt_bn_relu counts them, or None for strides it does not take."""
-    spatial = 1
-    for n in x.shape[2:]:
-        spatial *= n
+    spatial = x.shape[2:].numel()
     if x.is_contiguous():
         return x.shape[0], spatial
-    fmt = {4: torch.channels_last, 5: torch.channels_last_3d}.get(x.dim())
-    vl = 8 if x.dtype == torch.float16 else 4
-    if fmt is not None and x.is_contiguous(memory_format=fmt):
-        # up to 256 channels: one channel per thread at any address; more: 16-byte groups only, which a view that does not
-        # start on a 16-byte boundary cannot have (sdirt_bn_relu refuses it)
-        C = x.shape[1]
-        if C <= 256 or (C % vl == 0 and C <= 256 * vl and x.data_ptr() % 16 == 0):
-            return x.shape[0] * spatial, 1
+    # pixel-major, up to 256 channels: one channel per thread at any address; more: 16-byte groups only, which a view that
+    # does not start on a 16-byte boundary cannot have (sdirt_bn_relu refuses it)
+    if _pixel_major(x) and (x.shape[1] <= _MAX_GROUPS or _groups_of_16_bytes(x, x.shape[1], _MAX_GROUPS)):
+        return x.shape[0] * spatial, 1
     return None
 
 
@@ -175,15 +179,11 @@ def _bn_tables(bn, device):
 def _bn_relu_(x, bn, relu):
     """dddnet.py:539-543 on a convolution's output, eval mode: one in-place pass; shapes / dtypes / strides the kernel does
     not take go through the torch ops (chosen here, before anything is launched)."""
-    if bn is None:
-        return F.relu(x, inplace=True) if relu else x
-    lay = _layout(x) if x.dtype in (torch.float16, torch.float32) and bn.track_running_stats and bn.running_mean is not None else None
+    lay = _layout(x) if bn is not None and x.dtype in _HALF and bn.track_running_stats and bn.running_mean is not None else None
     if lay is None:
-        x = bn(x)
+        x = bn(x) if bn is not None else x
         return F.relu(x, inplace=True) if relu else x
-    mean, invstd, gamma, beta = _bn_tables(bn, x.device)
-    _lib.check(_lib.lib().sdirt_bn_relu(dptr(x), lay[0], x.shape[1], lay[1], dptr(mean), dptr(invstd), dptr(gamma), dptr(beta),
-                                        1 if relu else 0, 1 if x.dtype == torch.float16 else 0, stream_ptr(x.device)))
+    _call("sdirt_bn_relu", x, dptr(x), lay[0], x.shape[1], lay[1], *map(dptr, _bn_tables(bn, x.device)), 1 if relu else 0, _HALF[x.dtype])
     return x
 
 
@@ -270,12 +270,10 @@ class Conv2x(nn.Module):
         self.up2 = nn.Upsample(scale_factor=2, mode="trilinear", align_corners=True)
 
     def _up2(self, x):
-        if (inference_fusions and x.is_cuda and x.dim() == 5 and not torch.is_grad_enabled() and not x.is_contiguous()
-                and x.is_contiguous(memory_format=torch.channels_last_3d) and x.dtype in (torch.float16, torch.float32)):
+        if inference_fusions and x.is_cuda and x.dim() == 5 and not torch.is_grad_enabled() and _pixel_major(x) and x.dtype in _HALF:
             B, C, D, H, W = x.shape
             out = torch.empty((B, C, 2 * D, 2 * H, 2 * W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last_3d)
-            _lib.check(_lib.lib().sdirt_upsample_trilinear_ndhwc(dptr(x), B, C, D, H, W, 2 * D, 2 * H, 2 * W,
-                                                                 1 if x.dtype == torch.float16 else 0, dptr(out), stream_ptr(x.device)))
+            _call("sdirt_upsample_trilinear_ndhwc", x, dptr(x), B, C, D, H, W, 2 * D, 2 * H, 2 * W, _HALF[x.dtype], dptr(out))
             return out
         return self.up2(x)
 
@@ -308,13 +306,12 @@ class Disp(nn.Module):
         self.maxdisp = maxdisp
 
     def forward(self, x):
-        if (inference_fusions and x.is_cuda and not torch.is_grad_enabled() and x.shape[1] == 1 and x.shape[2] <= 32
-                and self.maxdisp <= 64 and x.dtype in (torch.float16, torch.float32)):
+        if (inference_fusions and x.is_cuda and not torch.is_grad_enabled() and x.shape[1] == 1 and x.shape[2] <= _MAX_DISP_IN
+                and self.maxdisp <= _MAX_DISP_OUT and x.dtype in _HALF):
             x = x.contiguous()
             B, _, D0, H0, W0 = x.shape
             out = torch.empty((B, 1, 4 * H0, 4 * W0), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.lib().sdirt_disparity_regression(dptr(x), B, D0, H0, W0, self.maxdisp, 4 * H0, 4 * W0,
-                                                             1 if x.dtype == torch.float16 else 0, dptr(out), stream_ptr(x.device)))
+            _call("sdirt_disparity_regression", x, dptr(x), B, D0, H0, W0, self.maxdisp, 4 * H0, 4 * W0, _HALF[x.dtype], dptr(out))
             return out
         x = F.interpolate(x, [self.maxdisp, x.shape[3] * 4, x.shape[4] * 4], mode="trilinear",
                           align_corners=False)
