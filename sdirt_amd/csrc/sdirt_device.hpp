@@ -1080,4 +1080,30 @@ __device__ __forceinline__ bool splat_taps(const SplatGeom& gm, float sx, float 
     return splat_taps(gm, UDiv<Ieee>::make(gm.dy_rng), UDiv<Ieee>::make(gm.dx_rng), sx, sy, cx, cy, ra, tp);
 }
 
+// ---------------------------------------------------------------------------
+// the chief-ray centroid  c = -sum(ra o.xy) / (sum(ra) + 1e-9)
+// ---------------------------------------------------------------------------
+// The fp64 sums of a workgroup, each lane's (x * ra, y * ra, ra) stored at red[3][THREADS], added up in a fixed tree
+// order (deterministic): the totals end in red[0], red[THREADS], red[2 * THREADS].
+template <int THREADS>
+__device__ __forceinline__ void reduce_centroid(double* red)
+{
+    __syncthreads();
+    for (int off = THREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            red[threadIdx.x] += red[threadIdx.x + off];
+            red[THREADS + threadIdx.x] += red[THREADS + threadIdx.x + off];
+            red[2 * THREADS + threadIdx.x] += red[2 * THREADS + threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+}
+
+// The centre from the totals, in fp32 like the reference: every kernel that finishes a centroid ends here.
+__device__ __forceinline__ float2 centre_from_sums(double sx, double sy, double sr)
+{
+    const float den = (float)sr + (float)1e-9;
+    return make_float2(-((float)sx / den), -((float)sy / den));
+}
+
 }  // namespace sdirt

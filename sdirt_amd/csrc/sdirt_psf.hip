@@ -462,30 +462,91 @@ __device__ __forceinline__ void prio_by_work_left(int passes_left)
     else __builtin_amdgcn_s_setprio(0);
 }
 
-// The chief-ray centroid's fp64 sums of a workgroup, each lane's (x * ra, y * ra, ra) stored at red[3][THREADS],
-// added up in a fixed tree order (deterministic): the totals end in red[0], red[THREADS], red[2 * THREADS].
-template <int THREADS>
-__device__ __forceinline__ void reduce_centroid(double* red)
+// What a ray starts from and ends at, the same for every ray of a workgroup: wave-uniform but only ever vector
+// operands, so the kernels that have the VGPRs for it keep them there (in_vgpr).
+struct RayEnds {
+    float px, py, pzo;       // the object point
+    float pz, zs;            // the pupil plane's distance from it, the sensor plane
+};
+
+// THE sample loop of this file: lane t traces samples s0, s0 + THREADS, ... < s_end of (xs, ys) from the point through
+// `lens` to the sensor plane and hands each ray to per_ray.  PIN: this lane's sample addresses and the end of its loop
+// per lane, in VGPRs (in_vgpr_if), else indexed from the arrays.  PRIO: the issue priority counts DOWN the passes
+// that are left (prio_by_work_left; a workgroup that is not of the last generation starts at kNoPrio, so far below zero
+// that it never gets there), compiled out otherwise.
+template <class HotMath, int THREADS, bool PIN, bool PRIO, class Samples, class PerRay>
+__device__ __forceinline__ void for_each_traced_ray(const DevSurface* __restrict__ lens, int K, const void* trips,
+                                                    const RayEnds& e, Samples xs, Samples ys, int s0, int s_end,
+                                                    int passes_left, uint32_t* lds_mask, PerRay per_ray)
 {
-    __syncthreads();
-    for (int off = THREADS / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            red[threadIdx.x] += red[threadIdx.x + off];
-            red[THREADS + threadIdx.x] += red[THREADS + threadIdx.x + off];
-            red[2 * THREADS + threadIdx.x] += red[2 * THREADS + threadIdx.x + off];
-        }
-        __syncthreads();
+    GlobalF xp = in_vgpr_if<PIN>((GlobalF)(xs + s0));
+    GlobalF yp = in_vgpr_if<PIN>((GlobalF)(ys + s0));
+    const int end = in_vgpr_if<PIN>(s_end);
+    for (int s = s0, left = passes_left; s < end; s += THREADS, --left) {
+        if constexpr (PRIO) { if (left > 0) prio_by_work_left(left); }
+        Ray r = make_ray<HotMath>(e.px, e.py, e.pzo, PIN ? *xp : xs[s], PIN ? *yp : ys[s], e.pz);
+        if constexpr (PIN) { xp += THREADS; yp += THREADS; }
+        trace_ray<true, HotMath, true, true, true>(lens, 0, K, trips, r, lds_mask);
+        propagate_to<HotMath>(r, e.zs);
+        per_ray(r);
     }
 }
+constexpr int kNoPrio = INT32_MIN / 2;
 
-// psf_center: one workgroup per point, Sc rays, fp64 partial sums reduced in a
-// fixed order (deterministic).
-template <class HotMath>
+// A lane's share of the chief-ray centroid: fp64 sums of (x * ra, y * ra, ra) and whether any of its rays arrived.
+struct ChiefSums {
+    double sx = 0.0, sy = 0.0, sr = 0.0;
+    int any = 0;
+    __device__ __forceinline__ void add(const Ray& r)
+    {
+        sx += (double)(r.ox * r.ra);
+        sy += (double)(r.oy * r.ra);
+        sr += (double)r.ra;
+        any |= (r.ra == 1.0f);
+    }
+};
+// ... over the lane's samples of for_each_traced_ray; `extra` sees every ray after it was added
+template <class HotMath, int THREADS, bool PIN, bool PRIO, class Samples, class Extra>
+__device__ __forceinline__ ChiefSums chief_ray_sums(const DevSurface* __restrict__ lens, int K, const void* trips,
+                                                    const RayEnds& e, Samples xs, Samples ys, int s0, int s_end,
+                                                    int passes_left, uint32_t* lds_mask, Extra extra)
+{
+    ChiefSums a;
+    for_each_traced_ray<HotMath, THREADS, PIN, PRIO>(lens, K, trips, e, xs, ys, s0, s_end, passes_left, lds_mask, [&](const Ray& r) {
+        a.add(r);
+        extra(r);
+    });
+    return a;
+}
+
+// The start of a chief kernel's workgroup: the masks and the flag cleared, the point and the planes in VGPRs.
+__device__ __forceinline__ RayEnds chief_prologue(uint32_t* lds_mask, int* red_any, const float* __restrict__ po, int n,
+                                                  float pz, float zs)
+{
+    if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
+    if (threadIdx.x == 0) *red_any = 0;
+    __syncthreads();
+    RayEnds e;
+    e.px = in_vgpr(po[3 * n]); e.py = in_vgpr(po[3 * n + 1]); e.pzo = in_vgpr(po[3 * n + 2]);
+    e.pz = in_vgpr(pz); e.zs = in_vgpr(zs);
+    return e;
+}
+
+// psf_center: one workgroup per point, Sc rays, fp64 partial sums reduced in a fixed order (deterministic).
+// SLOPE (sdirt_chief_center_slope) also returns how the centre moves with the sensor plane: the sensor-plane point of a
+// ray is o = o' + d (zs - o'.z) / d.z, so with c = -sum(ra o.xy) / (sum(ra) + 1e-9)
+//   dc/dzs = -sum(ra d.xy / d.z) / (sum(ra) + 1e-9).
+// The slope terms are float64 from the fp32 direction after the last surface, summed per lane and then over the
+// workgroup by reduce_centroid, through the same LDS block once the centroid's totals have been read.  The centre is
+// the same in both forms because both are chief_ray_sums, reduce_centroid and centre_from_sums; everything of the slope
+// is under `if constexpr (SLOPE)`, so the plain form carries none of it.  Work-left priorities in the plain form only:
+// the slope pass runs once per gradient call, beside a staged trace.
+template <class HotMath, bool SLOPE>
 __global__ void __launch_bounds__(kFused, 8)
 k_chief_center(TripTable trips /* kernarg offset 0 */, const DevSurface* __restrict__ lens, int K,
                const float* __restrict__ po, const float* __restrict__ xc,
                const float* __restrict__ yc, int Sc, float pz, float zs,
-               float* __restrict__ center, int32_t* __restrict__ any_valid,
+               float* __restrict__ center, double* __restrict__ slope, int32_t* __restrict__ any_valid,
                uint32_t* __restrict__ conv_mask, int prio_from)
 {
     __shared__ uint32_t lds_mask[SDIRT_MAX_SURFACES];
@@ -494,104 +555,38 @@ k_chief_center(TripTable trips /* kernarg offset 0 */, const DevSurface* __restr
     const int n = blockIdx.x;
     const bool by_work_left = (int)blockIdx.x >= prio_from;
     const int passes = (Sc + kFused - 1) / kFused;
-    if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
-    if (threadIdx.x == 0) red_any = 0;
-    __syncthreads();
-    // what is wave-uniform but only ever a vector operand -- the point, the planes, this lane's sample addresses and
-    // the end of its loop -- in VGPRs, as in k_psf_lr; the launch is kFused wide
-    const float px = in_vgpr(po[3 * n]), py = in_vgpr(po[3 * n + 1]), pzo = in_vgpr(po[3 * n + 2]);
-    const float pzv = in_vgpr(pz), zsv = in_vgpr(zs);
-    GlobalF xcp = in_vgpr((GlobalF)xc + threadIdx.x);
-    GlobalF ycp = in_vgpr((GlobalF)yc + threadIdx.x);
-    const int sc_end = in_vgpr(Sc);
-    double sx = 0.0, sy = 0.0, sr = 0.0;
-    int any = 0;
-    int left = by_work_left ? passes : INT32_MIN / 2;
-    for (int s = threadIdx.x; s < sc_end; s += kFused, xcp += kFused, ycp += kFused, --left) {
-        if (left > 0) prio_by_work_left(left);
-        Ray r = make_ray<HotMath>(px, py, pzo, *xcp, *ycp, pzv);
-        trace_ray<true, HotMath, true, true, true>(lens, 0, K, kernarg_at(0), r, lds_mask);
-        propagate_to<HotMath>(r, zsv);
-        sx += (double)(r.ox * r.ra);
-        sy += (double)(r.oy * r.ra);
-        sr += (double)r.ra;
-        any |= (r.ra == 1.0f);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy; red[2][threadIdx.x] = sr;
-    if (any) red_any = 1;
-    reduce_centroid<kFused>(&red[0][0]);
-    if (threadIdx.x == 0) {
-        const float den = (float)red[2][0] + (float)1e-9;
-        center[2 * n] = -((float)red[0][0] / den);
-        center[2 * n + 1] = -((float)red[1][0] / den);
-        if (any_valid && red_any) atomicOr(any_valid, 1);
-    }
-    if (conv_mask && (int)threadIdx.x < K && lds_mask[threadIdx.x])
-        atomicOr(&conv_mask[threadIdx.x], lds_mask[threadIdx.x]);
-}
-
-// k_chief_center that also returns how the centre moves with the sensor plane (sdirt_chief_center_slope): the
-// sensor-plane point of a ray is o = o' + d (zs - o'.z) / d.z, so with c = -sum(ra o.xy) / (sum(ra) + 1e-9)
-//   dc/dzs = -sum(ra d.xy / d.z) / (sum(ra) + 1e-9).
-// The same rays and the same centroid sums in the same order (the centre is k_chief_center's, bit for bit); the slope
-// terms are float64 from the fp32 direction after the last surface, summed per lane and then over the workgroup in
-// reduce_centroid's fixed tree order, through the same LDS block once the centroid's totals have been read.  A kernel
-// of its own: k_chief_center keeps its registers and its ISA.  No work-left priorities: the pass runs once per
-// gradient call, beside a staged trace.
-template <class HotMath>
-__global__ void __launch_bounds__(kFused, 8)
-k_chief_center_slope(TripTable trips /* kernarg offset 0 */, const DevSurface* __restrict__ lens, int K,
-                     const float* __restrict__ po, const float* __restrict__ xc,
-                     const float* __restrict__ yc, int Sc, float pz, float zs,
-                     float* __restrict__ center, double* __restrict__ slope, int32_t* __restrict__ any_valid,
-                     uint32_t* __restrict__ conv_mask)
-{
-    __shared__ uint32_t lds_mask[SDIRT_MAX_SURFACES];
-    __shared__ double red[3][kFused];
-    __shared__ int red_any;
-    const int n = blockIdx.x;
-    if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
-    if (threadIdx.x == 0) red_any = 0;
-    __syncthreads();
-    const float px = in_vgpr(po[3 * n]), py = in_vgpr(po[3 * n + 1]), pzo = in_vgpr(po[3 * n + 2]);
-    const float pzv = in_vgpr(pz), zsv = in_vgpr(zs);
-    GlobalF xcp = in_vgpr((GlobalF)xc + threadIdx.x);
-    GlobalF ycp = in_vgpr((GlobalF)yc + threadIdx.x);
-    const int sc_end = in_vgpr(Sc);
-    double sx = 0.0, sy = 0.0, sr = 0.0, tx = 0.0, ty = 0.0;
-    int any = 0;
-    for (int s = threadIdx.x; s < sc_end; s += kFused, xcp += kFused, ycp += kFused) {
-        Ray r = make_ray<HotMath>(px, py, pzo, *xcp, *ycp, pzv);
-        trace_ray<true, HotMath, true, true, true>(lens, 0, K, kernarg_at(0), r, lds_mask);
-        propagate_to<HotMath>(r, zsv);
-        sx += (double)(r.ox * r.ra);
-        sy += (double)(r.oy * r.ra);
-        sr += (double)r.ra;
-        any |= (r.ra == 1.0f);
-        if (r.ra != 0.0f) {                       // a dead ray's direction is whatever the trace left
-            const double z = (double)r.dz;
-            tx += (double)r.ra * ((double)r.dx / z);
-            ty += (double)r.ra * ((double)r.dy / z);
-        }
-    }
-    red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy; red[2][threadIdx.x] = sr;
-    if (any) red_any = 1;
+    const RayEnds e = chief_prologue(lds_mask, &red_any, po, n, pz, zs);
+    double tx = 0.0, ty = 0.0;
+    const ChiefSums a = chief_ray_sums<HotMath, kFused, true, !SLOPE>(
+        lens, K, kernarg_at(0), e, xc, yc, (int)threadIdx.x, Sc, by_work_left ? passes : kNoPrio, lds_mask, [&](const Ray& r) {
+            if constexpr (SLOPE) {
+                if (r.ra != 0.0f) {                       // a dead ray's direction is whatever the trace left
+                    const double z = (double)r.dz;
+                    tx += (double)r.ra * ((double)r.dx / z);
+                    ty += (double)r.ra * ((double)r.dy / z);
+                }
+            }
+        });
+    if constexpr (!SLOPE) __builtin_amdgcn_s_setprio(0);
+    red[0][threadIdx.x] = a.sx; red[1][threadIdx.x] = a.sy; red[2][threadIdx.x] = a.sr;
+    if (a.any) red_any = 1;
     reduce_centroid<kFused>(&red[0][0]);
     const double sum_ra = red[2][0];
     if (threadIdx.x == 0) {
-        const float den = (float)red[2][0] + (float)1e-9;
-        center[2 * n] = -((float)red[0][0] / den);
-        center[2 * n + 1] = -((float)red[1][0] / den);
+        const float2 c = centre_from_sums(red[0][0], red[1][0], red[2][0]);
+        center[2 * n] = c.x;
+        center[2 * n + 1] = c.y;
         if (any_valid && red_any) atomicOr(any_valid, 1);
     }
-    __syncthreads();                              // everyone has read the centroid's totals: the block is free again
-    red[0][threadIdx.x] = tx; red[1][threadIdx.x] = ty; red[2][threadIdx.x] = 0.0;
-    reduce_centroid<kFused>(&red[0][0]);
-    if (threadIdx.x == 0) {
-        const double den = sum_ra + 1e-9;
-        slope[2 * n] = -(red[0][0] / den);
-        slope[2 * n + 1] = -(red[1][0] / den);
+    if constexpr (SLOPE) {
+        __syncthreads();                          // everyone has read the centroid's totals: the block is free again
+        red[0][threadIdx.x] = tx; red[1][threadIdx.x] = ty; red[2][threadIdx.x] = 0.0;
+        reduce_centroid<kFused>(&red[0][0]);
+        if (threadIdx.x == 0) {
+            const double den = sum_ra + 1e-9;
+            slope[2 * n] = -(red[0][0] / den);
+            slope[2 * n + 1] = -(red[1][0] / den);
+        }
     }
     if (conv_mask && (int)threadIdx.x < K && lds_mask[threadIdx.x])
         atomicOr(&conv_mask[threadIdx.x], lds_mask[threadIdx.x]);
@@ -639,28 +634,11 @@ k_chief_slices(TripTable trips /* kernarg offset 0 */, SplitArgs sa, const DevSu
         zero_a[i] = 0.0f;
         if (zero_b) zero_b[i] = 0.0f;
     }
-    if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
-    if (threadIdx.x == 0) red_any = 0;
-    __syncthreads();
-    const float px = in_vgpr(po[3 * n]), py = in_vgpr(po[3 * n + 1]), pzo = in_vgpr(po[3 * n + 2]);
-    const float pzv = in_vgpr(pz), zsv = in_vgpr(zs);
-    double sx = 0.0, sy = 0.0, sr = 0.0;
-    int any = 0;
-    const int s_end = in_vgpr(min(Sc, (j + 1) * chunk));
-    const int s0 = j * chunk + (int)threadIdx.x;
-    GlobalF xcp = in_vgpr((GlobalF)xc + s0);
-    GlobalF ycp = in_vgpr((GlobalF)yc + s0);
-    for (int s = s0; s < s_end; s += kFused, xcp += kFused, ycp += kFused) {
-        Ray r = make_ray<HotMath>(px, py, pzo, *xcp, *ycp, pzv);
-        trace_ray<true, HotMath, true, true, true>(lens, 0, K, trip_words, r, lds_mask);
-        propagate_to<HotMath>(r, zsv);
-        sx += (double)(r.ox * r.ra);
-        sy += (double)(r.oy * r.ra);
-        sr += (double)r.ra;
-        any |= (r.ra == 1.0f);
-    }
-    red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy; red[2][threadIdx.x] = sr;
-    if (any) red_any = 1;
+    const RayEnds e = chief_prologue(lds_mask, &red_any, po, n, pz, zs);
+    const ChiefSums a = chief_ray_sums<HotMath, kFused, true, false>(
+        lens, K, trip_words, e, xc, yc, j * chunk + (int)threadIdx.x, min(Sc, (j + 1) * chunk), kNoPrio, lds_mask, [](const Ray&) {});
+    red[0][threadIdx.x] = a.sx; red[1][threadIdx.x] = a.sy; red[2][threadIdx.x] = a.sr;
+    if (a.any) red_any = 1;
     reduce_centroid<kFused>(&red[0][0]);
     if (threadIdx.x == 0) {
         double* o = part + (int64_t)blockIdx.x * 3;
@@ -889,74 +867,57 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, LoopBlock lb /* 64 */, PrimarySet
         center += (int64_t)w * N * 2;
     }
     // the point, the pupil plane's distance from it and the sensor plane: vector operands of every ray
-    const float px = pin(po[3 * n]), py = pin(po[3 * n + 1]), pzo = pin(po[3 * n + 2]);
-    const float zs = pin(zs_s);
-    // the issue priority of the last generation counts DOWN the passes that are left; every other workgroup starts so
-    // far below zero that it never gets there
-    constexpr int kNoPrio = INT32_MIN / 2;
+    const RayEnds e = {pin(po[3 * n]), pin(po[3 * n + 1]), pin(po[3 * n + 2]), pz, pin(zs_s)};
 
     if (CENTER) {
-        // ---- chief-ray centre of this point (same arithmetic and reduction order as
-        // k_chief_center; the fp64 scratch aliases the not-yet-used tile memory)
+        // ---- chief-ray centre of this point: k_chief_center's sums (ChiefSums::add), reduction (reduce_centroid) and
+        // finish (centre_from_sums); the fp64 scratch aliases the not-yet-used tile memory.  The loop is for_each_traced_ray's
+        // text once more: called from here, the three strict-IEEE L + R instantiations (BIG = false; at their VGPR budget,
+        // the point reloaded from scratch per ray) get another register assignment, one v_mov more per chief ray.
         double* redd = reinterpret_cast<double*>(tiles_raw);         // [3][THREADS]
         if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
         if (threadIdx.x == 0) c_sh[0] = 0.0f;
         __syncthreads();
-        double sx = 0.0, sy = 0.0, sr = 0.0;
-        int any = 0;
-        // this lane's samples: addresses and the end of the loop per lane, in VGPRs
+        ChiefSums a;
         GlobalF xcp = pin((GlobalF)(ca.xc + threadIdx.x));
         GlobalF ycp = pin((GlobalF)(ca.yc + threadIdx.x));
         const int sc_end = pin(ca.Sc);
-        int left = by_work_left ? passes_c + passes_p : kNoPrio;
+        int left = by_work_left ? passes_c + passes_p : kNoPrio;             // the primary passes count as well
         for (int s = threadIdx.x; s < sc_end; s += THREADS, --left) {
             if (left > 0) prio_by_work_left(left);
-            Ray r = make_ray<HotMath>(px, py, pzo, kPin ? *xcp : ca.xc[s], kPin ? *ycp : ca.yc[s], pz);
+            Ray r = make_ray<HotMath>(e.px, e.py, e.pzo, kPin ? *xcp : ca.xc[s], kPin ? *ycp : ca.yc[s], e.pz);
             if constexpr (kPin) { xcp += THREADS; ycp += THREADS; }
             // (the masks of a call that asks for none are gathered all the same and dropped below: one flag less to keep)
             trace_ray<true, HotMath, true, true, true>(ca.lens_c, 0, K, kernarg_at(kTripsCAt + 64 * w), r, lds_mask);
-            propagate_to<HotMath>(r, zs);
-            sx += (double)(r.ox * r.ra);
-            sy += (double)(r.oy * r.ra);
-            sr += (double)r.ra;
-            any |= (r.ra == 1.0f);
+            propagate_to<HotMath>(r, e.zs);
+            a.add(r);
         }
-        redd[threadIdx.x] = sx; redd[THREADS + threadIdx.x] = sy; redd[2 * THREADS + threadIdx.x] = sr;
-        if (any) c_sh[0] = 1.0f;                                     // benign race: all write 1
-        __syncthreads();
-        for (int off = THREADS / 2; off > 0; off >>= 1) {
-            if ((int)threadIdx.x < off) {
-                redd[threadIdx.x] += redd[threadIdx.x + off];
-                redd[THREADS + threadIdx.x] += redd[THREADS + threadIdx.x + off];
-                redd[2 * THREADS + threadIdx.x] += redd[2 * THREADS + threadIdx.x + off];
-            }
-            __syncthreads();
-        }
+        redd[threadIdx.x] = a.sx; redd[THREADS + threadIdx.x] = a.sy; redd[2 * THREADS + threadIdx.x] = a.sr;
+        if (a.any) c_sh[0] = 1.0f;                                   // benign race: all write 1
+        reduce_centroid<THREADS>(redd);
         if (ca.conv_mask_c && (int)threadIdx.x < K && lds_mask[threadIdx.x])
             atomicOr(&ca.conv_mask_c[threadIdx.x], lds_mask[threadIdx.x]);
         const float any_f = c_sh[0];
-        const float den = (float)redd[2 * THREADS] + (float)1e-9;
-        const float ccx = -((float)redd[0] / den), ccy = -((float)redd[THREADS] / den);
+        const float2 cc = centre_from_sums(redd[0], redd[THREADS], redd[2 * THREADS]);
         __syncthreads();                                             // everyone has read redd / c_sh
         if (threadIdx.x == 0) {
-            ca.center_out[2 * n] = ccx; ca.center_out[2 * n + 1] = ccy;
-            c_sh[0] = ccx; c_sh[1] = ccy;
+            ca.center_out[2 * n] = cc.x; ca.center_out[2 * n + 1] = cc.y;
+            c_sh[0] = cc.x; c_sh[1] = cc.y;
             if (ca.any_valid && any_f != 0.0f) atomicOr(ca.any_valid, 1);
         }
     }
 
     const bool from_parts = !CENTER && sa.part != nullptr;
     if (from_parts && threadIdx.x == 0) {
-        // the chief-ray centre from the slices' partial sums, added in slice order (k_chief_slices);
-        // the finish is k_chief_center's
+        // the chief-ray centre from the slices' partial sums, added in slice order (k_chief_slices)
         double sx = 0.0, sy = 0.0, sr = 0.0;
         for (int q = 0; q < sa.nslice; ++q) {
             const double* pq = sa.part + ((int64_t)n * sa.nslice + q) * 3;
             sx += pq[0]; sy += pq[1]; sr += pq[2];
         }
-        const float den = (float)sr + (float)1e-9;
-        c_sh[0] = -((float)sx / den);
-        c_sh[1] = -((float)sy / den);
+        const float2 cc = centre_from_sums(sx, sy, sr);
+        c_sh[0] = cc.x;
+        c_sh[1] = cc.y;
         if (j == 0) { ca.center_out[2 * n] = c_sh[0]; ca.center_out[2 * n + 1] = c_sh[1]; }
     }
     for (int i = threadIdx.x; i < (HAVE_R ? 2 : 1) * tile; i += blockDim.x) tiles[i] = (ACC)0;
@@ -965,7 +926,7 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, LoopBlock lb /* 64 */, PrimarySet
 
     const float cx = pin((CENTER || from_parts) ? c_sh[0] : center[2 * n]);
     const float cy = pin((CENTER || from_parts) ? c_sh[1] : center[2 * n + 1]);
-    const int s_end = pin(min(S, (j + 1) * chunk));
+    const int s_end = min(S, (j + 1) * chunk);
     const void* kernarg = kernarg_at(0);
     // the reciprocals of the window's extent, the same for every ray of the launch: once per workgroup (Lean; the
     // quotient of a ray stays Lean::div_y with this y -- the same bits; Ieee divides by the extent itself)
@@ -1023,20 +984,9 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, LoopBlock lb /* 64 */, PrimarySet
             atomicAdd(&trr[tp.i_br], (ACC)(tp.w_br * sr));
         }
     };
-    {
-        const int s0 = j * chunk + (int)threadIdx.x;
-        GlobalF x2p = pin(x2 + s0);
-        GlobalF y2p = pin(y2 + s0);
-        int left = by_work_left ? passes_p : kNoPrio;
-        for (int s = s0; s < s_end; s += THREADS, --left) {
-            if (left > 0) prio_by_work_left(left);
-            Ray r = make_ray<HotMath>(px, py, pzo, kPin ? *x2p : x2[s], kPin ? *y2p : y2[s], pz);
-            if constexpr (kPin) { x2p += THREADS; y2p += THREADS; }
-            trace_ray<true, HotMath, true, true, true>(lens, 0, K, primary_trips, r, lds_mask);
-            propagate_to<HotMath>(r, zs);
-            splat(r.ox, r.oy, r.dx, r.dz, r.ra);
-        }
-    }
+    for_each_traced_ray<HotMath, THREADS, kPin, true>(
+        lens, K, primary_trips, e, x2, y2, j * chunk + (int)threadIdx.x, s_end,
+        by_work_left ? passes_p : kNoPrio, lds_mask, [&](const Ray& r) { splat(r.ox, r.oy, r.dx, r.dz, r.ra); });
     __builtin_amdgcn_s_setprio(0);               // (it is 0 already in a workgroup that never raised it)
     __syncthreads();
 
@@ -1328,14 +1278,15 @@ static int launch_psf_lr(const PsfLaunch& L)
     }); }); });
 }
 
-static int launch_chief_center(const PsfLaunch& L)
+// `slope`: also the centre's derivative in the sensor plane (the SLOPE form of the kernel)
+static int launch_chief_center(const PsfLaunch& L, double* slope = nullptr)
 {
-    with_math(L.flags, [&](auto m) {
-        k_chief_center<decltype(m)><<<(int)L.N, kFused, 0, L.st>>>(
-            L.ttc.t[0], L.ca.lens_c, L.K, L.po, L.ca.xc, L.ca.yc, L.ca.Sc, L.pz, L.zs, L.ca.center_out, L.ca.any_valid,
-            L.ca.conv_mask_c, last_generation_from(L.N));
+    with_math(L.flags, [&](auto m) { return with_bool(slope != nullptr, [&](auto sl) {
+        k_chief_center<decltype(m), decltype(sl)::value><<<(int)L.N, kFused, 0, L.st>>>(
+            L.ttc.t[0], L.ca.lens_c, L.K, L.po, L.ca.xc, L.ca.yc, L.ca.Sc, L.pz, L.zs, L.ca.center_out, slope,
+            L.ca.any_valid, L.ca.conv_mask_c, last_generation_from(L.N));
         return 0;
-    });
+    }); });
     LAUNCH_CHECK();
     return SDIRT_OK;
 }
@@ -1544,10 +1495,10 @@ int sdirt_psf_normalize(float* psf, int64_t N, int32_t ks, void* stream)
     return SDIRT_OK;
 }
 
-int sdirt_chief_center(const sdirt_lens* lens, const float* point_obj, int64_t N, const float* xc,
-                       const float* yc, int64_t Sc, double pupil_z, double d_sensor,
-                       const int32_t* trips, uint32_t flags, float* center, int32_t* any_valid,
-                       uint32_t* conv_mask, void* stream)
+// sdirt_chief_center and, with `slope`, sdirt_chief_center_slope
+static int chief_center_entry(const sdirt_lens* lens, const float* point_obj, int64_t N, const float* xc, const float* yc,
+                              int64_t Sc, double pupil_z, double d_sensor, const int32_t* trips, uint32_t flags,
+                              float* center, double* slope, int32_t* any_valid, uint32_t* conv_mask, void* stream)
 {
     PsfLaunch L;
     if (int rc = check_psf_args(L, false, nullptr, 0, lens, point_obj, N, nullptr, nullptr, 0, xc, yc, Sc, pupil_z,
@@ -1556,7 +1507,16 @@ int sdirt_chief_center(const sdirt_lens* lens, const float* point_obj, int64_t N
     if (N == 0) return SDIRT_OK;
     L.flags = flags; L.st = as_stream(stream);
     L.ca.center_out = center; L.ca.any_valid = any_valid; L.ca.conv_mask_c = conv_mask;
-    return launch_chief_center(L);
+    return launch_chief_center(L, slope);
+}
+
+int sdirt_chief_center(const sdirt_lens* lens, const float* point_obj, int64_t N, const float* xc,
+                       const float* yc, int64_t Sc, double pupil_z, double d_sensor,
+                       const int32_t* trips, uint32_t flags, float* center, int32_t* any_valid,
+                       uint32_t* conv_mask, void* stream)
+{
+    return chief_center_entry(lens, point_obj, N, xc, yc, Sc, pupil_z, d_sensor, trips, flags, center, nullptr, any_valid,
+                              conv_mask, stream);
 }
 
 int sdirt_chief_center_slope(const sdirt_lens* lens, const float* point_obj, int64_t N, const float* xc,
@@ -1565,18 +1525,8 @@ int sdirt_chief_center_slope(const sdirt_lens* lens, const float* point_obj, int
                              uint32_t* conv_mask, void* stream)
 {
     if (!slope) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null slope");
-    PsfLaunch L;
-    if (int rc = check_psf_args(L, false, nullptr, 0, lens, point_obj, N, nullptr, nullptr, 0, xc, yc, Sc, pupil_z,
-                                d_sensor, 0, nullptr, nullptr, trips, center, nullptr))
-        return rc;
-    if (N == 0) return SDIRT_OK;
-    with_math(flags, [&](auto m) {
-        k_chief_center_slope<decltype(m)><<<(int)N, kFused, 0, as_stream(stream)>>>(
-            L.ttc.t[0], L.ca.lens_c, L.K, L.po, L.ca.xc, L.ca.yc, L.ca.Sc, L.pz, L.zs, center, slope, any_valid, conv_mask);
-        return 0;
-    });
-    LAUNCH_CHECK();
-    return SDIRT_OK;
+    return chief_center_entry(lens, point_obj, N, xc, yc, Sc, pupil_z, d_sensor, trips, flags, center, slope, any_valid,
+                              conv_mask, stream);
 }
 
 int sdirt_psf_lr(const sdirt_lens* lens, const float* point_obj, int64_t N, const float* x2,

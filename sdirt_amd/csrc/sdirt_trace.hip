@@ -244,19 +244,11 @@ k_center_from_rays(sdirt_rays R, int64_t S, int64_t N, float* __restrict__ cente
     }
     red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy; red[2][threadIdx.x] = sr;
     if (any) red_any = 1;
-    __syncthreads();
-    for (int off = kBlock / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + off];
-            red[1][threadIdx.x] += red[1][threadIdx.x + off];
-            red[2][threadIdx.x] += red[2][threadIdx.x + off];
-        }
-        __syncthreads();
-    }
+    reduce_centroid<kBlock>(&red[0][0]);
     if (threadIdx.x == 0) {
-        const float den = (float)red[2][0] + (float)1e-9;
-        center[2 * n] = -((float)red[0][0] / den);
-        center[2 * n + 1] = -((float)red[1][0] / den);
+        const float2 c = centre_from_sums(red[0][0], red[1][0], red[2][0]);
+        center[2 * n] = c.x;
+        center[2 * n + 1] = c.y;
         if (any_valid && red_any) atomicOr(any_valid, 1);
     }
 }

@@ -48,7 +48,7 @@ def chief_centre(cox, coy, cdx, cdy, cdz, cra, s, s0):
 
 def chief_slope_terms(cdx, cdy, cdz, cra):
     """The per-ray terms ra d.xy / d.z of dc/ds = -sum(terms) / (sum(ra) + 1e-9): float64 [Sc, N, 2], 0 for a ray
-    without weight.  The same float64 operations, one by one, as k_chief_center_slope's."""
+    without weight.  The same float64 operations, one by one, as k_chief_center<SLOPE>'s."""
     live = cra != 0
     z = torch.where(live, cdz, torch.ones_like(cdz)).double()
     ra = cra.double()

@@ -18,6 +18,8 @@ L + R with SDIRT_PSF_DETERMINISTIC (float64 tiles in 1024-thread workgroups).
                       never cuts.  Bound below; centres bit-equal
   interleaved         SDIRT_PSF_INTERLEAVED (pstride = 2 ks^2) against separate L / R arrays
   Lean / strict IEEE  the centres of both policies (valid rays are bit-identical)
+  chief-pass edges    Sc = 1, 511, 513, 1500 (fewer rays than lanes, one lane idle, a second pass with one ray, a ragged
+                      third pass) through every kernel that runs the chief-ray loop or finishes a centroid
 
 All calls run the maximal trip table (trips = NULL: SDIRT_NEWTON_MAXITER everywhere), the long Newton tables with the
 periodic exit."""
@@ -27,7 +29,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_state, make_lens
+from conftest import load_state, make_lens, ulp_diff
 
 from sdirt_amd import _lib
 from sdirt_amd.basics import dptr, stream_ptr
@@ -56,13 +58,15 @@ def _disc(n, radius, seed):
 
 
 class Setup:
-    def __init__(self, lens, points, spp, seed=3, waves=1):
-        self.lens, self.S, self.W = lens, spp, waves
+    sc = SC                               # chief-ray samples per point (also of a Setup that a test fills in by hand)
+
+    def __init__(self, lens, points, spp, seed=3, waves=1, sc=SC):
+        self.lens, self.S, self.W, self.sc = lens, spp, waves, sc
         self.po = lens._points_to_object(torch.tensor(points)).clone()
         self.N = self.po.shape[0]
         pr, prc = lens.entrance_pupil()[1], lens.entrance_pupil(shrink_pupil=True)[1]
         xy = [_disc(spp, pr, seed + 10 * w) for w in range(waves)]
-        cxy = [_disc(SC, prc, seed + 10 * w + 5) for w in range(waves)]
+        cxy = [_disc(sc, prc, seed + 10 * w + 5) for w in range(waves)]
         self.x2, self.y2 = (torch.stack([p[i] for p in xy]).contiguous() for i in (0, 1))      # [W, S]
         self.xc, self.yc = (torch.stack([p[i] for p in cxy]).contiguous() for i in (0, 1))     # [W, Sc]
         self.pz, self.zs, self.ps = float(lens.entrance_pupil()[0]), float(lens.d_sensor), float(lens.pixel_size)
@@ -74,17 +78,17 @@ def _out(N, ks, waves=None):
     return torch.full(shape, -1.0, device=DEV), torch.full(shape, -1.0, device=DEV)
 
 
-def fused(s, ks, flags=0, w=0, wvln=0.589, out=None):
+def fused(s, ks, flags=0, w=0, wvln=0.589, out=None, dp=DP):
     """sdirt_psf_lr_centered on wavelength slot w's samples -> (centres, L, R, primary masks, chief-ray masks)."""
     h = _lib.lib()
     L, R = out if out is not None else _out(s.N, ks)
     cen = torch.full((s.N, 2), -1.0, device=DEV)
     anyv = torch.zeros(1, dtype=torch.int32, device=DEV)
     mp, mc = (torch.zeros(MS, dtype=torch.int32, device=DEV) for _ in range(2))
-    dpp = _lib.DpParams(*DP)
+    dpp = _lib.DpParams(*dp)
     _lib.check(h.sdirt_psf_lr_centered(
         s.lens.dev_lens(wvln), s.lens.dev_lens(0.589), dptr(s.po), s.N, dptr(s.x2[w]), dptr(s.y2[w]), s.S, dptr(s.xc[w]),
-        dptr(s.yc[w]), SC, s.pz, s.zs, s.ps, ks, C.byref(dpp), None, None, flags, dptr(cen), dptr(anyv), dptr(L), dptr(R),
+        dptr(s.yc[w]), s.sc, s.pz, s.zs, s.ps, ks, C.byref(dpp), None, None, flags, dptr(cen), dptr(anyv), dptr(L), dptr(R),
         dptr(mp), dptr(mc), s.st))
     torch.cuda.synchronize()
     assert int(anyv.item()) == 1
@@ -100,7 +104,7 @@ def unfused(s, ks, flags=0):
     mp, mc = (torch.zeros(MS, dtype=torch.int32, device=DEV) for _ in range(2))
     dpp = _lib.DpParams(*DP)
     g = s.lens.dev_lens(0.589)
-    _lib.check(h.sdirt_chief_center(g, dptr(s.po), s.N, dptr(s.xc[0]), dptr(s.yc[0]), SC, s.pz, s.zs, None,
+    _lib.check(h.sdirt_chief_center(g, dptr(s.po), s.N, dptr(s.xc[0]), dptr(s.yc[0]), s.sc, s.pz, s.zs, None,
                                     flags & _lib.PSF_STRICT_IEEE, dptr(cen), dptr(anyv), dptr(mc), s.st))
     _lib.check(h.sdirt_psf_lr(g, dptr(s.po), s.N, dptr(s.x2[0]), dptr(s.y2[0]), s.S, s.pz, s.zs, s.ps, ks, dptr(cen),
                               C.byref(dpp), None, flags, dptr(L), dptr(R), dptr(mp), s.st))
@@ -119,7 +123,7 @@ def rgb(s, ks, wvlns, flags=0):
     dpp = _lib.DpParams(*DP)
     handles = (C.c_void_p * W)(*[s.lens.dev_lens(v) for v in wvlns])
     _lib.check(h.sdirt_psf_rgb_centered(
-        handles, W, s.lens.dev_lens(0.589), dptr(s.po), s.N, dptr(s.x2), dptr(s.y2), s.S, dptr(s.xc), dptr(s.yc), SC, s.pz,
+        handles, W, s.lens.dev_lens(0.589), dptr(s.po), s.N, dptr(s.x2), dptr(s.y2), s.S, dptr(s.xc), dptr(s.yc), s.sc, s.pz,
         s.zs, s.ps, ks, C.byref(dpp), None, None, flags, dptr(cen), dptr(anyv), dptr(L), dptr(R), dptr(mp), dptr(mc), s.st))
     torch.cuda.synchronize()
     assert bool((anyv == 1).all())
@@ -202,3 +206,83 @@ def test_lean_and_strict_ieee_centres(lens):
     assert torch.equal(lean[0], ieee[0]), float((lean[0] - ieee[0]).abs().max())
     lean_u, ieee_u = unfused(s, 21, 0), unfused(s, 21, _lib.PSF_STRICT_IEEE)
     assert torch.equal(lean_u[0], ieee_u[0]) and torch.equal(lean_u[0], lean[0])
+
+
+# ------------------------------------------------------------------ the edges of the chief-ray loop
+def _centre_entry(s, flags, slope):
+    """sdirt_chief_center / sdirt_chief_center_slope -> (centres, any_valid, chief-ray masks)."""
+    h = _lib.lib()
+    cen = torch.full((s.N, 2), -1.0, device=DEV)
+    anyv = torch.zeros(1, dtype=torch.int32, device=DEV)
+    mc = torch.zeros(MS, dtype=torch.int32, device=DEV)
+    head = (s.lens.dev_lens(0.589), dptr(s.po), s.N, dptr(s.xc[0]), dptr(s.yc[0]), s.sc, s.pz, s.zs, None, flags, dptr(cen))
+    if slope:
+        sl = torch.full((s.N, 2), float("nan"), dtype=torch.float64, device=DEV)
+        _lib.check(h.sdirt_chief_center_slope(*head, dptr(sl), dptr(anyv), dptr(mc), s.st))
+    else:
+        _lib.check(h.sdirt_chief_center(*head, dptr(anyv), dptr(mc), s.st))
+    torch.cuda.synchronize()
+    return cen, anyv, mc
+
+
+def _staged(s, flags):
+    """The same chief rays by the staged chain: sdirt_sample_rays, sdirt_trace2sensor on the green lens,
+    sdirt_center_from_rays -> ((centres, any_valid, the trace's masks), the sensor-plane bundle)."""
+    from sdirt_amd.basics import Ray
+    h = _lib.lib()
+    ray = Ray.empty((s.sc, s.N), 0.589, DEV)
+    cen = torch.full((s.N, 2), -1.0, device=DEV)
+    anyv = torch.zeros(1, dtype=torch.int32, device=DEV)
+    mc = torch.zeros(MS, dtype=torch.int32, device=DEV)
+    _lib.check(h.sdirt_sample_rays(dptr(s.po), s.N, dptr(s.xc[0]), dptr(s.yc[0]), s.sc, s.pz, ray.c_rays(), s.st))
+    _lib.check(h.sdirt_trace2sensor(s.lens.dev_lens(0.589), None, flags, s.zs, ray.c_rays(), ray.c_rays(), ray.numel,
+                                    dptr(mc), s.st))
+    _lib.check(h.sdirt_center_from_rays(ray.c_rays(), s.sc, s.N, dptr(cen), dptr(anyv), s.st))
+    torch.cuda.synchronize()
+    return (cen, anyv, mc), ray
+
+
+@pytest.mark.parametrize("sc", [1, 511, 513, 1500])
+def test_chief_ray_pass_at_the_edges_of_its_loop(lens, sc):
+    """Everything else here runs the chief-ray pass at Sc = 2048, a whole number of passes of a 512- and of a 1024-thread
+    workgroup.  The routes of 512 threads under the strict-IEEE policy -- sdirt_chief_center, sdirt_chief_center_slope,
+    sdirt_psf_lr_centered with r <= 0.5 and with r > 0.5 (the indexed sample loop) -- trace the same rays, add them in the
+    same tree and finish alike: centres, any_valid and the chief-ray masks are the same bits.  So are the centres and
+    any_valid of the Lean fused call (the pinned sample loop; valid rays are bit-identical under both policies).
+    Another tree -- 1024 threads (ks 65, SDIRT_PSF_DETERMINISTIC), 256 threads (sdirt_center_from_rays over the staged
+    trace of the same rays) -- gives float64 sums that differ in their last bits: against the float64 sums of the staged
+    rays taken here, either cast to float32 may fall one step either way and the quotient rounds once more, 4 steps of
+    the centre; masks and any_valid are equal."""
+    ieee = _lib.PSF_STRICT_IEEE
+    s = Setup(lens, POINTS, 1000, sc=sc)
+    ref = _centre_entry(s, ieee, slope=False)
+    assert int(ref[1].item()) == 1 and bool((ref[2] != 0).any()) and bool(torch.isfinite(ref[0]).all())
+
+    def three(f):                                             # (centres, any_valid, chief-ray masks) of a fused call
+        return f[0], torch.ones(1, dtype=torch.int32, device=DEV), f[4]    # (fused() has asserted any_valid == 1)
+    same_tree = {
+        "sdirt_chief_center_slope": _centre_entry(s, ieee, slope=True),
+        "fused, r 0.5": three(fused(s, 21, ieee)),
+        "fused, r 0.65": three(fused(s, 21, ieee, dp=(*DP[:3], 0.65))),
+    }
+    for name, got in same_tree.items():
+        for what, x, y in zip(("centres", "any_valid", "chief-ray masks"), got, ref):
+            assert torch.equal(x.view(torch.int32), y.view(torch.int32)), f"Sc {sc}, {name}: {what} differ"
+    lean = fused(s, 21, 0)
+    assert torch.equal(lean[0].view(torch.int32), ref[0].view(torch.int32)), f"Sc {sc}, Lean fused: centres differ"
+
+    staged, ray = _staged(s, ieee)
+    ra = ray.ra.double()                                                         # [Sc, N]
+    sx, sy = ((ray.o[..., i] * ray.ra).double().sum(0) for i in (0, 1))          # the kernels' fp32 products, float64 sums
+    den = ra.sum(0).float() + torch.tensor(1e-9, dtype=torch.float32, device=DEV)
+    want = torch.stack([-(sx.float() / den), -(sy.float() / den)], 1)
+    assert bool(torch.isfinite(want).all()) and float(ra.sum(0).min()) >= 1.0
+    other_tree = {
+        "1024 threads": three(fused(s, 65, ieee | _lib.PSF_DETERMINISTIC)),
+        "sdirt_center_from_rays": staged,
+    }
+    for name, got in {"512 threads": ref, **other_tree}.items():
+        d = int(ulp_diff(got[0].cpu().numpy(), want.cpu().numpy()).max())
+        print(f"Sc {sc}, {name}: centres {d} float32 steps from the float64 sums")
+        assert d <= 4, (sc, name, d)
+        assert torch.equal(got[1], ref[1]) and torch.equal(got[2], ref[2]), f"Sc {sc}, {name}: any_valid or masks differ"
