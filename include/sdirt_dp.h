@@ -601,8 +601,17 @@ int sdirt_host_uniform_fill(void* th_state /*host, in/out*/, int64_t state_bytes
 /* Counts how often the lean arithmetic (the default, see SDIRT_PSF_STRICT_IEEE) differs from correctly rounded IEEE:
  * mode 0 = sqrt on every fp32 bit pattern in [first, first+count) (exhaustive for 0, 2^32);
  * mode 1 = division on `count` pseudo-random operand pairs (all mantissas, exponents within
- * +-exp_span of 0); mode 2 = division on mantissa pairs [first, first+count) of all 2^46.
- * out (dev, 9 x uint64): out[0] = mismatches, out[1..8] = examples. */
+ * +-exp_span of 0); mode 2 = division on mantissa pairs [first, first+count) of all 2^46;
+ * mode 3 = the square root of known-positive arguments on every fp32 bit pattern in [first, first+count) that lies in
+ * [2^-100, 2^100].
+ * out (dev, 9 x uint64): out[0] = mismatches, out[1..8] = examples.
+ * mode 4 compares the lean arithmetic with itself: the conic sag's quotient a / sqrt(1 - a) with its division seeded by
+ * the hardware reciprocal of the root and by the root's own hardware reciprocal square root, and the one expression
+ * that reads it, G(a) = fma(0.5, a / sqrt(1 - a), 1 + sqrt(1 - a)), on every fp32 bit pattern of a in
+ * [first, first+count), which must lie inside [0, 2^32) (exhaustive for 0, 2^32).  out[0] = values checked;
+ * out[1] = differing G where 1 - a is a positive normal float; out[2] = differing G elsewhere, not NaN under both;
+ * out[3] = differing bare quotients, not NaN under both; out[4], out[5], out[6] = the smallest bit pattern of a counted
+ * in out[1], out[2], out[3] (UINT64_MAX: none); out[7] = out[8] = 0. */
 int sdirt_selftest_math(int32_t mode, uint64_t first, uint64_t count, int32_t exp_span,
                         uint64_t* out /*dev [9]*/, void* stream);
 

@@ -226,6 +226,9 @@ struct Ray {
 //                exhaustive); 0, inf and denormals are NOT handled.  (The analogous shortening of
 //                the division -- unrefined v_rcp seed, one residual correction -- is NOT exact:
 //                47045 of the 2^46 mantissa pairs miss the IEEE quotient.)
+//          sqrt_pos_rsq + div_seeded: the conic sag's a / sqrt_pos(1 - a) takes the root's own v_rsq_f32 for the
+//                division's v_rcp_f32.  Not exact as a quotient; exact in the ONE expression that reads it, on every
+//                fp32 a (mode 4, exhaustive): the proof stands in sag_g_dgd.
 //        No operand on a valid ray is denormal or zero-denominator (eps = 1e-9 guards, unit
 //        direction vectors, |positions| in [1e-6, 2e4] mm), so valid rays are bit-identical
 //        to the Ieee instantiation; tests/test_gpu_parity.py runs both against the oracle.
@@ -319,11 +322,34 @@ struct Lean {
         const float d = __builtin_fmaf(-s, s, x);            // exact residual of the 1-ulp estimate
         return __builtin_fmaf(d, h, s);
     }
+    // sqrt_pos(x) -- the same five operations, the same bits -- that also hands out its v_rsq_f32(x): within 1 ulp of
+    // 1/sqrt(x), hence within 1.5 ulp of 1 / sqrt_pos(x), which is as good a seed for ONE division by the root as the
+    // v_rcp_f32 of the root (1 ulp) that div() would issue: see div_seeded
+    static __device__ __forceinline__ float sqrt_pos_rsq(float x, float& r)
+    {
+        r = __builtin_amdgcn_rsqf(x);
+        const float s = x * r;
+        const float h = 0.5f * r;
+        const float d = __builtin_fmaf(-s, s, x);
+        return __builtin_fmaf(d, h, s);
+    }
+    // div(a, b) behind its v_rcp_f32, with a given seed y0 ~ 1/b in the v_rcp's place: the same five operations.  NOT
+    // div(a, b) for every (a, b, y0): the refined reciprocal y can differ from recip(b) in its last bit, and over
+    // independent (a, x) pairs with b = sqrt_pos(x), y0 = v_rsq_f32(x) the all-ones-mantissa divisor under a power-of-two
+    // numerator then misses the IEEE quotient by one ulp (see the note at recip below).  It has ONE caller, sag_g_dgd,
+    // where a determines b and the quotient has one consumer: the proof that nothing changes THERE stands at that call.
+    static __device__ __forceinline__ float div_seeded(float a, float b, float y0)
+    {
+        const float y = __builtin_fmaf(__builtin_fmaf(-b, y0, 1.0f), y0, y0);
+        const float q0 = a * y;
+        return __builtin_fmaf(__builtin_fmaf(-b, q0, a), y, q0);
+    }
     // div() in two halves: div(a, b) == div_y(a, b, recip(b)).  (The seed must be v_rcp_f32(b):
     // seeding the Newton step from a related quantity instead -- the square root's own
     // half-reciprocal for a / sqrt(x), the square of 1/b's reciprocal for a / (b*b) -- was tried to
     // save the v_rcp_f32 and gives a reciprocal that differs in the last bit for 80 + 6 arguments,
-    // of which the all-ones-mantissa divisors then miss the IEEE quotient for some numerators.)
+    // of which the all-ones-mantissa divisors then miss the IEEE quotient for some numerators.  div_seeded is that
+    // first form, kept for the one place where numerator and divisor are not independent: sag_g_dgd.)
     static __device__ __forceinline__ float recip(float b)
     {
         const float y0 = __builtin_amdgcn_rcpf(b);
@@ -432,10 +458,29 @@ __device__ __forceinline__ void sag_g_dgd(const C& k, const NoPoly&, int, float 
 {
     // UNITK: 1 + k is 1.0f, the product with it is the identity and is left out
     const float a = UNITK ? r2 * k.c2 : (k.onepk * r2) * k.c2;
-    const float sf = INSIDE ? M::sqrt_pos(1.0f - a) : M::sqrt(1.0f - a);
-    const float onesf = 1.0f + sf;
-    g = M::div(r2 * k.c, onesf);
-    dgd = M::div(M::add_half_quot(onesf, a, sf) * k.c, onesf * onesf);   // (onesf + (a/2)/sf) * c / onesf^2
+    if constexpr (INSIDE && M::kFused) {
+        // Lean, radicand known positive and normal: a / sf is seeded with the root's own v_rsq_f32 instead of a
+        // v_rcp_f32(sf) -- one transcendental of the five of an evaluation less.  The quotient is taken right behind the
+        // root, so that the seed is dead before g and dgd are formed.
+        // Proof that no bit of dgd changes.  sf is a function of a alone and the quotient q has one reader,
+        // G(a) = fma(0.5, q, 1 + sf) (add_half_quot): the claim is univariate, holds for every lens, and is checked on
+        // the device on ALL 2^32 bit patterns of a (sdirt_selftest_math mode 4, tests/test_gpu_sag_seed.py): G has the
+        // same bits under either seed wherever 1 - a is a positive normal float, and where it is not (a >= 1, a = -inf,
+        // NaN) G is NaN under both.  The bare quotient does differ, in its last bit, at a handful of a (the same run
+        // counts them): there sf has an all-ones mantissa under a power-of-two a (a = 2^-23, 2^-24: sf = 1 - 2^-24) and
+        // 1 + sf rounds to 2.0f, whose half-ulp swallows q / 2 and either neighbour of it.
+        float r;
+        const float sf = M::sqrt_pos_rsq(1.0f - a, r);
+        const float q = M::div_seeded(a, sf, r);
+        const float onesf = 1.0f + sf;
+        g = M::div(r2 * k.c, onesf);
+        dgd = M::div(__builtin_fmaf(0.5f, q, onesf) * k.c, onesf * onesf);   // add_half_quot(onesf, a, sf) * c / onesf^2
+    } else {
+        const float sf = INSIDE ? M::sqrt_pos(1.0f - a) : M::sqrt(1.0f - a);
+        const float onesf = 1.0f + sf;
+        g = M::div(r2 * k.c, onesf);
+        dgd = M::div(M::add_half_quot(onesf, a, sf) * k.c, onesf * onesf);   // (onesf + (a/2)/sf) * c / onesf^2
+    }
 }
 
 // WANT_G = false: only dgd is asked for (the surface normal, refract()): the terms of g are left out and the powers

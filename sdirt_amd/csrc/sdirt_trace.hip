@@ -271,10 +271,19 @@ __device__ __forceinline__ uint32_t mix32(uint64_t x)
 //         (a = 1.m_a, b = 1.m_b; exhaustive when first = 0, count = 2^46).
 // out[0] = number of results whose bits differ from the IEEE result, out[1..] = up to 8
 // offending operand bit patterns.
+// mode 4: the sag's a / sqrt_pos(1 - a) under its two seeds -- v_rcp_f32 of the root (Lean::div) and the root's own
+//         v_rsq_f32 (Lean::div_seeded) -- over every fp32 bit pattern i of a in [first, first+count) (exhaustive when
+//         first = 0, count = 2^32), and what reads it, G(a) = fma(0.5, a / sf, 1 + sf) (sag_g_dgd).  Nothing here is
+//         compared with IEEE: the question is whether the two seeds can be told apart.
+//         out[0] = values checked; out[1] = a whose G differs in its bits where 1 - a is a positive normal float (the
+//         INSIDE contract of sag_g_dgd); out[2] = a elsewhere whose G differs and is not NaN under both; out[3] = a
+//         whose bare quotient differs (not NaN under both; informative); out[4], out[5], out[6] = the smallest bit
+//         pattern counted in out[1], out[2], out[3] (all ones: none); out[7], out[8] = 0.
 __global__ void k_selftest_math(int mode, uint64_t first, uint64_t count, int exp_span,
                                 unsigned long long* __restrict__ out)
 {
     unsigned long long bad = 0;
+    unsigned long long n_checked = 0, n_inside = 0, n_outside = 0, n_quot = 0;       // mode 4
     for (uint64_t i = first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < first + count;
          i += (uint64_t)gridDim.x * blockDim.x) {
         if (mode == 0) {
@@ -293,6 +302,28 @@ __global__ void k_selftest_math(int mode, uint64_t first, uint64_t count, int ex
                 __float_as_uint(Lean::sqrt_pos(x)) != __float_as_uint(__builtin_sqrtf(x))) {
                 const unsigned long long k = atomicAdd(&out[0], 1ull);
                 if (k < 8) out[1 + k] = i;
+            }
+        } else if (mode == 4) {
+            const float a = __uint_as_float((uint32_t)i);
+            const float x = 1.0f - a;
+            float r;
+            const float sf = Lean::sqrt_pos_rsq(x, r);
+            const float onesf = 1.0f + sf;
+            const float q_rcp = Lean::div(a, sf), q_rsq = Lean::div_seeded(a, sf, r);
+            const float g_rcp = __builtin_fmaf(0.5f, q_rcp, onesf), g_rsq = __builtin_fmaf(0.5f, q_rsq, onesf);
+            ++n_checked;
+            if (__float_as_uint(g_rcp) != __float_as_uint(g_rsq)) {
+                if (x >= 0x1p-126f && x < __builtin_inff()) {
+                    ++n_inside;
+                    atomicMin(&out[4], (unsigned long long)i);
+                } else if (!(g_rcp != g_rcp && g_rsq != g_rsq)) {
+                    ++n_outside;
+                    atomicMin(&out[5], (unsigned long long)i);
+                }
+            }
+            if (__float_as_uint(q_rcp) != __float_as_uint(q_rsq) && !(q_rcp != q_rcp && q_rsq != q_rsq)) {
+                ++n_quot;
+                atomicMin(&out[6], (unsigned long long)i);
             }
         } else if (mode == 2) {
             // exhaustive division: i enumerates ALL mantissa pairs, operands in [1, 2)
@@ -317,6 +348,12 @@ __global__ void k_selftest_math(int mode, uint64_t first, uint64_t count, int ex
         }
     }
     (void)bad;
+    if (mode == 4) {
+        if (n_checked) atomicAdd(&out[0], n_checked);
+        if (n_inside) atomicAdd(&out[1], n_inside);
+        if (n_outside) atomicAdd(&out[2], n_outside);
+        if (n_quot) atomicAdd(&out[3], n_quot);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -546,9 +583,13 @@ int sdirt_center_from_rays(sdirt_rays rays, int64_t S, int64_t N, float* center,
 int sdirt_selftest_math(int32_t mode, uint64_t first, uint64_t count, int32_t exp_span,
                         uint64_t* out, void* stream)
 {
-    if (!out || mode < 0 || mode > 3 || exp_span < 0 || exp_span > 60)
+    if (!out || mode < 0 || mode > 4 || exp_span < 0 || exp_span > 60)
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    // mode 4 walks bit patterns of ONE fp32: nothing beyond 2^32 (the other modes keep the ranges they always took)
+    if (mode == 4 && (first > (1ull << 32) || count > (1ull << 32) - first))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "mode 4: [first, first+count) outside [0, 2^32)");
     HIP_TRY(hipMemsetAsync(out, 0, sizeof(uint64_t) * 9, as_stream(stream)));
+    if (mode == 4) HIP_TRY(hipMemsetAsync(out + 4, 0xff, sizeof(uint64_t) * 3, as_stream(stream)));   // "none yet"
     if (count == 0) return SDIRT_OK;
     k_selftest_math<<<256 * 32, 256, 0, as_stream(stream)>>>(mode, first, count, exp_span,
                                                             (unsigned long long*)out);

@@ -4,6 +4,8 @@ against the compiler's correctly rounded sequences, on the GPU.
   division: all 2^46 (mantissa_a, mantissa_b) pairs, operands in [1,2)   (~2.5 min)
   sqrt    : every fp32 with exponent in [-100, 128)                      (~0.5 s)
   sqrt_pos: every fp32 in [2^-100, 2^100]                                (~0.5 s)
+and of the sag's a / sqrt_pos(1 - a) seeded with the root's v_rsq_f32 against the same division seeded with
+v_rcp_f32 of the root, with the expression that reads it, on every fp32 a   (~0.5 s)
 Output is kept in profiles/rNN/selftest_math.txt."""
 import os
 import sys
@@ -39,6 +41,14 @@ print("sqrt, +0 / +inf / NaN / -0 / negatives:", run(0, 0, 1), run(0, 0x7F800000
 t = time.time()
 print("sqrt_pos (rsq + Markstein), every fp32 in [2^-100, 2^100]:", run(3, 0, 1 << 32),
       f"{time.time() - t:.1f} s")
+t = time.time()
+_lib.check(h.sdirt_selftest_math(4, 0, 1 << 32, 0, dptr(out), stream_ptr(dev)))
+torch.cuda.synchronize()
+o = [int(v) & 0xFFFFFFFFFFFFFFFF for v in out.cpu().numpy()]
+first = ["none" if v == 0xFFFFFFFFFFFFFFFF else f"{v:#010x}" for v in o[4:7]]
+print(f"sag seed (v_rsq of the radicand for v_rcp of the root), every fp32 a: checked {o[0]:#x}; "
+      f"G differs, 1 - a positive normal: {o[1]} (first a {first[0]}); G differs elsewhere, not NaN under both: {o[2]} "
+      f"(first a {first[1]}); bare quotient differs: {o[3]} (first a {first[2]})   {time.time() - t:.1f} s")
 t = time.time()
 total = 0
 step = 1 << 42
