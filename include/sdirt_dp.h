@@ -237,6 +237,31 @@ int sdirt_trace2sensor(const sdirt_lens* lens, const int32_t* trips /*host [K]*/
 /* Ray.propagate_to, deeplens/basics.py:256-264. */
 int sdirt_propagate_to(double z, sdirt_rays rays, int64_t n_rays, void* stream);
 
+/* Ray-traced rendering of a textured fronto-parallel plane through the lens: the backward renderer that
+ * render_single_img(method='raytracing') names, deeplens/optics.py:497-538, 630-635, 756-780 (sample_sensor, trace2obj and
+ * the caller of the undefined render_sample_ray / render_compute_image); the definition is DESIGN.md §7o.
+ * Ray (s, i, j) starts at (x1[j], y1[i], z_sensor), aims at (x2, y2, z_pupil)[s, i, j], is traced BACKWARD through all
+ * K surfaces with the batch-wide trip table and carried to z = depth: landing point (px, py), weight ra in {0, 1}.
+ * Its dual-pixel weights are the staged splat's closed form (sl, sr) on x_tan = d.x / (-d.z) of the sampled direction d
+ * (the ray arrives along -d), as (w_L, w_R) = (sr, sl): the image is indexed by sensor position, psf_lr's grids by its
+ * negative, and L and R are named by how they shift with defocus in psf_lr's grids; dp == NULL: one view, w = 1.
+ * With u = tex_w / 2 - px inv_texel, v = tex_h / 2 + py inv_texel (fp32) the texture is read bilinearly at
+ * (v - 0.5, u - 0.5) with replicate addressing, and
+ *   num[side, k, i, j] = sum_s w_side ra t_k,   den[side, i, j] = sum_s w_side ra     (float64, samples in order)
+ * are OVERWRITTEN (a call may be launched again with another trip table).  No atomics on the sums: the same call gives
+ * the same bits.  landing, when given, receives px, py, ra, w_L, w_R of every ray (w_R = 1 without dp).  mask, when
+ * given, is OR-ed with the per-surface convergence masks as by sdirt_trace. */
+int sdirt_render_plane(const sdirt_lens* lens, const int32_t* trips /*host [K]*/, uint32_t flags,
+                       const float* x1 /*dev [W]*/, const float* y1 /*dev [H]*/, double z_sensor,
+                       const float* x2 /*dev [S,H,W]*/, const float* y2 /*dev [S,H,W]*/, double z_pupil,
+                       int32_t spp, int32_t height, int32_t width,
+                       const sdirt_dp_params* dp /*host, or NULL: one view, unit weights*/,
+                       double depth, double inv_texel,
+                       const float* tex /*dev [T,Ht,Wt]*/, int32_t n_tex, int32_t tex_h, int32_t tex_w,
+                       double* num /*dev [V,T,H,W], V = dp ? 2 : 1*/, double* den /*dev [V,H,W]*/,
+                       float* landing /*dev [5,S,H,W] or NULL: px, py, ra, w_L, w_R of every ray*/,
+                       uint32_t* mask /*dev or NULL*/, void* stream);
+
 /* Centroid part of Lensgroup.psf_center, deeplens/optics.py:902-904:
  * center[n] = -(sum_s o*ra / (sum_s ra + 1e-9)).xy (sums in float64);  any_valid (dev int32,
  * zeroed by caller, may be NULL) is set to 1 if any ray has ra == 1.  Point-major bundle. */

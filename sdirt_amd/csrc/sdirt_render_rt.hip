@@ -1,0 +1,181 @@
+// sdirt_render_rt.hip -- ray-traced rendering of a textured fronto-parallel plane through the lens (MI355X / gfx950
+// only): the backward renderer the reference names and never defines (deeplens/optics.py:497-538 sample_sensor,
+// :630-635 trace2obj, :756-780 render_single_img(method='raytracing')).  One kernel: sample a sensor-side ray, take
+// its dual-pixel weights, trace it backward through every surface, carry it to the plane, read the texture, sum.
+// No PSF, no window, no per-pixel normalisation of a kernel: the yardstick for the PSF renders.
+#include <hip/hip_runtime.h>
+
+#include "../../include/sdirt_dp.h"
+#include "sdirt_trace.hpp"
+
+using namespace sdirt;
+
+namespace {
+
+constexpr int kDpNone = 0, kDpSmall = 1, kDpBig = 2;
+constexpr int kMaxPlanes = 4;          // texture planes one launch accumulates: 2 (NT + 1) doubles per lane
+
+// Everything of a launch behind the trip table (which sits at kernel-argument offset 0, as in k_trace).
+struct PlaneLaunch {
+    const DevSurface* lens;
+    int K;
+    const float* x1;                   // [W] sensor x of the pixel columns
+    const float* y1;                   // [H] sensor y of the pixel rows
+    const float* x2;                   // [S, H, W] pupil points
+    const float* y2;
+    float z_sensor, z_pupil, depth, inv_texel;
+    int S, H, W;
+    const float* tex;                  // the first plane of this launch, [NT, Ht, Wt]
+    int Ht, Wt;
+    int64_t view_stride;               // elements between the views of num: n_tex H W
+    double* num;                       // this launch's first plane of view 0
+    double* den;                       // [V, H, W]
+    float* landing;                    // [5, S, H, W] or null
+    uint32_t* conv_mask;               // [K] or null
+};
+
+// floor(a) as a texel index clamped to [0, n - 1] (replicate addressing).  A NaN -- the landing point of a dead ray, which
+// contributes nothing -- goes to texel 0: fmaxf returns its other operand, so nothing out of range is ever converted.
+__device__ __forceinline__ int clamped_texel(float fl, int off, int n)
+{
+    const float c = __builtin_fminf(__builtin_fmaxf(fl, -2.0f), (float)n);
+    const int i = (int)c + off;
+    return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
+}
+
+// A lane owns a pixel, a wave 64 consecutive pixels of the row-major sensor, and walks that pixel's samples in order:
+// the [S, H, W] pupil arrays are read as contiguous 256-byte runs, the 2 (NT + 1) float64 sums of a pixel stay in the
+// lane's registers and are written once (OVERWRITTEN: a wrong bet on the trip table launches the call again), and
+// the summation order is the sample order -- the same bits every run.
+template <class M, int DP, int NT>
+__global__ void __launch_bounds__(kBlock)
+k_render_plane(TripTable trips /* kernarg offset 0 */, PlaneLaunch a, DevDpParams dp)
+{
+    __shared__ uint32_t lds_mask[SDIRT_MAX_SURFACES];
+    if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
+    __syncthreads();
+    constexpr int V = DP == kDpNone ? 1 : 2;
+    const int64_t HW = (int64_t)a.H * a.W;
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p < HW) {
+        const int i = (int)(p / a.W), j = (int)(p - (int64_t)i * a.W);
+        const float ox = a.x1[j], oy = a.y1[i];
+        const float half_w = (float)a.Wt * 0.5f, half_h = (float)a.Ht * 0.5f;
+        const int64_t plane = (int64_t)a.Ht * a.Wt;
+        const auto div_fmh = UDiv<M>::make(dp.fmh);
+        double num[V][NT] = {}, den[V] = {};
+        for (int s = 0; s < a.S; ++s) {
+            const int64_t q = (int64_t)s * HW + p;
+            Ray r = make_ray<M>(ox, oy, a.z_sensor, a.x2[q], a.y2[q], a.z_pupil);
+            // monte_carlo.py:48 on the ray as it ARRIVES at the sensor (direction -d), the staged splat's division.
+            // The image is indexed by SENSOR position, psf_lr's grids by its negative (monte_carlo.py:24 flips the
+            // points): what the splat's sl-weighted rays form is, column for column, psf_lr's L turned by 180 degrees.
+            // The lens and the sub-pixel model are symmetric under that turn with the two sub-pixels exchanged, so
+            // the view that shifts with defocus as psf_lr's L does is the sr-weighted one: (w_L, w_R) = (sr, sl).
+            float w[2] = {1.0f, 1.0f};
+            if (DP != kDpNone) {
+                const float x_tan = r.dx / (-r.dz);
+                if (DP == kDpBig) dp_weights_big(dp, x_tan, w[1], w[0]);
+                else dp_weights_small<M>(dp, div_fmh, x_tan, w[1], w[0]);
+            }
+            trace_ray<false, M, true, /*UNIT_W*/ true, /*MASKS*/ true>(a.lens, 0, a.K, kernarg_at(0), r, lds_mask);
+            propagate_to<Ieee>(r, a.depth);                       // k_propagate's arithmetic
+            if (a.landing) {
+                const int64_t M5 = (int64_t)a.S * HW;
+                a.landing[q] = r.ox; a.landing[M5 + q] = r.oy; a.landing[2 * M5 + q] = r.ra;
+                a.landing[3 * M5 + q] = w[0]; a.landing[4 * M5 + q] = DP != kDpNone ? w[1] : 1.0f;
+            }
+            if (!(r.ra != 0.0f)) continue;
+            // the lookup of DESIGN.md §7o, one rounding per operation
+            const float u = half_w - r.ox * a.inv_texel, v = half_h + r.oy * a.inv_texel;
+            const float ta = u - 0.5f, tb = v - 0.5f;
+            const float c0 = __builtin_floorf(ta), r0 = __builtin_floorf(tb);
+            const float fu = ta - c0, fv = tb - r0;
+            const int cl = clamped_texel(c0, 0, a.Wt), cr = clamped_texel(c0, 1, a.Wt);
+            const int rt = clamped_texel(r0, 0, a.Ht), rb = clamped_texel(r0, 1, a.Ht);
+            const double du = fu, dv = fv;
+            const double w00 = (1.0 - dv) * (1.0 - du), w01 = (1.0 - dv) * du, w10 = dv * (1.0 - du), w11 = dv * du;
+            double wr[V];
+#pragma unroll
+            for (int side = 0; side < V; ++side) {
+                wr[side] = (double)w[side] * (double)r.ra;
+                den[side] += wr[side];
+            }
+#pragma unroll
+            for (int k = 0; k < NT; ++k) {
+                const float* __restrict__ t = a.tex + k * plane;
+                const double t00 = t[rt * a.Wt + cl], t01 = t[rt * a.Wt + cr], t10 = t[rb * a.Wt + cl], t11 = t[rb * a.Wt + cr];
+                const double tk = w00 * t00 + w01 * t01 + w10 * t10 + w11 * t11;
+#pragma unroll
+                for (int side = 0; side < V; ++side) num[side][k] += wr[side] * tk;
+            }
+        }
+#pragma unroll
+        for (int side = 0; side < V; ++side) {
+            a.den[side * HW + p] = den[side];
+#pragma unroll
+            for (int k = 0; k < NT; ++k) a.num[side * a.view_stride + k * HW + p] = num[side][k];
+        }
+    }
+    __syncthreads();
+    if (a.conv_mask && (int)threadIdx.x < a.K && lds_mask[threadIdx.x])
+        atomicOr(&a.conv_mask[threadIdx.x], lds_mask[threadIdx.x]);
+}
+
+// One instantiation per (math policy, dual-pixel form, planes per launch).
+template <class M, int DP>
+int launch_planes(int nt, dim3 grid, hipStream_t st, const TripTable& tt, const PlaneLaunch& a, const DevDpParams& dp)
+{
+    switch (nt) {
+    case 1: k_render_plane<M, DP, 1><<<grid, kBlock, 0, st>>>(tt, a, dp); break;
+    case 2: k_render_plane<M, DP, 2><<<grid, kBlock, 0, st>>>(tt, a, dp); break;
+    case 3: k_render_plane<M, DP, 3><<<grid, kBlock, 0, st>>>(tt, a, dp); break;
+    default: k_render_plane<M, DP, kMaxPlanes><<<grid, kBlock, 0, st>>>(tt, a, dp); break;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int sdirt_render_plane(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, const float* x1,
+                                  const float* y1, double z_sensor, const float* x2, const float* y2, double z_pupil,
+                                  int32_t spp, int32_t height, int32_t width, const sdirt_dp_params* dp, double depth,
+                                  double inv_texel, const float* tex, int32_t n_tex, int32_t tex_h, int32_t tex_w,
+                                  double* num, double* den, float* landing, uint32_t* mask, void* stream)
+{
+    if (!lens) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null lens");
+    if (any_null(x1, y1, x2, y2, tex, num, den)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!all_positive(spp, height, width, n_tex, tex_h, tex_w))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "spp, the sensor's and the texture's extents must be at least 1");
+    if ((int64_t)tex_h * tex_w > INT32_MAX) return fail(SDIRT_ERR_INVALID_ARGUMENT, "texture plane above 2^31 texels");
+    const int64_t HW = (int64_t)height * width;
+    if (HW > (int64_t)INT32_MAX * kBlock) return fail(SDIRT_ERR_INVALID_ARGUMENT, "sensor too large");
+    TripTable tt;
+    if (int rc = make_trips(lens, trips, tt)) return rc;
+    const DevDpParams dpp = make_dp(dp);
+    PlaneLaunch a;
+    a.lens = lens->dev; a.K = lens->n_surfaces;
+    a.x1 = x1; a.y1 = y1; a.x2 = x2; a.y2 = y2;
+    a.z_sensor = (float)z_sensor; a.z_pupil = (float)z_pupil; a.depth = (float)depth; a.inv_texel = (float)inv_texel;
+    a.S = spp; a.H = height; a.W = width;
+    a.Ht = tex_h; a.Wt = tex_w;
+    a.view_stride = (int64_t)n_tex * HW;
+    a.den = den; a.landing = landing; a.conv_mask = mask;
+    const dim3 grid((unsigned)((HW + kBlock - 1) / kBlock));
+    hipStream_t st = as_stream(stream);
+    // a launch sums up to kMaxPlanes planes; more planes: further launches over the same rays (den, landing and the
+    // masks come out the same from each)
+    for (int t0 = 0; t0 < n_tex; t0 += kMaxPlanes) {
+        const int nt = n_tex - t0 < kMaxPlanes ? n_tex - t0 : kMaxPlanes;
+        a.tex = tex + (int64_t)t0 * tex_h * tex_w;
+        a.num = num + (int64_t)t0 * HW;
+        with_math(flags, [&](auto m) {
+            using Mm = decltype(m);
+            if (!dp) return launch_planes<Mm, kDpNone>(nt, grid, st, tt, a, dpp);
+            return dpp.big ? launch_planes<Mm, kDpBig>(nt, grid, st, tt, a, dpp)
+                           : launch_planes<Mm, kDpSmall>(nt, grid, st, tt, a, dpp);
+        });
+        LAUNCH_CHECK();
+    }
+    return SDIRT_OK;
+}

@@ -1984,6 +1984,20 @@ for _name in ("sample_parallel_2D", "sample_point_source_2D", "sample_pupil", "s
     setattr(Lensgroup, _name, _bind_analysis(_name))
 
 
+# the ray-traced render of a textured plane and the reference's sensor-side samplers (sdirt_amd/render_rt.py)
+def _bind_render_rt(name):
+    def method(self, *args, **kwargs):
+        from . import render_rt
+        return getattr(render_rt, name)(self, *args, **kwargs)
+    method.__name__ = name
+    method.__doc__ = f"sdirt_amd.render_rt.{name}."
+    return method
+
+
+for _name in ("sample_sensor", "trace2obj", "render_plane", "render_single_img"):
+    setattr(Lensgroup, _name, _bind_render_rt(_name))
+
+
 def intersect_lines_2d_lstsq_fp32(origins, directions):
     """optics.py:1470-1515 as the reference evaluates it: all pairs, the 2x2 systems
     [Di, -Dj] x = Oj - Oi solved in fp32 by torch.linalg.lstsq (CPU: LAPACK gelsy),
