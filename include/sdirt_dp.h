@@ -159,6 +159,13 @@ int sdirt_lens_create(const sdirt_surface_desc* surfaces /*host*/, int32_t n_sur
                       sdirt_lens** out_lens);
 void sdirt_lens_destroy(sdirt_lens* lens);
 int32_t sdirt_lens_num_surfaces(const sdirt_lens* lens);
+/* 1 when every launch through this handle runs the strict-IEEE kernels whatever its flags say (as if
+ * SDIRT_PSF_STRICT_IEEE were set), 0 otherwise.  The Lean sag evaluation seeds 1 / (1 + sf)^2 with the square of its
+ * 1 / (1 + sf); that is the IEEE quotient for every operand pair but one, which only a curved surface with k > -1 and a
+ * curvature of mantissa 0x5413cc or 0x5413cd (|c| = 0.41421354 or 0.41421357 times a power of two) can reach.
+ * sdirt_lens_create finds such a surface and marks the handle.  The launchers that take rays and no lens (the splat
+ * and its backward passes) do not see the mark: pass them SDIRT_PSF_STRICT_IEEE for such a lens. */
+int32_t sdirt_lens_strict_ieee(const sdirt_lens* lens);
 
 /* ---- staged path (same decomposition as the reference) ------------------ */
 
@@ -636,9 +643,17 @@ int sdirt_host_uniform_fill(void* th_state /*host, in/out*/, int64_t state_bytes
  * [first, first+count), which must lie inside [0, 2^32) (exhaustive for 0, 2^32).  out[0] = values checked;
  * out[1] = differing G where 1 - a is a positive normal float; out[2] = differing G elsewhere, not NaN under both;
  * out[3] = differing bare quotients, not NaN under both; out[4], out[5], out[6] = the smallest bit pattern of a counted
- * in out[1], out[2], out[3] (UINT64_MAX: none); out[7] = out[8] = 0. */
+ * in out[1], out[2], out[3] (UINT64_MAX: none); out[7] = out[8] = 0.
+ * mode 5 compares the lean arithmetic with itself once more: the sag's second quotient n / (1 + sf)^2 with its division
+ * seeded by the hardware reciprocal of the square and by the square of the refined 1 / (1 + sf).  out (dev,
+ * 64 + 4096 x uint64).  Stage A: onesf = 1 + j 2^-23 for j in [first, first+count), inside [0, 2^23] (exhaustive for
+ * 0, 2^23 + 1); E = those whose refined reciprocal of onesf^2 differs between the seeds.  Stage B: every member of E
+ * (the first 4096) under all 2^23 numerator mantissas, the two quotients bit for bit.  out[0] = onesf checked;
+ * out[1] = |E|; out[2] = pairs checked; out[3] = pairs that differ; out[4..19] = up to 16 of them, bits of onesf << 32 |
+ * bits of the numerator; out[64 ...] = the members of E, bits of onesf.  exp_span = 1 puts EVERY onesf of the range
+ * into E (count <= 4096): the full scan of the pairs, 2048 calls. */
 int sdirt_selftest_math(int32_t mode, uint64_t first, uint64_t count, int32_t exp_span,
-                        uint64_t* out /*dev [9]*/, void* stream);
+                        uint64_t* out /*dev [9]; mode 5: [4160]*/, void* stream);
 
 /* The fused PSF kernel reads the dual-pixel weights (sl, sr) of a ray from a table over x_tan that belongs to the
  * SENSOR (h, f, w, r): built in float64 once per parameter set on the stream of the first call that needs it, kept in

@@ -90,6 +90,7 @@ SIGNATURES = {
     "sdirt_lens_create": (C.c_int, [C.POINTER(SurfaceDesc), _I32, C.POINTER(_P)]),
     "sdirt_lens_destroy": (None, [_P]),
     "sdirt_lens_num_surfaces": (_I32, [_P]),
+    "sdirt_lens_strict_ieee": (_I32, [_P]),
     "sdirt_points_to_object": (C.c_int, [_P, _I64, _D, _D, _D, _D, _P, _P]),
     "sdirt_pupil_samples": (C.c_int, [_P, _P, _I64, _D, _P, _P, _P]),
     "sdirt_sample_rays": (C.c_int, [_P, _I64, _P, _P, _I64, _D, Rays, _P]),

@@ -229,6 +229,10 @@ struct Ray {
 //          sqrt_pos_rsq + div_seeded: the conic sag's a / sqrt_pos(1 - a) takes the root's own v_rsq_f32 for the
 //                division's v_rcp_f32.  Not exact as a quotient; exact in the ONE expression that reads it, on every
 //                fp32 a (mode 4, exhaustive): the proof stands in sag_g_dgd.
+//          recip + div_y + div_seeded: for k > -1 the sag's second quotient, by (1 + sf)^2, takes the square of the first
+//                one's refined reciprocal for its v_rcp_f32.  Exact for every divisor in [1, 2] and numerator but ONE
+//                pair (mode 5), which a lens can reach with two curvature mantissas only; such a lens runs Ieee
+//                (sdirt_trace.hip: sag_seed_exception): the proof stands in sag_g_dgd.
 //        No operand on a valid ray is denormal or zero-denominator (eps = 1e-9 guards, unit
 //        direction vectors, |positions| in [1e-6, 2e4] mm), so valid rays are bit-identical
 //        to the Ieee instantiation; tests/test_gpu_parity.py runs both against the oracle.
@@ -336,8 +340,10 @@ struct Lean {
     // div(a, b) behind its v_rcp_f32, with a given seed y0 ~ 1/b in the v_rcp's place: the same five operations.  NOT
     // div(a, b) for every (a, b, y0): the refined reciprocal y can differ from recip(b) in its last bit, and over
     // independent (a, x) pairs with b = sqrt_pos(x), y0 = v_rsq_f32(x) the all-ones-mantissa divisor under a power-of-two
-    // numerator then misses the IEEE quotient by one ulp (see the note at recip below).  It has ONE caller, sag_g_dgd,
-    // where a determines b and the quotient has one consumer: the proof that nothing changes THERE stands at that call.
+    // numerator then misses the IEEE quotient by one ulp (see the note at recip below).  Its callers are the two
+    // quotients of sag_g_dgd: a / sf, where a determines b and the quotient has one consumer, and N c / onesf^2 seeded
+    // with the square of recip(onesf), where b is confined to the squares of [1, 2] and the one pair that misses is kept
+    // out on the host: the proof that nothing changes THERE stands at each call.
     static __device__ __forceinline__ float div_seeded(float a, float b, float y0)
     {
         const float y = __builtin_fmaf(__builtin_fmaf(-b, y0, 1.0f), y0, y0);
@@ -348,8 +354,8 @@ struct Lean {
     // seeding the Newton step from a related quantity instead -- the square root's own
     // half-reciprocal for a / sqrt(x), the square of 1/b's reciprocal for a / (b*b) -- was tried to
     // save the v_rcp_f32 and gives a reciprocal that differs in the last bit for 80 + 6 arguments,
-    // of which the all-ones-mantissa divisors then miss the IEEE quotient for some numerators.  div_seeded is that
-    // first form, kept for the one place where numerator and divisor are not independent: sag_g_dgd.)
+    // of which the all-ones-mantissa divisors then miss the IEEE quotient for some numerators.  div_seeded is both
+    // forms, kept for the one place where the operands are not free: sag_g_dgd.)
     static __device__ __forceinline__ float recip(float b)
     {
         const float y0 = __builtin_amdgcn_rcpf(b);
@@ -453,9 +459,12 @@ struct ConicS {      // the same constants straight from SGPRs (cold paths)
 template <class S>
 __device__ __forceinline__ ConicS conic_s(const S& s) { return ConicS{s.c(), s.c2(), s.onepk(), s.d()}; }
 
-template <class M, bool INSIDE, class C, bool UNITK = false>
+// SEED2 (Lean, INSIDE, k > -1 only: newton_k's copies KGT and UNITK): 1 / onesf^2 is seeded with the square of the
+// refined 1 / onesf -- see below.
+template <class M, bool INSIDE, class C, bool UNITK = false, bool SEED2 = false>
 __device__ __forceinline__ void sag_g_dgd(const C& k, const NoPoly&, int, float r2, float& g, float& dgd)
 {
+    static_assert(!SEED2 || (INSIDE && M::kFused), "the seeded 1 / onesf^2 is Lean's, inside the conic's domain");
     // UNITK: 1 + k is 1.0f, the product with it is the identity and is left out
     const float a = UNITK ? r2 * k.c2 : (k.onepk * r2) * k.c2;
     if constexpr (INSIDE && M::kFused) {
@@ -473,8 +482,29 @@ __device__ __forceinline__ void sag_g_dgd(const C& k, const NoPoly&, int, float 
         const float sf = M::sqrt_pos_rsq(1.0f - a, r);
         const float q = M::div_seeded(a, sf, r);
         const float onesf = 1.0f + sf;
-        g = M::div(r2 * k.c, onesf);
-        dgd = M::div(__builtin_fmaf(0.5f, q, onesf) * k.c, onesf * onesf);   // add_half_quot(onesf, a, sf) * c / onesf^2
+        const float n2 = __builtin_fmaf(0.5f, q, onesf) * k.c;               // add_half_quot(onesf, a, sf) * c
+        if constexpr (SEED2) {
+            // k > -1: a lies in [0, 1], sf in [0, 1], onesf in [1, 2].  The second quotient's v_rcp_f32(onesf^2) is
+            // replaced by the square of the first one's refined reciprocal y1 = recip(onesf) -- a seed within 2 ulp of
+            // 1 / onesf^2, one v_mul_f32 for a v_rcp_f32: three transcendentals per evaluation instead of four.  g is
+            // Lean::div in its two halves, the same bits.
+            // Proof that dgd is the IEEE quotient still.  The recurrence scales exactly with the numerator's exponent and
+            // sign, so the operands are the 2^23 + 1 floats onesf of [1, 2] times the 2^23 numerator mantissas, and the
+            // device runs them (sdirt_selftest_math mode 5, tests/test_gpu_sag_seed2.py; all 2^46 pairs once, as a tool
+            // run).  The refined reciprocal of onesf^2 differs between the two seeds for 6 values of onesf, and on
+            // those the quotient misses for ONE pair: onesf = 0x3fb504f3, whose square rounds to the all-ones mantissa
+            // 0x3fffffff, under a power-of-two numerator.  That onesf has one preimage a, N = fma(0.5, a / sf, onesf) is
+            // then one float, and fl(N * c) is a power of two for two mantissas of c only: make_dev_surface
+            // (sag_seed_exception) finds such a curvature on the host and the launchers run that lens under Ieee.  So
+            // no lens reaches the pair under Lean, and this code is exact for every lens it runs on.
+            // A radicand of 0 (a rounds to 1) gives sf = NaN, hence NaN for g and dgd, under this form as under div().
+            const float y1 = M::recip(onesf);
+            g = M::div_y(r2 * k.c, onesf, y1);
+            dgd = M::div_seeded(n2, onesf * onesf, y1 * y1);
+        } else {
+            g = M::div(r2 * k.c, onesf);
+            dgd = M::div(n2, onesf * onesf);
+        }
     } else {
         const float sf = INSIDE ? M::sqrt_pos(1.0f - a) : M::sqrt(1.0f - a);
         const float onesf = 1.0f + sf;
@@ -485,16 +515,17 @@ __device__ __forceinline__ void sag_g_dgd(const C& k, const NoPoly&, int, float 
 
 // WANT_G = false: only dgd is asked for (the surface normal, refract()): the terms of g are left out and the powers
 // stop at r2 ** (deg - 1), the highest one dgd has.
-template <class M, bool INSIDE, class C, bool UNITK = false, class P = Poly, bool WANT_G = true>
+template <class M, bool INSIDE, class C, bool UNITK = false, class P = Poly, bool WANT_G = true, bool SEED2 = false>
 __device__ __forceinline__ void sag_g_dgd(const C& k, const P& pol, int deg, float r2, float& g, float& dgd)
 {
+    static_assert(!SEED2 || WANT_G, "the seed of 1 / onesf^2 is the reciprocal g is divided with");
     // `deg` is compared where it is branched on, once per evaluation: s_cmp + s_cbranch_scc.  Left alone, the compiler
     // hoists the seven comparisons of the unrolled loop below out of the Newton loops as seven 64-bit
     // condition masks -- 14 SGPRs held across every trip of an asphere, at the very place where the kernels that trace
     // are at their SGPR limit, paid for with values parked in VGPR lanes (v_readlane / v_writelane) all around it;
     // the branch on a mask is s_andn2 + s_cbranch_vcc, so the scalar unit has the same two instructions either way
     asm volatile("" : "+s"(deg));
-    sag_g_dgd<M, INSIDE, C, UNITK>(k, NoPoly{}, 0, r2, g, dgd);
+    sag_g_dgd<M, INSIDE, C, UNITK, SEED2>(k, NoPoly{}, 0, r2, g, dgd);
     dgd = dgd + pol.ai(0);
     if (WANT_G) g = g + pol.ai(0) * r2;
     // The terms are a chain of wave-uniform BRANCHES, one per term, each left at the first term the surface does not
@@ -547,6 +578,15 @@ __device__ __forceinline__ NewtonEnd newton_k(const S& s, const P& pol, const Ra
                                               uint32_t& mask_out)
 {
     using CV = ConicV;
+    // Lean on the k > -1 side (KGT; UNITK is a sphere): onesf lies in [1, 2] and 1 / onesf^2 takes its seed from 1 / onesf
+    // (sag_g_dgd, SEED2).  k <= -1 keeps Lean::div: onesf is unbounded there, a diverged ray's onesf^2 overflows and the
+    // two forms then part between NaN and inf -- which |ft| > tol, hence the convergence masks, would show.
+    constexpr bool SEED2 = KGT && M::kFused;
+    static_assert(KGT || !UNITK, "1 + k == 1 lies on the k > -1 side");
+    auto sag = [&](const CV& kv, int dg, float q2, float& g, float& dgd) __attribute__((always_inline)) {
+        if constexpr (std::is_same<P, NoPoly>::value) sag_g_dgd<M, true, CV, UNITK, SEED2>(kv, pol, dg, q2, g, dgd);
+        else sag_g_dgd<M, true, CV, UNITK, P, true, SEED2>(kv, pol, dg, q2, g, dgd);
+    };
     const bool adaptive = trips < 0;
     const int cap = adaptive ? -trips : trips;
     const float tol_loose = (float)50e-6, eps = (float)1e-9;
@@ -597,7 +637,7 @@ __device__ __forceinline__ NewtonEnd newton_k(const S& s, const P& pol, const Ra
         // which only a ray whose Newton iteration has diverged holds -- it fails |ft| < 10e-6 and is dead under
         // either root.
         float g, dgd;
-        sag_g_dgd<M, true, CV, UNITK>(k, pol, deg, r2, g, dgd);
+        sag(k, deg, r2, g, dgd);
         const float ft = (g + k.d) - nz;
         const float dfdt = M::dfdt(dgd, dd * t + dox, r.dz);            // dgd * dr2dt - dz, dr2dt = 2((dx^2+dy^2) t + (dx ox + dy oy))
         const unsigned long long open = __ballot(__builtin_fabsf(ft) > tol_loose);
@@ -672,7 +712,7 @@ __device__ __forceinline__ NewtonEnd newton_k(const S& s, const P& pol, const Ra
     const float tight = alive ? s.lim_tight() : -1.0f;
     const float r2 = rr < tight ? rr : 0.0f;
     float g, dgd;
-    sag_g_dgd<M, true, CV, UNITK>(k, pol, deg, r2, g, dgd);
+    sag(k, deg, r2, g, dgd);
     const float ft = (g + k.d) - nz;
     const float dfdt = M::dfdt(dgd, dd * t + dox, r.dz);
     t = t - M::newton_step(ft, dfdt + eps);

@@ -111,7 +111,19 @@ struct sdirt_lens {
     sdirt::DevSurface* dev;               // device table [n_surfaces]
     std::vector<sdirt::DevSurface> host;  // host mirror
     mutable DpWeightTable dp_table;       // filled by the PSF calls that render through this handle
+    bool strict_ieee;                     // a surface can reach the seeded sag quotient's exception: every launch runs Ieee
 };
+
+// The flags a launch through these handles runs under: SDIRT_PSF_STRICT_IEEE is added for a lens that
+// sdirt_lens_create marked (sdirt_trace.hip: sag_seed_exception) -- about one curvature in four million.  Taken once
+// at the head of a launcher, so that with_math and everything else that reads the flag (the dual-pixel weight table)
+// see the same policy.
+inline uint32_t routed_flags(uint32_t flags, const sdirt_lens* lens) { return lens && lens->strict_ieee ? flags | SDIRT_PSF_STRICT_IEEE : flags; }
+inline uint32_t routed_flags(uint32_t flags, const sdirt_lens* const* lens, int n)
+{
+    for (int i = 0; lens && i < n; ++i) flags = routed_flags(flags, lens[i]);
+    return flags;
+}
 
 // Newton trip counts of one launch, one signed byte per surface, passed by value at a FIXED
 // offset of the kernel-argument segment; the kernels read the dword of surface k from there

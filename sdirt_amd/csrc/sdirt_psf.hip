@@ -1118,6 +1118,7 @@ struct PsfLaunch {
     SplitArgs sa;
     hipStream_t st;
     const sdirt_lens* table_owner;   // the handle whose dual-pixel weight table the call may use: lens[0]
+    bool strict_ieee;                // one of the call's handles is routed to the strict-IEEE kernels (routed_flags)
     // the plan
     SplatBlock sblk;
     DevDpParams dpp;
@@ -1154,6 +1155,7 @@ static int check_psf_args(PsfLaunch& L, bool primary, const sdirt_lens* const* l
     const int K = ref->n_surfaces;
     L = PsfLaunch{};
     if (primary) L.table_owner = lens[0];
+    L.strict_ieee = (routed_flags(0u, lens_c) | (primary ? routed_flags(0u, lens, W) : 0u)) != 0u;
     for (int w = 0; primary && w < W; ++w) {
         L.ls.p[w] = lens[w]->dev;
         if (int rc = make_trips(lens[w], trips ? trips + (size_t)w * K : nullptr, L.tt.t[w])) return rc;
@@ -1175,6 +1177,7 @@ static int plan_psf(PsfLaunch& L, double ps, const sdirt_dp_params* dp, uint32_t
                     uint32_t* conv_mask, void* stream)
 {
     const int tile = L.ks * L.ks;
+    if (L.strict_ieee) flags |= SDIRT_PSF_STRICT_IEEE;
     L.flags = flags; L.l = l_psf; L.r = r_psf; L.conv_mask = conv_mask; L.st = as_stream(stream);
     // SDIRT_PSF_INTERLEAVED: l_psf / r_psf are the two halves of ONE [N, 2, ks, ks] array
     L.interleaved = (flags & SDIRT_PSF_INTERLEAVED) != 0;
@@ -1505,7 +1508,7 @@ static int chief_center_entry(const sdirt_lens* lens, const float* point_obj, in
                                 d_sensor, 0, nullptr, nullptr, trips, center, nullptr))
         return rc;
     if (N == 0) return SDIRT_OK;
-    L.flags = flags; L.st = as_stream(stream);
+    L.flags = L.strict_ieee ? flags | SDIRT_PSF_STRICT_IEEE : flags; L.st = as_stream(stream);
     L.ca.center_out = center; L.ca.any_valid = any_valid; L.ca.conv_mask_c = conv_mask;
     return launch_chief_center(L, slope);
 }

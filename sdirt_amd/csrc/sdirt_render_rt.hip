@@ -169,7 +169,7 @@ extern "C" int sdirt_render_plane(const sdirt_lens* lens, const int32_t* trips, 
         const int nt = n_tex - t0 < kMaxPlanes ? n_tex - t0 : kMaxPlanes;
         a.tex = tex + (int64_t)t0 * tex_h * tex_w;
         a.num = num + (int64_t)t0 * HW;
-        with_math(flags, [&](auto m) {
+        with_math(routed_flags(flags, lens), [&](auto m) {
             using Mm = decltype(m);
             if (!dp) return launch_planes<Mm, kDpNone>(nt, grid, st, tt, a, dpp);
             return dpp.big ? launch_planes<Mm, kDpBig>(nt, grid, st, tt, a, dpp)

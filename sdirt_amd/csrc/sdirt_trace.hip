@@ -34,9 +34,37 @@ static float plane_r2_max(float r)
     return x;
 }
 
+// Can a curved surface with k > -1 and this curvature reach the one operand pair at which the seeded second quotient
+// of the sag (sag_g_dgd, SEED2) misses the IEEE quotient: onesf = 1 + sf = kSeed2Onesf (its square rounds to the
+// all-ones mantissa 0x3fffffff) under a power-of-two numerator fl(N c), N = fma(0.5, a / sf, onesf)?  Plain IEEE float
+// arithmetic: sqrt_pos is the correctly rounded root (selftest mode 3), and N has the same bits under either seed of
+// a / sf (mode 4).  onesf(a) does not increase with a, so the floats a of [0, 1) that map to kSeed2Onesf are found by
+// bisection on the bit pattern and a walk -- there is one -- and each gives one N.  The aperture is not looked at: the
+// answer holds for every ray.
+constexpr uint32_t kSeed2Onesf = 0x3fb504f3u;
+static float bits_float(uint32_t u) { float f; std::memcpy(&f, &u, sizeof f); return f; }
+static uint32_t float_bits(float f) { uint32_t u; std::memcpy(&u, &f, sizeof u); return u; }
+static bool sag_seed_exception(float c)
+{
+    const auto onesf_of = [](uint32_t abits) { return 1.0f + std::sqrt(1.0f - bits_float(abits)); };
+    const float target = bits_float(kSeed2Onesf);
+    uint32_t lo = 0u, hi = 0x3f800000u;                 // a = +0 (onesf = 2) ... a = 1 (onesf = 1)
+    while (lo < hi) {                                   // the first a with onesf(a) <= target
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (onesf_of(mid) <= target) hi = mid; else lo = mid + 1;
+    }
+    for (uint32_t ab = lo; ab < 0x3f800000u && onesf_of(ab) == target; ++ab) {
+        const float a = bits_float(ab), sf = std::sqrt(1.0f - a);
+        const float n = std::fmaf(0.5f, a / sf, target) * c;
+        if (n != 0.0f && std::isfinite(n) && (float_bits(n) & 0x007fffffu) == 0u) return true;
+    }
+    return false;
+}
+
 // Per-surface constant block; every double->float rounding happens here, at the
-// same place the reference's torch scalar handling performs it.
-static DevSurface make_dev_surface(const sdirt_surface_desc& in)
+// same place the reference's torch scalar handling performs it.  needs_ieee: set where the surface is one of the
+// few whose curvature can reach the seeded sag quotient's one exception (sag_seed_exception); never cleared.
+static DevSurface make_dev_surface(const sdirt_surface_desc& in, bool& needs_ieee)
 {
     DevSurface s;
     std::memset(&s, 0, sizeof(s));
@@ -53,6 +81,7 @@ static DevSurface make_dev_surface(const sdirt_surface_desc& in)
         h.d_plus_R = in.d + 1.0f / in.c;
         h.d_plus_R_b = h.d_plus_R;
         h.lim_tight = in.k > -1.0f ? std::min(h.r2_lim, h.lim_loose) : h.r2_lim;
+        if (in.k > -1.0f && sag_seed_exception(h.c)) needs_ieee = true;
     } else {
         h.lim_tight = (float)in.r;                    // planes: the aperture radius itself ...
         h.r2_lim = plane_r2_max(h.lim_tight);         // ... and the largest x^2 + y^2 whose root passes it
@@ -356,6 +385,60 @@ __global__ void k_selftest_math(int mode, uint64_t first, uint64_t count, int ex
     }
 }
 
+// mode 5: the sag's second quotient n / onesf^2 under its two seeds -- v_rcp_f32(onesf^2) (Lean::div) and the square of
+//         the refined 1 / onesf (Lean::div_seeded; sag_g_dgd, SEED2) -- on the operands the k > -1 copies can hold: onesf
+//         in [1, 2], every numerator mantissa (the recurrence scales exactly with the numerator's exponent and sign).
+//         Stage A (k_selftest_seed2_a): onesf = 1 + j 2^-23 for j in [first, first + count) of [0, 2^23]; the set E of
+//         those whose refined reciprocal of onesf^2 differs between the seeds.  exp_span = 1: EVERY onesf of the range
+//         is put into E instead (the full scan of the pairs; a tool run, a range of at most kSeed2Cap at a time).
+//         Stage B (k_selftest_seed2_b): every member of E under all 2^23 numerators 1.m, the two quotients bit for bit.
+//         out[0] = onesf checked; out[1] = |E| (members beyond kSeed2Cap are counted and not run); out[2] = pairs
+//         checked; out[3] = pairs that differ; out[4 .. 19] = up to 16 of them, onesf << 32 | numerator;
+//         out[kSeed2Words ...] = the members of E (bit patterns of onesf), kSeed2Cap words, in no particular order.
+constexpr int kSeed2Cap = 4096, kSeed2Words = 64, kSeed2Misses = 16;
+
+__global__ void k_selftest_seed2_a(uint64_t first, uint64_t count, int all, unsigned long long* __restrict__ out)
+{
+    unsigned long long n_checked = 0;
+    for (uint64_t j = first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < first + count;
+         j += (uint64_t)gridDim.x * blockDim.x) {
+        const float onesf = __uint_as_float(0x3f800000u + (uint32_t)j);
+        const float b = onesf * onesf;
+        const float y1 = Lean::recip(onesf), s0 = y1 * y1;
+        const float y_rcp = Lean::recip(b);
+        const float y_sq = __builtin_fmaf(__builtin_fmaf(-b, s0, 1.0f), s0, s0);
+        ++n_checked;
+        if (all || __float_as_uint(y_rcp) != __float_as_uint(y_sq)) {
+            const unsigned long long k = atomicAdd(&out[1], 1ull);
+            if (k < (unsigned long long)kSeed2Cap) out[kSeed2Words + k] = __float_as_uint(onesf);
+        }
+    }
+    if (n_checked) atomicAdd(&out[0], n_checked);
+}
+
+__global__ void k_selftest_seed2_b(unsigned long long* __restrict__ out)
+{
+    const unsigned long long ne = out[1] < (unsigned long long)kSeed2Cap ? out[1] : (unsigned long long)kSeed2Cap;
+    const uint64_t total = (uint64_t)ne << 23;
+    unsigned long long n_checked = 0, n_bad = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const float onesf = __uint_as_float((uint32_t)out[kSeed2Words + (i >> 23)]);
+        const float n = __uint_as_float(0x3f800000u | (uint32_t)(i & 0x7fffffu));
+        const float b = onesf * onesf;
+        const float y1 = Lean::recip(onesf);
+        const float q_rcp = Lean::div(n, b), q_sq = Lean::div_seeded(n, b, y1 * y1);
+        ++n_checked;
+        if (__float_as_uint(q_rcp) != __float_as_uint(q_sq)) {
+            ++n_bad;
+            const unsigned long long k = atomicAdd(&out[3], 1ull);
+            if (k < (unsigned long long)kSeed2Misses)
+                out[4 + k] = ((unsigned long long)__float_as_uint(onesf) << 32) | __float_as_uint(n);
+        }
+    }
+    if (n_checked) atomicAdd(&out[2], n_checked);
+    (void)n_bad;
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -396,7 +479,8 @@ int sdirt_lens_create(const sdirt_surface_desc* surfaces, int32_t n_surfaces, sd
     L->n_surfaces = n_surfaces;
     L->dev = nullptr;
     L->host.resize(n_surfaces);
-    for (int i = 0; i < n_surfaces; ++i) L->host[i] = make_dev_surface(surfaces[i]);
+    L->strict_ieee = false;
+    for (int i = 0; i < n_surfaces; ++i) L->host[i] = make_dev_surface(surfaces[i], L->strict_ieee);
     hipError_t e = hipMalloc(&L->dev, sizeof(DevSurface) * n_surfaces);
     if (e == hipSuccess)
         e = hipMemcpy(L->dev, L->host.data(), sizeof(DevSurface) * n_surfaces,
@@ -426,6 +510,8 @@ void sdirt_lens_destroy(sdirt_lens* lens)
 }
 
 int32_t sdirt_lens_num_surfaces(const sdirt_lens* lens) { return lens ? lens->n_surfaces : 0; }
+
+int32_t sdirt_lens_strict_ieee(const sdirt_lens* lens) { return lens && lens->strict_ieee ? 1 : 0; }
 
 int sdirt_points_to_object(const float* points, int64_t N, double tan_hfov, double r_last,
                            double sensor_w, double sensor_h, float* point_obj, void* stream)
@@ -502,6 +588,7 @@ static int launch_trace(const sdirt_lens* lens, int32_t first, int32_t last, int
                         uint32_t* conv_mask, void* stream, bool to_sensor, double z_sensor)
 {
     if (!lens) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null lens");
+    flags = routed_flags(flags, lens);
     if (first < 0 || last > lens->n_surfaces || first > last)
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "surface range [%d,%d) outside [0,%d]", first, last,
                     lens->n_surfaces);
@@ -583,8 +670,20 @@ int sdirt_center_from_rays(sdirt_rays rays, int64_t S, int64_t N, float* center,
 int sdirt_selftest_math(int32_t mode, uint64_t first, uint64_t count, int32_t exp_span,
                         uint64_t* out, void* stream)
 {
-    if (!out || mode < 0 || mode > 4 || exp_span < 0 || exp_span > 60)
+    if (!out || mode < 0 || mode > 5 || exp_span < 0 || exp_span > 60)
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (mode == 5) {
+        // onesf = 1 + j 2^-23, j in [first, first + count) of [0, 2^23]; `out` holds kSeed2Words + kSeed2Cap words
+        if (exp_span > 1 || first > (1ull << 23) + 1 || count > (1ull << 23) + 1 - first || (exp_span == 1 && count > (uint64_t)kSeed2Cap))
+            return fail(SDIRT_ERR_INVALID_ARGUMENT, "mode 5: [first, first+count) outside [0, 2^23], or a full scan of more than %d "
+                                                    "divisors in one call", kSeed2Cap);
+        HIP_TRY(hipMemsetAsync(out, 0, sizeof(uint64_t) * (kSeed2Words + kSeed2Cap), as_stream(stream)));
+        if (count == 0) return SDIRT_OK;
+        k_selftest_seed2_a<<<256, 256, 0, as_stream(stream)>>>(first, count, exp_span, (unsigned long long*)out);
+        k_selftest_seed2_b<<<256 * 32, 256, 0, as_stream(stream)>>>((unsigned long long*)out);
+        LAUNCH_CHECK();
+        return SDIRT_OK;
+    }
     // mode 4 walks bit patterns of ONE fp32: nothing beyond 2^32 (the other modes keep the ranges they always took)
     if (mode == 4 && (first > (1ull << 32) || count > (1ull << 32) - first))
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "mode 4: [first, first+count) outside [0, 2^32)");

@@ -507,7 +507,7 @@ int sdirt_trace2sensor_record(const sdirt_lens* lens, const int32_t* trips, uint
     if (int rc = make_trips(lens, trips, tt)) return rc;
     if (M < 0) return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_rays < 0");
     if (M == 0) return SDIRT_OK;
-    with_math(flags, [&](auto m) {
+    with_math(routed_flags(flags, lens), [&](auto m) {
         k_trace_record<decltype(m)><<<grid_for(M, kBlock), kBlock, 0, as_stream(stream)>>>(
             tt, lens->dev, lens->n_surfaces, rays, out, M, conv_mask, (float)d_sensor, (float*)workspace);
         return 0;
@@ -541,7 +541,7 @@ static int launch_trace_grad(bool eta, const sdirt_lens* lens, const int32_t* tr
     if (n_workgroups != grid)
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_workgroups=%d, the launch has %d (sdirt_trace2sensor_grad_workgroups)",
                     n_workgroups, grid);
-    with_math(flags, [&](auto m) {
+    with_math(routed_flags(flags, lens), [&](auto m) {
         auto* kernel = eta ? k_trace_grad<decltype(m), true> : k_trace_grad<decltype(m), false>;
         kernel<<<grid, kBlock, 0, as_stream(stream)>>>(
             tt, lens->dev, lens->n_surfaces, (const float*)workspace, ra, ray_grad, M, (float)d_sensor, partial);
@@ -582,7 +582,7 @@ int sdirt_trace2sensor_grad_points(const sdirt_lens* lens, const int32_t* trips,
     if (N * (int64_t)ns > 0x7fffffffll) return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_points * n_slices exceeds the grid");
     // the slices cover the spp axis in runs of `chunk` samples (a trailing slice may be empty: it stores zeros)
     const int64_t chunk = std::max<int64_t>(1, (S + ns - 1) / ns);
-    with_math(flags, [&](auto m) {
+    with_math(routed_flags(flags, lens), [&](auto m) {
         k_trace_grad_points<decltype(m)><<<(unsigned)(N * ns), kBlock, 0, as_stream(stream)>>>(
             tt, lens->dev, lens->n_surfaces, (const float*)workspace, ra, ray_grad, S * N, S, ns, chunk, (float)d_sensor, x2, y2,
             (float)pupil_z, partial);
