@@ -651,9 +651,17 @@ int sdirt_host_uniform_fill(void* th_state /*host, in/out*/, int64_t state_bytes
  * (the first 4096) under all 2^23 numerator mantissas, the two quotients bit for bit.  out[0] = onesf checked;
  * out[1] = |E|; out[2] = pairs checked; out[3] = pairs that differ; out[4..19] = up to 16 of them, bits of onesf << 32 |
  * bits of the numerator; out[64 ...] = the members of E, bits of onesf.  exp_span = 1 puts EVERY onesf of the range
- * into E (count <= 4096): the full scan of the pairs, 2048 calls. */
+ * into E (count <= 4096): the full scan of the pairs, 2048 calls.
+ * mode 6 is mode 4's question about the next shortening: the same quotient, seeded with the root's hardware reciprocal
+ * square root, with and without the two operations that refine the seed before it is used, and G(a), on every fp32 bit
+ * pattern of a in [first, first+count) inside [0, 2^32).  out (dev, 64 + 4096 x uint64): out[0] = values checked;
+ * out[1], out[2] = differing G where 1 - a is a positive normal float, for a >= 0 and for a < 0; out[3] = differing G
+ * elsewhere, not NaN under both; out[4] = differing bare quotients, not NaN under both; out[5], out[6], out[7] = the
+ * smallest bit pattern of a counted in out[1], out[2], out[3] (UINT64_MAX: none); out[8] = the hardware reciprocal square
+ * root of 1 - a less the correctly rounded one, in floats (signed), at a = 0x3dc39c73, and out[9] = its bits (both 0
+ * when the range leaves that a out); out[64 ...] = the a counted in out[4] (the first 4096 to arrive, unordered). */
 int sdirt_selftest_math(int32_t mode, uint64_t first, uint64_t count, int32_t exp_span,
-                        uint64_t* out /*dev [9]; mode 5: [4160]*/, void* stream);
+                        uint64_t* out /*dev [9]; modes 5 and 6: [4160]*/, void* stream);
 
 /* The fused PSF kernel reads the dual-pixel weights (sl, sr) of a ray from a table over x_tan that belongs to the
  * SENSOR (h, f, w, r): built in float64 once per parameter set on the stream of the first call that needs it, kept in

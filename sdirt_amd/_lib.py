@@ -262,3 +262,17 @@ def check(rc):
 
 def device_count():
     return lib().sdirt_device_count()
+
+
+SELFTEST_LIST_WORDS, SELFTEST_LIST_CAP = 64, 4096     # sdirt_selftest_math modes 5 and 6: header words, list capacity
+SEED_ONCE_PROBE = 0x3DC39C73
+
+
+def decode_seed_once(words):
+    """The 64 + 4096 uint64 words sdirt_selftest_math mode 6 leaves (include/sdirt_dp.h) -> dict."""
+    o = [int(v) & 0xFFFFFFFFFFFFFFFF for v in words]
+    none = 0xFFFFFFFFFFFFFFFF
+    listed = sorted(o[SELFTEST_LIST_WORDS:SELFTEST_LIST_WORDS + min(o[4], SELFTEST_LIST_CAP)])
+    return dict(checked=o[0], g_pos=o[1], g_neg=o[2], g_outside=o[3], n_quot=o[4],
+                first_g=[None if v == none else v for v in o[5:8]],
+                seed_offset=o[8] - (1 << 64) if o[8] >> 63 else o[8], seed_bits=o[9], quot=listed)

@@ -229,6 +229,8 @@ struct Ray {
 //          sqrt_pos_rsq + div_seeded: the conic sag's a / sqrt_pos(1 - a) takes the root's own v_rsq_f32 for the
 //                division's v_rcp_f32.  Not exact as a quotient; exact in the ONE expression that reads it, on every
 //                fp32 a (mode 4, exhaustive): the proof stands in sag_g_dgd.
+//          div_seeded_once: for k > -1 that quotient also drops the two fma that refine the seed.  Exact in the same ONE
+//                expression on every fp32 a >= 0 (mode 6, exhaustive), not on one a < 0: k <= -1 keeps div_seeded.
 //          recip + div_y + div_seeded: for k > -1 the sag's second quotient, by (1 + sf)^2, takes the square of the first
 //                one's refined reciprocal for its v_rcp_f32.  Exact for every divisor in [1, 2] and numerator but ONE
 //                pair (mode 5), which a lens can reach with two curvature mantissas only; such a lens runs Ieee
@@ -350,6 +352,17 @@ struct Lean {
         const float q0 = a * y;
         return __builtin_fmaf(__builtin_fmaf(-b, q0, a), y, q0);
     }
+    // div_seeded(a, b, y0) without the two fma that refine the seed: the estimate a * y0 and ONE residual correction, by
+    // the raw seed.  NOT a division in general: with y0 within 1.5 ulp of 1/b it misses the IEEE quotient, by one ulp,
+    // for about 7e-10 of the operand pairs (the same shortening behind v_rcp_f32 misses 47045 of the 2^46 mantissa
+    // pairs: see sqrt_pos above) -- and more often than div_seeded does.  It has ONE caller, the a / sf of sag_g_dgd,
+    // where a determines b and y0 and the quotient's one reader absorbs every miss: the proof (mode 6, every fp32 a on
+    // the device) stands at that call.  Use it nowhere else without such a proof.
+    static __device__ __forceinline__ float div_seeded_once(float a, float b, float y0)
+    {
+        const float q0 = a * y0;
+        return __builtin_fmaf(__builtin_fmaf(-b, q0, a), y0, q0);
+    }
     // div() in two halves: div(a, b) == div_y(a, b, recip(b)).  (The seed must be v_rcp_f32(b):
     // seeding the Newton step from a related quantity instead -- the square root's own
     // half-reciprocal for a / sqrt(x), the square of 1/b's reciprocal for a / (b*b) -- was tried to
@@ -460,7 +473,7 @@ template <class S>
 __device__ __forceinline__ ConicS conic_s(const S& s) { return ConicS{s.c(), s.c2(), s.onepk(), s.d()}; }
 
 // SEED2 (Lean, INSIDE, k > -1 only: newton_k's copies KGT and UNITK): 1 / onesf^2 is seeded with the square of the
-// refined 1 / onesf -- see below.
+// refined 1 / onesf, and a / sf takes the root's v_rsq_f32 as it comes (div_seeded_once) -- see below.
 template <class M, bool INSIDE, class C, bool UNITK = false, bool SEED2 = false>
 __device__ __forceinline__ void sag_g_dgd(const C& k, const NoPoly&, int, float r2, float& g, float& dgd)
 {
@@ -478,9 +491,17 @@ __device__ __forceinline__ void sag_g_dgd(const C& k, const NoPoly&, int, float 
         // NaN) G is NaN under both.  The bare quotient does differ, in its last bit, at a handful of a (the same run
         // counts them): there sf has an all-ones mantissa under a power-of-two a (a = 2^-23, 2^-24: sf = 1 - 2^-24) and
         // 1 + sf rounds to 2.0f, whose half-ulp swallows q / 2 and either neighbour of it.
+        // SEED2 (k > -1: a >= 0): the two fma that refine the seed before the quotient uses it are left out as well --
+        // q0 = a r, one residual correction by r (Lean::div_seeded_once), ten vector instructions and the v_rsq from a to
+        // G instead of twelve.  The same univariate argument, run the same way (mode 6, tests/test_gpu_sag_seed3.py): over
+        // ALL 2^32 bit patterns of a the bare quotient differs from div_seeded's at 10, nine of them in [2^-23, 2^-6],
+        // where half of q's last bit is 2^-8 of G's or less and G rounds either neighbour to the same float; no a >= 0
+        // changes a bit of G, and none outside the domain (a >= 1, NaN) makes G anything but NaN under both.  The tenth,
+        // a = 0xc525406d (-2644.03), DOES change G: q is of G's own magnitude there.  Negative a is the k <= -1 side, so
+        // that side, the normals and the recording trace keep div_seeded.
         float r;
         const float sf = M::sqrt_pos_rsq(1.0f - a, r);
-        const float q = M::div_seeded(a, sf, r);
+        const float q = SEED2 ? M::div_seeded_once(a, sf, r) : M::div_seeded(a, sf, r);
         const float onesf = 1.0f + sf;
         const float n2 = __builtin_fmaf(0.5f, q, onesf) * k.c;               // add_half_quot(onesf, a, sf) * c
         if constexpr (SEED2) {

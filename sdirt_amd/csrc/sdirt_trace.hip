@@ -439,6 +439,64 @@ __global__ void k_selftest_seed2_b(unsigned long long* __restrict__ out)
     (void)n_bad;
 }
 
+// mode 6: the sag's a / sqrt_pos(1 - a), seeded with the root's v_rsq_f32, with and without the two fma that refine the
+//         seed -- Lean::div_seeded and Lean::div_seeded_once -- over every fp32 bit pattern i of a in [first, first+count)
+//         (exhaustive when first = 0, count = 2^32), and what reads it, G(a) = fma(0.5, a / sf, 1 + sf) (sag_g_dgd).
+//         As in mode 4 nothing is compared with IEEE: can the two forms be told apart behind G?
+//         out[0] = values checked; out[1], out[2] = a whose G differs in its bits where 1 - a is a positive normal float
+//         (the INSIDE contract of sag_g_dgd), a >= 0 and a < 0; out[3] = a elsewhere whose G differs and is not NaN under
+//         both; out[4] = a whose bare quotient differs (not NaN under both; informative); out[5], out[6], out[7] = the
+//         smallest bit pattern counted in out[1], out[2], out[3] (all ones: none); out[8] = v_rsq_f32(1 - a) less the
+//         correctly rounded 1 / sqrt(1 - a), in floats (a signed count), at a = kSeedOnceProbe, the one argument at which
+//         a CPU restatement with a seed one float low told the forms apart; out[9] = the bits of that v_rsq_f32 (0: the
+//         range leaves the probe out); out[kSeedOnceWords ...] = the a counted in out[4], the first kSeedOnceCap to
+//         arrive, in no particular order.
+constexpr int kSeedOnceCap = 4096, kSeedOnceWords = 64;
+constexpr uint32_t kSeedOnceProbe = 0x3dc39c73u;
+
+__global__ void k_selftest_seed_once(uint64_t first, uint64_t count, unsigned long long* __restrict__ out)
+{
+    unsigned long long n_checked = 0, n_pos = 0, n_neg = 0, n_outside = 0;
+    for (uint64_t i = first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < first + count;
+         i += (uint64_t)gridDim.x * blockDim.x) {
+        const float a = __uint_as_float((uint32_t)i);
+        const float x = 1.0f - a;
+        float r;
+        const float sf = Lean::sqrt_pos_rsq(x, r);
+        const float onesf = 1.0f + sf;
+        const float q_two = Lean::div_seeded(a, sf, r), q_once = Lean::div_seeded_once(a, sf, r);
+        const float g_two = __builtin_fmaf(0.5f, q_two, onesf), g_once = __builtin_fmaf(0.5f, q_once, onesf);
+        ++n_checked;
+        if (__float_as_uint(g_two) != __float_as_uint(g_once)) {
+            if (x >= 0x1p-126f && x < __builtin_inff()) {
+                if (a >= 0.0f) {
+                    ++n_pos;
+                    atomicMin(&out[5], (unsigned long long)i);
+                } else {
+                    ++n_neg;
+                    atomicMin(&out[6], (unsigned long long)i);
+                }
+            } else if (!(g_two != g_two && g_once != g_once)) {
+                ++n_outside;
+                atomicMin(&out[7], (unsigned long long)i);
+            }
+        }
+        if (__float_as_uint(q_two) != __float_as_uint(q_once) && !(q_two != q_two && q_once != q_once)) {
+            const unsigned long long k = atomicAdd(&out[4], 1ull);
+            if (k < (unsigned long long)kSeedOnceCap) out[kSeedOnceWords + k] = i;
+        }
+        if ((uint32_t)i == kSeedOnceProbe) {
+            const float exact = (float)(1.0 / __builtin_sqrt((double)x));      // one argument; the test restates it
+            out[8] = (unsigned long long)((long long)__float_as_uint(r) - (long long)__float_as_uint(exact));
+            out[9] = __float_as_uint(r);
+        }
+    }
+    if (n_checked) atomicAdd(&out[0], n_checked);
+    if (n_pos) atomicAdd(&out[1], n_pos);
+    if (n_neg) atomicAdd(&out[2], n_neg);
+    if (n_outside) atomicAdd(&out[3], n_outside);
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -670,8 +728,19 @@ int sdirt_center_from_rays(sdirt_rays rays, int64_t S, int64_t N, float* center,
 int sdirt_selftest_math(int32_t mode, uint64_t first, uint64_t count, int32_t exp_span,
                         uint64_t* out, void* stream)
 {
-    if (!out || mode < 0 || mode > 5 || exp_span < 0 || exp_span > 60)
+    if (!out || mode < 0 || mode > 6 || exp_span < 0 || exp_span > 60)
         return fail(SDIRT_ERR_INVALID_ARGUMENT, "bad argument");
+    if (mode == 6) {
+        // bit patterns of ONE fp32, as mode 4; `out` holds kSeedOnceWords + kSeedOnceCap words
+        if (first > (1ull << 32) || count > (1ull << 32) - first)
+            return fail(SDIRT_ERR_INVALID_ARGUMENT, "mode 6: [first, first+count) outside [0, 2^32)");
+        HIP_TRY(hipMemsetAsync(out, 0, sizeof(uint64_t) * (kSeedOnceWords + kSeedOnceCap), as_stream(stream)));
+        HIP_TRY(hipMemsetAsync(out + 5, 0xff, sizeof(uint64_t) * 3, as_stream(stream)));               // "none yet"
+        if (count == 0) return SDIRT_OK;
+        k_selftest_seed_once<<<256 * 32, 256, 0, as_stream(stream)>>>(first, count, (unsigned long long*)out);
+        LAUNCH_CHECK();
+        return SDIRT_OK;
+    }
     if (mode == 5) {
         // onesf = 1 + j 2^-23, j in [first, first + count) of [0, 2^23]; `out` holds kSeed2Words + kSeed2Cap words
         if (exp_span > 1 || first > (1ull << 23) + 1 || count > (1ull << 23) + 1 - first || (exp_span == 1 && count > (uint64_t)kSeed2Cap))

@@ -10,6 +10,9 @@ and of the sag's n / onesf^2 seeded with the square of the refined 1 / onesf aga
 whose refined reciprocal differs, under every numerator mantissa             (~0.1 s)
   --seed2        that last check alone
   --seed2-full   ... and then ALL 2^23 + 1 divisors of [1, 2] under all 2^23 numerators   (~1 min)
+and of that first quotient, seeded with v_rsq_f32, with and without the two fma that refine the seed, with the
+expression that reads it, on every fp32 a                                    (~0.5 s)
+  --seed-once    that last check alone (kept in profiles/sag_seed3/selftest_seed_once.txt)
 Output is kept in profiles/rNN/selftest_math.txt."""
 import os
 import sys
@@ -70,8 +73,30 @@ def seed2():
           f"{sorted((hex(a), hex(b)) for a, b in found)}   ({time.time() - t0:.0f} s)")
 
 
+def seed_once():
+    """mode 6; returns the decoded counts (_lib.decode_seed_once)."""
+    big = torch.zeros(_lib.SELFTEST_LIST_WORDS + _lib.SELFTEST_LIST_CAP, dtype=torch.int64, device=dev)
+    t0 = time.time()
+    _lib.check(h.sdirt_selftest_math(6, 0, 1 << 32, 0, dptr(big), stream_ptr(dev)))
+    torch.cuda.synchronize()
+    s = _lib.decode_seed_once(big.cpu().numpy())
+    first = ["none" if v is None else f"{v:#010x}" for v in s["first_g"]]
+    print(f"sag seed, refined twice against not refined (a * r, one residual step by r), every fp32 a: checked "
+          f"{s['checked']:#x}; G differs, 1 - a positive normal, a >= 0: {s['g_pos']} (first a {first[0]}); a < 0: "
+          f"{s['g_neg']} (first a {first[1]}); G differs elsewhere, not NaN under both: {s['g_outside']} (first a "
+          f"{first[2]}); bare quotient differs: {s['n_quot']}, the first 16: {[f'{v:#010x}' for v in s['quot'][:16]]}; "
+          f"v_rsq_f32(1 - a) at a = {_lib.SEED_ONCE_PROBE:#010x}: {s['seed_bits']:#010x}, {s['seed_offset']:+d} floats "
+          f"from the correctly rounded one   {time.time() - t0:.1f} s", flush=True)
+    if s["n_quot"] > 16:
+        print(f"  all {len(s['quot'])} listed: {[f'{v:#010x}' for v in s['quot']]}", flush=True)
+    return s
+
+
 if "--seed2" in sys.argv or "--seed2-full" in sys.argv:
     seed2()
+    sys.exit(0)
+if "--seed-once" in sys.argv:
+    seed_once()
     sys.exit(0)
 t = time.time()
 print("sqrt, every fp32 in [2^-100, inf):", run(0, pat(-100), 0x7F800000 - pat(-100)),
@@ -90,6 +115,7 @@ print(f"sag seed (v_rsq of the radicand for v_rcp of the root), every fp32 a: ch
       f"G differs, 1 - a positive normal: {o[1]} (first a {first[0]}); G differs elsewhere, not NaN under both: {o[2]} "
       f"(first a {first[1]}); bare quotient differs: {o[3]} (first a {first[2]})   {time.time() - t:.1f} s")
 seed2()
+seed_once()
 t = time.time()
 total = 0
 step = 1 << 42
