@@ -589,12 +589,39 @@ struct NewtonEnd {
     }
 };
 
+// `inside ? rr : 0.0f`, inside = rr < bound (LT) or rr > bound, for a wave that usually has all of its lanes inside.
+// The compare makes the lane mask in vcc as before; it is held against exec on the scalar unit, and when the two are
+// equal -- every active lane passed -- the select is the identity in every lane that runs (a v_cndmask whose mask bit
+// is set writes its true operand) and is branched over: rr is read where it stands.  Otherwise the v_cndmask runs, in
+// place, on rr's own register (rr has no other reader at either site).  A NaN rr fails the compare, so its wave takes
+// the select.  The s_cmp and the branch are the two wait states a VALU read of vcc needs behind the VALU write of it
+// (the compiler's own s_nop 1 between v_cmp and v_cndmask).
+template <bool LT>
+__device__ __forceinline__ float zero_outside_wave(float rr, float bound)
+{
+    if (LT)
+        asm("v_cmp_lt_f32_e32 vcc, %0, %1\n\t"
+            "s_cmp_eq_u64 vcc, exec\n\t"
+            "s_cbranch_scc1 .Lwave_inside_%=\n\t"
+            "v_cndmask_b32_e32 %0, 0, %0, vcc\n"
+            ".Lwave_inside_%=:" : "+v"(rr) : "v"(bound) : "vcc", "scc");
+    else
+        asm("v_cmp_gt_f32_e32 vcc, %0, %1\n\t"
+            "s_cmp_eq_u64 vcc, exec\n\t"
+            "s_cbranch_scc1 .Lwave_inside_%=\n\t"
+            "v_cndmask_b32_e32 %0, 0, %0, vcc\n"
+            ".Lwave_inside_%=:" : "+v"(rr) : "v"(bound) : "vcc", "scc");
+    return rr;
+}
+
 // surfaces.py:523-586.  `trips` loop iterations (wave-uniform), then the extra
 // differentiable step; the validity test is left to the caller (NewtonEnd).
 // mask_out (wave-uniform, lives in SGPRs) gets bit j set when ANY active lane of
 // the wave had |f(t)| > 50e-6 in trip j -- the per-wave share of the reference's
 // batch-wide `.any()` loop condition (surfaces.py:547).
-template <class M, bool KGT, class P, bool UNITK = false, class S = Surf>
+// WAVE (Lean only: the fused PSF kernels and the staged k_trace; not the recording trace, not k_render_plane):
+// `inside ? rr : 0` goes through zero_outside_wave, in the trips and in the tail.
+template <class M, bool KGT, class P, bool UNITK = false, bool WAVE = false, class S = Surf>
 __device__ __forceinline__ NewtonEnd newton_k(const S& s, const P& pol, const Ray& r, const bool alive, int trips,
                                               uint32_t& mask_out)
 {
@@ -646,11 +673,18 @@ __device__ __forceinline__ NewtonEnd newton_k(const S& s, const P& pol, const Ra
     unsigned long long open_cur = 0ull, open_prev = 0ull, fixed = 0ull;   // lane masks of the last trips
     auto trip = [&](auto periodic_exit) __attribute__((always_inline)) {
         left -= 1;
-        const float nx = r.ox + r.dx * t, ny = r.oy + r.dy * t, nz = r.oz + r.dz * t;
+        // WAVE: nz is formed behind the select, where it fills the wait state a read of the select's register needs
+        constexpr bool kWave = WAVE && M::kFused;
+        const float nx = r.ox + r.dx * t, ny = r.oy + r.dy * t;
+        float nz;
+        if constexpr (!kWave) nz = r.oz + r.dz * t;
         const float rr = nx * nx + ny * ny;
         // g(x*valid, y*valid) (surfaces.py:694-696): (x*1)^2 + (y*1)^2 is rr bit for bit, and
         // (x*0)^2 + (y*0)^2 is 0 for every finite position
-        const float r2 = (KGT ? rr < bound : rr > bound) ? rr : 0.0f;
+        float r2;
+        if constexpr (kWave) r2 = zero_outside_wave<KGT>(rr, bound);
+        else r2 = (KGT ? rr < bound : rr > bound) ? rr : 0.0f;
+        if constexpr (kWave) nz = r.oz + r.dz * t;
         // sqrt_pos on either side of k = -1.  k > -1: r2 < lim_loose, the radicand 1 - a lies in (0, 1].  k <= -1:
         // a <= 0, the radicand is >= 1 -- and where r2 or a overflows (radicand +inf: sqrt gives inf, sqrt_pos NaN)
         // g and dgd are NaN under either form, because Lean::div by an infinite 1 + sf is NaN.  sqrt_pos is verified
@@ -726,12 +760,17 @@ __device__ __forceinline__ NewtonEnd newton_k(const S& s, const P& pol, const Ra
     mask_out = mask;
     const float t1 = t - t0;   // :563
     t = t0 + t1;               // :567
+    constexpr bool kWave = WAVE && M::kFused;
     float nx = r.ox + r.dx * t, ny = r.oy + r.dy * t;
-    const float nz = r.oz + r.dz * t;
+    float nz;
+    if constexpr (!kWave) nz = r.oz + r.dz * t;
     float rr = nx * nx + ny * ny;
     // _valid (surfaces.py:724-733): rr < r2_lim [and rr < lim_loose] = rr < lim_tight
     const float tight = alive ? s.lim_tight() : -1.0f;
-    const float r2 = rr < tight ? rr : 0.0f;
+    float r2;
+    if constexpr (kWave) r2 = zero_outside_wave<true>(rr, tight);
+    else r2 = rr < tight ? rr : 0.0f;
+    if constexpr (kWave) nz = r.oz + r.dz * t;                     // behind the select, as in the trips
     float g, dgd;
     sag(k, deg, r2, g, dgd);
     const float ft = (g + k.d) - nz;
@@ -853,7 +892,7 @@ __device__ __forceinline__ void refract(const S& s, const P& pol, Ray& r, const 
 // Newton copy without the product by 1 + k and the sphere's own validity, nothing decoded.  Otherwise the copy is chosen
 // by the side of k = -1 (a pure conic with 1 + k == 1 takes the k > -1 copy: its product by 1.0f changes no bit), and
 // only a surface without terms can be of kind 1 (a kind-1 surface with k != 0, which the reference has no class for).
-template <class M, bool UNIT_W = false, bool SPHERE = false, class P, class S>
+template <class M, bool UNIT_W = false, bool SPHERE = false, bool WAVE = false, class P, class S>
 __device__ __forceinline__ bool curved_hit(const S& s, const P& pol, Ray& r, int trips, uint32_t& mask)
 {
     const bool alive = r.ra > 0.0f;
@@ -861,10 +900,10 @@ __device__ __forceinline__ bool curved_hit(const S& s, const P& pol, Ray& r, int
     // (surfaces.py:727-743); the branch is wave-uniform and taken once, outside the loop
     NewtonEnd e;
     if constexpr (SPHERE)
-        e = newton_k<M, true, P, true>(s, pol, r, alive, trips, mask);
+        e = newton_k<M, true, P, true, WAVE>(s, pol, r, alive, trips, mask);
     else
-        e = s.k_gt_m1() ? newton_k<M, true>(s, pol, r, alive, trips, mask)
-                        : newton_k<M, false>(s, pol, r, alive, trips, mask);
+        e = s.k_gt_m1() ? newton_k<M, true, P, false, WAVE>(s, pol, r, alive, trips, mask)
+                        : newton_k<M, false, P, false, WAVE>(s, pol, r, alive, trips, mask);
     const float t = e.t;
     const float nx = r.ox + t * r.dx, ny = r.oy + t * r.dy, nz = r.oz + t * r.dz;
     bool v;
@@ -897,7 +936,7 @@ __device__ __forceinline__ bool curved_hit(const S& s, const P& pol, Ray& r, int
 // the test holds exactly when x^2 + y^2 <= X, X the largest fp32 whose rounded root is <= r; the host finds X once
 // (make_dev_surface: plane_r2_max) and puts it in the r2_lim word, which no kernel reads for a plane otherwise.  NaN
 // and +inf fail both forms.  Lean compares against X -- one v_cmp for v_sqrt + 10; Ieee keeps the literal root.
-template <bool FWD, class M, bool UNIT_W = false, class F, class S>
+template <bool FWD, class M, bool UNIT_W = false, bool WAVE = false, class F, class S>
 __device__ __forceinline__ uint32_t surface_reaction(const S& s, const DevSurface* __restrict__ blk,
                                                      int trips, Ray& r, F between)
 {
@@ -905,7 +944,7 @@ __device__ __forceinline__ uint32_t surface_reaction(const S& s, const DevSurfac
     bool v = false;
     // wave-uniform, every one, and ONE scalar test each: a bit of the visit word the host wrote (visit_bits)
     const uint32_t f = s.a[0];
-    if (f & kHitSphere) v = curved_hit<M, UNIT_W, true>(s, NoPoly{}, r, trips, mask);
+    if (f & kHitSphere) v = curved_hit<M, UNIT_W, true, WAVE>(s, NoPoly{}, r, trips, mask);
     Poly pol;
     if (f & kHitOther) {
         if (f & kHitPlane) {
@@ -917,10 +956,10 @@ __device__ __forceinline__ uint32_t surface_reaction(const S& s, const DevSurfac
             r.ox = v ? nx : r.ox; r.oy = v ? ny : r.oy; r.oz = v ? nz : r.oz;
             r.ra = M::keep_if(r.ra, v);
         }
-        if (f & kHitConic) v = curved_hit<M, UNIT_W>(s, NoPoly{}, r, trips, mask);
+        if (f & kHitConic) v = curved_hit<M, UNIT_W, false, WAVE>(s, NoPoly{}, r, trips, mask);
         if (f & kHitTerms) {
             pol = s.poly(blk);                    // the polynomial block is fetched (one more round trip) on aspheres only
-            v = curved_hit<M, UNIT_W>(s, pol, r, trips, mask);
+            v = curved_hit<M, UNIT_W, false, WAVE>(s, pol, r, trips, mask);
         }
     }
     between(mask);

@@ -486,7 +486,7 @@ __device__ __forceinline__ void for_each_traced_ray(const DevSurface* __restrict
         if constexpr (PRIO) { if (left > 0) prio_by_work_left(left); }
         Ray r = make_ray<HotMath>(e.px, e.py, e.pzo, PIN ? *xp : xs[s], PIN ? *yp : ys[s], e.pz);
         if constexpr (PIN) { xp += THREADS; yp += THREADS; }
-        trace_ray<true, HotMath, true, true, true>(lens, 0, K, trips, r, lds_mask);
+        trace_ray<true, HotMath, true, true, true, /*WAVE*/ true>(lens, 0, K, trips, r, lds_mask);
         propagate_to<HotMath>(r, e.zs);
         per_ray(r);
     }
@@ -888,7 +888,8 @@ k_psf_lr(SplatBlock sb /* kernarg offset 0 */, LoopBlock lb /* 64 */, PrimarySet
             Ray r = make_ray<HotMath>(e.px, e.py, e.pzo, kPin ? *xcp : ca.xc[s], kPin ? *ycp : ca.yc[s], e.pz);
             if constexpr (kPin) { xcp += THREADS; ycp += THREADS; }
             // (the masks of a call that asks for none are gathered all the same and dropped below: one flag less to keep)
-            trace_ray<true, HotMath, true, true, true>(ca.lens_c, 0, K, kernarg_at(kTripsCAt + 64 * w), r, lds_mask);
+            trace_ray<true, HotMath, true, true, true, /*WAVE*/ true>(ca.lens_c, 0, K, kernarg_at(kTripsCAt + 64 * w), r,
+                                                                      lds_mask);
             propagate_to<HotMath>(r, e.zs);
             a.add(r);
         }

@@ -213,7 +213,8 @@ k_trace(TripTable trips /* kernarg offset 0 */, const DevSurface* __restrict__ l
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M;
          i += (int64_t)gridDim.x * blockDim.x) {
         Ray r = load_ray(R, i);
-        trace_ray<FWD, MP, PREFETCH>(lens, first, last, kernarg_at(0), r, conv_mask ? lds_mask : nullptr);
+        trace_ray<FWD, MP, PREFETCH, false, false, /*WAVE*/ true>(lens, first, last, kernarg_at(0), r,
+                                                                   conv_mask ? lds_mask : nullptr);
         if (TO_SENSOR) propagate_to<MP>(r, z_sensor);
         store_ray(W, i, r);
     }

@@ -47,7 +47,9 @@ __device__ __forceinline__ void lds_or_first_lane(uint32_t* p, uint32_t m)
 // UNIT_W: every ray's weight is exactly 0 or 1 (the fused kernels: make_ray's 1, then 0/1 flags only) -- one weight
 // update per visit (refract()).
 // MASKS: lds_mask is never null (the fused kernels gather the masks whether the call asks for them or not).
-template <bool FWD, class M = Ieee, bool PREFETCH = true, bool UNIT_W = false, bool MASKS = false>
+// WAVE: the selects that are the identity when all 64 lanes of the wave pass their test are branched over then (Lean
+// only: the fused PSF kernels and k_trace; sdirt_device.hpp: zero_outside_wave).
+template <bool FWD, class M = Ieee, bool PREFETCH = true, bool UNIT_W = false, bool MASKS = false, bool WAVE = false>
 __device__ __forceinline__ void trace_ray(const DevSurface* __restrict__ lens, int first, int last,
                                           const void* trip_words, Ray& r, uint32_t* lds_mask)
 {
@@ -74,7 +76,7 @@ __device__ __forceinline__ void trace_ray(const DevSurface* __restrict__ lens, i
         // the next index is formed in k's own register and nothing is copied for it at the back edge.
         // (MASKS: `lds_mask && m != 0u` with an lds_mask that is never null still came out as two 64-bit masks, an
         // s_or_b64 and a branch on vcc -- six scalar instructions per visit for a compare and a branch)
-        surface_reaction<FWD, M, UNIT_W>(s, lens + k, surf_trips(cur, k), r, [&](uint32_t m) {
+        surface_reaction<FWD, M, UNIT_W, WAVE>(s, lens + k, surf_trips(cur, k), r, [&](uint32_t m) {
             if (MASKS ? m != 0u : lds_mask && m != 0u) lds_or_first_lane(&lds_mask[k], m);
             if (PREFETCH) issue_next();
         });

@@ -34,13 +34,18 @@ the flags word and the trip word that the prefetch delivers set to the given sur
 (known bits are tracked, so the byte of a trip word whose four bytes are equal survives the shift by 8 * (k & 3)).
 A branch whose condition is known is followed; one whose condition is not (a lane mask, the loop's own exit, the
 "any trip open" test) is walked both ways, paths that leave the loop are dropped, and the shortest and the longest
-path are printed.  `exec` counts as non-zero.
+path are printed.  `exec` counts as non-zero.  --all-valid takes the branches of zero_outside_wave (sdirt_device.hpp:
+`s_cbranch_scc1 .Lwave_inside_N` over a v_cndmask) instead of walking both sides: the visit of a wave whose 64 rays
+all pass their validity tests.
 """
 import argparse
 import json
 import re
 from collections import OrderedDict, defaultdict
 
+# zero_outside_wave (sdirt_device.hpp): `s_cbranch_scc1 .Lwave_inside_N` over a v_cndmask when the wave's lanes all pass
+WAVE_LABEL = re.compile(r"^(\.Lwave_inside_\d+):")
+ALL_VALID = False                    # --all-valid: --path takes those branches (a wave whose 64 rays are all valid)
 TRANS = re.compile(r"^v_(rcp|rsq|sqrt|sin|cos|exp|log)_(f32|f16|legacy)")
 F64 = re.compile(r"^v_\w+_f64|^v_cvt_f64|^v_cvt_\w+_f64")
 
@@ -111,6 +116,10 @@ def program(body):
     cur, last_label = ("straight", 0), None
     hdr = re.compile(r"^(\.LBB\d+_\d+):")
     for l in body:
+        m = WAVE_LABEL.match(l)
+        if m:                        # a label inside an inline-asm statement: a branch target, not a block of the compiler's
+            items.append(("label", m.group(1)[2:]))
+            continue
         m = hdr.match(l)
         if m:
             label = last_label = m.group(1)[2:]
@@ -530,7 +539,9 @@ def walk(items, where, inside, loop, start, st_in, flags, tw, show):
             if op.startswith("s_cbranch"):
                 tgt = where[args.strip()[2:]]
                 cond = op.split("_")[2]
-                if cond in ("scc0", "scc1"):
+                if ALL_VALID and args.strip().startswith(".Lwave_inside_"):
+                    take = True
+                elif cond in ("scc0", "scc1"):
                     take = None if st.scc is None else st.scc == (cond == "scc1")
                 elif cond in ("vccz", "vccnz"):
                     v = _get64(st, "vcc")
@@ -579,11 +590,15 @@ def main():
     ap.add_argument("--flags", help="--path: the surface's flags word, if not the class's usual one")
     ap.add_argument("--loop", help="--path: the surface loop's header (BBn_m) if not the kernel's last one")
     ap.add_argument("--show", action="store_true", help="--path: list the scalar instructions of the longest path")
+    ap.add_argument("--all-valid", action="store_true", help="--path: every lane of the wave passes its validity tests: the "
+                    "branches over the selects that are then the identity are taken (without it they fork)")
     ap.add_argument("asm")
     ap.add_argument("pattern")
     ap.add_argument("--json")
     ap.add_argument("--label", default="")
     args = ap.parse_args()
+    global ALL_VALID
+    ALL_VALID = args.all_valid
     body = kernel_body(open(args.asm).read().splitlines(), args.pattern)
     if args.path:
         out = print_path(args, body)
