@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import load_state, make_lens
+from render_rt_f64 import weights_f64
 
 from sdirt_amd import _lib
 from sdirt_amd.basics import dptr, stream_ptr
@@ -51,22 +52,6 @@ def table(on):
 @pytest.fixture(scope="module")
 def lens():
     return make_lens("rf50mm", DEV, load_state("rf50mm"))
-
-
-def weights_f64(x, h, f, w, r):
-    """(sl, sr) of the small-radius model in float64, literally: clamp, arccos, u - sin(2u) / 2."""
-    x = np.asarray(x, np.float64)
-
-    def area(a, b):                                    # of the circle of radius r between abscissae a <= b
-        ua, ub = np.arccos(np.clip(a, -r, r) / r), np.arccos(np.clip(b, -r, r) / r)
-        return r * r * ((ua - np.sin(2 * ua) / 2) - (ub - np.sin(2 * ub) / 2))
-
-    fx, fmh = f * x, f - h
-    xr, xm, xl = w - (fx - w) * h / fmh, -fx * h / fmh, -w - (fx + w) * h / fmh      # through the microlens
-    sr_ml, sl_ml = area(xm, xr), area(xl, xm)
-    xr, xm, xl = (np.clip(v, -0.5, 0.5) for v in (w - h * x, -h * x, -w - h * x))    # straight onto the pixel
-    sr_mg, sl_mg = (xr - xm) - area(xm, xr), (xm - xl) - area(xl, xm)
-    return sl_ml + sl_mg, sr_ml + sr_mg
 
 
 def saturation_points(h, f, w, r):

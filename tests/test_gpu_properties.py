@@ -869,7 +869,16 @@ def test_obliquity_factor_of_callers_rays_and_of_the_lean_bundles(lens, monkeypa
     lens.trace(a)
     lens.trace(b)
     assert torch.equal(a.soa.view(torch.int32), b.soa.view(torch.int32))                 # the same rays either way
-    assert torch.equal(b.soa.view(torch.int32), d.soa.view(torch.int32)) or True         # (d went on to the sensor plane)
+    # ... and the same as a bundle that carried the factor from its construction on and went the way `b` went (`d`
+    # went on to the sensor plane): the same draw under TRACK_OBLIQ = True, through trace() only
+    monkeypatch.setattr(basics, "TRACK_OBLIQ", True)
+    torch.manual_seed(3)
+    c3 = lens.sample_from_points(o=pts, spp=64)
+    assert c3.has_obliq and c3.soa.shape[0] == 7
+    lens.trace(c3)
+    assert torch.equal(c3.soa.view(torch.int32), b.soa.view(torch.int32))                # the seven lean rows
+    assert torch.equal(c3.obliq.view(torch.int32), b.obliq.view(torch.int32))
+    monkeypatch.setattr(basics, "TRACK_OBLIQ", False)
     ob = b.obliq
     live = b.ra > 0
     assert ob.shape == (64, 2) and bool(torch.all(ob[live] > 0.5)) and bool(torch.any(ob[live] < 1.0))

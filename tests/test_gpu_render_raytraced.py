@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import make_lens
+from render_rt_f64 import weights_f64
 
 from sdirt_amd.basics import WAVE_RGB, Ray
 from sdirt_amd.render_rt import images_from_sums, plane_batch, plane_sums_float64, sensor_axes
@@ -112,22 +113,6 @@ def test_fused_rays_equal_the_staged_chain_bit_for_bit(lens, spp, precision):
 
 
 # ------------------------------------------------------------------------------------------------ 2. weights
-def weights_f64(x, h, f, w, r):
-    """(sl, sr) of monte_carlo.py:170-203 (r <= 0.5) in float64, literally: clamp, arccos, u - sin(2u) / 2."""
-    x = np.asarray(x, np.float64)
-
-    def area(a, b):
-        ua, ub = np.arccos(np.clip(a, -r, r) / r), np.arccos(np.clip(b, -r, r) / r)
-        return r * r * ((ua - np.sin(2 * ua) / 2) - (ub - np.sin(2 * ub) / 2))
-
-    fx, fmh = f * x, f - h
-    xr, xm, xl = w - (fx - w) * h / fmh, -fx * h / fmh, -w - (fx + w) * h / fmh
-    sr_ml, sl_ml = area(xm, xr), area(xl, xm)
-    xr, xm, xl = (np.clip(v, -0.5, 0.5) for v in (w - h * x, -h * x, -w - h * x))
-    sr_mg, sl_mg = (xr - xm) - area(xm, xr), (xm - xl) - area(xl, xm)
-    return sl_ml + sl_mg, sr_ml + sr_mg
-
-
 def test_weights_are_the_closed_form_of_the_arriving_direction(lens):
     """A weight is r^2 times four segment areas plus a strip width, and DESIGN.md §4 bounds one area of the polynomial
     (seg_acos) by 3.1e-7 absolute against float64: 4 r^2 3.1e-7 for the weight, the bound taken from there."""
