@@ -269,6 +269,37 @@ int sdirt_render_plane(const sdirt_lens* lens, const int32_t* trips /*host [K]*/
                        float* landing /*dev [5,S,H,W] or NULL: px, py, ra, w_L, w_R of every ray*/,
                        uint32_t* mask /*dev or NULL*/, void* stream);
 
+/* Ray-traced rendering of a STACK of fronto-parallel layers with coverage, composited front to back along every ray:
+ * a scene with more than one depth, so with occlusion (the reference has none: deeplens/optics.py:756-780 names a
+ * ray-traced renderer it never defines, and renders one depth); the definition is DESIGN.md §7p.
+ * Rays, dual-pixel weights, backward trace and trip table are sdirt_render_plane's and do not depend on the layers.
+ * depth and inv_texel are HOST arrays of n_layers doubles, 1 <= n_layers <= SDIRT_MAX_LAYERS, rounded to fp32; the
+ * rounded depths must satisfy 0 > depth[0] > depth[1] > ...: layer 0 is nearest to the lens and is met first.  The ray
+ * as the trace left it is carried to every depth[l] on its own (never from layer to layer), so the landing point
+ * (px_l, py_l) is sdirt_render_plane's at depth[l] in every bit.  There sdirt_render_plane's lookup with inv_texel[l]
+ * reads the coverage a_l from alpha[l] and the colours t_{l,k} from tex + l tex_layer_stride + k tex_h tex_w
+ * (tex_layer_stride in elements; 0: one [T,Ht,Wt] shared by all layers).  Per ray, in float64, one rounding per
+ * operation:  T = 1, c_k = 0;  for l = 0 .. n_layers-1: g = T a_l, c_k = c_k + g t_{l,k}, T = T (1 - a_l);  o = 1 - T
+ * (layers behind T == 0 are not read).  For a ray with ra != 0, with wr = w_side ra:
+ *   num[side, k, i, j] = sum_s wr c_k,   den[side, i, j] = sum_s wr,   cov[side, i, j] = sum_s wr o
+ * (samples in order, no atomics, OVERWRITTEN).  landing, when given, receives ra, w_L, w_R, px_0, py_0, ...,
+ * px_{L-1}, py_{L-1} of every ray -- every layer's point, read or not.  More than four planes run as further
+ * launches.  Never allocates, never synchronises. */
+#define SDIRT_MAX_LAYERS 16
+int sdirt_render_layers(const sdirt_lens* lens, const int32_t* trips /*host [K]*/, uint32_t flags,
+                        const float* x1 /*dev [W]*/, const float* y1 /*dev [H]*/, double z_sensor,
+                        const float* x2 /*dev [S,H,W]*/, const float* y2 /*dev [S,H,W]*/, double z_pupil,
+                        int32_t spp, int32_t height, int32_t width,
+                        const sdirt_dp_params* dp /*host, or NULL: one view, unit weights*/,
+                        int32_t n_layers, const double* depth /*host [L]*/, const double* inv_texel /*host [L]*/,
+                        const float* alpha /*dev [L,Ht,Wt] in [0, 1]*/,
+                        const float* tex /*dev [L,T,Ht,Wt], or [T,Ht,Wt] with stride 0*/, int64_t tex_layer_stride,
+                        int32_t n_tex, int32_t tex_h, int32_t tex_w,
+                        double* num /*dev [V,T,H,W], V = dp ? 2 : 1*/, double* den /*dev [V,H,W]*/,
+                        double* cov /*dev [V,H,W]*/,
+                        float* landing /*dev [3+2L,S,H,W] or NULL*/,
+                        uint32_t* mask /*dev or NULL*/, void* stream);
+
 /* Centroid part of Lensgroup.psf_center, deeplens/optics.py:902-904:
  * center[n] = -(sum_s o*ra / (sum_s ra + 1e-9)).xy (sums in float64);  any_valid (dev int32,
  * zeroed by caller, may be NULL) is set to 1 if any ray has ra == 1.  Point-major bundle. */

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("SDIRT_AMD_LIB") or os.path.join(HERE, "libsdirt_dp.so
 
 ABI_VERSION = 4          # SDIRT_ABI_VERSION of include/sdirt_dp.h this binding was written against
 MAX_SURFACES = 64
+MAX_LAYERS = 16          # SDIRT_MAX_LAYERS
 MAX_AI = 8
 NEWTON_MAXITER = 10
 MAX_KS = 141
@@ -102,6 +103,9 @@ SIGNATURES = {
     "sdirt_propagate_to": (C.c_int, [_D, Rays, _I64, _P]),
     "sdirt_render_plane": (C.c_int, [_P, C.POINTER(_I32), _U32, _P, _P, _D, _P, _P, _D, _I32, _I32, _I32,
                                      C.POINTER(DpParams), _D, _D, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "sdirt_render_layers": (C.c_int, [_P, C.POINTER(_I32), _U32, _P, _P, _D, _P, _P, _D, _I32, _I32, _I32,
+                                      C.POINTER(DpParams), _I32, C.POINTER(_D), C.POINTER(_D), _P, _P, _I64,
+                                      _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "sdirt_center_from_rays": (C.c_int, [Rays, _I64, _I64, _P, _P, _P]),
     "sdirt_forward_integral": (C.c_int, [Rays, _I64, _I64, _D, _I32, _P, C.POINTER(DpParams), _U32,
                                          _P, _P, _P]),

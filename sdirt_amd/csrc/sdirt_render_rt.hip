@@ -3,6 +3,8 @@
 // :630-635 trace2obj, :756-780 render_single_img(method='raytracing')).  One kernel: sample a sensor-side ray, take
 // its dual-pixel weights, trace it backward through every surface, carry it to the plane, read the texture, sum.
 // No PSF, no window, no per-pixel normalisation of a kernel: the yardstick for the PSF renders.
+// A second kernel, k_render_layers, renders a STACK of such planes, each with a coverage map, composited front to back
+// along every ray: a scene with depth discontinuities, which the reference cannot render at all.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sdirt_dp.h"
@@ -135,6 +137,149 @@ int launch_planes(int nt, dim3 grid, hipStream_t st, const TripTable& tt, const 
     return 0;
 }
 
+// ---- a stack of planes with coverage, composited front to back along every ray ----------------------
+
+// Everything of a layered launch behind the trip table.  depth and inv_texel of every layer travel here, in the kernel
+// arguments: the layer index is wave-uniform, so they arrive through scalar loads and need no table on the device.
+struct LayersLaunch {
+    const DevSurface* lens;
+    int K;
+    const float* x1;
+    const float* y1;
+    const float* x2;
+    const float* y2;
+    float z_sensor, z_pupil;
+    int S, H, W, L;
+    float depth[SDIRT_MAX_LAYERS];     // 0 > depth[0] > depth[1] > ...: layer 0 is met first by a backward ray
+    float inv_texel[SDIRT_MAX_LAYERS];
+    const float* alpha;                // [L, Ht, Wt]
+    const float* tex;                  // the first plane of this launch in layer 0
+    int64_t layer_stride;              // elements between the layers of tex; 0: one [NT, Ht, Wt] shared by all
+    int Ht, Wt;
+    int64_t view_stride;
+    double* num;
+    double* den;                       // [V, H, W]
+    double* cov;                       // [V, H, W]
+    float* landing;                    // [3 + 2 L, S, H, W] or null
+    uint32_t* conv_mask;
+};
+
+// The lookup of DESIGN.md §7o at a landing point, one rounding per operation (k_render_plane's statements, which
+// tools/variants/rt_*.py edit by their text, stay where they are): the four taps' offsets in a plane under replicate
+// addressing and their float64 weights.  A layer reads its coverage and each of its colour planes through one of these.
+struct Taps {
+    int i00, i01, i10, i11;
+    double w00, w01, w10, w11;
+    __device__ __forceinline__ Taps(float px, float py, float inv_texel, int Ht, int Wt)
+    {
+        const float half_w = (float)Wt * 0.5f, half_h = (float)Ht * 0.5f;
+        const float u = half_w - px * inv_texel, v = half_h + py * inv_texel;
+        const float ta = u - 0.5f, tb = v - 0.5f;
+        const float c0 = __builtin_floorf(ta), r0 = __builtin_floorf(tb);
+        const float fu = ta - c0, fv = tb - r0;
+        const int cl = clamped_texel(c0, 0, Wt), cr = clamped_texel(c0, 1, Wt);
+        const int rt = clamped_texel(r0, 0, Ht), rb = clamped_texel(r0, 1, Ht);
+        i00 = rt * Wt + cl; i01 = rt * Wt + cr; i10 = rb * Wt + cl; i11 = rb * Wt + cr;
+        const double du = fu, dv = fv;
+        w00 = (1.0 - dv) * (1.0 - du); w01 = (1.0 - dv) * du; w10 = dv * (1.0 - du); w11 = dv * du;
+    }
+    __device__ __forceinline__ double read(const float* __restrict__ t) const
+    {
+        const double t00 = t[i00], t01 = t[i01], t10 = t[i10], t11 = t[i11];
+        return w00 * t00 + w01 * t01 + w10 * t10 + w11 * t11;
+    }
+};
+
+// k_render_plane's geometry and per-ray program up to the end of the trace.  Then every layer's landing point is
+// propagate_to<Ieee> on a COPY of the ray as the trace left it (never chained from layer to layer: each equals
+// k_render_plane's landing at that depth in every bit), and the ray's colour c_k and transmittance T are composited in
+// float64 in the order of DESIGN.md §7p.  A lane whose T has reached 0 skips the lookups of the layers behind (with
+// finite textures they add exact zeros); their landing points are still written when a record is asked for.
+template <class M, int DP, int NT>
+__global__ void __launch_bounds__(kBlock)
+k_render_layers(TripTable trips /* kernarg offset 0 */, LayersLaunch a, DevDpParams dp)
+{
+    __shared__ uint32_t lds_mask[SDIRT_MAX_SURFACES];
+    if (threadIdx.x < SDIRT_MAX_SURFACES) lds_mask[threadIdx.x] = 0;
+    __syncthreads();
+    constexpr int V = DP == kDpNone ? 1 : 2;
+    const int64_t HW = (int64_t)a.H * a.W;
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p < HW) {
+        const int i = (int)(p / a.W), j = (int)(p - (int64_t)i * a.W);
+        const float ox = a.x1[j], oy = a.y1[i];
+        const int64_t plane = (int64_t)a.Ht * a.Wt;
+        const int64_t rows = (int64_t)a.S * HW;
+        const auto div_fmh = UDiv<M>::make(dp.fmh);
+        double num[V][NT] = {}, den[V] = {}, cov[V] = {};
+        for (int s = 0; s < a.S; ++s) {
+            const int64_t q = (int64_t)s * HW + p;
+            Ray r = make_ray<M>(ox, oy, a.z_sensor, a.x2[q], a.y2[q], a.z_pupil);
+            float wv[2] = {1.0f, 1.0f};                        // the views' weights (w_L, w_R) = (sr, sl): see k_render_plane
+            if (DP != kDpNone) {
+                const float x_tan = r.dx / (-r.dz);
+                if (DP == kDpBig) dp_weights_big(dp, x_tan, wv[1], wv[0]);
+                else dp_weights_small<M>(dp, div_fmh, x_tan, wv[1], wv[0]);
+            }
+            trace_ray<false, M, true, /*UNIT_W*/ true, /*MASKS*/ true>(a.lens, 0, a.K, kernarg_at(0), r, lds_mask);
+            if (a.landing) {
+                a.landing[q] = r.ra; a.landing[rows + q] = wv[0]; a.landing[2 * rows + q] = DP != kDpNone ? wv[1] : 1.0f;
+            }
+            const bool live = r.ra != 0.0f;
+            double T = 1.0, c[NT] = {};
+            for (int l = 0; l < a.L; ++l) {
+                const bool reads = live && T != 0.0;
+                if (!reads && !a.landing) break;
+                Ray at = r;
+                propagate_to<Ieee>(at, a.depth[l]);
+                if (a.landing) {
+                    a.landing[(3 + 2 * l) * rows + q] = at.ox; a.landing[(4 + 2 * l) * rows + q] = at.oy;
+                }
+                if (!reads) continue;
+                const Taps taps(at.ox, at.oy, a.inv_texel[l], a.Ht, a.Wt);
+                const double al = taps.read(a.alpha + l * plane);
+                const double g = T * al;
+                const float* __restrict__ tl = a.tex + l * a.layer_stride;
+#pragma unroll
+                for (int k = 0; k < NT; ++k) c[k] = c[k] + g * taps.read(tl + k * plane);
+                T = T * (1.0 - al);
+            }
+            if (!live) continue;
+            const double o = 1.0 - T;
+#pragma unroll
+            for (int side = 0; side < V; ++side) {
+                const double wr = (double)wv[side] * (double)r.ra;
+                den[side] += wr;
+                cov[side] += wr * o;
+#pragma unroll
+                for (int k = 0; k < NT; ++k) num[side][k] += wr * c[k];
+            }
+        }
+#pragma unroll
+        for (int side = 0; side < V; ++side) {
+            a.den[side * HW + p] = den[side];
+            a.cov[side * HW + p] = cov[side];
+#pragma unroll
+            for (int k = 0; k < NT; ++k) a.num[side * a.view_stride + k * HW + p] = num[side][k];
+        }
+    }
+    __syncthreads();
+    if (a.conv_mask && (int)threadIdx.x < a.K && lds_mask[threadIdx.x])
+        atomicOr(&a.conv_mask[threadIdx.x], lds_mask[threadIdx.x]);
+}
+
+template <class M, int DP>
+int launch_layers(int nt, dim3 grid, hipStream_t st, const TripTable& tt, const LayersLaunch& a, const DevDpParams& dp)
+{
+    switch (nt) {
+    case 1: k_render_layers<M, DP, 1><<<grid, kBlock, 0, st>>>(tt, a, dp); break;
+    case 2: k_render_layers<M, DP, 2><<<grid, kBlock, 0, st>>>(tt, a, dp); break;
+    case 3: k_render_layers<M, DP, 3><<<grid, kBlock, 0, st>>>(tt, a, dp); break;
+    default: k_render_layers<M, DP, kMaxPlanes><<<grid, kBlock, 0, st>>>(tt, a, dp); break;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int sdirt_render_plane(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, const float* x1,
@@ -174,6 +319,64 @@ extern "C" int sdirt_render_plane(const sdirt_lens* lens, const int32_t* trips, 
             if (!dp) return launch_planes<Mm, kDpNone>(nt, grid, st, tt, a, dpp);
             return dpp.big ? launch_planes<Mm, kDpBig>(nt, grid, st, tt, a, dpp)
                            : launch_planes<Mm, kDpSmall>(nt, grid, st, tt, a, dpp);
+        });
+        LAUNCH_CHECK();
+    }
+    return SDIRT_OK;
+}
+
+extern "C" int sdirt_render_layers(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, const float* x1,
+                                   const float* y1, double z_sensor, const float* x2, const float* y2, double z_pupil,
+                                   int32_t spp, int32_t height, int32_t width, const sdirt_dp_params* dp,
+                                   int32_t n_layers, const double* depth, const double* inv_texel, const float* alpha,
+                                   const float* tex, int64_t tex_layer_stride, int32_t n_tex, int32_t tex_h,
+                                   int32_t tex_w, double* num, double* den, double* cov, float* landing, uint32_t* mask,
+                                   void* stream)
+{
+    if (!lens) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null lens");
+    if (any_null(x1, y1, x2, y2, depth, inv_texel, alpha, tex, num, den, cov))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!all_positive(spp, height, width, n_tex, tex_h, tex_w))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "spp, the sensor's and the texture's extents must be at least 1");
+    if (n_layers < 1 || n_layers > SDIRT_MAX_LAYERS)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_layers must be in 1 .. SDIRT_MAX_LAYERS");
+    if ((int64_t)tex_h * tex_w > INT32_MAX) return fail(SDIRT_ERR_INVALID_ARGUMENT, "texture plane above 2^31 texels");
+    if (tex_layer_stride < 0) return fail(SDIRT_ERR_INVALID_ARGUMENT, "negative tex_layer_stride");
+    const int64_t HW = (int64_t)height * width;
+    if (HW > (int64_t)INT32_MAX * kBlock) return fail(SDIRT_ERR_INVALID_ARGUMENT, "sensor too large");
+    LayersLaunch a;
+    for (int l = 0; l < SDIRT_MAX_LAYERS; ++l) {
+        const bool used = l < n_layers;
+        // the fp32 values the kernel carries the rays to must themselves be negative and strictly descending
+        a.depth[l] = used ? (float)depth[l] : 0.0f;
+        a.inv_texel[l] = used ? (float)inv_texel[l] : 0.0f;
+        if (used && !(a.depth[l] < (l ? a.depth[l - 1] : 0.0f)))
+            return fail(SDIRT_ERR_INVALID_ARGUMENT, "layer depths must be negative and strictly descending (nearest first)");
+    }
+    TripTable tt;
+    if (int rc = make_trips(lens, trips, tt)) return rc;
+    const DevDpParams dpp = make_dp(dp);
+    a.lens = lens->dev; a.K = lens->n_surfaces;
+    a.x1 = x1; a.y1 = y1; a.x2 = x2; a.y2 = y2;
+    a.z_sensor = (float)z_sensor; a.z_pupil = (float)z_pupil;
+    a.S = spp; a.H = height; a.W = width; a.L = n_layers;
+    a.alpha = alpha; a.layer_stride = tex_layer_stride;
+    a.Ht = tex_h; a.Wt = tex_w;
+    a.view_stride = (int64_t)n_tex * HW;
+    a.den = den; a.cov = cov; a.landing = landing; a.conv_mask = mask;
+    const dim3 grid((unsigned)((HW + kBlock - 1) / kBlock));
+    hipStream_t st = as_stream(stream);
+    // more than kMaxPlanes colour planes: further launches over the same rays (den, cov, landing and the masks come out
+    // the same from each)
+    for (int t0 = 0; t0 < n_tex; t0 += kMaxPlanes) {
+        const int nt = n_tex - t0 < kMaxPlanes ? n_tex - t0 : kMaxPlanes;
+        a.tex = tex + (int64_t)t0 * tex_h * tex_w;
+        a.num = num + (int64_t)t0 * HW;
+        with_math(routed_flags(flags, lens), [&](auto m) {
+            using Mm = decltype(m);
+            if (!dp) return launch_layers<Mm, kDpNone>(nt, grid, st, tt, a, dpp);
+            return dpp.big ? launch_layers<Mm, kDpBig>(nt, grid, st, tt, a, dpp)
+                           : launch_layers<Mm, kDpSmall>(nt, grid, st, tt, a, dpp);
         });
         LAUNCH_CHECK();
     }

@@ -1994,7 +1994,7 @@ def _bind_render_rt(name):
     return method
 
 
-for _name in ("sample_sensor", "trace2obj", "render_plane", "render_single_img"):
+for _name in ("sample_sensor", "trace2obj", "render_plane", "render_layers", "render_rgbd", "render_single_img"):
     setattr(Lensgroup, _name, _bind_render_rt(_name))
 
 

@@ -60,6 +60,28 @@ def trace2obj(lens, ray, depth=DEPTH):
 
 
 # ------------------------------------------------------------------------------------ float64 restatement
+def _bilinear_float64(planes, px, py, inv_texel, live):
+    """§7o's lookup of planes [N, Ht, Wt] fp32 at (px, py) [S, H, W] fp32 with inv_texel texels per mm (rounded to fp32
+    here) -> [N, S, H, W] float64.  Dead rays land anywhere (NaN included) and contribute nothing: they are given a
+    texel to read and come out as 0.  The one copy of the lookup: plane_sums_float64 and layer_sums_float64 read
+    through it."""
+    N, Ht, Wt = planes.shape
+    inv = torch.tensor(float(inv_texel), dtype=torch.float32, device=px.device)
+    u = Wt / 2 - px * inv                                    # fp32, one rounding per operation
+    v = Ht / 2 + py * inv
+    a, b = u - 0.5, v - 0.5
+    c0, r0 = torch.floor(a), torch.floor(b)
+    fu, fv = (a - c0).double(), (b - r0).double()
+    c0 = torch.where(live, c0, torch.zeros_like(c0)).clamp(-2, Wt).nan_to_num(nan=0.0).long()
+    r0 = torch.where(live, r0, torch.zeros_like(r0)).clamp(-2, Ht).nan_to_num(nan=0.0).long()
+    cl, cr = c0.clamp(0, Wt - 1), (c0 + 1).clamp(0, Wt - 1)
+    rt, rb = r0.clamp(0, Ht - 1), (r0 + 1).clamp(0, Ht - 1)
+    t64 = planes.double()
+    t = ((1 - fv) * (1 - fu)) * t64[:, rt, cl] + ((1 - fv) * fu) * t64[:, rt, cr] \
+        + (fv * (1 - fu)) * t64[:, rb, cl] + (fv * fu) * t64[:, rb, cr]
+    return torch.where(live, t, torch.zeros((), dtype=torch.float64, device=px.device))
+
+
 def plane_sums_float64(landing, tex, inv_texel, views=None, return_abs=False):
     """The lookup and the sums of DESIGN.md §7o from the rays' landing record, in plain torch (any device).
 
@@ -74,23 +96,9 @@ def plane_sums_float64(landing, tex, inv_texel, views=None, return_abs=False):
     V = 2 if views is None else int(views)
     T, Ht, Wt = tex.shape
     px, py, ra = landing[0], landing[1], landing[2]
-    inv = torch.tensor(float(inv_texel), dtype=torch.float32, device=landing.device)
-    u = Wt / 2 - px * inv                                    # fp32, one rounding per operation
-    v = Ht / 2 + py * inv
-    a, b = u - 0.5, v - 0.5
-    c0, r0 = torch.floor(a), torch.floor(b)
-    fu, fv = (a - c0).double(), (b - r0).double()
     live = ra != 0
-    # dead rays land anywhere (NaN included) and contribute nothing: give them a texel to read, then leave them out
-    c0 = torch.where(live, c0, torch.zeros_like(c0)).clamp(-2, Wt).nan_to_num(nan=0.0).long()
-    r0 = torch.where(live, r0, torch.zeros_like(r0)).clamp(-2, Ht).nan_to_num(nan=0.0).long()
-    cl, cr = c0.clamp(0, Wt - 1), (c0 + 1).clamp(0, Wt - 1)
-    rt, rb = r0.clamp(0, Ht - 1), (r0 + 1).clamp(0, Ht - 1)
-    t64 = tex.double()
-    t = ((1 - fv) * (1 - fu)) * t64[:, rt, cl] + ((1 - fv) * fu) * t64[:, rt, cr] \
-        + (fv * (1 - fu)) * t64[:, rb, cl] + (fv * fu) * t64[:, rb, cr]                     # [T, S, H, W]
+    t = _bilinear_float64(tex, px, py, inv_texel, live)                                     # [T, S, H, W]
     zero = torch.zeros((), dtype=torch.float64, device=landing.device)
-    t = torch.where(live, t, zero)
     w = torch.where(live, landing[3:3 + V].double() * ra.double(), zero)                    # [V, S, H, W]
     terms = w[:, None] * t[None]                                                            # [V, T, S, H, W]
     num, den = terms.sum(2), w.sum(1)
@@ -226,6 +234,253 @@ def render_plane(lens, img, depth, spp=64, dp=None, wvln=DEFAULT_WAVE, scale=Non
     if return_sums:
         res = res + (num, den)
     return res if len(res) > 1 else res[0]
+
+
+# ------------------------------------------------------------------------------------ a stack of layers
+def layer_sums_float64(landing, alpha, tex, inv_texels, views=None, return_abs=False):
+    """The lookups, the compositing and the sums of DESIGN.md §7p from the rays' landing record, in plain torch.
+
+    landing [3 + 2 L, S, H, W] fp32: ra, w_L, w_R, then (px_l, py_l) of every layer; alpha [L, Ht, Wt] fp32; tex
+    [L, T, Ht, Wt] fp32, or [T, Ht, Wt] shared by all layers; inv_texels: L numbers, texels per mm on every layer
+    (rounded to fp32 here).  views as in plane_sums_float64 (rows 1 and 2).
+    -> num [V, T, H, W], den [V, H, W], cov [V, H, W] float64; with return_abs also the sums of |wr c_k| [V, T, H, W]
+    and of |wr o| [V, H, W]."""
+    landing = torch.as_tensor(landing, dtype=torch.float32)
+    dev = landing.device
+    alpha = torch.as_tensor(alpha, dtype=torch.float32, device=dev)
+    tex = torch.as_tensor(tex, dtype=torch.float32, device=dev)
+    V = 2 if views is None else int(views)
+    L = int(alpha.shape[0])
+    if landing.shape[0] != 3 + 2 * L or len(inv_texels) != L:
+        raise ValueError(f"{L} layers need a landing record of {3 + 2 * L} rows and {L} inv_texels")
+    if tex.dim() == 3:
+        tex = tex.unsqueeze(0).expand(L, *tex.shape)
+    ra = landing[0]
+    live = ra != 0
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    T = torch.ones(ra.shape, dtype=torch.float64, device=dev)
+    c = torch.zeros((tex.shape[1],) + tuple(ra.shape), dtype=torch.float64, device=dev)
+    for l in range(L):
+        px, py = landing[3 + 2 * l], landing[4 + 2 * l]
+        a = _bilinear_float64(alpha[l:l + 1], px, py, inv_texels[l], live)[0]
+        t = _bilinear_float64(tex[l], px, py, inv_texels[l], live)
+        g = T * a
+        c = c + g * t
+        T = T * (1 - a)
+    o = 1 - T
+    w = torch.where(live, landing[1:1 + V].double() * ra.double(), zero)                    # [V, S, H, W]
+    terms = torch.where(live, w[:, None] * c[None], zero)                                   # [V, T, S, H, W]
+    oterms = torch.where(live, w * o, zero)
+    num, den, cov = terms.sum(2), w.sum(1), oterms.sum(1)
+    return (num, den, cov, terms.abs().sum(2), oterms.abs().sum(1)) if return_abs else (num, den, cov)
+
+
+def _check_layers(alpha, tex, depths, inv_texels=None, scan=True):
+    """The scene of §7p: -> (L, T, Ht, Wt, shared).  alpha [L, Ht, Wt] in [0, 1], tex [L, T, Ht, Wt] or [T, Ht, Wt].
+    scan=False leaves out the one check that reads alpha (and so waits for the device): its range."""
+    if not torch.is_tensor(alpha) or alpha.dim() != 3:
+        raise ValueError("alpha must be a [L, Ht, Wt] tensor")
+    if not torch.is_tensor(tex) or tex.dim() not in (3, 4):
+        raise ValueError("the layers' image must be a [L, C, Ht, Wt] tensor, or [C, Ht, Wt] shared by all layers")
+    if alpha.dtype != torch.float32 or tex.dtype != torch.float32:
+        raise ValueError("alpha and the layers' image must be float32")
+    L, Ht, Wt = (int(v) for v in alpha.shape)
+    if not 1 <= L <= _lib.MAX_LAYERS:
+        raise ValueError(f"{L} layers: between 1 and {_lib.MAX_LAYERS} are supported")
+    shared = tex.dim() == 3
+    if tuple(tex.shape[-2:]) != (Ht, Wt) or (not shared and int(tex.shape[0]) != L):
+        raise ValueError(f"alpha is {tuple(alpha.shape)}, the layers' image {tuple(tex.shape)}: layers or extents differ")
+    depths = [float(d) for d in depths]
+    if len(depths) != L or (inv_texels is not None and len(inv_texels) != L):
+        raise ValueError(f"{L} layers need {L} depths and {L} scales")
+    z = np.asarray(depths, np.float32)
+    if not (z[0] < 0 and bool((z[1:] < z[:-1]).all())):
+        raise ValueError("layer depths must be negative and strictly descending (the nearest layer first)")
+    if scan and alpha.device.type != "meta" and alpha.numel() and not bool(((alpha >= 0) & (alpha <= 1)).all()):
+        raise ValueError("alpha must lie in [0, 1]")
+    return L, int(tex.shape[-3]), Ht, Wt, shared
+
+
+def layer_batch(lens, alpha, tex, depths, inv_texels, x2, y2, dp=None, wvln=DEFAULT_WAVE, pixel_center=True,
+                landing=False, check_alpha=True):
+    """ONE launch of the layered kernel (one batch of the Newton trip rule): plane_batch with a stack of layers.
+    alpha [L, Ht, Wt], tex [L, T, Ht, Wt] (or [T, Ht, Wt] shared by all layers: layer stride 0), depths and inv_texels
+    L numbers each, the nearest layer first.
+    -> dict: num [V, T, H, W], den, cov [V, H, W] float64, trips, and landing ([3 + 2 L, S, H, W]: ra, w_L, w_R, px_0,
+    py_0, ...) or None.  check_alpha=False: the caller has verified that alpha lies in [0, 1] (render_layers does, once
+    per call and not once per launch: the check reads all of alpha and waits for the device)."""
+    L, T, Ht, Wt, shared = _check_layers(alpha, tex, depths, inv_texels, scan=check_alpha)
+    lens._require_gpu()
+    H, W = (int(v) for v in lens.sensor_res)
+    S = int(x2.shape[0])
+    K = len(lens.surfaces)
+    V = 1 if dp is None else 2
+    dev = lens.device
+    x1, y1 = sensor_axes(lens, pixel_center)
+    if tuple(x2.shape) != (S, H, W) or tuple(y2.shape) != (S, H, W):
+        raise ValueError(f"pupil points must be [spp, {H}, {W}], got {tuple(x2.shape)} and {tuple(y2.shape)}")
+    if tex.device != dev or alpha.device != dev:
+        raise ValueError("alpha and tex must be on the lens's device")
+    x2 = x2.to(dev, torch.float32).contiguous()
+    y2 = y2.to(dev, torch.float32).contiguous()
+    alpha, tex = alpha.contiguous(), tex.contiguous()
+    num = torch.empty((V, T, H, W), dtype=torch.float64, device=dev)
+    den = torch.empty((V, H, W), dtype=torch.float64, device=dev)
+    cov = torch.empty((V, H, W), dtype=torch.float64, device=dev)
+    land = torch.empty((3 + 2 * L, S, H, W), dtype=torch.float32, device=dev) if landing else None
+    dpp = None if dp is None else C.byref(_lib.DpParams(*(float(v) for v in dp)))
+    z = (C.c_double * L)(*(float(d) for d in depths))
+    inv = (C.c_double * L)(*(float(v) for v in inv_texels))
+    pupilz, _ = lens.exit_pupil()
+    wv = float(wvln if wvln < 10 else wvln * 1e-3)
+    handle = lens.dev_lens(wv)
+    flags = lens._math_flags()
+
+    def enqueue(trips, mask_ptr):
+        with lens._timed("render_layers"):
+            _lib.check(_lib.lib().sdirt_render_layers(
+                handle, trips, flags, dptr(x1), dptr(y1), float(lens.d_sensor), dptr(x2), dptr(y2), float(pupilz),
+                S, H, W, dpp, L, z, inv, dptr(alpha), dptr(tex), 0 if shared else T * Ht * Wt, T, Ht, Wt, dptr(num),
+                dptr(den), dptr(cov), dptr(land), mask_ptr, stream_ptr(dev)))
+
+    key = ("render_layers", round(wv, 6), lens.precision)
+    trips = lens._run_with_trips(key, range(K - 1, -1, -1), enqueue)
+    return {"num": num, "den": den, "cov": cov, "trips": np.asarray(trips, np.int32), "landing": land}
+
+
+@torch.no_grad()
+def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, scales=None, pixel_center=True,
+                  photometric=False, pupil_points=None, return_sums=False):
+    """The image(s) the lens forms of a stack of fronto-parallel layers, ray traced with occlusion.
+
+    img [L, C, Ht, Wt] fp32, or [C, Ht, Wt] shared by all layers; alpha [L, Ht, Wt] fp32 in [0, 1]: layer l covers the
+    ray by alpha[l] where the ray meets z = depths[l]; depths (mm): 0 > depths[0] > depths[1] > ..., the nearest first.
+    Every layer is spread over scales[l] x the sensor's extent (default calc_scale_ray(depths[l]): the layers register
+    on the sensor under perspective).  Along a ray the layers are composited front to back; what passes every layer is
+    black.  dp, wvln (a number or C wavelengths), spp > 64, pixel_center, photometric and pupil_points as in
+    render_plane.  -> (L, R) with dp, else one image, each [C, H, W] fp32.
+    return_sums: num [V, C, H, W], den and cov [V, H, W] ([V, C, H, W] with C wavelengths) are appended; cov / den is
+    the share of a pixel's light that met some layer.  No gradients."""
+    if not torch.is_tensor(img) or img.dim() not in (3, 4):
+        raise ValueError("img must be a [L, C, Ht, Wt] tensor, or [C, Ht, Wt] shared by all layers")
+    if scales is not None and len(scales) != len(depths):
+        raise ValueError(f"{len(scales)} scales for {len(depths)} depths")
+    L, Cn, Ht, Wt, shared = _check_layers(alpha, img, depths)
+    chroma = _check_render_arguments(lens, img.unsqueeze(0) if shared else img, spp, wvln, pupil_points)
+    if alpha.device != lens.device:
+        raise ValueError(f"alpha is on {alpha.device}, the lens on {lens.device}")
+    lens._require_gpu()
+    spp = int(spp)
+    H, W = (int(v) for v in lens.sensor_res)
+    V = 1 if dp is None else 2
+    if scales is None:
+        scales = scale_per_layer(lens, depths)
+    inv_texels = [1.0 / (float(s) * lens.pixel_size * W / Wt) for s in scales]
+    pupilz, pupilr = lens.exit_pupil()
+    if chroma:
+        groups = [(wvln[c], img[c:c + 1] if shared else img[:, c:c + 1].contiguous()) for c in range(Cn)]
+    else:
+        groups = [(wvln, img)]
+    nums = [torch.zeros((V, g[1].shape[-3], H, W), dtype=torch.float64, device=lens.device) for g in groups]
+    dens = [torch.zeros((V, H, W), dtype=torch.float64, device=lens.device) for _ in groups]
+    covs = [torch.zeros((V, H, W), dtype=torch.float64, device=lens.device) for _ in groups]
+    for s0 in range(0, spp, CHUNK_SPP):
+        n = min(CHUNK_SPP, spp - s0)
+        for g, (wv, tex) in enumerate(groups):
+            if pupil_points is None:
+                o2 = lens.sample_pupil((H, W), n, pupilr=pupilr, pupilz=pupilz)
+                x2, y2 = o2[..., 0], o2[..., 1]
+            else:
+                x2, y2 = (p[g, s0:s0 + n] if chroma else p[s0:s0 + n] for p in pupil_points)
+            part = layer_batch(lens, alpha, tex, depths, inv_texels, x2, y2, dp, wv, pixel_center, check_alpha=False)
+            nums[g] += part["num"]
+            dens[g] += part["den"]
+            covs[g] += part["cov"]
+    if chroma:
+        num, den, cov = torch.cat(nums, 1), torch.stack(dens, 1), torch.stack(covs, 1)     # [V, C, H, W] each
+        den_b = den
+    else:
+        num, den, cov = nums[0], dens[0], covs[0]
+        den_b = den.unsqueeze(1)
+    out = images_from_sums(num, den_b, spp, photometric).float()
+    res = (out[0], out[1]) if dp is not None else (out[0],)
+    if return_sums:
+        res = res + (num, den, cov)
+    return res if len(res) > 1 else res[0]
+
+
+def scale_per_layer(lens, depths):
+    """calc_scale_ray of every layer depth (each traces randomly drawn rays of its own)."""
+    return [lens.calc_scale_ray(float(d)) for d in depths]
+
+
+def layers_from_rgbd(depth, layer_depths, extend=True):
+    """Cut a depth map into the coverage maps of a layer stack: depth [H, W] (or [1, H, W]; mm, negative),
+    layer_depths: L depths, the nearest first -> alpha [L, H, W] fp32 of zeros and ones on depth's device.
+    Every pixel belongs to the layer nearest to it in 1 / depth (of two equally near ones, to the nearer to the lens).
+    extend: the pixel also covers every layer BEHIND its own, so the last layer is opaque, no ray falls through a
+    disocclusion (it meets what the occluder's own surroundings show there) and cov == den; without it alpha is
+    one-hot over the layers."""
+    depth = torch.as_tensor(depth)
+    if depth.dim() == 3 and depth.shape[0] == 1:
+        depth = depth[0]
+    if depth.dim() != 2:
+        raise ValueError("depth must be [H, W] or [1, H, W]")
+    z = torch.as_tensor([float(d) for d in layer_depths], dtype=torch.float64, device=depth.device)
+    if z.numel() < 1 or not (bool((z < 0).all()) and bool((z[1:] < z[:-1]).all())):
+        raise ValueError("layer depths must be negative and strictly descending (the nearest layer first)")
+    if depth.device.type != "meta" and not bool((depth < 0).all()):
+        raise ValueError("depth must be negative (mm in front of the lens)")
+    dist = (1.0 / depth.double()[None] - 1.0 / z[:, None, None]).abs()                     # [L, H, W]
+    own = dist.argmin(0)                                       # the first of equal minima: the nearer layer
+    idx = torch.arange(z.numel(), device=depth.device)[:, None, None]
+    return ((idx >= own[None]) if extend else (idx == own[None])).float()
+
+
+def uniform_layer_depths(depth, n_layers):
+    """Up to n_layers depths uniform in 1 / depth from the nearest to the farthest value of `depth` (mm, negative), the
+    nearest first.  The kernel carries its rays to depths rounded to fp32, so layers whose depths are equal after that
+    rounding are one layer: a map of one depth, or of a range below fp32's resolution, gives fewer layers than asked for."""
+    near, far = float(depth.max()), float(depth.min())
+    if int(n_layers) == 1 and near != far:
+        return [2.0 / (1.0 / near + 1.0 / far)]
+    inv = np.linspace(1.0 / near, 1.0 / far, int(n_layers))
+    zs = [near] + [float(1.0 / v) for v in inv[1:-1]] + [far]
+    out = []
+    for z in zs:
+        if not out or np.float32(z) < np.float32(out[-1]):
+            out.append(z)
+    return out
+
+
+@torch.no_grad()
+def render_rgbd(lens, img, depth, layer_depths=None, n_layers=8, spp=64, dp=None, wvln=DEFAULT_WAVE, scales=None,
+                pixel_center=True, photometric=False, pupil_points=None, extend=True):
+    """The ray-traced dual-pixel pair of an RGB-D frame -- the input PSFNet.render takes -- with occlusion: img
+    [B, C, H, W] fp32, depth [B, 1, H, W] (mm, negative).  Every frame is cut into layers by layers_from_rgbd (at
+    layer_depths, or at n_layers depths uniform in 1 / depth between the frame's nearest and farthest) that all show
+    the frame's image, and rendered by render_layers: one call per batch element, the other arguments as there (default
+    scales: calc_scale_ray once per distinct stack of depths, so frames that share their layers register alike).
+    -> (L, R) with dp, else one image, each [B, C, H, W] fp32.  No gradients."""
+    if not torch.is_tensor(img) or img.dim() != 4:
+        raise ValueError("img must be a [B, C, H, W] tensor")
+    if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1 or depth.shape[0] != img.shape[0] \
+            or depth.shape[-2:] != img.shape[-2:]:
+        raise ValueError(f"depth must be [B, 1, H, W] for an image of {tuple(img.shape)}")
+    if int(n_layers) < 1 or int(n_layers) > _lib.MAX_LAYERS:
+        raise ValueError(f"n_layers must be between 1 and {_lib.MAX_LAYERS}")
+    views, scales_of = [], {}
+    for b in range(img.shape[0]):
+        zs = uniform_layer_depths(depth[b, 0], n_layers) if layer_depths is None else [float(d) for d in layer_depths]
+        alpha = layers_from_rgbd(depth[b, 0], zs, extend).to(img.device)
+        if scales is None and tuple(zs) not in scales_of:      # calc_scale_ray traces rays of its own: once per stack
+            scales_of[tuple(zs)] = scale_per_layer(lens, zs)
+        out = render_layers(lens, img[b], alpha, zs, spp=spp, dp=dp, wvln=wvln,
+                            scales=scales_of[tuple(zs)] if scales is None else scales,
+                            pixel_center=pixel_center, photometric=photometric, pupil_points=pupil_points)
+        views.append(out if dp is not None else (out,))
+    res = tuple(torch.stack(v) for v in zip(*views))
+    return res if dp is not None else res[0]
 
 
 def render_single_img(lens, img_org, depth=DEPTH, spp=64, unwarp=False, save_name=None, return_tensor=False, noise=0,
