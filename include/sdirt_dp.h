@@ -300,6 +300,39 @@ int sdirt_render_layers(const sdirt_lens* lens, const int32_t* trips /*host [K]*
                         float* landing /*dev [3+2L,S,H,W] or NULL*/,
                         uint32_t* mask /*dev or NULL*/, void* stream);
 
+/* The backward pass of sdirt_render_layers into the textures and the coverage maps: a scatter.
+ * galpha and gtex are ADDED TO -- sdirt_render_layers OVERWRITES its outputs, this entry does NOT: the caller zeroes
+ * the two buffers once and then runs every chunk of samples, every wavelength group and (inside one call) every launch
+ * of four planes into them.  The adds are float64 atomics, whose sum depends on the order they arrive in: two runs of
+ * this entry need NOT agree in every bit (they agree within §7q's summation bound); everything else about it is
+ * deterministic.
+ * Every argument up to tex_w is sdirt_render_layers'; trips is the table the forward ENDED with (there is no mask: the
+ * forward verified it), so every ray, weight and landing point is the forward's in every bit.  gnum is the adjoint
+ * of num; den does not depend on the scene and cov gets no adjoint.  For a ray with ra != 0 of pixel p, in float64,
+ * one rounding per operation:  q_k = (w_L ra) gnum[0,k,p] + (w_R ra) gnum[1,k,p];  T_0 = 1, and over ALL layers
+ * (those behind T == 0 too, which the forward never reads):  g_l = T_l a_l,  D_l = sum_k q_k t_{l,k},
+ * T_{l+1} = T_l (1 - a_l);  then back to front, R = 0:  d = D_l - R,  e_l = T_l d,  R = R + a_l d.  With the lookup's
+ * four taps j and weights w_j:
+ *   gtex[l, k, tap j]  += (q_k g_l) w_j      (at gtex + l gtex_layer_stride; stride 0: every layer adds into one [T,Ht,Wt])
+ *   galpha[l, tap j]   += e_l w_j
+ * Two taps that replicate addressing puts on one texel both add to it.  Terms whose factor T_l is 0 are not issued.
+ * Either of galpha and gtex may be NULL (that gradient is not wanted), not both.  alpha may be NULL: every layer is
+ * opaque (only the first is ever met), and galpha must be NULL then.  Refuses what sdirt_render_layers refuses, a
+ * NULL gnum and a negative gtex_layer_stride.  Never allocates, never synchronises. */
+int sdirt_render_layers_grad(const sdirt_lens* lens, const int32_t* trips /*host [K]: the forward's final table*/,
+                             uint32_t flags, const float* x1 /*dev [W]*/, const float* y1 /*dev [H]*/, double z_sensor,
+                             const float* x2 /*dev [S,H,W]*/, const float* y2 /*dev [S,H,W]*/, double z_pupil,
+                             int32_t spp, int32_t height, int32_t width,
+                             const sdirt_dp_params* dp /*host, or NULL: one view, unit weights*/,
+                             int32_t n_layers, const double* depth /*host [L]*/, const double* inv_texel /*host [L]*/,
+                             const float* alpha /*dev [L,Ht,Wt] in [0, 1], or NULL: opaque*/,
+                             const float* tex /*dev [L,T,Ht,Wt], or [T,Ht,Wt] with stride 0*/, int64_t tex_layer_stride,
+                             int32_t n_tex, int32_t tex_h, int32_t tex_w,
+                             const double* gnum /*dev [V,T,H,W], V = dp ? 2 : 1*/,
+                             double* galpha /*dev [L,Ht,Wt] or NULL, ADDED to*/,
+                             double* gtex /*dev [L,T,Ht,Wt], or [T,Ht,Wt] with stride 0, or NULL, ADDED to*/,
+                             int64_t gtex_layer_stride, void* stream);
+
 /* Centroid part of Lensgroup.psf_center, deeplens/optics.py:902-904:
  * center[n] = -(sum_s o*ra / (sum_s ra + 1e-9)).xy (sums in float64);  any_valid (dev int32,
  * zeroed by caller, may be NULL) is set to 1 if any ray has ra == 1.  Point-major bundle. */

@@ -5,6 +5,8 @@
 // No PSF, no window, no per-pixel normalisation of a kernel: the yardstick for the PSF renders.
 // A second kernel, k_render_layers, renders a STACK of such planes, each with a coverage map, composited front to back
 // along every ray: a scene with depth discontinuities, which the reference cannot render at all.
+// A third, k_render_layers_grad, is that render's backward pass into the textures and the coverage maps:
+// the same rays again, and a scatter of float64 atomic adds -- ADDED to its outputs, not the same bits on every run.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sdirt_dp.h"
@@ -280,6 +282,148 @@ int launch_layers(int nt, dim3 grid, hipStream_t st, const TripTable& tt, const 
     return 0;
 }
 
+// ---- the layered render's backward: a scatter into the textures and the coverage maps ---------------
+
+// Everything of a backward launch behind the trip table.  (Named b in the kernel, its layers m, its weights ws: the
+// statements of the two forward kernels, which tools/variants/rt_*.py and rl_*.py find by their text, stay unique.)
+struct LayersGradLaunch {
+    const DevSurface* lens;
+    int K;
+    const float* x1;
+    const float* y1;
+    const float* x2;
+    const float* y2;
+    float z_sensor, z_pupil;
+    int S, H, W, L;
+    float depth[SDIRT_MAX_LAYERS];
+    float inv_texel[SDIRT_MAX_LAYERS];
+    const float* alpha;                // [L, Ht, Wt], or null: every layer opaque
+    const float* tex;                  // the first plane of this launch in layer 0
+    int64_t layer_stride;
+    int Ht, Wt;
+    int64_t view_stride;               // elements between the views of gnum: n_tex H W
+    const double* gnum;                // this launch's first plane of view 0
+    double* galpha;                    // [L, Ht, Wt] or null, ADDED to
+    double* gtex;                      // this launch's first plane in layer 0, or null, ADDED to
+    int64_t gtex_layer_stride;         // elements between the layers of gtex; 0: one [NT, Ht, Wt] all layers add into
+};
+
+// The four adds of one lookup's adjoint: v w_j into each tap.  Under replicate addressing two taps can be one texel;
+// both adds go to it.  One global_atomic_add_f64 each (docs/KERNEL_NOTES.md), no return value, no loop.
+__device__ __forceinline__ void scatter_taps(double* __restrict__ g, const Taps& tp, double v)
+{
+    atomicAdd(g + tp.i00, v * tp.w00);
+    atomicAdd(g + tp.i01, v * tp.w01);
+    atomicAdd(g + tp.i10, v * tp.w10);
+    atomicAdd(g + tp.i11, v * tp.w11);
+}
+
+// k_render_layers' geometry and per-ray program up to the end of the trace, with the trip table the forward ended
+// with (no convergence masks: that table is the one the forward verified), so every landing point, ra and weight is
+// the forward's in every bit.  Then two walks over the layers of a live ray, all in float64, one rounding per
+// operation, in the order of DESIGN.md §7q:
+//   front to back over ALL layers -- also those behind T == 0, which the forward never read: the coverage gradient of
+//   the texel that stopped the ray depends on them -- D_m = sum_k q_k t_{m,k} and T_m go to a lane-major LDS stash
+//   [L][2][kBlock] (a register array indexed by m would go to scratch), and the colour adjoint (q_k g_m) w_j is added;
+//   back to front: d = D_m - R, (T_m d) w_j is added to the coverage gradient, R = R + a_m d.  The taps and a_m are
+//   formed again there (the same fp32 steps on the same ray: the same bits; four cached loads) instead of being stashed:
+//   two doubles per layer and lane keep 16 layers within 64 KB of LDS.
+// Terms whose factor T_m (colour: g_m) is 0 are exact zeros and are not issued.  Without a coverage gradient the
+// front-to-back walk ends where T reaches 0, as the forward's does, and nothing is stashed.
+// The outputs are ADDED to with float64 atomics: the sums depend on the order the adds arrive in, so two runs need
+// NOT agree in every bit (they agree within the summation bound of §7q).  Everything else here is deterministic.
+template <class M, int DP, int NT>
+__global__ void __launch_bounds__(kBlock)
+k_render_layers_grad(TripTable trips /* kernarg offset 0 */, LayersGradLaunch b, DevDpParams dp)
+{
+    extern __shared__ double stash[];                          // [L][2][kBlock]: D_m, T_m of this lane's ray
+    constexpr int V = DP == kDpNone ? 1 : 2;
+    const int64_t HW = (int64_t)b.H * b.W;
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= HW) return;
+    const int i = (int)(p / b.W), j = (int)(p - (int64_t)i * b.W);
+    const float ox = b.x1[j], oy = b.y1[i];
+    const int64_t plane = (int64_t)b.Ht * b.Wt;
+    const auto div_fmh = UDiv<M>::make(dp.fmh);
+    double* const mine = stash + threadIdx.x;
+    double gn[V][NT];
+#pragma unroll
+    for (int side = 0; side < V; ++side)
+#pragma unroll
+        for (int k = 0; k < NT; ++k) gn[side][k] = b.gnum[side * b.view_stride + k * HW + p];
+    for (int s = 0; s < b.S; ++s) {
+        const int64_t q = (int64_t)s * HW + p;
+        Ray r = make_ray<M>(ox, oy, b.z_sensor, b.x2[q], b.y2[q], b.z_pupil);
+        float ws[2] = {1.0f, 1.0f};                            // (w_L, w_R) = (sr, sl): see k_render_plane
+        if (DP != kDpNone) {
+            const float x_tan = r.dx / (-r.dz);
+            if (DP == kDpBig) dp_weights_big(dp, x_tan, ws[1], ws[0]);
+            else dp_weights_small<M>(dp, div_fmh, x_tan, ws[1], ws[0]);
+        }
+        trace_ray<false, M, true, /*UNIT_W*/ true, /*MASKS*/ false>(b.lens, 0, b.K, kernarg_at(0), r, nullptr);
+        if (!(r.ra != 0.0f)) continue;
+        double qk[NT];
+#pragma unroll
+        for (int k = 0; k < NT; ++k) {
+            qk[k] = ((double)ws[0] * (double)r.ra) * gn[0][k];
+            if (V == 2) qk[k] = qk[k] + ((double)ws[1] * (double)r.ra) * gn[V - 1][k];
+        }
+        double Tm = 1.0;
+        int walked = 0;                                        // layers the first walk visited
+        for (int m = 0; m < b.L; ++m) {
+            if (!b.galpha && Tm == 0.0) break;
+            Ray hit = r;
+            propagate_to<Ieee>(hit, b.depth[m]);
+            const Taps tp(hit.ox, hit.oy, b.inv_texel[m], b.Ht, b.Wt);
+            const double cover = b.alpha ? tp.read(b.alpha + m * plane) : 1.0;
+            const double gm = Tm * cover;
+            if (b.galpha) {
+                const float* __restrict__ tm = b.tex + m * b.layer_stride;
+                double D = 0.0;
+#pragma unroll
+                for (int k = 0; k < NT; ++k) {
+                    const double term = qk[k] * tp.read(tm + k * plane);
+                    D = k == 0 ? term : D + term;
+                }
+                mine[(2 * m) * kBlock] = D;
+                mine[(2 * m + 1) * kBlock] = Tm;
+            }
+            if (b.gtex && gm != 0.0) {
+                double* __restrict__ gt = b.gtex + m * b.gtex_layer_stride;
+#pragma unroll
+                for (int k = 0; k < NT; ++k) scatter_taps(gt + k * plane, tp, qk[k] * gm);
+            }
+            Tm = Tm * (1.0 - cover);
+            walked = m + 1;
+        }
+        if (!b.galpha) continue;
+        double R = 0.0;
+        for (int m = walked - 1; m >= 0; --m) {
+            const double D = mine[(2 * m) * kBlock], Tb = mine[(2 * m + 1) * kBlock];
+            Ray hit = r;
+            propagate_to<Ieee>(hit, b.depth[m]);
+            const Taps tp(hit.ox, hit.oy, b.inv_texel[m], b.Ht, b.Wt);
+            const double cover = tp.read(b.alpha + m * plane);
+            const double d = D - R;
+            if (Tb != 0.0) scatter_taps(b.galpha + m * plane, tp, Tb * d);
+            R = R + cover * d;
+        }
+    }
+}
+
+template <class M, int DP>
+int launch_layers_grad(int nt, dim3 grid, size_t lds, hipStream_t st, const TripTable& tt, const LayersGradLaunch& b,
+                       const DevDpParams& dp)
+{
+    switch (nt) {
+    case 1: k_render_layers_grad<M, DP, 1><<<grid, kBlock, lds, st>>>(tt, b, dp); break;
+    case 2: k_render_layers_grad<M, DP, 2><<<grid, kBlock, lds, st>>>(tt, b, dp); break;
+    case 3: k_render_layers_grad<M, DP, 3><<<grid, kBlock, lds, st>>>(tt, b, dp); break;
+    default: k_render_layers_grad<M, DP, kMaxPlanes><<<grid, kBlock, lds, st>>>(tt, b, dp); break;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int sdirt_render_plane(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, const float* x1,
@@ -377,6 +521,68 @@ extern "C" int sdirt_render_layers(const sdirt_lens* lens, const int32_t* trips,
             if (!dp) return launch_layers<Mm, kDpNone>(nt, grid, st, tt, a, dpp);
             return dpp.big ? launch_layers<Mm, kDpBig>(nt, grid, st, tt, a, dpp)
                            : launch_layers<Mm, kDpSmall>(nt, grid, st, tt, a, dpp);
+        });
+        LAUNCH_CHECK();
+    }
+    return SDIRT_OK;
+}
+
+extern "C" int sdirt_render_layers_grad(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, const float* x1,
+                                        const float* y1, double z_sensor, const float* x2, const float* y2,
+                                        double z_pupil, int32_t spp, int32_t height, int32_t width,
+                                        const sdirt_dp_params* dp, int32_t n_layers, const double* depth,
+                                        const double* inv_texel, const float* alpha, const float* tex,
+                                        int64_t tex_layer_stride, int32_t n_tex, int32_t tex_h, int32_t tex_w,
+                                        const double* gnum, double* galpha, double* gtex, int64_t gtex_layer_stride,
+                                        void* stream)
+{
+    if (!lens) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null lens");
+    if (any_null(x1, y1, x2, y2, depth, inv_texel, tex, gnum)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!galpha && !gtex) return fail(SDIRT_ERR_INVALID_ARGUMENT, "galpha and gtex are both null: no gradient is asked for");
+    if (!alpha && galpha) return fail(SDIRT_ERR_INVALID_ARGUMENT, "galpha without alpha: an opaque stack has no coverage gradient");
+    if (!all_positive(spp, height, width, n_tex, tex_h, tex_w))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "spp, the sensor's and the texture's extents must be at least 1");
+    if (n_layers < 1 || n_layers > SDIRT_MAX_LAYERS)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_layers must be in 1 .. SDIRT_MAX_LAYERS");
+    if ((int64_t)tex_h * tex_w > INT32_MAX) return fail(SDIRT_ERR_INVALID_ARGUMENT, "texture plane above 2^31 texels");
+    if (tex_layer_stride < 0 || gtex_layer_stride < 0) return fail(SDIRT_ERR_INVALID_ARGUMENT, "negative layer stride");
+    const int64_t HW = (int64_t)height * width;
+    if (HW > (int64_t)INT32_MAX * kBlock) return fail(SDIRT_ERR_INVALID_ARGUMENT, "sensor too large");
+    LayersGradLaunch b;
+    for (int l = 0; l < SDIRT_MAX_LAYERS; ++l) {
+        const bool used = l < n_layers;
+        b.depth[l] = used ? (float)depth[l] : 0.0f;
+        b.inv_texel[l] = used ? (float)inv_texel[l] : 0.0f;
+        if (used && !(b.depth[l] < (l ? b.depth[l - 1] : 0.0f)))
+            return fail(SDIRT_ERR_INVALID_ARGUMENT, "layer depths must be negative and strictly descending (nearest first)");
+    }
+    TripTable tt;
+    if (int rc = make_trips(lens, trips, tt)) return rc;
+    const DevDpParams dpp = make_dp(dp);
+    b.lens = lens->dev; b.K = lens->n_surfaces;
+    b.x1 = x1; b.y1 = y1; b.x2 = x2; b.y2 = y2;
+    b.z_sensor = (float)z_sensor; b.z_pupil = (float)z_pupil;
+    b.S = spp; b.H = height; b.W = width; b.L = n_layers;
+    b.alpha = alpha; b.layer_stride = tex_layer_stride;
+    b.Ht = tex_h; b.Wt = tex_w;
+    b.view_stride = (int64_t)n_tex * HW;
+    b.galpha = galpha; b.gtex_layer_stride = gtex_layer_stride;
+    const dim3 grid((unsigned)((HW + kBlock - 1) / kBlock));
+    // the stash of the two walks: two doubles per layer and lane, at most 64 KB; none without a coverage gradient
+    const size_t lds = galpha ? (size_t)n_layers * 2 * kBlock * sizeof(double) : 0;
+    hipStream_t st = as_stream(stream);
+    // more than kMaxPlanes colour planes: further launches over the same rays; the coverage gradient is linear in the
+    // planes' D_m, so each launch adds that of its own planes
+    for (int t0 = 0; t0 < n_tex; t0 += kMaxPlanes) {
+        const int nt = n_tex - t0 < kMaxPlanes ? n_tex - t0 : kMaxPlanes;
+        b.tex = tex + (int64_t)t0 * tex_h * tex_w;
+        b.gnum = gnum + (int64_t)t0 * HW;
+        b.gtex = gtex ? gtex + (int64_t)t0 * tex_h * tex_w : nullptr;
+        with_math(routed_flags(flags, lens), [&](auto m) {
+            using Mm = decltype(m);
+            if (!dp) return launch_layers_grad<Mm, kDpNone>(nt, grid, lds, st, tt, b, dpp);
+            return dpp.big ? launch_layers_grad<Mm, kDpBig>(nt, grid, lds, st, tt, b, dpp)
+                           : launch_layers_grad<Mm, kDpSmall>(nt, grid, lds, st, tt, b, dpp);
         });
         LAUNCH_CHECK();
     }

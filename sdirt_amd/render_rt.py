@@ -8,6 +8,9 @@ through every surface, carry it to the plane, read the texture, sum -- is ONE HI
 csrc/sdirt_render_rt.hip); this module is its host side, the reference's two samplers, `render_single_img`, and a
 pure-torch float64 restatement of the lookup and the sums (`plane_sums_float64`) that tests and tools check it with.
 
+The layered render (render_layers, render_rgbd) and the opt-in gradients of all three renders in the
+textures and the coverage (scene_grad=True, sdirt_render_layers_grad) live here as well.
+
 Functions take the lens as their first argument; Lensgroup binds them under the reference's method names.
 """
 import ctypes as C
@@ -60,12 +63,12 @@ def trace2obj(lens, ray, depth=DEPTH):
 
 
 # ------------------------------------------------------------------------------------ float64 restatement
-def _bilinear_float64(planes, px, py, inv_texel, live):
-    """§7o's lookup of planes [N, Ht, Wt] fp32 at (px, py) [S, H, W] fp32 with inv_texel texels per mm (rounded to fp32
-    here) -> [N, S, H, W] float64.  Dead rays land anywhere (NaN included) and contribute nothing: they are given a
-    texel to read and come out as 0.  The one copy of the lookup: plane_sums_float64 and layer_sums_float64 read
-    through it."""
-    N, Ht, Wt = planes.shape
+def _taps_float64(px, py, inv_texel, live, Ht, Wt):
+    """The four taps of §7o's lookup in a [Ht, Wt] plane at (px, py) [S, H, W] fp32 with inv_texel texels per mm (rounded
+    to fp32 here) -> (idx [4, S, H, W] int64: the taps' offsets in the flattened plane under replicate addressing,
+    w [4, S, H, W] float64: w00, w01, w10, w11).  Dead rays land anywhere (NaN included): they are given a texel to
+    read with weights of 0 (so that autograd through a read finds no NaN on them), and the caller leaves them out.  The one copy of the
+    lookup: the sums and the gradients of this module read through it."""
     inv = torch.tensor(float(inv_texel), dtype=torch.float32, device=px.device)
     u = Wt / 2 - px * inv                                    # fp32, one rounding per operation
     v = Ht / 2 + py * inv
@@ -76,10 +79,25 @@ def _bilinear_float64(planes, px, py, inv_texel, live):
     r0 = torch.where(live, r0, torch.zeros_like(r0)).clamp(-2, Ht).nan_to_num(nan=0.0).long()
     cl, cr = c0.clamp(0, Wt - 1), (c0 + 1).clamp(0, Wt - 1)
     rt, rb = r0.clamp(0, Ht - 1), (r0 + 1).clamp(0, Ht - 1)
-    t64 = planes.double()
-    t = ((1 - fv) * (1 - fu)) * t64[:, rt, cl] + ((1 - fv) * fu) * t64[:, rt, cr] \
-        + (fv * (1 - fu)) * t64[:, rb, cl] + (fv * fu) * t64[:, rb, cr]
-    return torch.where(live, t, torch.zeros((), dtype=torch.float64, device=px.device))
+    idx = torch.stack((rt * Wt + cl, rt * Wt + cr, rb * Wt + cl, rb * Wt + cr))
+    w = torch.stack(((1 - fv) * (1 - fu), (1 - fv) * fu, fv * (1 - fu), fv * fu))
+    return idx, torch.where(live, w, torch.zeros((), dtype=torch.float64, device=px.device))
+
+
+def _read_taps(planes, idx, w, live):
+    """planes [N, Ht, Wt] fp32 read through the taps of _taps_float64 -> [N, S, H, W] float64 (0 on dead rays):
+    w00 t00 + w01 t01 + w10 t10 + w11 t11, summed left to right."""
+    t64 = planes.double().flatten(1)
+    t = w[0] * t64[:, idx[0]] + w[1] * t64[:, idx[1]] + w[2] * t64[:, idx[2]] + w[3] * t64[:, idx[3]]
+    return torch.where(live, t, torch.zeros((), dtype=torch.float64, device=idx.device))
+
+
+def _bilinear_float64(planes, px, py, inv_texel, live):
+    """§7o's lookup of planes [N, Ht, Wt] fp32 at (px, py) [S, H, W] fp32 with inv_texel texels per mm (rounded to fp32
+    here) -> [N, S, H, W] float64.  Dead rays land anywhere (NaN included) and contribute nothing: they are given a
+    texel to read and come out as 0."""
+    idx, w = _taps_float64(px, py, inv_texel, live, int(planes.shape[-2]), int(planes.shape[-1]))
+    return _read_taps(planes, idx, w, live)
 
 
 def plane_sums_float64(landing, tex, inv_texel, views=None, return_abs=False):
@@ -178,9 +196,8 @@ def _check_render_arguments(lens, img, spp, wvln, pupil_points):
     return chroma
 
 
-@torch.no_grad()
 def render_plane(lens, img, depth, spp=64, dp=None, wvln=DEFAULT_WAVE, scale=None, pixel_center=True,
-                 photometric=False, pupil_points=None, return_sums=False):
+                 photometric=False, pupil_points=None, return_sums=False, scene_grad=False):
     """The image(s) the lens forms of the textured plane z = depth (mm, negative), ray traced.
 
     img [B, C, Ht, Wt] fp32 on the lens's device: the texture, spread over scale x the sensor's extent (scale: object
@@ -194,9 +211,27 @@ def render_plane(lens, img, depth, spp=64, dp=None, wvln=DEFAULT_WAVE, scale=Non
     photometric: num / spp instead of num / den (vignetting and dual-pixel shading stay in the image).
     pupil_points=(x2, y2), each [spp, H, W] ([C, spp, H, W] with C wavelengths): the pupil points instead of a draw.
     return_sums: the float64 sums are appended: num [V, B, C, H, W] and den [V, H, W] ([V, C, H, W] with C wavelengths).
-    No gradients."""
-    chroma = _check_render_arguments(lens, img, spp, wvln, pupil_points)
+    No gradients by default: the call runs without recording, whatever requires one.  scene_grad=True opts in (named
+    as local_dp_psf_render_volume names it): in grad mode, with `img` requiring a gradient, the call goes through
+    _RenderRecorded and `img` gets the gradient of DESIGN.md §7q (one opaque layer); otherwise scene_grad=True is the
+    plain call.  return_sums together with a recorded gradient raises ValueError."""
+    _check_render_arguments(lens, img, spp, wvln, pupil_points)
+    recorded = bool(scene_grad) and torch.is_grad_enabled() and img.requires_grad
+    if recorded and return_sums:
+        raise ValueError("return_sums with a recorded gradient: the float64 sums carry none")
     lens._require_gpu()
+    args = (depth, spp, dp, wvln, scale, pixel_center, photometric, pupil_points)
+    if recorded:
+        res = _RenderRecorded.apply(img, None, lens, _plane_forward, args)
+        return res if dp is not None else res[0]
+    with torch.no_grad():
+        return _plane_forward(lens, img, None, *args, return_sums=return_sums)
+
+
+def _plane_forward(lens, img, alpha, depth, spp, dp, wvln, scale, pixel_center, photometric, pupil_points,
+                   return_sums=False, record=None):
+    """render_plane behind its argument checks.  record: a dict that receives what _RenderRecorded's backward needs."""
+    chroma = not np.isscalar(wvln)
     spp = int(spp)
     B, Cn, Ht, Wt = (int(v) for v in img.shape)
     H, W = (int(v) for v in lens.sensor_res)
@@ -223,6 +258,12 @@ def render_plane(lens, img, depth, spp=64, dp=None, wvln=DEFAULT_WAVE, scale=Non
             part = plane_batch(lens, tex, depth, x2, y2, dp, wv, inv_texel, pixel_center)
             nums[g] += part["num"]
             dens[g] += part["den"]
+            if record is not None:
+                record["chunks"].append((g, x2.to(lens.device, torch.float32), y2.to(lens.device, torch.float32),
+                                         part["trips"]))
+    if record is not None:
+        record.update(wv=[g[0] for g in groups], den=dens, depths=[float(depth)], inv_texels=[inv_texel], dp=dp,
+                      pixel_center=pixel_center, spp=spp, photometric=photometric, chroma=chroma, plane=True)
     if chroma:
         num, den = torch.stack(nums, 2), torch.stack(dens, 1)               # [V, B, C, H, W], [V, C, H, W]
         den_b = den.unsqueeze(1)
@@ -348,9 +389,8 @@ def layer_batch(lens, alpha, tex, depths, inv_texels, x2, y2, dp=None, wvln=DEFA
     return {"num": num, "den": den, "cov": cov, "trips": np.asarray(trips, np.int32), "landing": land}
 
 
-@torch.no_grad()
 def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, scales=None, pixel_center=True,
-                  photometric=False, pupil_points=None, return_sums=False):
+                  photometric=False, pupil_points=None, return_sums=False, scene_grad=False):
     """The image(s) the lens forms of a stack of fronto-parallel layers, ray traced with occlusion.
 
     img [L, C, Ht, Wt] fp32, or [C, Ht, Wt] shared by all layers; alpha [L, Ht, Wt] fp32 in [0, 1]: layer l covers the
@@ -360,7 +400,11 @@ def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, 
     black.  dp, wvln (a number or C wavelengths), spp > 64, pixel_center, photometric and pupil_points as in
     render_plane.  -> (L, R) with dp, else one image, each [C, H, W] fp32.
     return_sums: num [V, C, H, W], den and cov [V, H, W] ([V, C, H, W] with C wavelengths) are appended; cov / den is
-    the share of a pixel's light that met some layer.  No gradients."""
+    the share of a pixel's light that met some layer.
+    No gradients by default.  scene_grad=True opts in: in grad mode, with `img` or `alpha` requiring a gradient, the
+    call goes through _RenderRecorded and both get the gradient of DESIGN.md §7q (fp32, of their own shape; a shared
+    image gets the sum over its layers); otherwise scene_grad=True is the plain call.  dp, the lens, depths, scales and
+    pupil_points get none.  return_sums together with a recorded gradient raises ValueError."""
     if not torch.is_tensor(img) or img.dim() not in (3, 4):
         raise ValueError("img must be a [L, C, Ht, Wt] tensor, or [C, Ht, Wt] shared by all layers")
     if scales is not None and len(scales) != len(depths):
@@ -369,7 +413,23 @@ def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, 
     chroma = _check_render_arguments(lens, img.unsqueeze(0) if shared else img, spp, wvln, pupil_points)
     if alpha.device != lens.device:
         raise ValueError(f"alpha is on {alpha.device}, the lens on {lens.device}")
+    recorded = bool(scene_grad) and torch.is_grad_enabled() and (img.requires_grad or alpha.requires_grad)
+    if recorded and return_sums:
+        raise ValueError("return_sums with a recorded gradient: the float64 sums carry none")
     lens._require_gpu()
+    args = (depths, spp, dp, wvln, scales, pixel_center, photometric, pupil_points)
+    if recorded:
+        res = _RenderRecorded.apply(img, alpha, lens, _layers_forward, args)
+        return res if dp is not None else res[0]
+    with torch.no_grad():
+        return _layers_forward(lens, img, alpha, *args, return_sums=return_sums)
+
+
+def _layers_forward(lens, img, alpha, depths, spp, dp, wvln, scales, pixel_center, photometric, pupil_points,
+                    return_sums=False, record=None):
+    """render_layers behind its argument checks.  record: a dict that receives what _RenderRecorded's backward needs."""
+    L, Cn, Ht, Wt, shared = _check_layers(alpha, img, depths, scan=False)
+    chroma = not np.isscalar(wvln)
     spp = int(spp)
     H, W = (int(v) for v in lens.sensor_res)
     V = 1 if dp is None else 2
@@ -396,6 +456,12 @@ def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, 
             nums[g] += part["num"]
             dens[g] += part["den"]
             covs[g] += part["cov"]
+            if record is not None:
+                record["chunks"].append((g, x2.to(lens.device, torch.float32), y2.to(lens.device, torch.float32),
+                                         part["trips"]))
+    if record is not None:
+        record.update(wv=[g[0] for g in groups], den=dens, depths=[float(d) for d in depths], inv_texels=inv_texels,
+                      dp=dp, pixel_center=pixel_center, spp=spp, photometric=photometric, chroma=chroma, plane=False)
     if chroma:
         num, den, cov = torch.cat(nums, 1), torch.stack(dens, 1), torch.stack(covs, 1)     # [V, C, H, W] each
         den_b = den
@@ -453,15 +519,23 @@ def uniform_layer_depths(depth, n_layers):
     return out
 
 
-@torch.no_grad()
 def render_rgbd(lens, img, depth, layer_depths=None, n_layers=8, spp=64, dp=None, wvln=DEFAULT_WAVE, scales=None,
-                pixel_center=True, photometric=False, pupil_points=None, extend=True):
+                pixel_center=True, photometric=False, pupil_points=None, extend=True, scene_grad=False):
     """The ray-traced dual-pixel pair of an RGB-D frame -- the input PSFNet.render takes -- with occlusion: img
     [B, C, H, W] fp32, depth [B, 1, H, W] (mm, negative).  Every frame is cut into layers by layers_from_rgbd (at
     layer_depths, or at n_layers depths uniform in 1 / depth between the frame's nearest and farthest) that all show
     the frame's image, and rendered by render_layers: one call per batch element, the other arguments as there (default
     scales: calc_scale_ray once per distinct stack of depths, so frames that share their layers register alike).
-    -> (L, R) with dp, else one image, each [B, C, H, W] fp32.  No gradients."""
+    -> (L, R) with dp, else one image, each [B, C, H, W] fp32.
+    No gradients by default.  scene_grad=True: render_layers' -- img[b], which all layers of frame b show, gets the
+    gradient summed over its layers; `depth` gets none (layers_from_rgbd is a hard assignment)."""
+    with torch.set_grad_enabled(bool(scene_grad) and torch.is_grad_enabled()):
+        return _render_rgbd(lens, img, depth, layer_depths, n_layers, spp, dp, wvln, scales, pixel_center, photometric,
+                            pupil_points, extend, scene_grad)
+
+
+def _render_rgbd(lens, img, depth, layer_depths, n_layers, spp, dp, wvln, scales, pixel_center, photometric,
+                 pupil_points, extend, scene_grad):
     if not torch.is_tensor(img) or img.dim() != 4:
         raise ValueError("img must be a [B, C, H, W] tensor")
     if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1 or depth.shape[0] != img.shape[0] \
@@ -472,15 +546,238 @@ def render_rgbd(lens, img, depth, layer_depths=None, n_layers=8, spp=64, dp=None
     views, scales_of = [], {}
     for b in range(img.shape[0]):
         zs = uniform_layer_depths(depth[b, 0], n_layers) if layer_depths is None else [float(d) for d in layer_depths]
-        alpha = layers_from_rgbd(depth[b, 0], zs, extend).to(img.device)
+        alpha = layers_from_rgbd(depth[b, 0].detach(), zs, extend).to(img.device)
         if scales is None and tuple(zs) not in scales_of:      # calc_scale_ray traces rays of its own: once per stack
             scales_of[tuple(zs)] = scale_per_layer(lens, zs)
         out = render_layers(lens, img[b], alpha, zs, spp=spp, dp=dp, wvln=wvln,
                             scales=scales_of[tuple(zs)] if scales is None else scales,
-                            pixel_center=pixel_center, photometric=photometric, pupil_points=pupil_points)
+                            pixel_center=pixel_center, photometric=photometric, pupil_points=pupil_points,
+                            scene_grad=scene_grad)
         views.append(out if dp is not None else (out,))
     res = tuple(torch.stack(v) for v in zip(*views))
     return res if dp is not None else res[0]
+
+
+# ------------------------------------------------------------------------------------ gradients
+def layer_grads_float64(landing, alpha, tex, inv_texels, gnum, views=None, return_abs=False):
+    """The adjoint of DESIGN.md §7q from the rays' landing record, in plain torch and without autograd: what
+    sdirt_render_layers_grad adds to zeroed buffers, every term in the kernel's bits, the terms of a texel summed in
+    index_add_'s order.
+
+    landing, alpha, tex, inv_texels, views as in layer_sums_float64; alpha=None: every layer opaque (no coverage
+    gradient); gnum [V, T, H, W] float64: the adjoint of num.
+    -> galpha [L, Ht, Wt] (None without alpha), gtex of tex's shape (a shared [T, Ht, Wt] gets the sum over the layers),
+    float64; with return_abs also the sums of |term| of both, absolute values taken before any cancellation: colour
+    |q|_k g_l w_j with |q|_k = sum_side wr |gnum|, coverage T_l (Dbar_l + Rbar_{l+1}) w_j with Dbar_l = sum_k |q|_k
+    |t_{l,k}| and Rbar the recursion of R on Dbar."""
+    landing = torch.as_tensor(landing, dtype=torch.float32)
+    dev = landing.device
+    tex = torch.as_tensor(tex, dtype=torch.float32, device=dev)
+    gnum = torch.as_tensor(gnum, dtype=torch.float64, device=dev)
+    V = 2 if views is None else int(views)
+    L = len(inv_texels)
+    if landing.shape[0] != 3 + 2 * L:
+        raise ValueError(f"{L} layers need a landing record of {3 + 2 * L} rows and {L} inv_texels")
+    opaque = alpha is None
+    if not opaque:
+        alpha = torch.as_tensor(alpha, dtype=torch.float32, device=dev)
+        if alpha.shape[0] != L:
+            raise ValueError(f"alpha has {alpha.shape[0]} layers, inv_texels {L}")
+    shared = tex.dim() == 3
+    NT, Ht, Wt = (int(v) for v in tex.shape[-3:])
+    if tuple(gnum.shape) != (V, NT) + tuple(landing.shape[2:]):
+        raise ValueError(f"gnum must be {(V, NT) + tuple(landing.shape[2:])}, got {tuple(gnum.shape)}")
+    ra = landing[0]
+    live = ra != 0
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    wr = torch.where(live, landing[1:1 + V].double() * ra.double(), zero)                   # [V, S, H, W]
+    q = wr[0] * gnum[0][:, None]                                                            # [T, S, H, W]
+    qa = wr[0] * gnum[0].abs()[:, None]
+    if V == 2:
+        q, qa = q + wr[1] * gnum[1][:, None], qa + wr[1] * gnum[1].abs()[:, None]
+    gtex = torch.zeros(tex.shape, dtype=torch.float64, device=dev)
+    gtex_abs = torch.zeros_like(gtex)
+    galpha = None if opaque else torch.zeros(alpha.shape, dtype=torch.float64, device=dev)
+    galpha_abs = None if opaque else torch.zeros_like(galpha)
+
+    def scatter(buf, idx, w, val, sel):
+        flat = buf.view(-1)
+        for j in range(4):
+            flat.index_add_(0, idx[j][sel], (val * w[j])[sel])
+
+    T = torch.ones(ra.shape, dtype=torch.float64, device=dev)
+    kept = []
+    for l in range(L):
+        idx, w = _taps_float64(landing[3 + 2 * l], landing[4 + 2 * l], inv_texels[l], live, Ht, Wt)
+        a = torch.ones_like(T) if opaque else _read_taps(alpha[l:l + 1], idx, w, live)[0]
+        t = _read_taps(tex if shared else tex[l], idx, w, live)
+        g = T * a
+        D, Dbar = q[0] * t[0], qa[0] * t[0].abs()
+        for k in range(1, NT):
+            D, Dbar = D + q[k] * t[k], Dbar + qa[k] * t[k].abs()
+        sel = live & (g != 0)
+        for k in range(NT):
+            scatter(gtex[k] if shared else gtex[l, k], idx, w, q[k] * g, sel)
+            scatter(gtex_abs[k] if shared else gtex_abs[l, k], idx, w, qa[k] * g, sel)
+        kept.append((idx, w, a, D, Dbar, T))
+        T = T * (1 - a)
+    if not opaque:
+        R, Rbar = torch.zeros_like(T), torch.zeros_like(T)
+        for l in range(L - 1, -1, -1):
+            idx, w, a, D, Dbar, Tl = kept[l]
+            d = D - R
+            sel = live & (Tl != 0)
+            scatter(galpha[l], idx, w, Tl * d, sel)
+            scatter(galpha_abs[l], idx, w, Tl * (Dbar + Rbar), sel)
+            R, Rbar = R + a * d, a * Dbar + (1 - a) * Rbar
+    return (galpha, gtex, galpha_abs, gtex_abs) if return_abs else (galpha, gtex)
+
+
+def gnum_from_image_grad(G, den_total, spp=None, photometric=False):
+    """The adjoint of the float64 sums `num` from the adjoint G of the image(s) images_from_sums made of them:
+    G / den_total where den_total > 0 and 0 elsewhere (photometric: G / spp), float64.  G [V, ..., H, W] of any float
+    dtype, den_total [V, H, W]: the TOTAL over every chunk of samples, broadcast over the dimensions between."""
+    G = G.double()
+    if photometric:
+        return G / float(spp)
+    d = den_total.view(den_total.shape[:1] + (1,) * (G.dim() - den_total.dim()) + den_total.shape[1:])
+    return torch.where(d > 0, G / torch.where(d > 0, d, torch.ones_like(d)), torch.zeros_like(G))
+
+
+def layer_grad_batch(lens, alpha, tex, depths, inv_texels, x2, y2, trips, gnum, dp=None, wvln=DEFAULT_WAVE,
+                     pixel_center=True, galpha=None, gtex=None):
+    """ONE call of sdirt_render_layers_grad: the counterpart of layer_batch (same scene, pupil points, dp, wvln and
+    pixel_center), with `trips` the table that call ended with (its "trips") and gnum [V, T, H, W] float64 the adjoint
+    of its num.  alpha=None: every layer opaque (render_plane's scene with L = 1), no coverage gradient.
+    galpha [L, Ht, Wt], gtex (tex's shape) float64 on the lens's device: the buffers the gradients are ADDED to; None:
+    a zeroed one is made; False: that gradient is not wanted.  -> (galpha, gtex), None where not wanted.
+    The adds are float64 atomics: two calls need not agree in every bit."""
+    dev = lens.device
+    if alpha is None:
+        if not torch.is_tensor(tex) or tex.dim() not in (3, 4) or tex.dtype != torch.float32:
+            raise ValueError("the layers' image must be a float32 [L, C, Ht, Wt] tensor, or [C, Ht, Wt] shared by all layers")
+        shared = tex.dim() == 3
+        L, (T, Ht, Wt) = len(depths), (int(v) for v in tex.shape[-3:])
+        if not 1 <= L <= _lib.MAX_LAYERS or len(inv_texels) != L or (not shared and int(tex.shape[0]) != L):
+            raise ValueError(f"{L} depths, {len(inv_texels)} scales and an image of {tuple(tex.shape)}: layers differ")
+        if galpha is not None and galpha is not False:
+            raise ValueError("an opaque stack (alpha=None) has no coverage gradient")
+        galpha = False
+    else:
+        L, T, Ht, Wt, shared = _check_layers(alpha, tex, depths, inv_texels, scan=False)
+        if alpha.device != dev:
+            raise ValueError("alpha and tex must be on the lens's device")
+        alpha = alpha.contiguous()
+    if tex.device != dev:
+        raise ValueError("alpha and tex must be on the lens's device")
+    if galpha is False and gtex is False:
+        raise ValueError("galpha and gtex are both False: no gradient is asked for")
+    H, W = (int(v) for v in lens.sensor_res)
+    S = int(x2.shape[0])
+    K = len(lens.surfaces)
+    V = 1 if dp is None else 2
+    if tuple(x2.shape) != (S, H, W) or tuple(y2.shape) != (S, H, W):
+        raise ValueError(f"pupil points must be [spp, {H}, {W}], got {tuple(x2.shape)} and {tuple(y2.shape)}")
+    if len(trips) != K:
+        raise ValueError(f"{len(trips)} trip counts for a lens of {K} surfaces")
+    if not torch.is_tensor(gnum) or gnum.dtype != torch.float64 or gnum.device != dev or tuple(gnum.shape) != (V, T, H, W):
+        raise ValueError(f"gnum must be float64 {(V, T, H, W)} on the lens's device")
+
+    def buffer(given, like, name):
+        if given is False:
+            return None
+        if given is None:
+            return torch.zeros(like.shape, dtype=torch.float64, device=dev)
+        if not torch.is_tensor(given) or given.dtype != torch.float64 or given.device != dev \
+                or given.shape != like.shape or not given.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float64 {tuple(like.shape)} on the lens's device")
+        return given
+
+    lens._require_gpu()
+    galpha = buffer(galpha, alpha, "galpha")
+    gtex = buffer(gtex, tex, "gtex")
+    x1, y1 = sensor_axes(lens, pixel_center)
+    x2 = x2.to(dev, torch.float32).contiguous()
+    y2 = y2.to(dev, torch.float32).contiguous()
+    tex, gnum = tex.contiguous(), gnum.contiguous()
+    dpp = None if dp is None else C.byref(_lib.DpParams(*(float(v) for v in dp)))
+    z = (C.c_double * L)(*(float(d) for d in depths))
+    inv = (C.c_double * L)(*(float(v) for v in inv_texels))
+    pupilz, _ = lens.exit_pupil()
+    wv = float(wvln if wvln < 10 else wvln * 1e-3)
+    stride = 0 if shared else T * Ht * Wt
+    with lens._timed("render_layers_grad"):
+        _lib.check(_lib.lib().sdirt_render_layers_grad(
+            lens.dev_lens(wv), (C.c_int32 * K)(*[int(t) for t in trips]), lens._math_flags(), dptr(x1), dptr(y1),
+            float(lens.d_sensor), dptr(x2), dptr(y2), float(pupilz), S, H, W, dpp, L, z, inv, dptr(alpha), dptr(tex),
+            stride, T, Ht, Wt, dptr(gnum), dptr(galpha), dptr(gtex), stride, stream_ptr(dev)))
+    return galpha, gtex
+
+
+class _RenderRecorded(torch.autograd.Function):
+    """render_plane / render_layers(scene_grad=True) under autograd.  The forward is the plain call (the same
+    launches, the same images in every bit), which also keeps, per chunk of samples and wavelength group, the pupil
+    points x2, y2 -- 8 bytes per ray, the only record that grows with the sample count -- and the trip table the
+    launch ended with, and per call the wavelengths, pixel_center, dp, the depths, the inv_texels and the TOTAL den of
+    every group.  The backward forms gnum = G / den_total (gnum_from_image_grad) once per wavelength group, zeroes
+    float64 buffers of the inputs' shapes, runs sdirt_render_layers_grad over every recorded chunk into them and returns
+    them in the inputs' dtype.  It traces through the lens AS IT STANDS THEN: a lens changed (surfaces, sensor, focus,
+    precision) between forward and backward is the caller's error."""
+
+    @staticmethod
+    def forward(ctx, img, alpha, lens, run, args):
+        record = {"chunks": []}
+        with torch.no_grad():
+            res = run(lens, img, alpha, *args, record=record)
+        res = res if isinstance(res, tuple) else (res,)
+        ctx.lens, ctx.record = lens, record
+        ctx.save_for_backward(img, *(() if alpha is None else (alpha,)))
+        ctx.set_materialize_grads(False)
+        return res
+
+    @staticmethod
+    def backward(ctx, *G):
+        lens, rec = ctx.lens, ctx.record
+        img, alpha = (ctx.saved_tensors + (None,))[:2]
+        need_img, need_alpha = ctx.needs_input_grad[0], alpha is not None and ctx.needs_input_grad[1]
+        if all(g is None for g in G) or not (need_img or need_alpha):
+            return None, None, None, None, None
+        shape = next(g.shape for g in G if g is not None)
+        G = torch.stack([torch.zeros(shape, dtype=torch.float64, device=lens.device) if g is None else g.double()
+                         for g in G])                                     # [V, (B,) C, H, W]
+        H, W = (int(v) for v in shape[-2:])
+        Ht, Wt = (int(v) for v in img.shape[-2:])
+        V, chroma, plane = G.shape[0], rec["chroma"], rec["plane"]
+        with torch.no_grad():
+            gimg = torch.zeros(img.shape, dtype=torch.float64, device=lens.device) if need_img else None
+            galpha = torch.zeros(alpha.shape, dtype=torch.float64, device=lens.device) if need_alpha else None
+            # per wavelength group: the forward's planes, their adjoint, and the buffer their gradient is added to
+            if not chroma:
+                texs = [img.detach().reshape(-1, Ht, Wt) if plane else img.detach()]
+                gnums = [gnum_from_image_grad(G.reshape(V, -1, H, W), rec["den"][0], rec["spp"], rec["photometric"])]
+                gtexs = [(gimg.view(-1, Ht, Wt) if plane else gimg) if need_img else None]
+            else:
+                texs, gnums, gtexs = [], [], []
+                for c in range(len(rec["wv"])):
+                    ch = img.detach()[:, c] if plane else (img.detach()[c:c + 1] if img.dim() == 3 else img.detach()[:, c:c + 1])
+                    texs.append(ch.contiguous())
+                    gnums.append(gnum_from_image_grad(G[:, :, c] if plane else G[:, c:c + 1], rec["den"][c], rec["spp"],
+                                                      rec["photometric"]))
+                    gtexs.append(torch.zeros(texs[-1].shape, dtype=torch.float64, device=lens.device) if need_img else None)
+            for g, x2, y2, trips in rec["chunks"]:
+                layer_grad_batch(lens, None if plane else alpha.detach(), texs[g], rec["depths"], rec["inv_texels"], x2, y2,
+                                 trips, gnums[g].contiguous(), rec["dp"], rec["wv"][g], rec["pixel_center"],
+                                 galpha=galpha if need_alpha else False, gtex=gtexs[g] if need_img else False)
+            if chroma and need_img:
+                for c, gt in enumerate(gtexs):
+                    if plane:
+                        gimg[:, c] = gt
+                    elif img.dim() == 3:
+                        gimg[c:c + 1] = gt
+                    else:
+                        gimg[:, c:c + 1] = gt
+        return (gimg.to(img.dtype) if need_img else None, galpha.to(alpha.dtype) if need_alpha else None,
+                None, None, None)
 
 
 def render_single_img(lens, img_org, depth=DEPTH, spp=64, unwarp=False, save_name=None, return_tensor=False, noise=0,
