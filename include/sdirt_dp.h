@@ -333,6 +333,35 @@ int sdirt_render_layers_grad(const sdirt_lens* lens, const int32_t* trips /*host
                              double* gtex /*dev [L,T,Ht,Wt], or [T,Ht,Wt] with stride 0, or NULL, ADDED to*/,
                              int64_t gtex_layer_stride, void* stream);
 
+/* The backward pass of sdirt_render_layers into the dual-pixel parameters h, f, w: a reduction.
+ * Every argument up to tex_w is sdirt_render_layers_grad's (alpha may be NULL: every layer opaque); trips is the table
+ * the forward ENDED with.  gnum is the adjoint of num, gden [2,H,W] the adjoint of den, or NULL (the photometric image
+ * num / spp has none).  For a ray with ra != 0 of pixel p, in float64, one rounding per operation: c_k is the
+ * forward's composite (its walk ends where T reaches 0),
+ *   A_side = ra (gnum[side,0,p] c_0 + ... + gnum[side,T-1,p] c_{T-1} + gden[side,p])        (left to right, gden last)
+ * and with dZ_a/d(h, f, w), a = right, middle, left, of the sub-pixel model (the float64 chords on the forward's fp32
+ * clamp decisions, as sdirt_forward_integral_grad and sdirt_dp_energy_grad take them) at the kernel's own fp32
+ * x_tan = dx / (-dz):  dw_L = dZ_m - dZ_r,  dw_R = dZ_l - dZ_m  ((w_L, w_R) = (s_r, s_l)), the ray's term is
+ * A_0 dw_L + A_1 dw_R.  r gets no gradient.
+ *   partial[g, b, 0..2] = the sum of the terms of workgroup b (256 consecutive pixels of the row-major sensor, each
+ *                         lane its samples in order) for the g-th group of four planes; gden counts in group 0 only
+ * partial is [ceil(n_tex / 4), ceil(H W / 256), 3] float64 and is OVERWRITTEN; the caller adds its rows.  No atomics:
+ * the same bits on every run.  x_tan, when given, receives the fp32 x_tan of every ray.
+ * Refuses what sdirt_render_layers_grad refuses, a NULL dp (one view has no sub-pixel model), dp->r <= 0,
+ * dp->f == dp->h, a NULL gnum and a NULL partial.  Never allocates, never synchronises. */
+int sdirt_render_layers_dp_grad(const sdirt_lens* lens, const int32_t* trips /*host [K]: the forward's final table*/,
+                                uint32_t flags, const float* x1 /*dev [W]*/, const float* y1 /*dev [H]*/,
+                                double z_sensor, const float* x2 /*dev [S,H,W]*/, const float* y2 /*dev [S,H,W]*/,
+                                double z_pupil, int32_t spp, int32_t height, int32_t width,
+                                const sdirt_dp_params* dp /*host, not NULL*/,
+                                int32_t n_layers, const double* depth /*host [L]*/, const double* inv_texel /*host [L]*/,
+                                const float* alpha /*dev [L,Ht,Wt] in [0, 1], or NULL: opaque*/,
+                                const float* tex /*dev [L,T,Ht,Wt], or [T,Ht,Wt] with stride 0*/,
+                                int64_t tex_layer_stride, int32_t n_tex, int32_t tex_h, int32_t tex_w,
+                                const double* gnum /*dev [2,T,H,W]*/, const double* gden /*dev [2,H,W] or NULL*/,
+                                double* partial /*dev [ceil(T/4),ceil(HW/256),3], OVERWRITTEN*/,
+                                float* x_tan /*dev [S,H,W] or NULL*/, void* stream);
+
 /* Centroid part of Lensgroup.psf_center, deeplens/optics.py:902-904:
  * center[n] = -(sum_s o*ra / (sum_s ra + 1e-9)).xy (sums in float64);  any_valid (dev int32,
  * zeroed by caller, may be NULL) is set to 1 if any ray has ra == 1.  Point-major bundle. */

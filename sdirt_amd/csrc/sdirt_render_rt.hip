@@ -7,9 +7,13 @@
 // along every ray: a scene with depth discontinuities, which the reference cannot render at all.
 // A third, k_render_layers_grad, is that render's backward pass into the textures and the coverage maps:
 // the same rays again, and a scatter of float64 atomic adds -- ADDED to its outputs, not the same bits on every run.
+// A fourth, k_render_layers_dp_grad, is its backward pass into the dual-pixel parameters h, f, w: the
+// same rays once more, the weights' derivative per ray (sdirt_dp_grad.hpp), one row of three sums per workgroup --
+// no atomics, the same bits on every run.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sdirt_dp.h"
+#include "sdirt_dp_grad.hpp"
 #include "sdirt_trace.hpp"
 
 using namespace sdirt;
@@ -424,6 +428,119 @@ int launch_layers_grad(int nt, dim3 grid, size_t lds, hipStream_t st, const Trip
     return 0;
 }
 
+// ---- the layered render's backward into the dual-pixel parameters h, f, w ---------------------------
+
+static_assert(kBlock == kGradThreads, "block_sum_store reduces a workgroup of kGradThreads");
+
+// Everything of a dual-pixel backward launch behind the trip table.  (Named e in the kernel, its layers n, its ray at
+// a layer `met`: the statements of the three kernels above, which tools/variants/*.py find by their text, stay unique.
+// There is no weight array: the adjoint needs the weights' derivative, not the weights.)
+struct LayersDpGradLaunch {
+    const DevSurface* lens;
+    int K;
+    const float* x1;
+    const float* y1;
+    const float* x2;
+    const float* y2;
+    float z_sensor, z_pupil;
+    int S, H, W, L;
+    float depth[SDIRT_MAX_LAYERS];
+    float inv_texel[SDIRT_MAX_LAYERS];
+    const float* alpha;                // [L, Ht, Wt], or null: every layer opaque
+    const float* tex;                  // the first plane of this launch in layer 0
+    int64_t layer_stride;
+    int Ht, Wt;
+    int64_t view_stride;               // elements between the views of gnum: n_tex H W
+    const double* gnum;                // this launch's first plane of view 0
+    const double* gden;                // [2, H, W], or null: no adjoint of den (photometric; a plane group past the first)
+    double* partial;                   // this launch's [ceil(H W / kBlock), 3], OVERWRITTEN
+    float* x_tan;                      // [S, H, W] or null
+};
+
+// k_render_layers_grad's geometry and per-ray program up to the end of the trace, with the trip table the forward
+// ended with, so x_tan, ra and every landing point are the forward's in every bit.  Then, for a live ray, the
+// forward's walk over the layers (it ends where T reaches 0) gives the composite c_k, and
+//   A_side = ra (gnum[side, 0] c_0 + ... + gnum[side, NT-1] c_{NT-1} + gden[side])
+// is what the ray's weight w_side is multiplied by in the loss.  The weights' derivative in h, f, w (dz_boundaries: the
+// float64 chords on the forward's fp32 clamp decisions) is evaluated AFTER the trace and only where A_0, A_1 are not
+// both 0: six float64 square roots and a division chain that dead rays, and pixels no adjoint reaches, never pay for,
+// and whose registers are not live across the surface loop (x_tan alone is carried over it).
+// A lane adds its rays' terms in sample order; the workgroup's sum (wave_sum, block_sum_store<3>) is one row of
+// `partial`, OVERWRITTEN.  Lanes past H W take part with zeros.  No atomics: the same bits on every run.
+template <class M, int DP, int NT>
+__global__ void __launch_bounds__(kBlock)
+k_render_layers_dp_grad(TripTable trips /* kernarg offset 0 */, LayersDpGradLaunch e, DevDpParams dp, DpGrad q)
+{
+    const int64_t HW = (int64_t)e.H * e.W;
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    double acc[3] = {};
+    if (p < HW) {
+        const int i = (int)(p / e.W), j = (int)(p - (int64_t)i * e.W);
+        const float ox = e.x1[j], oy = e.y1[i];
+        const int64_t plane = (int64_t)e.Ht * e.Wt;
+        const auto div_fmh = UDiv<M>::make(dp.fmh);
+        double gn[2][NT], gd[2];
+#pragma unroll
+        for (int side = 0; side < 2; ++side) {
+            gd[side] = e.gden ? e.gden[side * HW + p] : 0.0;
+#pragma unroll
+            for (int k = 0; k < NT; ++k) gn[side][k] = e.gnum[side * e.view_stride + k * HW + p];
+        }
+        for (int s = 0; s < e.S; ++s) {
+            const int64_t at_q = (int64_t)s * HW + p;
+            Ray r = make_ray<M>(ox, oy, e.z_sensor, e.x2[at_q], e.y2[at_q], e.z_pupil);
+            const float x_tan = r.dx / (-r.dz);                // what the forward's dp_weights_* call reads
+            if (e.x_tan) e.x_tan[at_q] = x_tan;
+            trace_ray<false, M, true, /*UNIT_W*/ true, /*MASKS*/ false>(e.lens, 0, e.K, kernarg_at(0), r, nullptr);
+            const bool dead = !(r.ra != 0.0f);
+            if (dead) continue;
+            double Tn = 1.0, cn[NT] = {};
+            for (int n = 0; n < e.L; ++n) {
+                if (Tn == 0.0) break;
+                Ray met = r;
+                propagate_to<Ieee>(met, e.depth[n]);
+                const Taps tq(met.ox, met.oy, e.inv_texel[n], e.Ht, e.Wt);
+                const double cover = e.alpha ? tq.read(e.alpha + n * plane) : 1.0;
+                const double share = Tn * cover;
+                const float* __restrict__ tn = e.tex + n * e.layer_stride;
+#pragma unroll
+                for (int k = 0; k < NT; ++k) cn[k] = cn[k] + share * tq.read(tn + k * plane);
+                Tn = Tn * (1.0 - cover);
+            }
+            double A[2];
+#pragma unroll
+            for (int side = 0; side < 2; ++side) {
+                double sum = gn[side][0] * cn[0];
+#pragma unroll
+                for (int k = 1; k < NT; ++k) sum = sum + gn[side][k] * cn[k];
+                A[side] = (double)r.ra * (sum + gd[side]);
+            }
+            if (A[0] == 0.0 && A[1] == 0.0) continue;
+            double dZ[3][3];
+            dz_boundaries<DP == kDpBig, M>(dp, div_fmh, q, x_tan, dZ);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double dwl = dZ[1][c] - dZ[0][c], dwr = dZ[2][c] - dZ[1][c];      // (w_L, w_R) = (s_r, s_l)
+                acc[c] += A[0] * dwl + A[1] * dwr;
+            }
+        }
+    }
+    block_sum_store<3>(acc, e.partial + (int64_t)blockIdx.x * 3);
+}
+
+template <class M, int DP>
+int launch_layers_dp_grad(int nt, dim3 grid, hipStream_t st, const TripTable& tt, const LayersDpGradLaunch& e,
+                          const DevDpParams& dp, const DpGrad& q)
+{
+    switch (nt) {
+    case 1: k_render_layers_dp_grad<M, DP, 1><<<grid, kBlock, 0, st>>>(tt, e, dp, q); break;
+    case 2: k_render_layers_dp_grad<M, DP, 2><<<grid, kBlock, 0, st>>>(tt, e, dp, q); break;
+    case 3: k_render_layers_dp_grad<M, DP, 3><<<grid, kBlock, 0, st>>>(tt, e, dp, q); break;
+    default: k_render_layers_dp_grad<M, DP, kMaxPlanes><<<grid, kBlock, 0, st>>>(tt, e, dp, q); break;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int sdirt_render_plane(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, const float* x1,
@@ -583,6 +700,69 @@ extern "C" int sdirt_render_layers_grad(const sdirt_lens* lens, const int32_t* t
             if (!dp) return launch_layers_grad<Mm, kDpNone>(nt, grid, lds, st, tt, b, dpp);
             return dpp.big ? launch_layers_grad<Mm, kDpBig>(nt, grid, lds, st, tt, b, dpp)
                            : launch_layers_grad<Mm, kDpSmall>(nt, grid, lds, st, tt, b, dpp);
+        });
+        LAUNCH_CHECK();
+    }
+    return SDIRT_OK;
+}
+
+extern "C" int sdirt_render_layers_dp_grad(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, const float* x1,
+                                           const float* y1, double z_sensor, const float* x2, const float* y2,
+                                           double z_pupil, int32_t spp, int32_t height, int32_t width,
+                                           const sdirt_dp_params* dp, int32_t n_layers, const double* depth,
+                                           const double* inv_texel, const float* alpha, const float* tex,
+                                           int64_t tex_layer_stride, int32_t n_tex, int32_t tex_h, int32_t tex_w,
+                                           const double* gnum, const double* gden, double* partial, float* x_tan,
+                                           void* stream)
+{
+    if (!lens) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null lens");
+    if (any_null(x1, y1, x2, y2, depth, inv_texel, tex, gnum, partial)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!dp) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null dp: one view with unit weights has no sub-pixel model");
+    if (!(dp->r > 0.0)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->r must be > 0");
+    if (!(dp->f != dp->h)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "dp->f must differ from dp->h");
+    if (!all_positive(spp, height, width, n_tex, tex_h, tex_w))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "spp, the sensor's and the texture's extents must be at least 1");
+    if (n_layers < 1 || n_layers > SDIRT_MAX_LAYERS)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_layers must be in 1 .. SDIRT_MAX_LAYERS");
+    if ((int64_t)tex_h * tex_w > INT32_MAX) return fail(SDIRT_ERR_INVALID_ARGUMENT, "texture plane above 2^31 texels");
+    if (tex_layer_stride < 0) return fail(SDIRT_ERR_INVALID_ARGUMENT, "negative layer stride");
+    const int64_t HW = (int64_t)height * width;
+    if (HW > (int64_t)INT32_MAX * kBlock) return fail(SDIRT_ERR_INVALID_ARGUMENT, "sensor too large");
+    LayersDpGradLaunch e;
+    for (int l = 0; l < SDIRT_MAX_LAYERS; ++l) {
+        const bool used = l < n_layers;
+        e.depth[l] = used ? (float)depth[l] : 0.0f;
+        e.inv_texel[l] = used ? (float)inv_texel[l] : 0.0f;
+        if (used && !(e.depth[l] < (l ? e.depth[l - 1] : 0.0f)))
+            return fail(SDIRT_ERR_INVALID_ARGUMENT, "layer depths must be negative and strictly descending (nearest first)");
+    }
+    TripTable tt;
+    if (int rc = make_trips(lens, trips, tt)) return rc;
+    const DevDpParams dpp = make_dp(dp);
+    const DpGrad q = make_dp_grad(dp);
+    e.lens = lens->dev; e.K = lens->n_surfaces;
+    e.x1 = x1; e.y1 = y1; e.x2 = x2; e.y2 = y2;
+    e.z_sensor = (float)z_sensor; e.z_pupil = (float)z_pupil;
+    e.S = spp; e.H = height; e.W = width; e.L = n_layers;
+    e.alpha = alpha; e.layer_stride = tex_layer_stride;
+    e.Ht = tex_h; e.Wt = tex_w;
+    e.view_stride = (int64_t)n_tex * HW;
+    e.x_tan = x_tan;
+    const int64_t rows = (HW + kBlock - 1) / kBlock;
+    const dim3 grid((unsigned)rows);
+    hipStream_t st = as_stream(stream);
+    // more than kMaxPlanes colour planes: further launches over the same rays, each into a slice of `partial` of its
+    // own; the adjoint of den belongs to the ray, not to a plane, and is counted in the first launch only
+    for (int t0 = 0; t0 < n_tex; t0 += kMaxPlanes) {
+        const int nt = n_tex - t0 < kMaxPlanes ? n_tex - t0 : kMaxPlanes;
+        e.tex = tex + (int64_t)t0 * tex_h * tex_w;
+        e.gnum = gnum + (int64_t)t0 * HW;
+        e.gden = t0 == 0 ? gden : nullptr;
+        e.partial = partial + (int64_t)(t0 / kMaxPlanes) * rows * 3;
+        with_math(routed_flags(flags, lens), [&](auto m) {
+            using Mm = decltype(m);
+            return dpp.big ? launch_layers_dp_grad<Mm, kDpBig>(nt, grid, st, tt, e, dpp, q)
+                           : launch_layers_dp_grad<Mm, kDpSmall>(nt, grid, st, tt, e, dpp, q);
         });
         LAUNCH_CHECK();
     }

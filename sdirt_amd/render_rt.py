@@ -9,7 +9,8 @@ csrc/sdirt_render_rt.hip); this module is its host side, the reference's two sam
 pure-torch float64 restatement of the lookup and the sums (`plane_sums_float64`) that tests and tools check it with.
 
 The layered render (render_layers, render_rgbd) and the opt-in gradients of all three renders in the
-textures and the coverage (scene_grad=True, sdirt_render_layers_grad) live here as well.
+textures and the coverage (scene_grad=True, sdirt_render_layers_grad) and in the dual-pixel parameters
+h, f, w (dp_grad=True, sdirt_render_layers_dp_grad) live here as well.
 
 Functions take the lens as their first argument; Lensgroup binds them under the reference's method names.
 """
@@ -197,7 +198,7 @@ def _check_render_arguments(lens, img, spp, wvln, pupil_points):
 
 
 def render_plane(lens, img, depth, spp=64, dp=None, wvln=DEFAULT_WAVE, scale=None, pixel_center=True,
-                 photometric=False, pupil_points=None, return_sums=False, scene_grad=False):
+                 photometric=False, pupil_points=None, return_sums=False, scene_grad=False, dp_grad=False):
     """The image(s) the lens forms of the textured plane z = depth (mm, negative), ray traced.
 
     img [B, C, Ht, Wt] fp32 on the lens's device: the texture, spread over scale x the sensor's extent (scale: object
@@ -214,15 +215,19 @@ def render_plane(lens, img, depth, spp=64, dp=None, wvln=DEFAULT_WAVE, scale=Non
     No gradients by default: the call runs without recording, whatever requires one.  scene_grad=True opts in (named
     as local_dp_psf_render_volume names it): in grad mode, with `img` requiring a gradient, the call goes through
     _RenderRecorded and `img` gets the gradient of DESIGN.md §7q (one opaque layer); otherwise scene_grad=True is the
-    plain call.  return_sums together with a recorded gradient raises ValueError."""
+    plain call.  dp_grad=True opts in to the gradient of DESIGN.md §7r in the dual-pixel parameters: h, f, w of dp may
+    then be 0-d tensors, and those that require a gradient get one, in their dtype and on their device (r gets none;
+    dp=None raises ValueError); the two options compose.  Without dp_grad tensors in dp are turned into floats.
+    return_sums together with a recorded gradient raises ValueError."""
     _check_render_arguments(lens, img, spp, wvln, pupil_points)
     recorded = bool(scene_grad) and torch.is_grad_enabled() and img.requires_grad
-    if recorded and return_sums:
+    leaves = _dp_leaves(dp, dp_grad)
+    if (recorded or any(v is not None for v in leaves)) and return_sums:
         raise ValueError("return_sums with a recorded gradient: the float64 sums carry none")
     lens._require_gpu()
     args = (depth, spp, dp, wvln, scale, pixel_center, photometric, pupil_points)
-    if recorded:
-        res = _RenderRecorded.apply(img, None, lens, _plane_forward, args)
+    if recorded or any(v is not None for v in leaves):
+        res = _recorded_call(lens, img, None, _plane_forward, args, recorded, leaves)
         return res if dp is not None else res[0]
     with torch.no_grad():
         return _plane_forward(lens, img, None, *args, return_sums=return_sums)
@@ -262,7 +267,7 @@ def _plane_forward(lens, img, alpha, depth, spp, dp, wvln, scale, pixel_center, 
                 record["chunks"].append((g, x2.to(lens.device, torch.float32), y2.to(lens.device, torch.float32),
                                          part["trips"]))
     if record is not None:
-        record.update(wv=[g[0] for g in groups], den=dens, depths=[float(depth)], inv_texels=[inv_texel], dp=dp,
+        record.update(wv=[g[0] for g in groups], den=dens, num=nums, depths=[float(depth)], inv_texels=[inv_texel], dp=dp,
                       pixel_center=pixel_center, spp=spp, photometric=photometric, chroma=chroma, plane=True)
     if chroma:
         num, den = torch.stack(nums, 2), torch.stack(dens, 1)               # [V, B, C, H, W], [V, C, H, W]
@@ -390,7 +395,7 @@ def layer_batch(lens, alpha, tex, depths, inv_texels, x2, y2, dp=None, wvln=DEFA
 
 
 def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, scales=None, pixel_center=True,
-                  photometric=False, pupil_points=None, return_sums=False, scene_grad=False):
+                  photometric=False, pupil_points=None, return_sums=False, scene_grad=False, dp_grad=False):
     """The image(s) the lens forms of a stack of fronto-parallel layers, ray traced with occlusion.
 
     img [L, C, Ht, Wt] fp32, or [C, Ht, Wt] shared by all layers; alpha [L, Ht, Wt] fp32 in [0, 1]: layer l covers the
@@ -404,7 +409,10 @@ def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, 
     No gradients by default.  scene_grad=True opts in: in grad mode, with `img` or `alpha` requiring a gradient, the
     call goes through _RenderRecorded and both get the gradient of DESIGN.md §7q (fp32, of their own shape; a shared
     image gets the sum over its layers); otherwise scene_grad=True is the plain call.  dp, the lens, depths, scales and
-    pupil_points get none.  return_sums together with a recorded gradient raises ValueError."""
+    pupil_points get none.  dp_grad=True opts in to the gradient of DESIGN.md §7r: h, f, w of dp may then be 0-d
+    tensors, and those that require a gradient get one, in their dtype and on their device (r gets none; dp=None raises
+    ValueError); the two options compose, one backward running both kernels from the one record.  return_sums together
+    with a recorded gradient raises ValueError."""
     if not torch.is_tensor(img) or img.dim() not in (3, 4):
         raise ValueError("img must be a [L, C, Ht, Wt] tensor, or [C, Ht, Wt] shared by all layers")
     if scales is not None and len(scales) != len(depths):
@@ -414,12 +422,13 @@ def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, 
     if alpha.device != lens.device:
         raise ValueError(f"alpha is on {alpha.device}, the lens on {lens.device}")
     recorded = bool(scene_grad) and torch.is_grad_enabled() and (img.requires_grad or alpha.requires_grad)
-    if recorded and return_sums:
+    leaves = _dp_leaves(dp, dp_grad)
+    if (recorded or any(v is not None for v in leaves)) and return_sums:
         raise ValueError("return_sums with a recorded gradient: the float64 sums carry none")
     lens._require_gpu()
     args = (depths, spp, dp, wvln, scales, pixel_center, photometric, pupil_points)
-    if recorded:
-        res = _RenderRecorded.apply(img, alpha, lens, _layers_forward, args)
+    if recorded or any(v is not None for v in leaves):
+        res = _recorded_call(lens, img, alpha, _layers_forward, args, recorded, leaves)
         return res if dp is not None else res[0]
     with torch.no_grad():
         return _layers_forward(lens, img, alpha, *args, return_sums=return_sums)
@@ -460,7 +469,7 @@ def _layers_forward(lens, img, alpha, depths, spp, dp, wvln, scales, pixel_cente
                 record["chunks"].append((g, x2.to(lens.device, torch.float32), y2.to(lens.device, torch.float32),
                                          part["trips"]))
     if record is not None:
-        record.update(wv=[g[0] for g in groups], den=dens, depths=[float(d) for d in depths], inv_texels=inv_texels,
+        record.update(wv=[g[0] for g in groups], den=dens, num=nums, depths=[float(d) for d in depths], inv_texels=inv_texels,
                       dp=dp, pixel_center=pixel_center, spp=spp, photometric=photometric, chroma=chroma, plane=False)
     if chroma:
         num, den, cov = torch.cat(nums, 1), torch.stack(dens, 1), torch.stack(covs, 1)     # [V, C, H, W] each
@@ -520,7 +529,7 @@ def uniform_layer_depths(depth, n_layers):
 
 
 def render_rgbd(lens, img, depth, layer_depths=None, n_layers=8, spp=64, dp=None, wvln=DEFAULT_WAVE, scales=None,
-                pixel_center=True, photometric=False, pupil_points=None, extend=True, scene_grad=False):
+                pixel_center=True, photometric=False, pupil_points=None, extend=True, scene_grad=False, dp_grad=False):
     """The ray-traced dual-pixel pair of an RGB-D frame -- the input PSFNet.render takes -- with occlusion: img
     [B, C, H, W] fp32, depth [B, 1, H, W] (mm, negative).  Every frame is cut into layers by layers_from_rgbd (at
     layer_depths, or at n_layers depths uniform in 1 / depth between the frame's nearest and farthest) that all show
@@ -528,14 +537,17 @@ def render_rgbd(lens, img, depth, layer_depths=None, n_layers=8, spp=64, dp=None
     scales: calc_scale_ray once per distinct stack of depths, so frames that share their layers register alike).
     -> (L, R) with dp, else one image, each [B, C, H, W] fp32.
     No gradients by default.  scene_grad=True: render_layers' -- img[b], which all layers of frame b show, gets the
-    gradient summed over its layers; `depth` gets none (layers_from_rgbd is a hard assignment)."""
-    with torch.set_grad_enabled(bool(scene_grad) and torch.is_grad_enabled()):
+    gradient summed over its layers; `depth` gets none (layers_from_rgbd is a hard assignment).  dp_grad=True:
+    render_layers' -- h, f, w get the sum over the batch."""
+    if dp_grad and dp is None:
+        raise ValueError("dp_grad=True with dp=None: one view with unit weights has no sub-pixel model")
+    with torch.set_grad_enabled((bool(scene_grad) or bool(dp_grad)) and torch.is_grad_enabled()):
         return _render_rgbd(lens, img, depth, layer_depths, n_layers, spp, dp, wvln, scales, pixel_center, photometric,
-                            pupil_points, extend, scene_grad)
+                            pupil_points, extend, scene_grad, dp_grad)
 
 
 def _render_rgbd(lens, img, depth, layer_depths, n_layers, spp, dp, wvln, scales, pixel_center, photometric,
-                 pupil_points, extend, scene_grad):
+                 pupil_points, extend, scene_grad, dp_grad=False):
     if not torch.is_tensor(img) or img.dim() != 4:
         raise ValueError("img must be a [B, C, H, W] tensor")
     if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1 or depth.shape[0] != img.shape[0] \
@@ -552,7 +564,7 @@ def _render_rgbd(lens, img, depth, layer_depths, n_layers, spp, dp, wvln, scales
         out = render_layers(lens, img[b], alpha, zs, spp=spp, dp=dp, wvln=wvln,
                             scales=scales_of[tuple(zs)] if scales is None else scales,
                             pixel_center=pixel_center, photometric=photometric, pupil_points=pupil_points,
-                            scene_grad=scene_grad)
+                            scene_grad=scene_grad, dp_grad=dp_grad)
         views.append(out if dp is not None else (out,))
     res = tuple(torch.stack(v) for v in zip(*views))
     return res if dp is not None else res[0]
@@ -714,23 +726,217 @@ def layer_grad_batch(lens, alpha, tex, depths, inv_texels, x2, y2, trips, gnum, 
     return galpha, gtex
 
 
+# ------------------------------------------------------------------------------------ gradients in h, f, w
+def gden_from_image_grad(G, num_total, den_total, photometric=False):
+    """The adjoint of the float64 sums `den` from the adjoint G of the image(s) num / den:
+    gden[side] = -sum_k G[side, k] num_total[side, k] / den_total[side]^2 where den_total > 0 and 0 elsewhere, float64
+    [V, H, W]; the sum runs over every dimension between the view and the pixel.  G and num_total [V, ..., H, W],
+    den_total [V, H, W]: the TOTALS over every chunk of samples.  photometric: the image is num / spp, den has no
+    adjoint: -> None."""
+    if photometric:
+        return None
+    G, num_total = G.double(), num_total.double()
+    if G.shape != num_total.shape or G.dim() < 3 or tuple(den_total.shape) != (G.shape[0],) + tuple(G.shape[-2:]):
+        raise ValueError(f"G and num_total must be one [V, ..., H, W], den_total [V, H, W]; got {tuple(G.shape)}, "
+                         f"{tuple(num_total.shape)} and {tuple(den_total.shape)}")
+    s = (G * num_total).reshape(G.shape[0], -1, *G.shape[-2:]).sum(1)
+    ok = den_total > 0
+    d = torch.where(ok, den_total, torch.ones_like(den_total))
+    return torch.where(ok, -s / (d * d), torch.zeros_like(s))
+
+
+def _dz_float64(t, h, f, w, r):
+    """d/d(h, f, w) of the three boundaries' Z_a (a = +1, 0, -1: right, middle, left) of the sub-pixel model at
+    x_tan = t (float64, any shape) -> [3 (a), 3 (h, f, w), ...] float64, by the formulas of DESIGN.md §7r: with x1 the
+    boundary projected through the microlens, x2 the margin boundary and A'(x) = -2 sqrt(max((r - x)(r + x), 0)),
+      r <= 0.5:  dZ = [|x1| <= r] A'(x1) dx1 + [|x2| <= 0.5] (-1 - [|x2| <= r] A'(x2)) dx2
+      r >  0.5:  dZ = [|x1| <= 0.5] T'(x1) dx1 + [|x2| <= 0.5] (-1 - T'(x2)) dx2,  T'(x) = -1 where |x| <= sqrt(r^2 - 1/4),
+                 else A'(x)
+      dx1 = (-u f / D^2, -h t / D + u h / D^2, a f / D),  u = f t - a w,  D = f - h;      dx2 = (-t, 0, a).
+    Every decision is taken in float64 here, by the kernel on the forward's fp32 values: a ray within rounding of
+    |x2| = 0.5 (or, r > 0.5, |x1| = 0.5), where the derivative jumps, can come out on the other side."""
+    D = f - h
+    zero = torch.zeros_like(t)
+
+    def chord(x):
+        return -2.0 * torch.sqrt(torch.clamp((r - x) * (r + x), min=0.0))
+
+    rows = []
+    for a in (1.0, 0.0, -1.0):
+        u = f * t - a * w
+        x1 = a * w - u * h / D
+        x2 = a * w - h * t
+        if r <= 0.5:
+            c1 = torch.where(x1.abs() <= r, chord(x1), zero)
+            c2 = torch.where(x2.abs() <= 0.5, -1.0 - torch.where(x2.abs() <= r, chord(x2), zero), zero)
+        else:
+            edge = (r * r - 0.25) ** 0.5
+            c1 = torch.where(x1.abs() <= 0.5, torch.where(x1.abs() <= edge, -torch.ones_like(t), chord(x1)), zero)
+            c2 = torch.where(x2.abs() <= 0.5, -1.0 - torch.where(x2.abs() <= edge, -torch.ones_like(t), chord(x2)), zero)
+        d1 = (-u * f / (D * D), -h * t / D + u * h / (D * D), a * f / D + zero)
+        d2 = (-t, zero, a + zero)
+        rows.append(torch.stack([c1 * d1[j] + c2 * d2[j] for j in range(3)]))
+    return torch.stack(rows)
+
+
+def layer_dp_grads_float64(landing, x_tan, alpha, tex, inv_texels, gnum, gden, dp, return_abs=False):
+    """The adjoint of DESIGN.md §7r from the forward's landing record, in plain torch and without autograd: what
+    sdirt_render_layers_dp_grad's partial rows add up to.
+
+    landing, alpha (None: every layer opaque), tex, inv_texels as in layer_sums_float64; x_tan [S, H, W] fp32: the
+    kernel's x_tan of every ray; gnum [2, T, H, W], gden [2, H, W] or None, float64; dp = (h, f, w, r).
+    Per live ray: c_k by the forward's walk (a layer behind T == 0 is not read), A_side = ra (gnum[side, 0] c_0 + ... +
+    gden[side]), and the term A_0 dw_L + A_1 dw_R with (w_L, w_R) = (s_r, s_l), dw_L = dZ_m - dZ_r, dw_R = dZ_l - dZ_m
+    (_dz_float64).  -> [3] float64 (h, f, w); with return_abs also [3] the sums of |A_0 dw_L| + |A_1 dw_R|."""
+    landing = torch.as_tensor(landing, dtype=torch.float32)
+    dev = landing.device
+    tex = torch.as_tensor(tex, dtype=torch.float32, device=dev)
+    gnum = torch.as_tensor(gnum, dtype=torch.float64, device=dev)
+    x_tan = torch.as_tensor(x_tan, dtype=torch.float32, device=dev)
+    L = len(inv_texels)
+    if landing.shape[0] != 3 + 2 * L:
+        raise ValueError(f"{L} layers need a landing record of {3 + 2 * L} rows and {L} inv_texels")
+    if alpha is not None:
+        alpha = torch.as_tensor(alpha, dtype=torch.float32, device=dev)
+        if alpha.shape[0] != L:
+            raise ValueError(f"alpha has {alpha.shape[0]} layers, inv_texels {L}")
+    if x_tan.shape != landing.shape[1:]:
+        raise ValueError(f"x_tan must be {tuple(landing.shape[1:])}, got {tuple(x_tan.shape)}")
+    shared = tex.dim() == 3
+    NT = int(tex.shape[-3])
+    if tuple(gnum.shape) != (2, NT) + tuple(landing.shape[2:]):
+        raise ValueError(f"gnum must be {(2, NT) + tuple(landing.shape[2:])}, got {tuple(gnum.shape)}")
+    if gden is not None:
+        gden = torch.as_tensor(gden, dtype=torch.float64, device=dev)
+        if tuple(gden.shape) != (2,) + tuple(landing.shape[2:]):
+            raise ValueError(f"gden must be {(2,) + tuple(landing.shape[2:])}, got {tuple(gden.shape)}")
+    h, f, w, r = (float(v) for v in dp)
+    ra = landing[0]
+    live = ra != 0
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    T = torch.ones(ra.shape, dtype=torch.float64, device=dev)
+    c = torch.zeros((NT,) + tuple(ra.shape), dtype=torch.float64, device=dev)
+    for l in range(L):
+        reads = live & (T != 0)                                 # the forward's walk ends where T reaches 0
+        px, py = landing[3 + 2 * l], landing[4 + 2 * l]
+        a = torch.ones_like(T) if alpha is None else _bilinear_float64(alpha[l:l + 1], px, py, inv_texels[l], reads)[0]
+        t = _bilinear_float64(tex if shared else tex[l], px, py, inv_texels[l], reads)
+        g = T * a
+        c = torch.where(reads, c + g * t, c)
+        T = torch.where(reads, T * (1 - a), T)
+    A = []
+    for side in range(2):
+        s = gnum[side, 0] * c[0]
+        for k in range(1, NT):
+            s = s + gnum[side, k] * c[k]
+        if gden is not None:
+            s = s + gden[side]
+        A.append(torch.where(live, ra.double() * s, zero))
+    dZ = _dz_float64(x_tan.double(), h, f, w, r)                                             # [3, 3, S, H, W]
+    dwl, dwr = dZ[1] - dZ[0], dZ[2] - dZ[1]
+    used = live & ((A[0] != 0) | (A[1] != 0))
+    grad = torch.where(used, A[0] * dwl + A[1] * dwr, zero).flatten(1).sum(1)
+    if not return_abs:
+        return grad
+    return grad, torch.where(used, (A[0] * dwl).abs() + (A[1] * dwr).abs(), zero).flatten(1).sum(1)
+
+
+def layer_dp_grad_batch(lens, alpha, tex, depths, inv_texels, x2, y2, trips, gnum, gden, dp, wvln=DEFAULT_WAVE,
+                        pixel_center=True, x_tan=False):
+    """ONE call of sdirt_render_layers_dp_grad: the counterpart of layer_batch (same scene, pupil points, dp, wvln and
+    pixel_center), with `trips` the table that call ended with, gnum [2, T, H, W] float64 the adjoint of its num and
+    gden [2, H, W] float64 the adjoint of its den, or None.  alpha=None: every layer opaque (render_plane's scene with
+    L = 1).  -> [3] float64 on the lens's device: the gradient in (h, f, w), the entry's partial rows
+    [ceil(T / 4), ceil(H W / 256), 3] added by one .sum over that fixed layout -- the same bits on every run;
+    x_tan=True: -> (that, x_tan [S, H, W] fp32: the kernel's x_tan of every ray)."""
+    dev = lens.device
+    if dp is None:
+        raise ValueError("dp=None: one view with unit weights has no sub-pixel model to differentiate")
+    if alpha is None:
+        if not torch.is_tensor(tex) or tex.dim() not in (3, 4) or tex.dtype != torch.float32:
+            raise ValueError("the layers' image must be a float32 [L, C, Ht, Wt] tensor, or [C, Ht, Wt] shared by all layers")
+        shared = tex.dim() == 3
+        L, (T, Ht, Wt) = len(depths), (int(v) for v in tex.shape[-3:])
+        if not 1 <= L <= _lib.MAX_LAYERS or len(inv_texels) != L or (not shared and int(tex.shape[0]) != L):
+            raise ValueError(f"{L} depths, {len(inv_texels)} scales and an image of {tuple(tex.shape)}: layers differ")
+    else:
+        L, T, Ht, Wt, shared = _check_layers(alpha, tex, depths, inv_texels, scan=False)
+        if alpha.device != dev:
+            raise ValueError("alpha and tex must be on the lens's device")
+        alpha = alpha.contiguous()
+    if tex.device != dev:
+        raise ValueError("alpha and tex must be on the lens's device")
+    h, f, w, r = (float(v) for v in dp)
+    if not r > 0 or f == h:
+        raise ValueError("dp: r must be > 0 and f must differ from h")
+    H, W = (int(v) for v in lens.sensor_res)
+    S = int(x2.shape[0])
+    K = len(lens.surfaces)
+    if tuple(x2.shape) != (S, H, W) or tuple(y2.shape) != (S, H, W):
+        raise ValueError(f"pupil points must be [spp, {H}, {W}], got {tuple(x2.shape)} and {tuple(y2.shape)}")
+    if len(trips) != K:
+        raise ValueError(f"{len(trips)} trip counts for a lens of {K} surfaces")
+    if not torch.is_tensor(gnum) or gnum.dtype != torch.float64 or gnum.device != dev or tuple(gnum.shape) != (2, T, H, W):
+        raise ValueError(f"gnum must be float64 {(2, T, H, W)} on the lens's device")
+    if gden is not None and (not torch.is_tensor(gden) or gden.dtype != torch.float64 or gden.device != dev
+                             or tuple(gden.shape) != (2, H, W)):
+        raise ValueError(f"gden must be float64 {(2, H, W)} on the lens's device, or None")
+    lens._require_gpu()
+    x1, y1 = sensor_axes(lens, pixel_center)
+    x2 = x2.to(dev, torch.float32).contiguous()
+    y2 = y2.to(dev, torch.float32).contiguous()
+    tex, gnum = tex.contiguous(), gnum.contiguous()
+    gden = None if gden is None else gden.contiguous()
+    partial = torch.empty(((T + 3) // 4, (H * W + 255) // 256, 3), dtype=torch.float64, device=dev)
+    xt = torch.empty((S, H, W), dtype=torch.float32, device=dev) if x_tan else None
+    dpp = C.byref(_lib.DpParams(h, f, w, r))
+    z = (C.c_double * L)(*(float(d) for d in depths))
+    inv = (C.c_double * L)(*(float(v) for v in inv_texels))
+    pupilz, _ = lens.exit_pupil()
+    wv = float(wvln if wvln < 10 else wvln * 1e-3)
+    with lens._timed("render_layers_dp_grad"):
+        _lib.check(_lib.lib().sdirt_render_layers_dp_grad(
+            lens.dev_lens(wv), (C.c_int32 * K)(*[int(t) for t in trips]), lens._math_flags(), dptr(x1), dptr(y1),
+            float(lens.d_sensor), dptr(x2), dptr(y2), float(pupilz), S, H, W, dpp, L, z, inv, dptr(alpha), dptr(tex),
+            0 if shared else T * Ht * Wt, T, Ht, Wt, dptr(gnum), dptr(gden), dptr(partial), dptr(xt), stream_ptr(dev)))
+    grad = partial.view(-1, 3).sum(0)
+    return (grad, xt) if x_tan else grad
+
+
+def _dp_leaves(dp, dp_grad):
+    """The tensors among dp's h, f, w that get a gradient from a dp_grad=True call: -> (h, f, w) with None where the
+    entry is no tensor or requires none; all None without dp_grad, outside grad mode, or without such a tensor."""
+    if not dp_grad:
+        return (None, None, None)
+    if dp is None:
+        raise ValueError("dp_grad=True with dp=None: one view with unit weights has no sub-pixel model")
+    if not torch.is_grad_enabled():
+        return (None, None, None)
+    return tuple(v if torch.is_tensor(v) and v.requires_grad else None for v in tuple(dp)[:3])
+
+
 class _RenderRecorded(torch.autograd.Function):
-    """render_plane / render_layers(scene_grad=True) under autograd.  The forward is the plain call (the same
-    launches, the same images in every bit), which also keeps, per chunk of samples and wavelength group, the pupil
-    points x2, y2 -- 8 bytes per ray, the only record that grows with the sample count -- and the trip table the
-    launch ended with, and per call the wavelengths, pixel_center, dp, the depths, the inv_texels and the TOTAL den of
-    every group.  The backward forms gnum = G / den_total (gnum_from_image_grad) once per wavelength group, zeroes
-    float64 buffers of the inputs' shapes, runs sdirt_render_layers_grad over every recorded chunk into them and returns
-    them in the inputs' dtype.  It traces through the lens AS IT STANDS THEN: a lens changed (surfaces, sensor, focus,
-    precision) between forward and backward is the caller's error."""
+    """render_plane / render_layers(scene_grad=True and / or dp_grad=True) under autograd.  The forward is the plain
+    call (the same launches, the same images in every bit), which also keeps, per chunk of samples and wavelength
+    group, the pupil points x2, y2 -- 8 bytes per ray, the only record that grows with the sample count -- and the trip
+    table the launch ended with, and per call the wavelengths, pixel_center, dp, the depths, the inv_texels and the
+    TOTAL den and num of every group.  The backward forms gnum = G / den_total (gnum_from_image_grad) once per
+    wavelength group and runs over every recorded chunk
+      sdirt_render_layers_grad into zeroed float64 buffers of the inputs' shapes, where img or alpha
+      takes a gradient, and
+      sdirt_render_layers_dp_grad with gden = gden_from_image_grad, where h, f or w does: the chunks'
+      and the groups' [3] are added in the order recorded;
+    and returns them in the inputs' dtype (h, f, w: on their device).  It traces through the lens AS IT STANDS THEN: a
+    lens changed (surfaces, sensor, focus, precision) between forward and backward is the caller's error."""
 
     @staticmethod
-    def forward(ctx, img, alpha, lens, run, args):
+    def forward(ctx, img, alpha, lens, run, args, h=None, f=None, w=None):
         record = {"chunks": []}
         with torch.no_grad():
             res = run(lens, img, alpha, *args, record=record)
         res = res if isinstance(res, tuple) else (res,)
         ctx.lens, ctx.record = lens, record
+        ctx.dp_leaves = tuple((v.dtype, v.device) if v is not None else None for v in (h, f, w))
         ctx.save_for_backward(img, *(() if alpha is None else (alpha,)))
         ctx.set_materialize_grads(False)
         return res
@@ -740,34 +946,46 @@ class _RenderRecorded(torch.autograd.Function):
         lens, rec = ctx.lens, ctx.record
         img, alpha = (ctx.saved_tensors + (None,))[:2]
         need_img, need_alpha = ctx.needs_input_grad[0], alpha is not None and ctx.needs_input_grad[1]
-        if all(g is None for g in G) or not (need_img or need_alpha):
-            return None, None, None, None, None
+        need_dp = [leaf is not None and need for leaf, need in zip(ctx.dp_leaves, ctx.needs_input_grad[5:8])]
+        none = (None,) * 8
+        if all(g is None for g in G) or not (need_img or need_alpha or any(need_dp)):
+            return none
         shape = next(g.shape for g in G if g is not None)
         G = torch.stack([torch.zeros(shape, dtype=torch.float64, device=lens.device) if g is None else g.double()
                          for g in G])                                     # [V, (B,) C, H, W]
         H, W = (int(v) for v in shape[-2:])
         Ht, Wt = (int(v) for v in img.shape[-2:])
         V, chroma, plane = G.shape[0], rec["chroma"], rec["plane"]
+        scene = need_img or need_alpha
         with torch.no_grad():
             gimg = torch.zeros(img.shape, dtype=torch.float64, device=lens.device) if need_img else None
             galpha = torch.zeros(alpha.shape, dtype=torch.float64, device=lens.device) if need_alpha else None
-            # per wavelength group: the forward's planes, their adjoint, and the buffer their gradient is added to
+            # per wavelength group: the forward's planes, their image adjoint, and the buffer their gradient is added to
             if not chroma:
                 texs = [img.detach().reshape(-1, Ht, Wt) if plane else img.detach()]
-                gnums = [gnum_from_image_grad(G.reshape(V, -1, H, W), rec["den"][0], rec["spp"], rec["photometric"])]
+                Gs = [G.reshape(V, -1, H, W)]
                 gtexs = [(gimg.view(-1, Ht, Wt) if plane else gimg) if need_img else None]
             else:
-                texs, gnums, gtexs = [], [], []
+                texs, Gs, gtexs = [], [], []
                 for c in range(len(rec["wv"])):
                     ch = img.detach()[:, c] if plane else (img.detach()[c:c + 1] if img.dim() == 3 else img.detach()[:, c:c + 1])
                     texs.append(ch.contiguous())
-                    gnums.append(gnum_from_image_grad(G[:, :, c] if plane else G[:, c:c + 1], rec["den"][c], rec["spp"],
-                                                      rec["photometric"]))
+                    Gs.append(G[:, :, c] if plane else G[:, c:c + 1])
                     gtexs.append(torch.zeros(texs[-1].shape, dtype=torch.float64, device=lens.device) if need_img else None)
+            gnums = [gnum_from_image_grad(Gg, rec["den"][g], rec["spp"], rec["photometric"]).contiguous()
+                     for g, Gg in enumerate(Gs)]
+            if any(need_dp):
+                gdens = [gden_from_image_grad(Gg, rec["num"][g], rec["den"][g], rec["photometric"]) for g, Gg in enumerate(Gs)]
+                gdp = torch.zeros(3, dtype=torch.float64, device=lens.device)
+            stack = None if plane else alpha.detach()
             for g, x2, y2, trips in rec["chunks"]:
-                layer_grad_batch(lens, None if plane else alpha.detach(), texs[g], rec["depths"], rec["inv_texels"], x2, y2,
-                                 trips, gnums[g].contiguous(), rec["dp"], rec["wv"][g], rec["pixel_center"],
-                                 galpha=galpha if need_alpha else False, gtex=gtexs[g] if need_img else False)
+                if scene:
+                    layer_grad_batch(lens, stack, texs[g], rec["depths"], rec["inv_texels"], x2, y2, trips, gnums[g],
+                                     rec["dp"], rec["wv"][g], rec["pixel_center"],
+                                     galpha=galpha if need_alpha else False, gtex=gtexs[g] if need_img else False)
+                if any(need_dp):
+                    gdp += layer_dp_grad_batch(lens, stack, texs[g], rec["depths"], rec["inv_texels"], x2, y2, trips,
+                                               gnums[g], gdens[g], rec["dp"], rec["wv"][g], rec["pixel_center"])
             if chroma and need_img:
                 for c, gt in enumerate(gtexs):
                     if plane:
@@ -776,8 +994,22 @@ class _RenderRecorded(torch.autograd.Function):
                         gimg[c:c + 1] = gt
                     else:
                         gimg[:, c:c + 1] = gt
+            gleaf = [gdp[j].to(device=leaf[1], dtype=leaf[0]) if need else None
+                     for j, (leaf, need) in enumerate(zip(ctx.dp_leaves, need_dp))]
         return (gimg.to(img.dtype) if need_img else None, galpha.to(alpha.dtype) if need_alpha else None,
-                None, None, None)
+                None, None, None, *gleaf)
+
+
+def _recorded_call(lens, img, alpha, run, args, scene, leaves):
+    """The call through _RenderRecorded: img and alpha take part in the record only where scene_grad recorded them
+    (a dp_grad=True call alone leaves them without a gradient, whatever they require), h, f, w where dp_grad did; the
+    forward runs with dp as floats."""
+    dp = args[2]
+    floats = None if dp is None else tuple(float(v.detach()) if torch.is_tensor(v) else float(v) for v in dp)
+    args = args[:2] + (floats,) + args[3:]
+    if not scene:
+        img, alpha = img.detach(), None if alpha is None else alpha.detach()
+    return _RenderRecorded.apply(img, alpha, lens, run, args, *leaves)
 
 
 def render_single_img(lens, img_org, depth=DEPTH, spp=64, unwarp=False, save_name=None, return_tensor=False, noise=0,
