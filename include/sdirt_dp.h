@@ -362,6 +362,37 @@ int sdirt_render_layers_dp_grad(const sdirt_lens* lens, const int32_t* trips /*h
                                 double* partial /*dev [ceil(T/4),ceil(HW/256),3], OVERWRITTEN*/,
                                 float* x_tan /*dev [S,H,W] or NULL*/, void* stream);
 
+/* The backward pass of sdirt_render_layers into the layer depths and the layers' texel scales: a
+ * reduction.  Every argument up to tex_w is sdirt_render_layers_grad's (alpha may be NULL: every layer opaque, the ray
+ * meets layer 0 only); trips is the table the forward ENDED with; gnum is the adjoint of num.  den and ra do not depend
+ * on the depths: there is no gden.  A depth enters only after the trace, px_l = ox + dx (z_l - oz) / dz and
+ * u = Wt/2 - px_l inv_l, v = Ht/2 + py_l inv_l.  For a ray with ra != 0 of pixel p, in float64, one rounding per
+ * operation: sx = dx / dz, sy = dy / dz of the fp32 ray the trace left; q_k, T_l, a_l, t_{l,k}, g_l = T_l a_l, D_l,
+ * R_l and e_l = T_l (D_l - R_{l+1}) are sdirt_render_layers_grad's; every lookup's derivative is taken from its four
+ * taps, d/dfu = (1 - fv)(v01 - v00) + fv (v11 - v10), d/dfv = (1 - fu)(v10 - v00) + fu (v11 - v01) (two taps on one
+ * texel under replicate addressing: an exact 0);
+ *   Pu_l = e_l da_l/dfu + g_l (q_0 dt_{l,0}/dfu + q_1 dt_{l,1}/dfu + ...),  Pv_l alike with fv,
+ *   gz_l = inv_l (Pv_l sy - Pu_l sx),   ginv_l = Pv_l py_l - Pu_l px_l       (fp32 px_l, py_l, inv_l widened).
+ * The derivative is that of the piecewise-bilinear function, almost everywhere.
+ *   partial[g, b, l, 0..1] = the sums of gz_l and ginv_l over workgroup b (256 consecutive pixels of the row-major
+ *                            sensor, each lane its samples in order) for the g-th group of four planes
+ * partial is [ceil(n_tex / 4), ceil(H W / 256), L, 2] float64 and is OVERWRITTEN; the caller adds its rows (every term is
+ * linear in q, so the plane groups add).  No atomics: the same bits on every run.  ray_dir, when given, receives dx,
+ * dy, dz of every ray as the trace left it, dead rays included.  Dynamic LDS: 8 KB per layer (4 KB with a NULL alpha).
+ * Refuses what sdirt_render_layers_grad refuses, a NULL gnum and a NULL partial.  Never allocates, never synchronises. */
+int sdirt_render_layers_depth_grad(const sdirt_lens* lens, const int32_t* trips /*host [K]: the forward's final table*/,
+                                   uint32_t flags, const float* x1 /*dev [W]*/, const float* y1 /*dev [H]*/,
+                                   double z_sensor, const float* x2 /*dev [S,H,W]*/, const float* y2 /*dev [S,H,W]*/,
+                                   double z_pupil, int32_t spp, int32_t height, int32_t width,
+                                   const sdirt_dp_params* dp /*host, or NULL: one view, unit weights*/,
+                                   int32_t n_layers, const double* depth /*host [L]*/, const double* inv_texel /*host [L]*/,
+                                   const float* alpha /*dev [L,Ht,Wt] in [0, 1], or NULL: opaque*/,
+                                   const float* tex /*dev [L,T,Ht,Wt], or [T,Ht,Wt] with stride 0*/,
+                                   int64_t tex_layer_stride, int32_t n_tex, int32_t tex_h, int32_t tex_w,
+                                   const double* gnum /*dev [V,T,H,W], V = dp ? 2 : 1*/,
+                                   double* partial /*dev [ceil(T/4),ceil(HW/256),L,2], OVERWRITTEN*/,
+                                   float* ray_dir /*dev [3,S,H,W] or NULL*/, void* stream);
+
 /* Centroid part of Lensgroup.psf_center, deeplens/optics.py:902-904:
  * center[n] = -(sum_s o*ra / (sum_s ra + 1e-9)).xy (sums in float64);  any_valid (dev int32,
  * zeroed by caller, may be NULL) is set to 1 if any ray has ra == 1.  Point-major bundle. */

@@ -112,6 +112,9 @@ SIGNATURES = {
     "sdirt_render_layers_dp_grad": (C.c_int, [_P, C.POINTER(_I32), _U32, _P, _P, _D, _P, _P, _D, _I32, _I32, _I32,
                                               C.POINTER(DpParams), _I32, C.POINTER(_D), C.POINTER(_D), _P, _P, _I64,
                                               _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "sdirt_render_layers_depth_grad": (C.c_int, [_P, C.POINTER(_I32), _U32, _P, _P, _D, _P, _P, _D, _I32, _I32, _I32,
+                                                 C.POINTER(DpParams), _I32, C.POINTER(_D), C.POINTER(_D), _P, _P, _I64,
+                                                 _I32, _I32, _I32, _P, _P, _P, _P]),
     "sdirt_center_from_rays": (C.c_int, [Rays, _I64, _I64, _P, _P, _P]),
     "sdirt_forward_integral": (C.c_int, [Rays, _I64, _I64, _D, _I32, _P, C.POINTER(DpParams), _U32,
                                          _P, _P, _P]),

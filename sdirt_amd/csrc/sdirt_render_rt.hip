@@ -10,6 +10,9 @@
 // A fourth, k_render_layers_dp_grad, is its backward pass into the dual-pixel parameters h, f, w: the
 // same rays once more, the weights' derivative per ray (sdirt_dp_grad.hpp), one row of three sums per workgroup --
 // no atomics, the same bits on every run.
+// A fifth, k_render_layers_depth_grad, is its backward pass into the layer depths and the layers' texel scales
+// (DESIGN.md §7s): a layer's depth enters only after the trace, so the derivative is a bilinear lookup's derivative
+// times the ray's slope, pushed through §7q's compositing adjoint; one row of 2 L sums per workgroup, no atomics.
 #include <hip/hip_runtime.h>
 
 #include "../../include/sdirt_dp.h"
@@ -541,6 +544,223 @@ int launch_layers_dp_grad(int nt, dim3 grid, hipStream_t st, const TripTable& tt
     return 0;
 }
 
+// ---- the layered render's backward into the layer depths and texel scales ---------------------------
+
+// Everything of a depth backward launch behind the trip table.  (Named z in the kernel, its layers `lay`, its ray at a
+// layer `there`, its weights wz: the statements of the four kernels above, which tools/variants/*.py find by their
+// text, stay unique.)
+struct LayersDepthGradLaunch {
+    const DevSurface* lens;
+    int K;
+    const float* x1;
+    const float* y1;
+    const float* x2;
+    const float* y2;
+    float z_sensor, z_pupil;
+    int S, H, W, L;
+    float depth[SDIRT_MAX_LAYERS];
+    float inv_texel[SDIRT_MAX_LAYERS];
+    const float* alpha;                // [L, Ht, Wt], or null: every layer opaque
+    const float* tex;                  // the first plane of this launch in layer 0
+    int64_t layer_stride;
+    int Ht, Wt;
+    int64_t view_stride;               // elements between the views of gnum: n_tex H W
+    const double* gnum;                // this launch's first plane of view 0
+    double* partial;                   // this launch's [ceil(H W / kBlock), L, 2], OVERWRITTEN
+    float* ray_dir;                    // [3, S, H, W] or null
+};
+
+// Taps with the lookup's two fractions kept: what the derivative of a lookup in (fu, fv) is made of.  fu, fv are formed
+// by Taps' own fp32 statements on the same arguments (the same bits; the compiler folds the two copies into one), so
+// the floor decisions are the forward's.
+struct SlopeTaps {
+    Taps at;
+    double du, dv;
+    __device__ __forceinline__ SlopeTaps(float px, float py, float inv_texel, int Ht, int Wt)
+        : at(px, py, inv_texel, Ht, Wt)
+    {
+        const float half_w = (float)Wt * 0.5f, half_h = (float)Ht * 0.5f;
+        const float u = half_w - px * inv_texel, v = half_h + py * inv_texel;
+        const float ta = u - 0.5f, tb = v - 0.5f;
+        du = ta - __builtin_floorf(ta); dv = tb - __builtin_floorf(tb);
+    }
+    // d(read)/dfu and d(read)/dfv from the four taps the read takes.  Two taps that replicate addressing puts on one
+    // texel differ by an exact 0: the derivative of the clamped lookup outside the texture and on a 1-texel extent.
+    __device__ __forceinline__ void slopes(const float* __restrict__ t, double& dfu, double& dfv) const
+    {
+        const double v00 = t[at.i00], v01 = t[at.i01], v10 = t[at.i10], v11 = t[at.i11];
+        dfu = (1.0 - dv) * (v01 - v00) + dv * (v11 - v10);
+        dfv = (1.0 - du) * (v10 - v00) + du * (v11 - v01);
+    }
+};
+
+// block_sum_store of sdirt_dp_grad.hpp for a run-time number of components that sit lane-major in LDS
+// (mine[c * kBlock] is this thread's component c): the wave by shuffles, the waves 0 to 3 through LDS, the same fixed
+// tree.  Called by all threads of the workgroup.
+__device__ __forceinline__ void block_sum_store_rows(const double* mine, int comps, double* __restrict__ out)
+{
+    __shared__ double red_rows[kBlock / 64][2 * SDIRT_MAX_LAYERS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c = 0; c < comps; ++c) {
+        const double v = wave_sum(mine[c * kBlock]);
+        if (lane == 0) red_rows[wave][c] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < comps) {
+        double v = 0.0;
+        for (int k = 0; k < kBlock / 64; ++k) v += red_rows[k][threadIdx.x];
+        out[threadIdx.x] = v;
+    }
+}
+
+// k_render_layers_grad's geometry and per-ray program up to the end of the trace, with the trip table the forward
+// ended with, so the ray the trace leaves, ra, the weights and every landing point are the forward's in every bit.
+// No z_l enters before that point: the landing on layer l is px_l = ox + dx (z_l - oz) / dz, whose slope in z_l is
+// sx = dx / dz, and u = Wt/2 - px_l inv_l, v = Ht/2 + py_l inv_l.  For a live ray, all in float64, one rounding per
+// operation, in the order of DESIGN.md §7s:
+//   front to back over ALL layers: D_l = sum_k q_k t_{l,k} and T_l go to the lane's stash (§7q's first walk without
+//   its scatter);
+//   back to front: d = D_l - R, e = T_l d, g = T_l a_l, Pu = e da/dfu + g sum_k q_k dt_k/dfu (Pv alike), and
+//     gz_l   = inv_l (Pv sy - Pu sx)       the term of depth[l]
+//     ginv_l = Pv py_l - Pu px_l           the term of inv_texel[l]
+//   are added to the lane's two sums of layer l; R = R + a_l d.  Layers with T_l == 0 give exact zeros: not issued.
+// With a null alpha (every layer opaque) the ray meets layer 0 with a = 1 and T = 0 behind it: one layer, no stash,
+// Pu = sum_k q_k dt_k/dfu, and what lies behind is not read.
+// The lane's 2 L sums and its 2 L stash entries are indexed by a run-time layer: register arrays would go to scratch,
+// so both sit lane-major in dynamic LDS, [2 L][kBlock] sums and then [2 L][kBlock] stash (8 KB per layer, 128 KB at
+// L = 16; the stash is left out with a null alpha).  A lane adds its rays' terms in sample order; the workgroup's sum
+// is one row of `partial`, OVERWRITTEN.  Lanes past H W take part with zeros.  No atomics: the same bits on every run.
+template <class M, int DP, int NT>
+__global__ void __launch_bounds__(kBlock)
+k_render_layers_depth_grad(TripTable trips /* kernarg offset 0 */, LayersDepthGradLaunch z, DevDpParams dp)
+{
+    extern __shared__ double slab[];                           // [2 L][kBlock] sums, [2 L][kBlock] stash
+    constexpr int V = DP == kDpNone ? 1 : 2;
+    const int64_t HW = (int64_t)z.H * z.W;
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    double* const sums = slab + threadIdx.x;
+    double* const kept = slab + 2 * z.L * kBlock + threadIdx.x;
+    for (int c = 0; c < 2 * z.L; ++c) sums[c * kBlock] = 0.0;
+    if (p < HW) {
+        const int i = (int)(p / z.W), j = (int)(p - (int64_t)i * z.W);
+        const float ox = z.x1[j], oy = z.y1[i];
+        const int64_t plane = (int64_t)z.Ht * z.Wt;
+        const int64_t rays = (int64_t)z.S * HW;
+        const auto div_fmh = UDiv<M>::make(dp.fmh);
+        double gz[V][NT];
+#pragma unroll
+        for (int side = 0; side < V; ++side)
+#pragma unroll
+            for (int k = 0; k < NT; ++k) gz[side][k] = z.gnum[side * z.view_stride + k * HW + p];
+        for (int s = 0; s < z.S; ++s) {
+            const int64_t at_ray = (int64_t)s * HW + p;
+            Ray r = make_ray<M>(ox, oy, z.z_sensor, z.x2[at_ray], z.y2[at_ray], z.z_pupil);
+            float wz[2] = {1.0f, 1.0f};                        // (w_L, w_R) = (sr, sl): see k_render_plane
+            if (DP != kDpNone) {
+                const float x_tan = r.dx / (-r.dz);
+                if (DP == kDpBig) dp_weights_big(dp, x_tan, wz[1], wz[0]);
+                else dp_weights_small<M>(dp, div_fmh, x_tan, wz[1], wz[0]);
+            }
+            trace_ray<false, M, true, /*UNIT_W*/ true, /*MASKS*/ false>(z.lens, 0, z.K, kernarg_at(0), r, nullptr);
+            if (z.ray_dir) {
+                z.ray_dir[at_ray] = r.dx; z.ray_dir[rays + at_ray] = r.dy; z.ray_dir[2 * rays + at_ray] = r.dz;
+            }
+            const bool lives = r.ra != 0.0f;
+            if (!lives) continue;
+            const double sx = (double)r.dx / (double)r.dz, sy = (double)r.dy / (double)r.dz;
+            double qz[NT];
+#pragma unroll
+            for (int k = 0; k < NT; ++k) {
+                qz[k] = ((double)wz[0] * (double)r.ra) * gz[0][k];
+                if (V == 2) qz[k] = qz[k] + ((double)wz[1] * (double)r.ra) * gz[V - 1][k];
+            }
+            if (!z.alpha) {
+                Ray there = r;
+                propagate_to<Ieee>(there, z.depth[0]);
+                const SlopeTaps st(there.ox, there.oy, z.inv_texel[0], z.Ht, z.Wt);
+                double Pu = 0.0, Pv = 0.0;
+#pragma unroll
+                for (int k = 0; k < NT; ++k) {
+                    double tu, tv;
+                    st.slopes(z.tex + k * plane, tu, tv);
+                    Pu = k == 0 ? qz[k] * tu : Pu + qz[k] * tu;
+                    Pv = k == 0 ? qz[k] * tv : Pv + qz[k] * tv;
+                }
+                sums[0] += (double)z.inv_texel[0] * (Pv * sy - Pu * sx);
+                sums[kBlock] += Pv * (double)there.oy - Pu * (double)there.ox;
+                continue;
+            }
+            double Tz = 1.0;
+            for (int lay = 0; lay < z.L; ++lay) {
+                Ray there = r;
+                propagate_to<Ieee>(there, z.depth[lay]);
+                const Taps tz(there.ox, there.oy, z.inv_texel[lay], z.Ht, z.Wt);
+                const double cover = tz.read(z.alpha + lay * plane);
+                const float* __restrict__ tl = z.tex + lay * z.layer_stride;
+                double D = 0.0;
+#pragma unroll
+                for (int k = 0; k < NT; ++k) {
+                    const double term = qz[k] * tz.read(tl + k * plane);
+                    D = k == 0 ? term : D + term;
+                }
+                kept[(2 * lay) * kBlock] = D;
+                kept[(2 * lay + 1) * kBlock] = Tz;
+                Tz = Tz * (1.0 - cover);
+            }
+            double R = 0.0;
+            for (int lay = z.L - 1; lay >= 0; --lay) {
+                const double D = kept[(2 * lay) * kBlock], Tl = kept[(2 * lay + 1) * kBlock];
+                Ray there = r;
+                propagate_to<Ieee>(there, z.depth[lay]);
+                const SlopeTaps st(there.ox, there.oy, z.inv_texel[lay], z.Ht, z.Wt);
+                const double cover = st.at.read(z.alpha + lay * plane);
+                const double d = D - R;
+                if (Tl != 0.0) {
+                    double au, av;
+                    st.slopes(z.alpha + lay * plane, au, av);
+                    const float* __restrict__ tl = z.tex + lay * z.layer_stride;
+                    double Cu = 0.0, Cv = 0.0;
+#pragma unroll
+                    for (int k = 0; k < NT; ++k) {
+                        double tu, tv;
+                        st.slopes(tl + k * plane, tu, tv);
+                        Cu = k == 0 ? qz[k] * tu : Cu + qz[k] * tu;
+                        Cv = k == 0 ? qz[k] * tv : Cv + qz[k] * tv;
+                    }
+                    const double el = Tl * d, gl = Tl * cover;
+                    const double Pu = el * au + gl * Cu, Pv = el * av + gl * Cv;
+                    sums[(2 * lay) * kBlock] += (double)z.inv_texel[lay] * (Pv * sy - Pu * sx);
+                    sums[(2 * lay + 1) * kBlock] += Pv * (double)there.oy - Pu * (double)there.ox;
+                }
+                R = R + cover * d;
+            }
+        }
+    }
+    block_sum_store_rows(sums, 2 * z.L, z.partial + (int64_t)blockIdx.x * 2 * z.L);
+}
+
+template <class M, int DP, int NT>
+int launch_layers_depth_grad_as(dim3 grid, size_t lds, hipStream_t st, const TripTable& tt,
+                                const LayersDepthGradLaunch& z, const DevDpParams& dp)
+{
+    if (lds > 48 * 1024)                // deep stacks: opt in to the CU's LDS above the default allowance
+        if (int rc = allow_large_lds<&k_render_layers_depth_grad<M, DP, NT>>()) return rc;
+    k_render_layers_depth_grad<M, DP, NT><<<grid, kBlock, lds, st>>>(tt, z, dp);
+    return 0;
+}
+
+template <class M, int DP>
+int launch_layers_depth_grad(int nt, dim3 grid, size_t lds, hipStream_t st, const TripTable& tt,
+                             const LayersDepthGradLaunch& z, const DevDpParams& dp)
+{
+    switch (nt) {
+    case 1: return launch_layers_depth_grad_as<M, DP, 1>(grid, lds, st, tt, z, dp);
+    case 2: return launch_layers_depth_grad_as<M, DP, 2>(grid, lds, st, tt, z, dp);
+    case 3: return launch_layers_depth_grad_as<M, DP, 3>(grid, lds, st, tt, z, dp);
+    default: return launch_layers_depth_grad_as<M, DP, kMaxPlanes>(grid, lds, st, tt, z, dp);
+    }
+}
+
 }  // namespace
 
 extern "C" int sdirt_render_plane(const sdirt_lens* lens, const int32_t* trips, uint32_t flags, const float* x1,
@@ -764,6 +984,68 @@ extern "C" int sdirt_render_layers_dp_grad(const sdirt_lens* lens, const int32_t
             return dpp.big ? launch_layers_dp_grad<Mm, kDpBig>(nt, grid, st, tt, e, dpp, q)
                            : launch_layers_dp_grad<Mm, kDpSmall>(nt, grid, st, tt, e, dpp, q);
         });
+        LAUNCH_CHECK();
+    }
+    return SDIRT_OK;
+}
+
+extern "C" int sdirt_render_layers_depth_grad(const sdirt_lens* lens, const int32_t* trips, uint32_t flags,
+                                              const float* x1, const float* y1, double z_sensor, const float* x2,
+                                              const float* y2, double z_pupil, int32_t spp, int32_t height,
+                                              int32_t width, const sdirt_dp_params* dp, int32_t n_layers,
+                                              const double* depth, const double* inv_texel, const float* alpha,
+                                              const float* tex, int64_t tex_layer_stride, int32_t n_tex, int32_t tex_h,
+                                              int32_t tex_w, const double* gnum, double* partial, float* ray_dir,
+                                              void* stream)
+{
+    if (!lens) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null lens");
+    if (any_null(x1, y1, x2, y2, depth, inv_texel, tex, gnum, partial)) return fail(SDIRT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!all_positive(spp, height, width, n_tex, tex_h, tex_w))
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "spp, the sensor's and the texture's extents must be at least 1");
+    if (n_layers < 1 || n_layers > SDIRT_MAX_LAYERS)
+        return fail(SDIRT_ERR_INVALID_ARGUMENT, "n_layers must be in 1 .. SDIRT_MAX_LAYERS");
+    if ((int64_t)tex_h * tex_w > INT32_MAX) return fail(SDIRT_ERR_INVALID_ARGUMENT, "texture plane above 2^31 texels");
+    if (tex_layer_stride < 0) return fail(SDIRT_ERR_INVALID_ARGUMENT, "negative layer stride");
+    const int64_t HW = (int64_t)height * width;
+    if (HW > (int64_t)INT32_MAX * kBlock) return fail(SDIRT_ERR_INVALID_ARGUMENT, "sensor too large");
+    LayersDepthGradLaunch z;
+    for (int l = 0; l < SDIRT_MAX_LAYERS; ++l) {
+        const bool used = l < n_layers;
+        z.depth[l] = used ? (float)depth[l] : 0.0f;
+        z.inv_texel[l] = used ? (float)inv_texel[l] : 0.0f;
+        if (used && !(z.depth[l] < (l ? z.depth[l - 1] : 0.0f)))
+            return fail(SDIRT_ERR_INVALID_ARGUMENT, "layer depths must be negative and strictly descending (nearest first)");
+    }
+    TripTable tt;
+    if (int rc = make_trips(lens, trips, tt)) return rc;
+    const DevDpParams dpp = make_dp(dp);
+    z.lens = lens->dev; z.K = lens->n_surfaces;
+    z.x1 = x1; z.y1 = y1; z.x2 = x2; z.y2 = y2;
+    z.z_sensor = (float)z_sensor; z.z_pupil = (float)z_pupil;
+    z.S = spp; z.H = height; z.W = width; z.L = n_layers;
+    z.alpha = alpha; z.layer_stride = tex_layer_stride;
+    z.Ht = tex_h; z.Wt = tex_w;
+    z.view_stride = (int64_t)n_tex * HW;
+    z.ray_dir = ray_dir;
+    const int64_t rows = (HW + kBlock - 1) / kBlock;
+    const dim3 grid((unsigned)rows);
+    // the lane's 2 L sums, and with a coverage its 2 L stash entries: 4 or 8 KB per layer, at most 128 KB
+    const size_t lds = (size_t)n_layers * (alpha ? 4 : 2) * kBlock * sizeof(double);
+    hipStream_t st = as_stream(stream);
+    // more than kMaxPlanes colour planes: further launches over the same rays, each into a slice of `partial` of its
+    // own; every term is linear in q, so the slices add
+    for (int t0 = 0; t0 < n_tex; t0 += kMaxPlanes) {
+        const int nt = n_tex - t0 < kMaxPlanes ? n_tex - t0 : kMaxPlanes;
+        z.tex = tex + (int64_t)t0 * tex_h * tex_w;
+        z.gnum = gnum + (int64_t)t0 * HW;
+        z.partial = partial + (int64_t)(t0 / kMaxPlanes) * rows * 2 * n_layers;
+        const int rc = with_math(routed_flags(flags, lens), [&](auto m) {
+            using Mm = decltype(m);
+            if (!dp) return launch_layers_depth_grad<Mm, kDpNone>(nt, grid, lds, st, tt, z, dpp);
+            return dpp.big ? launch_layers_depth_grad<Mm, kDpBig>(nt, grid, lds, st, tt, z, dpp)
+                           : launch_layers_depth_grad<Mm, kDpSmall>(nt, grid, lds, st, tt, z, dpp);
+        });
+        if (rc) return rc;
         LAUNCH_CHECK();
     }
     return SDIRT_OK;

@@ -9,8 +9,9 @@ csrc/sdirt_render_rt.hip); this module is its host side, the reference's two sam
 pure-torch float64 restatement of the lookup and the sums (`plane_sums_float64`) that tests and tools check it with.
 
 The layered render (render_layers, render_rgbd) and the opt-in gradients of all three renders in the
-textures and the coverage (scene_grad=True, sdirt_render_layers_grad) and in the dual-pixel parameters
-h, f, w (dp_grad=True, sdirt_render_layers_dp_grad) live here as well.
+textures and the coverage (scene_grad=True, sdirt_render_layers_grad), in the dual-pixel parameters
+h, f, w (dp_grad=True, sdirt_render_layers_dp_grad) and in the layer depths and scales (depth_grad=True,
+sdirt_render_layers_depth_grad) live here as well.
 
 Functions take the lens as their first argument; Lensgroup binds them under the reference's method names.
 """
@@ -64,12 +65,13 @@ def trace2obj(lens, ray, depth=DEPTH):
 
 
 # ------------------------------------------------------------------------------------ float64 restatement
-def _taps_float64(px, py, inv_texel, live, Ht, Wt):
+def _taps_float64(px, py, inv_texel, live, Ht, Wt, fractions=False):
     """The four taps of §7o's lookup in a [Ht, Wt] plane at (px, py) [S, H, W] fp32 with inv_texel texels per mm (rounded
     to fp32 here) -> (idx [4, S, H, W] int64: the taps' offsets in the flattened plane under replicate addressing,
     w [4, S, H, W] float64: w00, w01, w10, w11).  Dead rays land anywhere (NaN included): they are given a texel to
     read with weights of 0 (so that autograd through a read finds no NaN on them), and the caller leaves them out.  The one copy of the
-    lookup: the sums and the gradients of this module read through it."""
+    lookup: the sums and the gradients of this module read through it.  fractions=True: -> (idx, w, fu, fv), the
+    lookup's two fractions as float64 (what its derivative in the landing point is made of)."""
     inv = torch.tensor(float(inv_texel), dtype=torch.float32, device=px.device)
     u = Wt / 2 - px * inv                                    # fp32, one rounding per operation
     v = Ht / 2 + py * inv
@@ -82,7 +84,8 @@ def _taps_float64(px, py, inv_texel, live, Ht, Wt):
     rt, rb = r0.clamp(0, Ht - 1), (r0 + 1).clamp(0, Ht - 1)
     idx = torch.stack((rt * Wt + cl, rt * Wt + cr, rb * Wt + cl, rb * Wt + cr))
     w = torch.stack(((1 - fv) * (1 - fu), (1 - fv) * fu, fv * (1 - fu), fv * fu))
-    return idx, torch.where(live, w, torch.zeros((), dtype=torch.float64, device=px.device))
+    w = torch.where(live, w, torch.zeros((), dtype=torch.float64, device=px.device))
+    return (idx, w, fu, fv) if fractions else (idx, w)
 
 
 def _read_taps(planes, idx, w, live):
@@ -198,7 +201,8 @@ def _check_render_arguments(lens, img, spp, wvln, pupil_points):
 
 
 def render_plane(lens, img, depth, spp=64, dp=None, wvln=DEFAULT_WAVE, scale=None, pixel_center=True,
-                 photometric=False, pupil_points=None, return_sums=False, scene_grad=False, dp_grad=False):
+                 photometric=False, pupil_points=None, return_sums=False, scene_grad=False, dp_grad=False,
+                 depth_grad=False):
     """The image(s) the lens forms of the textured plane z = depth (mm, negative), ray traced.
 
     img [B, C, Ht, Wt] fp32 on the lens's device: the texture, spread over scale x the sensor's extent (scale: object
@@ -218,16 +222,29 @@ def render_plane(lens, img, depth, spp=64, dp=None, wvln=DEFAULT_WAVE, scale=Non
     plain call.  dp_grad=True opts in to the gradient of DESIGN.md §7r in the dual-pixel parameters: h, f, w of dp may
     then be 0-d tensors, and those that require a gradient get one, in their dtype and on their device (r gets none;
     dp=None raises ValueError); the two options compose.  Without dp_grad tensors in dp are turned into floats.
-    return_sums together with a recorded gradient raises ValueError."""
+    depth_grad=True opts in to the gradient of DESIGN.md §7s in the plane's position: `depth` and `scale` may then be
+    0-d tensors, and those that require a gradient get one, in their dtype and on their device (the derivative of the
+    piecewise-bilinear lookup along every ray); it composes with the other two.  With scale=None the default
+    calc_scale_ray value is a constant: the texture keeps its extent while the plane moves.  Without depth_grad
+    tensors are turned into floats.  return_sums together with a recorded gradient (depth_grad=True included) raises
+    ValueError."""
     _check_render_arguments(lens, img, spp, wvln, pupil_points)
     recorded = bool(scene_grad) and torch.is_grad_enabled() and img.requires_grad
     leaves = _dp_leaves(dp, dp_grad)
-    if (recorded or any(v is not None for v in leaves)) and return_sums:
+    zleaves = _depth_leaves(depth, scale, depth_grad)
+    if any(v is not None and v.dim() != 0 for v in zleaves):
+        raise ValueError("depth_grad=True: depth and scale that take a gradient must be 0-d tensors")
+    if torch.is_tensor(depth) and depth.dim() == 0:             # the numbers the forward takes
+        depth = _as_floats(depth)
+    if torch.is_tensor(scale) and scale.dim() == 0:
+        scale = _as_floats(scale)
+    tracked = recorded or any(v is not None for v in leaves + zleaves)
+    if (tracked or depth_grad) and return_sums:
         raise ValueError("return_sums with a recorded gradient: the float64 sums carry none")
     lens._require_gpu()
     args = (depth, spp, dp, wvln, scale, pixel_center, photometric, pupil_points)
-    if recorded or any(v is not None for v in leaves):
-        res = _recorded_call(lens, img, None, _plane_forward, args, recorded, leaves)
+    if tracked:
+        res = _recorded_call(lens, img, None, _plane_forward, args, recorded, leaves, zleaves)
         return res if dp is not None else res[0]
     with torch.no_grad():
         return _plane_forward(lens, img, None, *args, return_sums=return_sums)
@@ -267,8 +284,9 @@ def _plane_forward(lens, img, alpha, depth, spp, dp, wvln, scale, pixel_center, 
                 record["chunks"].append((g, x2.to(lens.device, torch.float32), y2.to(lens.device, torch.float32),
                                          part["trips"]))
     if record is not None:
-        record.update(wv=[g[0] for g in groups], den=dens, num=nums, depths=[float(depth)], inv_texels=[inv_texel], dp=dp,
-                      pixel_center=pixel_center, spp=spp, photometric=photometric, chroma=chroma, plane=True)
+        record.update(wv=[g[0] for g in groups], den=dens, num=nums, depths=[float(depth)], inv_texels=[inv_texel],
+                      scales=[float(scale)], dp=dp, pixel_center=pixel_center, spp=spp, photometric=photometric,
+                      chroma=chroma, plane=True)
     if chroma:
         num, den = torch.stack(nums, 2), torch.stack(dens, 1)               # [V, B, C, H, W], [V, C, H, W]
         den_b = den.unsqueeze(1)
@@ -395,7 +413,8 @@ def layer_batch(lens, alpha, tex, depths, inv_texels, x2, y2, dp=None, wvln=DEFA
 
 
 def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, scales=None, pixel_center=True,
-                  photometric=False, pupil_points=None, return_sums=False, scene_grad=False, dp_grad=False):
+                  photometric=False, pupil_points=None, return_sums=False, scene_grad=False, dp_grad=False,
+                  depth_grad=False):
     """The image(s) the lens forms of a stack of fronto-parallel layers, ray traced with occlusion.
 
     img [L, C, Ht, Wt] fp32, or [C, Ht, Wt] shared by all layers; alpha [L, Ht, Wt] fp32 in [0, 1]: layer l covers the
@@ -411,24 +430,40 @@ def render_layers(lens, img, alpha, depths, spp=64, dp=None, wvln=DEFAULT_WAVE, 
     image gets the sum over its layers); otherwise scene_grad=True is the plain call.  dp, the lens, depths, scales and
     pupil_points get none.  dp_grad=True opts in to the gradient of DESIGN.md §7r: h, f, w of dp may then be 0-d
     tensors, and those that require a gradient get one, in their dtype and on their device (r gets none; dp=None raises
-    ValueError); the two options compose, one backward running both kernels from the one record.  return_sums together
-    with a recorded gradient raises ValueError."""
+    ValueError); the two options compose, one backward running both kernels from the one record.
+    depth_grad=True opts in to the gradient of DESIGN.md §7s in the layers' positions: `depths` and `scales` may then
+    each be a 1-D tensor of L, and those that require a gradient get one, in their dtype and on their device.  It is
+    the derivative of the piecewise-bilinear lookups along every ray, pushed through the compositing: on a hard matte
+    it lives on the transition texels of alpha.  With scales=None the default calc_scale_ray values are constants:
+    every layer keeps its extent while it moves.  A caller who wants the layers to stay registered on the sensor
+    builds `scales` from the depth tensor (a pinhole: scale proportional to -depth), and autograd chains the two.
+    It composes with scene_grad and dp_grad: one backward runs the kernels from the one record.  Without depth_grad
+    tensors are turned into floats.  return_sums together with a recorded gradient (depth_grad=True included) raises
+    ValueError."""
     if not torch.is_tensor(img) or img.dim() not in (3, 4):
         raise ValueError("img must be a [L, C, Ht, Wt] tensor, or [C, Ht, Wt] shared by all layers")
     if scales is not None and len(scales) != len(depths):
         raise ValueError(f"{len(scales)} scales for {len(depths)} depths")
+    zleaves = _depth_leaves(depths, scales, depth_grad)
+    if any(v is not None and v.dim() != 1 for v in zleaves):
+        raise ValueError(f"depth_grad=True: depths and scales that take a gradient must be 1-D tensors of {len(depths)}")
+    if torch.is_tensor(depths) and depths.dim() == 1:           # the numbers the forward takes (no gradient is lost:
+        depths = _as_floats(depths)                             # zleaves holds the tensors that take one)
+    if torch.is_tensor(scales) and scales.dim() == 1:
+        scales = _as_floats(scales)
     L, Cn, Ht, Wt, shared = _check_layers(alpha, img, depths)
     chroma = _check_render_arguments(lens, img.unsqueeze(0) if shared else img, spp, wvln, pupil_points)
     if alpha.device != lens.device:
         raise ValueError(f"alpha is on {alpha.device}, the lens on {lens.device}")
     recorded = bool(scene_grad) and torch.is_grad_enabled() and (img.requires_grad or alpha.requires_grad)
     leaves = _dp_leaves(dp, dp_grad)
-    if (recorded or any(v is not None for v in leaves)) and return_sums:
+    tracked = recorded or any(v is not None for v in leaves + zleaves)
+    if (tracked or depth_grad) and return_sums:
         raise ValueError("return_sums with a recorded gradient: the float64 sums carry none")
     lens._require_gpu()
     args = (depths, spp, dp, wvln, scales, pixel_center, photometric, pupil_points)
-    if recorded or any(v is not None for v in leaves):
-        res = _recorded_call(lens, img, alpha, _layers_forward, args, recorded, leaves)
+    if tracked:
+        res = _recorded_call(lens, img, alpha, _layers_forward, args, recorded, leaves, zleaves)
         return res if dp is not None else res[0]
     with torch.no_grad():
         return _layers_forward(lens, img, alpha, *args, return_sums=return_sums)
@@ -470,7 +505,8 @@ def _layers_forward(lens, img, alpha, depths, spp, dp, wvln, scales, pixel_cente
                                          part["trips"]))
     if record is not None:
         record.update(wv=[g[0] for g in groups], den=dens, num=nums, depths=[float(d) for d in depths], inv_texels=inv_texels,
-                      dp=dp, pixel_center=pixel_center, spp=spp, photometric=photometric, chroma=chroma, plane=False)
+                      scales=[float(s) for s in scales], dp=dp, pixel_center=pixel_center, spp=spp,
+                      photometric=photometric, chroma=chroma, plane=False)
     if chroma:
         num, den, cov = torch.cat(nums, 1), torch.stack(dens, 1), torch.stack(covs, 1)     # [V, C, H, W] each
         den_b = den
@@ -529,7 +565,8 @@ def uniform_layer_depths(depth, n_layers):
 
 
 def render_rgbd(lens, img, depth, layer_depths=None, n_layers=8, spp=64, dp=None, wvln=DEFAULT_WAVE, scales=None,
-                pixel_center=True, photometric=False, pupil_points=None, extend=True, scene_grad=False, dp_grad=False):
+                pixel_center=True, photometric=False, pupil_points=None, extend=True, scene_grad=False, dp_grad=False,
+                depth_grad=False):
     """The ray-traced dual-pixel pair of an RGB-D frame -- the input PSFNet.render takes -- with occlusion: img
     [B, C, H, W] fp32, depth [B, 1, H, W] (mm, negative).  Every frame is cut into layers by layers_from_rgbd (at
     layer_depths, or at n_layers depths uniform in 1 / depth between the frame's nearest and farthest) that all show
@@ -538,16 +575,18 @@ def render_rgbd(lens, img, depth, layer_depths=None, n_layers=8, spp=64, dp=None
     -> (L, R) with dp, else one image, each [B, C, H, W] fp32.
     No gradients by default.  scene_grad=True: render_layers' -- img[b], which all layers of frame b show, gets the
     gradient summed over its layers; `depth` gets none (layers_from_rgbd is a hard assignment).  dp_grad=True:
-    render_layers' -- h, f, w get the sum over the batch."""
+    render_layers' -- h, f, w get the sum over the batch.  depth_grad=True: render_layers' -- `layer_depths` and
+    `scales`, given as 1-D tensors, get the sum over the batch; the depth MAP still gets none, and so
+    do depths that uniform_layer_depths made of it."""
     if dp_grad and dp is None:
         raise ValueError("dp_grad=True with dp=None: one view with unit weights has no sub-pixel model")
-    with torch.set_grad_enabled((bool(scene_grad) or bool(dp_grad)) and torch.is_grad_enabled()):
+    with torch.set_grad_enabled((bool(scene_grad) or bool(dp_grad) or bool(depth_grad)) and torch.is_grad_enabled()):
         return _render_rgbd(lens, img, depth, layer_depths, n_layers, spp, dp, wvln, scales, pixel_center, photometric,
-                            pupil_points, extend, scene_grad, dp_grad)
+                            pupil_points, extend, scene_grad, dp_grad, depth_grad)
 
 
 def _render_rgbd(lens, img, depth, layer_depths, n_layers, spp, dp, wvln, scales, pixel_center, photometric,
-                 pupil_points, extend, scene_grad, dp_grad=False):
+                 pupil_points, extend, scene_grad, dp_grad=False, depth_grad=False):
     if not torch.is_tensor(img) or img.dim() != 4:
         raise ValueError("img must be a [B, C, H, W] tensor")
     if not torch.is_tensor(depth) or depth.dim() != 4 or depth.shape[1] != 1 or depth.shape[0] != img.shape[0] \
@@ -557,14 +596,15 @@ def _render_rgbd(lens, img, depth, layer_depths, n_layers, spp, dp, wvln, scales
         raise ValueError(f"n_layers must be between 1 and {_lib.MAX_LAYERS}")
     views, scales_of = [], {}
     for b in range(img.shape[0]):
-        zs = uniform_layer_depths(depth[b, 0], n_layers) if layer_depths is None else [float(d) for d in layer_depths]
+        zs = uniform_layer_depths(depth[b, 0], n_layers) if layer_depths is None else _as_floats(layer_depths)
         alpha = layers_from_rgbd(depth[b, 0].detach(), zs, extend).to(img.device)
         if scales is None and tuple(zs) not in scales_of:      # calc_scale_ray traces rays of its own: once per stack
             scales_of[tuple(zs)] = scale_per_layer(lens, zs)
-        out = render_layers(lens, img[b], alpha, zs, spp=spp, dp=dp, wvln=wvln,
+        moving = depth_grad and torch.is_tensor(layer_depths)     # the tensor itself goes on: it may take a gradient
+        out = render_layers(lens, img[b], alpha, layer_depths if moving else zs, spp=spp, dp=dp, wvln=wvln,
                             scales=scales_of[tuple(zs)] if scales is None else scales,
                             pixel_center=pixel_center, photometric=photometric, pupil_points=pupil_points,
-                            scene_grad=scene_grad, dp_grad=dp_grad)
+                            scene_grad=scene_grad, dp_grad=dp_grad, depth_grad=depth_grad)
         views.append(out if dp is not None else (out,))
     res = tuple(torch.stack(v) for v in zip(*views))
     return res if dp is not None else res[0]
@@ -903,6 +943,177 @@ def layer_dp_grad_batch(lens, alpha, tex, depths, inv_texels, x2, y2, trips, gnu
     return (grad, xt) if x_tan else grad
 
 
+# ------------------------------------------------------------------------------------ gradients in the depths
+def _tap_slopes(planes, idx, fu, fv, live, magnitudes=False):
+    """d/dfu and d/dfv of _read_taps(planes, ...) from the four taps it reads -> two [N, S, H, W] float64 (0 on dead
+    rays): (1 - fv)(v01 - v00) + fv (v11 - v10) and (1 - fu)(v10 - v00) + fu (v11 - v01).  Two taps that replicate
+    addressing puts on one texel differ by an exact 0.  magnitudes: the same with |v01 - v00|, ... (no cancellation)."""
+    t64 = planes.double().flatten(1)
+    v00, v01, v10, v11 = (t64[:, idx[j]] for j in range(4))
+    top, bottom, left, right = v01 - v00, v11 - v10, v10 - v00, v11 - v01
+    if magnitudes:
+        top, bottom, left, right = top.abs(), bottom.abs(), left.abs(), right.abs()
+    zero = torch.zeros((), dtype=torch.float64, device=idx.device)
+    return (torch.where(live, (1 - fv) * top + fv * bottom, zero), torch.where(live, (1 - fu) * left + fu * right, zero))
+
+
+def layer_depth_grads_float64(landing, ray_dir, alpha, tex, inv_texels, gnum, return_abs=False):
+    """The adjoint of DESIGN.md §7s from the forward's landing record and the backward's ray_dir record, in plain torch
+    and without autograd: what sdirt_render_layers_depth_grad's partial rows add up to.
+
+    landing, alpha (None: every layer opaque -- the ray meets layer 0 only), tex, inv_texels as in layer_sums_float64;
+    ray_dir [3, S, H, W] fp32: dx, dy, dz of every ray as the trace left it; gnum [V, T, H, W] float64 (V = 1: one
+    view from row 1 of landing, V = 2: rows 1 and 2).
+    Per live ray: sx = dx / dz, sy = dy / dz; q_k, T_l, a_l, g_l, D_l, R_l, e_l of layer_grads_float64; every lookup's
+    derivative from its four taps (_tap_slopes); Pu_l = e_l da_l/dfu + g_l sum_k q_k dt_{l,k}/dfu, Pv_l alike;
+    gz_l = inv_l (Pv_l sy - Pu_l sx), ginv_l = Pv_l py_l - Pu_l px_l; layers with T_l == 0 give nothing.
+    -> [L, 2] float64: the gradient in depths[l] and in inv_texels[l]; with return_abs also [L, 2] the sums of |term|,
+    absolute values taken before any cancellation: |Pu|_l = T_l (Dbar_l + Rbar_{l+1}) |da/dfu| + g_l sum_k |q|_k
+    |dt_k/dfu| with |d./dfu| = (1 - fv)|v01 - v00| + fv |v11 - v10|, |gz| = inv (|Pv| |sy| + |Pu| |sx|), |ginv| alike."""
+    landing = torch.as_tensor(landing, dtype=torch.float32)
+    dev = landing.device
+    tex = torch.as_tensor(tex, dtype=torch.float32, device=dev)
+    gnum = torch.as_tensor(gnum, dtype=torch.float64, device=dev)
+    ray_dir = torch.as_tensor(ray_dir, dtype=torch.float32, device=dev)
+    L = len(inv_texels)
+    if landing.shape[0] != 3 + 2 * L:
+        raise ValueError(f"{L} layers need a landing record of {3 + 2 * L} rows and {L} inv_texels")
+    opaque = alpha is None
+    if not opaque:
+        alpha = torch.as_tensor(alpha, dtype=torch.float32, device=dev)
+        if alpha.shape[0] != L:
+            raise ValueError(f"alpha has {alpha.shape[0]} layers, inv_texels {L}")
+    if tuple(ray_dir.shape) != (3,) + tuple(landing.shape[1:]):
+        raise ValueError(f"ray_dir must be {(3,) + tuple(landing.shape[1:])}, got {tuple(ray_dir.shape)}")
+    shared = tex.dim() == 3
+    NT, Ht, Wt = (int(v) for v in tex.shape[-3:])
+    V = int(gnum.shape[0]) if gnum.dim() == 4 else 0
+    if V not in (1, 2) or tuple(gnum.shape) != (V, NT) + tuple(landing.shape[2:]):
+        raise ValueError(f"gnum must be {('V', NT) + tuple(landing.shape[2:])} with V = 1 or 2, got {tuple(gnum.shape)}")
+    ra = landing[0]
+    live = ra != 0
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    dz = torch.where(live, ray_dir[2].double(), torch.ones((), dtype=torch.float64, device=dev))
+    sx = torch.where(live, ray_dir[0].double() / dz, zero)
+    sy = torch.where(live, ray_dir[1].double() / dz, zero)
+    wr = torch.where(live, landing[1:1 + V].double() * ra.double(), zero)                   # [V, S, H, W]
+    q = wr[0] * gnum[0][:, None]                                                            # [T, S, H, W]
+    qa = wr[0] * gnum[0].abs()[:, None]
+    if V == 2:
+        q, qa = q + wr[1] * gnum[1][:, None], qa + wr[1] * gnum[1].abs()[:, None]
+    T = torch.ones(ra.shape, dtype=torch.float64, device=dev)
+    kept = []
+    for l in range(1 if opaque else L):                         # an opaque layer 0 leaves T = 0: nothing behind it is read
+        idx, w, fu, fv = _taps_float64(landing[3 + 2 * l], landing[4 + 2 * l], inv_texels[l], live, Ht, Wt, fractions=True)
+        a = torch.ones_like(T) if opaque else _read_taps(alpha[l:l + 1], idx, w, live)[0]
+        t = _read_taps(tex if shared else tex[l], idx, w, live)
+        D, Dbar = q[0] * t[0], qa[0] * t[0].abs()
+        for k in range(1, NT):
+            D, Dbar = D + q[k] * t[k], Dbar + qa[k] * t[k].abs()
+        kept.append((idx, fu, fv, a, D, Dbar, T))
+        T = T * (1 - a)
+    grad = torch.zeros((L, 2), dtype=torch.float64, device=dev)
+    mags = torch.zeros((L, 2), dtype=torch.float64, device=dev)
+    R, Rbar = torch.zeros_like(T), torch.zeros_like(T)
+    for l in range(len(kept) - 1, -1, -1):
+        idx, fu, fv, a, D, Dbar, Tl = kept[l]
+        d = D - R
+        sel = live & (Tl != 0)
+        planes = tex if shared else tex[l]
+        tu, tv = _tap_slopes(planes, idx, fu, fv, live)
+        tua, tva = _tap_slopes(planes, idx, fu, fv, live, magnitudes=True)
+        Cu, Cv, Cua, Cva = q[0] * tu[0], q[0] * tv[0], qa[0] * tua[0], qa[0] * tva[0]
+        for k in range(1, NT):
+            Cu, Cv, Cua, Cva = Cu + q[k] * tu[k], Cv + q[k] * tv[k], Cua + qa[k] * tua[k], Cva + qa[k] * tva[k]
+        if opaque:
+            au = av = aua = ava = torch.zeros_like(T)
+        else:
+            (au,), (av,) = _tap_slopes(alpha[l:l + 1], idx, fu, fv, live)
+            (aua,), (ava,) = _tap_slopes(alpha[l:l + 1], idx, fu, fv, live, magnitudes=True)
+        e, g, eb = Tl * d, Tl * a, Tl * (Dbar + Rbar)
+        Pu, Pv = e * au + g * Cu, e * av + g * Cv
+        Pua, Pva = eb * aua + g * Cua, eb * ava + g * Cva
+        inv = float(np.float32(inv_texels[l]))
+        px, py = landing[3 + 2 * l].double(), landing[4 + 2 * l].double()
+        grad[l, 0] = torch.where(sel, inv * (Pv * sy - Pu * sx), zero).sum()
+        grad[l, 1] = torch.where(sel, Pv * py - Pu * px, zero).sum()
+        mags[l, 0] = torch.where(sel, inv * (Pva * sy.abs() + Pua * sx.abs()), zero).sum()
+        mags[l, 1] = torch.where(sel, Pva * py.abs() + Pua * px.abs(), zero).sum()
+        R, Rbar = R + a * d, a * Dbar + (1 - a) * Rbar
+    return (grad, mags) if return_abs else grad
+
+
+def layer_depth_grad_batch(lens, alpha, tex, depths, inv_texels, x2, y2, trips, gnum, dp=None, wvln=DEFAULT_WAVE,
+                           pixel_center=True, ray_dir=False):
+    """ONE call of sdirt_render_layers_depth_grad: the counterpart of layer_batch (same scene, pupil points, dp, wvln
+    and pixel_center), with `trips` the table that call ended with and gnum [V, T, H, W] float64 the adjoint of its num.
+    alpha=None: every layer opaque (render_plane's scene with L = 1).  -> [L, 2] float64 on the lens's device: the
+    gradient in depths[l] and in inv_texels[l], the entry's partial rows [ceil(T / 4), ceil(H W / 256), L, 2] added by
+    one .sum over that fixed layout -- the same bits on every run; ray_dir=True: -> (that, ray_dir [3, S, H, W] fp32:
+    dx, dy, dz of every ray as the trace left it)."""
+    dev = lens.device
+    if alpha is None:
+        if not torch.is_tensor(tex) or tex.dim() not in (3, 4) or tex.dtype != torch.float32:
+            raise ValueError("the layers' image must be a float32 [L, C, Ht, Wt] tensor, or [C, Ht, Wt] shared by all layers")
+        shared = tex.dim() == 3
+        L, (T, Ht, Wt) = len(depths), (int(v) for v in tex.shape[-3:])
+        if not 1 <= L <= _lib.MAX_LAYERS or len(inv_texels) != L or (not shared and int(tex.shape[0]) != L):
+            raise ValueError(f"{L} depths, {len(inv_texels)} scales and an image of {tuple(tex.shape)}: layers differ")
+    else:
+        L, T, Ht, Wt, shared = _check_layers(alpha, tex, depths, inv_texels, scan=False)
+        if alpha.device != dev:
+            raise ValueError("alpha and tex must be on the lens's device")
+        alpha = alpha.contiguous()
+    if tex.device != dev:
+        raise ValueError("alpha and tex must be on the lens's device")
+    H, W = (int(v) for v in lens.sensor_res)
+    S = int(x2.shape[0])
+    K = len(lens.surfaces)
+    V = 1 if dp is None else 2
+    if tuple(x2.shape) != (S, H, W) or tuple(y2.shape) != (S, H, W):
+        raise ValueError(f"pupil points must be [spp, {H}, {W}], got {tuple(x2.shape)} and {tuple(y2.shape)}")
+    if len(trips) != K:
+        raise ValueError(f"{len(trips)} trip counts for a lens of {K} surfaces")
+    if not torch.is_tensor(gnum) or gnum.dtype != torch.float64 or gnum.device != dev or tuple(gnum.shape) != (V, T, H, W):
+        raise ValueError(f"gnum must be float64 {(V, T, H, W)} on the lens's device")
+    lens._require_gpu()
+    x1, y1 = sensor_axes(lens, pixel_center)
+    x2 = x2.to(dev, torch.float32).contiguous()
+    y2 = y2.to(dev, torch.float32).contiguous()
+    tex, gnum = tex.contiguous(), gnum.contiguous()
+    partial = torch.empty(((T + 3) // 4, (H * W + 255) // 256, L, 2), dtype=torch.float64, device=dev)
+    rd = torch.empty((3, S, H, W), dtype=torch.float32, device=dev) if ray_dir else None
+    dpp = None if dp is None else C.byref(_lib.DpParams(*(float(v) for v in dp)))
+    z = (C.c_double * L)(*(float(d) for d in depths))
+    inv = (C.c_double * L)(*(float(v) for v in inv_texels))
+    pupilz, _ = lens.exit_pupil()
+    wv = float(wvln if wvln < 10 else wvln * 1e-3)
+    with lens._timed("render_layers_depth_grad"):
+        _lib.check(_lib.lib().sdirt_render_layers_depth_grad(
+            lens.dev_lens(wv), (C.c_int32 * K)(*[int(t) for t in trips]), lens._math_flags(), dptr(x1), dptr(y1),
+            float(lens.d_sensor), dptr(x2), dptr(y2), float(pupilz), S, H, W, dpp, L, z, inv, dptr(alpha), dptr(tex),
+            0 if shared else T * Ht * Wt, T, Ht, Wt, dptr(gnum), dptr(partial), dptr(rd), stream_ptr(dev)))
+    grad = partial.view(-1, L, 2).sum(0)
+    return (grad, rd) if ray_dir else grad
+
+
+def _depth_leaves(depths, scales, depth_grad):
+    """The tensors among a call's depths and scales that get a gradient from a depth_grad=True call: -> (depths,
+    scales), None where the argument is no tensor or requires none; both None without depth_grad or outside grad mode."""
+    if not depth_grad or not torch.is_grad_enabled():
+        return (None, None)
+    return tuple(v if torch.is_tensor(v) and v.requires_grad else None for v in (depths, scales))
+
+
+def _as_floats(v):
+    """A call's depths or scales as the forward takes them: floats (a list of them; a 0-d tensor or a number: one)."""
+    if v is None:
+        return None
+    if torch.is_tensor(v):
+        v = v.detach().double().tolist()
+    return float(v) if np.isscalar(v) else [float(x) for x in v]
+
+
 def _dp_leaves(dp, dp_grad):
     """The tensors among dp's h, f, w that get a gradient from a dp_grad=True call: -> (h, f, w) with None where the
     entry is no tensor or requires none; all None without dp_grad, outside grad mode, or without such a tensor."""
@@ -916,7 +1127,7 @@ def _dp_leaves(dp, dp_grad):
 
 
 class _RenderRecorded(torch.autograd.Function):
-    """render_plane / render_layers(scene_grad=True and / or dp_grad=True) under autograd.  The forward is the plain
+    """render_plane / render_layers(scene_grad=True, dp_grad=True and / or depth_grad=True) under autograd.  The forward is the plain
     call (the same launches, the same images in every bit), which also keeps, per chunk of samples and wavelength
     group, the pupil points x2, y2 -- 8 bytes per ray, the only record that grows with the sample count -- and the trip
     table the launch ended with, and per call the wavelengths, pixel_center, dp, the depths, the inv_texels and the
@@ -925,18 +1136,22 @@ class _RenderRecorded(torch.autograd.Function):
       sdirt_render_layers_grad into zeroed float64 buffers of the inputs' shapes, where img or alpha
       takes a gradient, and
       sdirt_render_layers_dp_grad with gden = gden_from_image_grad, where h, f or w does: the chunks'
-      and the groups' [3] are added in the order recorded;
-    and returns them in the inputs' dtype (h, f, w: on their device).  It traces through the lens AS IT STANDS THEN: a
+      and the groups' [3] are added in the order recorded, and
+      sdirt_render_layers_depth_grad, where `depths` or `scales` (1-D tensors of L; 0-d for
+      render_plane) does: the [L, 2] are added in the order recorded, `depths` gets gdepth and `scales` gets
+      ginv_texel_l (-inv_texel_l / scale_l);
+    and returns them in the inputs' dtype (h, f, w, depths, scales: on their device).  It traces through the lens AS IT STANDS THEN: a
     lens changed (surfaces, sensor, focus, precision) between forward and backward is the caller's error."""
 
     @staticmethod
-    def forward(ctx, img, alpha, lens, run, args, h=None, f=None, w=None):
+    def forward(ctx, img, alpha, lens, run, args, h=None, f=None, w=None, depths=None, scales=None):
         record = {"chunks": []}
         with torch.no_grad():
             res = run(lens, img, alpha, *args, record=record)
         res = res if isinstance(res, tuple) else (res,)
         ctx.lens, ctx.record = lens, record
         ctx.dp_leaves = tuple((v.dtype, v.device) if v is not None else None for v in (h, f, w))
+        ctx.depth_leaves = tuple((v.dtype, v.device, v.shape) if v is not None else None for v in (depths, scales))
         ctx.save_for_backward(img, *(() if alpha is None else (alpha,)))
         ctx.set_materialize_grads(False)
         return res
@@ -947,8 +1162,9 @@ class _RenderRecorded(torch.autograd.Function):
         img, alpha = (ctx.saved_tensors + (None,))[:2]
         need_img, need_alpha = ctx.needs_input_grad[0], alpha is not None and ctx.needs_input_grad[1]
         need_dp = [leaf is not None and need for leaf, need in zip(ctx.dp_leaves, ctx.needs_input_grad[5:8])]
-        none = (None,) * 8
-        if all(g is None for g in G) or not (need_img or need_alpha or any(need_dp)):
+        need_z = [leaf is not None and need for leaf, need in zip(ctx.depth_leaves, ctx.needs_input_grad[8:10])]
+        none = (None,) * 10
+        if all(g is None for g in G) or not (need_img or need_alpha or any(need_dp) or any(need_z)):
             return none
         shape = next(g.shape for g in G if g is not None)
         G = torch.stack([torch.zeros(shape, dtype=torch.float64, device=lens.device) if g is None else g.double()
@@ -977,6 +1193,8 @@ class _RenderRecorded(torch.autograd.Function):
             if any(need_dp):
                 gdens = [gden_from_image_grad(Gg, rec["num"][g], rec["den"][g], rec["photometric"]) for g, Gg in enumerate(Gs)]
                 gdp = torch.zeros(3, dtype=torch.float64, device=lens.device)
+            if any(need_z):
+                gz = torch.zeros((len(rec["depths"]), 2), dtype=torch.float64, device=lens.device)
             stack = None if plane else alpha.detach()
             for g, x2, y2, trips in rec["chunks"]:
                 if scene:
@@ -986,6 +1204,9 @@ class _RenderRecorded(torch.autograd.Function):
                 if any(need_dp):
                     gdp += layer_dp_grad_batch(lens, stack, texs[g], rec["depths"], rec["inv_texels"], x2, y2, trips,
                                                gnums[g], gdens[g], rec["dp"], rec["wv"][g], rec["pixel_center"])
+                if any(need_z):
+                    gz += layer_depth_grad_batch(lens, stack, texs[g], rec["depths"], rec["inv_texels"], x2, y2, trips,
+                                                 gnums[g], rec["dp"], rec["wv"][g], rec["pixel_center"])
             if chroma and need_img:
                 for c, gt in enumerate(gtexs):
                     if plane:
@@ -996,20 +1217,29 @@ class _RenderRecorded(torch.autograd.Function):
                         gimg[:, c:c + 1] = gt
             gleaf = [gdp[j].to(device=leaf[1], dtype=leaf[0]) if need else None
                      for j, (leaf, need) in enumerate(zip(ctx.dp_leaves, need_dp))]
+            gzs = [None, None]
+            if any(need_z):
+                # inv_texel = 1 / (scale pixel_size W / Wt): d inv_texel / d scale = -inv_texel / scale
+                chain = torch.tensor([-v / s for v, s in zip(rec["inv_texels"], rec["scales"])], dtype=torch.float64,
+                                     device=lens.device)
+                for j, vals in enumerate((gz[:, 0], gz[:, 1] * chain)):
+                    if need_z[j]:
+                        dtype, device, shape = ctx.depth_leaves[j]
+                        gzs[j] = vals.reshape(shape).to(device=device, dtype=dtype)
         return (gimg.to(img.dtype) if need_img else None, galpha.to(alpha.dtype) if need_alpha else None,
-                None, None, None, *gleaf)
+                None, None, None, *gleaf, *gzs)
 
 
-def _recorded_call(lens, img, alpha, run, args, scene, leaves):
+def _recorded_call(lens, img, alpha, run, args, scene, leaves, zleaves=(None, None)):
     """The call through _RenderRecorded: img and alpha take part in the record only where scene_grad recorded them
-    (a dp_grad=True call alone leaves them without a gradient, whatever they require), h, f, w where dp_grad did; the
-    forward runs with dp as floats."""
+    (a dp_grad=True call alone leaves them without a gradient, whatever they require), h, f, w where dp_grad did, the
+    depths and the scales where depth_grad did; the forward runs with dp, the depths and the scales as floats."""
     dp = args[2]
     floats = None if dp is None else tuple(float(v.detach()) if torch.is_tensor(v) else float(v) for v in dp)
-    args = args[:2] + (floats,) + args[3:]
+    args = (_as_floats(args[0]), args[1], floats, args[3], _as_floats(args[4])) + args[5:]
     if not scene:
         img, alpha = img.detach(), None if alpha is None else alpha.detach()
-    return _RenderRecorded.apply(img, alpha, lens, run, args, *leaves)
+    return _RenderRecorded.apply(img, alpha, lens, run, args, *leaves, *zleaves)
 
 
 def render_single_img(lens, img_org, depth=DEPTH, spp=64, unwarp=False, save_name=None, return_tensor=False, noise=0,
